@@ -517,9 +517,26 @@ def self_launch(n, rank_cmd=None, poll_s=0.05, grace_s=5.0):
     return rc
 
 
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files of a run together
+
+
+def dump_outputs(out_dir, arrays, budgets):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  An array larger than its budget (bytes) keeps a fixed,
+    seeded sample of its rows (first axis, in order): two builds run with the same arguments dump the same rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > budgets[name]:
+            rows = np.random.default_rng(0x5EED).choice(len(a), budgets[name] // a[0].nbytes, replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def run_workload(W, synth, args, workload, rank, world, *, n_tracks, K, steps, warmup, ramp, clip_blocks=0.0,
-                 use_dist=False, dist_mode=0, mem_budget=96e9, latency_blocks=0, verify=True, verify_tail=True):
-    """Build the session in HBM, run warmup + ramp untimed steps straight into `steps` timed ones, return the measurements."""
+                 use_dist=False, dist_mode=0, mem_budget=96e9, latency_blocks=0, verify=True, verify_tail=True, dump_dir=None):
+    """Build the session in HBM, run warmup + ramp untimed steps straight into `steps` timed ones, return the measurements.
+    `dump_dir`: write what the last timed step computed there (dump_outputs): the clamped master on the rank that holds it,
+    every rank's per-track block peaks."""
     from whitebox_amd.dist import Dist, PinnedBuffer
     desc, src_rate, n_buses, fmt = WORKLOADS[workload]
     total_blocks = (warmup + ramp + steps) * K
@@ -611,6 +628,14 @@ def run_workload(W, synth, args, workload, rank, world, *, n_tracks, K, steps, w
         dt = dist.max(dt)                              # MAX over ranks
 
     master_peak = float(np.abs(host_master.array).max()) if rank == result_rank else 0.0
+    if dump_dir:
+        # the last timed step's results, before the verify step below renders over them: master [K][C][F], peaks [K][tracks][C]
+        _, pk, _ = eng.ctx.fetch(peaks=True)
+        peaks = "peaks" if world == 1 else f"peaks_rank{rank}"
+        arrays, budgets = {peaks: pk}, {peaks: DUMP_MAX_BYTES // 2 // world}
+        if rank == result_rank:
+            arrays["master"], budgets["master"] = host_master.array[:K * 2 * F].reshape(K, 2, F), DUMP_MAX_BYTES // 2
+        dump_outputs(dump_dir, arrays, budgets)
     # what did the timed loop compute?  rewind, one more step like the timed ones, its head against the CPU oracle
     ver = None
     if verify:
@@ -792,7 +817,13 @@ def main():
                     "cores between compared blocks, a few seconds per configuration)")
     ap.add_argument("--sustain-blocks", type=int, default=655360, help="blocks of the sustained-clock run in `configs` "
                     "(2 000 steps of 256 blocks' worth: >= 1.5 s of uninterrupted load)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last of them "
+                    "computed as DIR/<name>.npy (float32): the clamped master [blocks][channels][frames] and the per-track block "
+                    "peaks [blocks][tracks][channels] (peaks_rank<r> with several ranks); at most 64 MB in all, an array over its "
+                    "share keeps a fixed, seeded sample of its blocks")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     global F
     F = args.block_frames
 
@@ -830,10 +861,13 @@ def main():
         os.environ["NCCL_DEBUG_FILE"] = rccl_log_path(rank)
     r = run_workload(W, synth, args, args.workload, rank, world, n_tracks=n_tracks, K=K, steps=args.steps,
                      warmup=args.warmup, ramp=ramp, clip_blocks=args.clip_blocks, use_dist=use_dist,
-                     dist_mode=dist_mode, latency_blocks=args.latency_blocks, verify=not args.no_verify, verify_tail=not args.no_verify_tail)
-    # every rank says what it ran on (stderr: stdout carries rank 0's one JSON line)
-    print(json.dumps({"rank": rank, "world": world, "device": r["device"], "tracks": n_tracks, "exchange": r["exchange"],
-                      "mix_ms_avg": r["mix_ms"], "seconds": r["dt"]}), file=sys.stderr, flush=True)
+                     dist_mode=dist_mode, latency_blocks=args.latency_blocks, verify=not args.no_verify, verify_tail=not args.no_verify_tail,
+                     dump_dir=args.dump_outputs)
+    # every rank says what it ran on (stderr: stdout carries rank 0's one JSON line).  One write of the whole line: the ranks
+    # share the pipe, and an unbuffered stderr (PYTHONUNBUFFERED) would let print's separate newline interleave with another rank's
+    sys.stderr.flush()
+    os.write(2, (json.dumps({"rank": rank, "world": world, "device": r["device"], "tracks": n_tracks, "exchange": r["exchange"],
+                             "mix_ms_avg": r["mix_ms"], "seconds": r["dt"]}) + "\n").encode())
     if rank != 0:
         return
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz from the REFERENCE'S OWN code (oracle/_ref/libwbref.so).
+"""Generate tests/golden/*.npz (and ref_cuts.json) from the REFERENCE'S OWN code (oracle/_ref/libwbref.so).
 
 Run in the container that has /root/reference:   python oracle/gen_golden.py
 The fixtures are data only — seeds/parameters of the synthetic inputs and the outputs the reference's
@@ -394,9 +394,34 @@ def gen_baseline_ref():
     np.savez_compressed(os.path.join(OUT, "baseline_ref.npz"), **arrs)
     print("baseline_ref.npz:", len(BASELINE_REF_CASES), "configurations")
 
+
+def gen_cuts():
+    """tests/golden/ref_cuts.json: where every build output of oracle/Makefile's cut recipes lies in the reference's sources (file,
+    first and last line) and the SHA-256 of its text — what tests/test_ref_engine.py checks the cuts against where the sources are
+    not there.  No source text is stored."""
+    import hashlib
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_engine as R
+    if not R.available():
+        raise SystemExit("oracle/_ref is not built (needs /root/reference)")
+    rec = {}
+    for inc, src in sorted(R.CUTS.items()):
+        with open(os.path.join(O.ORACLE_DIR, "_ref", inc)) as f:
+            text = f.read()
+        with open(os.path.join("/root/reference/src", src)) as f:
+            region = R.cut_region(text, f.read())
+        assert region is not None, (inc, "is not a verbatim region of", src)
+        rec[inc] = {"src": src, "first": region[0], "last": region[1], "sha256": hashlib.sha256(text.encode()).hexdigest()}
+    with open(os.path.join(OUT, "ref_cuts.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("ref_cuts.json:", len(rec), "cuts")
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("mip", "vu", "ingest", "sequencer", "baseline", "perf"):     # (the other fixtures are untouched)
-        {"mip": gen_mip, "vu": gen_vu, "ingest": gen_ingest, "sequencer": gen_sequencer, "baseline": gen_baseline_ref, "perf": gen_perf}[sys.argv[1]]()
+    if len(sys.argv) > 1 and sys.argv[1] in ("mip", "vu", "ingest", "sequencer", "baseline", "perf", "cuts"):     # (the other fixtures are untouched)
+        {"mip": gen_mip, "vu": gen_vu, "ingest": gen_ingest, "sequencer": gen_sequencer, "baseline": gen_baseline_ref, "perf": gen_perf,
+         "cuts": gen_cuts}[sys.argv[1]]()
     else:
         main()
         gen_mip()
@@ -404,3 +429,4 @@ if __name__ == "__main__":
         gen_ingest()
         gen_sequencer()
         gen_baseline_ref()
+        gen_cuts()

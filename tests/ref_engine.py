@@ -18,6 +18,28 @@ import oracle_ffi as O
 
 EXE = os.path.join(O.ORACLE_DIR, "_ref", "wbref_engine")
 
+CUTS = {   # build output under oracle/_ref/ -> the reference source it must be a verbatim, contiguous region of
+    "eng/vu_meter_h_body.inc": "engine/vu_meter.h", "eng/track_h_body.inc": "engine/track.h",
+    "eng/audio_record_h_body.inc": "engine/audio_record.h", "eng/engine_h_body.inc": "engine/engine.h",
+    "eng/track_cpp_body.inc": "engine/track.cpp",
+    "eng/engine_r1.inc": "engine/engine.cpp", "eng/engine_r2.inc": "engine/engine.cpp", "eng/engine_r3.inc": "engine/engine.cpp",
+    "eng/engine_r4.inc": "engine/engine.cpp", "eng/engine_r5.inc": "engine/engine.cpp", "eng/engine_r6.inc": "engine/engine.cpp",
+    "eng/assets_r1.inc": "engine/assets_table.cpp", "eng/assets_r2.inc": "engine/assets_table.cpp",
+    "eng/assets_r3.inc": "engine/assets_table.cpp", "eng/sample_r1.inc": "dsp/sample.cpp",
+    "deinterleave_impl.inc": "dsp/sample.cpp", "mip_impl.inc": "gfx/waveform_visual.cpp", "vu_meter_struct.inc": "engine/vu_meter.h",
+}
+
+
+def cut_region(text: str, whole: str) -> Optional[tuple]:
+    """(first line, last line) of the region of `whole` that the cut `text` is byte for byte; None if it is no such region"""
+    at = whole.find(text)
+    if at < 0 and whole.endswith(text[:-1]):     # (a region that runs to the end of a file without a final newline: awk adds one)
+        at = len(whole) - len(text) + 1
+    if at < 0 or not text.strip():
+        return None
+    first = whole.count("\n", 0, at) + 1
+    return first, first + text.count("\n") - 1
+
 
 def available(build: bool = True) -> bool:
     """is the reference executable there?  build=True (the tests, this container): oracle/Makefile's `ref` target runs first where

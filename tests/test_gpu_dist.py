@@ -116,6 +116,25 @@ def test_bench_multi_gpu_launch_paths():
         assert line["verify"]["ok"] and line["verify"]["peaks_equal"] and line["verify"]["plan_rows_equal"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """bench.py --dump-outputs: two runs with the same total of steps split differently into warm-up and timed ones end on the
+    same blocks of the same session, so they dump the same master and peaks; --steps is the number of timed steps"""
+    lines = {}
+    for name, warmup, steps in (("a", 1, 3), ("b", 2, 2)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--blocks", "64", "--steps", str(steps),
+                            "--warmup", str(warmup), "--ramp-steps", "2", "--no-cpu-baseline", "--no-configs", "--latency-blocks", "0",
+                            "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert lines[name]["steps"] == steps and lines[name]["ms_per_step"] > 0 and lines[name]["verify"]["ok"]
+    for f in ("master", "peaks"):
+        a, b = np.load(tmp_path / "a" / f"{f}.npy"), np.load(tmp_path / "b" / f"{f}.npy")
+        assert a.dtype == np.float32 and a.shape == ((64, 2, 512) if f == "master" else (64, 256, 2))
+        assert np.array_equal(bits(a), bits(b)), f
+    m = np.load(tmp_path / "a" / "master.npy")
+    assert 0.0 < np.abs(m).max() <= 1.0 and np.abs(m).max() == lines["a"]["master_peak"]
+
+
 @pytest.mark.parametrize("world", [2, 4])
 def test_ranks_that_share_the_device_exchange_over_rccl(world):
     """wbx_dist.hip with world > 1 between processes, on a box with ONE GPU: every rank claims a host of its own

@@ -11,6 +11,7 @@ sample-index math bit-exact.  What is actually asserted is tighter wherever the 
 """
 import dataclasses
 import os
+import re
 
 import numpy as np
 import pytest
@@ -34,6 +35,12 @@ def rms(a, b):
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
+
+
+def instance_id(name):
+    """a kernel instance's C++ name as a test id: "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>" -> "mix_kernel_2_true_4_0_1_1_1_256"
+    (the name itself holds "::", the separator of pytest's node ids)"""
+    return re.sub(r"[^0-9A-Za-z]+", "_", name.removeprefix("wbx::")).strip("_")
 
 
 def plan_rows(plan):
@@ -2027,7 +2034,7 @@ def test_clip_storage_slabs_grow_and_are_reused():
     ctx.close()
 
 
-@pytest.mark.parametrize("kw,block,expect", [
+INSTANCE_CASES = [
     (dict(), 512, "wbx::mix_kernel<4, true, 3, 0, 1, 1, 1, 256>"),                              # fp32 unity, one clip per track
     (dict(src_rate=44100), 512, "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>"),                # fp32 resampled, one clip per track
     (dict(src_rate=44100, seek=True), 512, "wbx::mix_kernel<2, true, 3, 0, 1, 1, 2, 128>"),     # ... tracks cut into clips
@@ -2043,7 +2050,11 @@ def test_clip_storage_slabs_grow_and_are_reused():
     (dict(fmt="i16", seek=True), 1024, "wbx::mix_kernel<2, true, 3, 0, 1, 1, 2, 256>"),         # 1024-frame blocks
     (dict(fmt="i16", src_rate=44100, seek=True), 256, "wbx::mix_kernel<2, true, 3, 2, 1, 1, 2, 64>"),    # the 16-bit family at 256 ...
     (dict(fmt="i16", src_rate=44100, seek=True), 1024, "wbx::mix_kernel<2, true, 3, 2, 1, 1, 2, 256>"),  # ... and 1024 frames
-])
+]
+
+
+@pytest.mark.parametrize("kw,block,expect", INSTANCE_CASES,
+                         ids=[f"kw{i}-{block}-{instance_id(expect)}" for i, (_, block, expect) in enumerate(INSTANCE_CASES)])
 def test_instance_selection(kw, block, expect):
     """Which mix_kernel instance a session takes (wbx_runtime.hip: mix_family, mix_two_channels_per_lane, launch_mix) — and
     that it renders the session like the oracle."""

@@ -33,8 +33,11 @@ def test_device_periods_resampled_session(block, channels):
     P.check_against_oracle(spec, 5, group_size=150, expect_exact=True)
 
 
-@pytest.mark.parametrize("block,instance", [(480, "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>"), (960, "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>"),
-                                            (224, "wbx::mix_kernel<2, true, 4, 0, 2, 1, 1, 256>"), (96, "wbx::mix_kernel<2, true, 4, 0, 4, 2, 1, 256>")])
+NEXT_SHAPE_CASES = [(480, "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>"), (960, "wbx::mix_kernel<2, true, 4, 0, 1, 1, 1, 256>"),
+                    (224, "wbx::mix_kernel<2, true, 4, 0, 2, 1, 1, 256>"), (96, "wbx::mix_kernel<2, true, 4, 0, 4, 2, 1, 256>")]
+
+
+@pytest.mark.parametrize("block,instance", NEXT_SHAPE_CASES, ids=[f"{b}-{P.instance_id(i)}" for b, i in NEXT_SHAPE_CASES])
 def test_device_periods_take_the_instances_of_the_next_shape(block, instance):
     spec = synth.make_session("pern", 64, n_blocks=8, block=block, seed=0x9E1, src_rate=44100)
     eng = build_engine(spec, max_blocks=8)

@@ -65,6 +65,29 @@ def test_bench_algorithmic_bytes_match_survey_figures():
     assert abs(512 * 32768 / 1e6 - 16.78) < 0.01 and abs(512 * 32768 * 0.91875 / 1e6 - 15.41) < 0.01
 
 
+def test_bench_dump_outputs_keep_their_budget_and_sample_the_same_rows(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files; an array within its budget is written whole, a larger one as the same seeded
+    sample of its rows, in order, on every run"""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod_dump", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    rng = np.random.default_rng(5)
+    master = rng.standard_normal((64, 2, 512))                      # float64 in: float32 out
+    peaks = np.arange(512 * 256 * 2, dtype=np.float32).reshape(512, 256, 2)
+    budgets = {"master": master.size * 4, "peaks": 100 * 256 * 2 * 4 + 5}
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"master": master, "peaks": peaks}, budgets)
+    m, p = np.load(tmp_path / "a" / "master.npy"), np.load(tmp_path / "a" / "peaks.npy")
+    assert m.dtype == np.float32 and np.array_equal(m, master.astype(np.float32))
+    assert p.dtype == np.float32 and p.shape == (100, 256, 2) and p.nbytes <= budgets["peaks"]
+    rows = p[:, 0, 0].astype(np.int64) // (256 * 2)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(p, peaks[rows])
+    assert np.array_equal(p, np.load(tmp_path / "b" / "peaks.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= b.DUMP_MAX_BYTES
+
+
 def test_perf_measurer_arithmetic_matches_reference_golden():
     """The product's load-figure arithmetic (wbx_calc_perf_update / wbx_calc_perf_usage / wbx_calc_buffer_period_ms: what
     wbx_engine_process feeds Engine::perf_measurer with, engine.cpp:52,1653) against the outputs of the reference's own

@@ -9,6 +9,7 @@ import os
 
 import pytest
 
+import golden_util as G
 import ref_engine as R
 import seq_sessions as S
 
@@ -70,34 +71,31 @@ def test_refusals_and_takes_are_both_exercised(exe):
     assert taken > 100 and refused > 10 and bad > 5, (taken, refused, bad)
 
 
-CUTS = {   # build output under oracle/_ref/ -> the reference source it must be a verbatim, contiguous region of
-    "eng/vu_meter_h_body.inc": "engine/vu_meter.h", "eng/track_h_body.inc": "engine/track.h",
-    "eng/audio_record_h_body.inc": "engine/audio_record.h", "eng/engine_h_body.inc": "engine/engine.h",
-    "eng/track_cpp_body.inc": "engine/track.cpp",
-    "eng/engine_r1.inc": "engine/engine.cpp", "eng/engine_r2.inc": "engine/engine.cpp", "eng/engine_r3.inc": "engine/engine.cpp",
-    "eng/engine_r4.inc": "engine/engine.cpp", "eng/engine_r5.inc": "engine/engine.cpp", "eng/engine_r6.inc": "engine/engine.cpp",
-    "eng/assets_r1.inc": "engine/assets_table.cpp", "eng/assets_r2.inc": "engine/assets_table.cpp",
-    "eng/assets_r3.inc": "engine/assets_table.cpp", "eng/sample_r1.inc": "dsp/sample.cpp",
-    "deinterleave_impl.inc": "dsp/sample.cpp", "mip_impl.inc": "gfx/waveform_visual.cpp", "vu_meter_struct.inc": "engine/vu_meter.h",
-}
-
-
 def test_every_cut_is_a_verbatim_region_of_the_reference(exe):
     """what oracle/ref_*_driver.cpp compile is the reference's text and nothing else: every build output of the recipe is, byte
     for byte, ONE contiguous region of the source file it was cut from; regions of one file do not overlap; no `Log::` line
-    survives in a cut except inside track.cpp's own `#if WB_DBG_LOG_*` blocks and audio_record.h's comment"""
+    survives in a cut except inside track.cpp's own `#if WB_DBG_LOG_*` blocks and audio_record.h's comment.  Every cut is the
+    one tests/golden/ref_cuts.json records (its region and SHA-256, oracle/gen_golden.py cuts): where the reference's sources are
+    not there (the build outputs travelled without them), the record stands in for them"""
+    import hashlib
+    import json
     import re
     ref_root = "/root/reference/src"
+    have_src = os.path.isdir(ref_root)
+    with open(os.path.join(G.GOLDEN, "ref_cuts.json")) as f:
+        rec = json.load(f)
+    assert sorted(rec) == sorted(R.CUTS)
     ranges = {}
-    for inc, src in CUTS.items():
-        text = open(os.path.join(R.O.ORACLE_DIR, "_ref", inc)).read()
-        whole = open(os.path.join(ref_root, src)).read()
-        at = whole.find(text)
-        if at < 0 and whole.endswith(text[:-1]):     # (a region that runs to the end of a file without a final newline: awk adds one)
-            at = len(whole) - len(text) + 1
-        assert at >= 0 and text.strip(), (inc, "is not a verbatim region of", src)
-        first = whole.count("\n", 0, at) + 1
-        last = first + text.count("\n") - 1
+    for inc, src in R.CUTS.items():
+        with open(os.path.join(R.O.ORACLE_DIR, "_ref", inc)) as f:
+            text = f.read()
+        first, last = rec[inc]["first"], rec[inc]["last"]
+        assert rec[inc]["src"] == src and text.strip(), inc
+        assert hashlib.sha256(text.encode()).hexdigest() == rec[inc]["sha256"], (inc, "is not the cut tests/golden/ref_cuts.json records")
+        assert last - first + 1 == text.count("\n"), inc
+        if have_src:
+            with open(os.path.join(ref_root, src)) as f:
+                assert R.cut_region(text, f.read()) == (first, last), (inc, "is not a verbatim region of", src, "at", first, last)
         ranges.setdefault(src, []).append((first, last, inc))
         for m in re.finditer(r"^.*Log::.*$", text, re.M):
             line = m.group(0)
