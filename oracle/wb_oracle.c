@@ -1114,19 +1114,25 @@ static void track_process(wbo_engine* e, wbo_track* t, float* const* out, double
  * bus order, then the clamp. */
 void wbo_engine_process(wbo_engine* e, float* const* out, float* bus_out) { wbo_engine_process_ex(e, out, bus_out, 1); }
 
-static void engine_process_impl(wbo_engine* e, float* const* out, float* bus_out, int clamp, int keep_out);
+static void engine_process_impl(wbo_engine* e, float* const* out, float* bus_out, int clamp, int keep_out, float* track_out);
 
 void wbo_engine_process_ex(wbo_engine* e, float* const* out, float* bus_out, int clamp) {
-  engine_process_impl(e, out, bus_out, clamp, 0);
+  engine_process_impl(e, out, bus_out, clamp, 0, NULL);
+}
+
+/* NOT in the reference: the same block, and each track's post-gain block buffer (the mixing_buffer that engine.cpp:1600-1617
+ * adds into the output) copied to track_out [n_tracks][C][F] — the inputs of any other order of the same additions. */
+void wbo_engine_process_tracks(wbo_engine* e, float* const* out, float* bus_out, int clamp, float* track_out) {
+  engine_process_impl(e, out, bus_out, clamp, 0, track_out);
 }
 
 /* NOT in the reference: Engine::process WITHOUT the output_buffer.clear() of engine.cpp:1598 — `out` holds the running,
  * un-clamped sum of the tracks that precede this engine's in a session split over several engines, and the track loop
  * (engine.cpp:1600-1617) continues it.  The checker for the product's wbx_set_master_init / WBX_DIST_CHAIN: a chain of
  * such calls over the shards is, addition for addition, one Engine::process over all tracks. */
-void wbo_engine_process_from(wbo_engine* e, float* const* out, int clamp) { engine_process_impl(e, out, NULL, clamp, 1); }
+void wbo_engine_process_from(wbo_engine* e, float* const* out, int clamp) { engine_process_impl(e, out, NULL, clamp, 1, NULL); }
 
-static void engine_process_impl(wbo_engine* e, float* const* out, float* bus_out, int clamp, int keep_out) {
+static void engine_process_impl(wbo_engine* e, float* const* out, float* bus_out, int clamp, int keep_out, float* track_out) {
   const uint32_t F = e->buffer_size, C = e->out_channels;
   double sample_rate = (double)e->sample_rate;
   double buffer_duration = (double)F / sample_rate;                /* :1578 */
@@ -1149,6 +1155,8 @@ static void engine_process_impl(wbo_engine* e, float* const* out, float* bus_out
     wbo_clear(e->mixbuf, C, F);
     track_process(e, t, e->mixbuf, sample_rate, current_beat_duration, buffer_duration_in_beats, e->sample_position,
                   current_playhead_position, next_playhead_pos, currently_playing);
+    if (track_out)
+      for (uint32_t c = 0; c < C; c++) memcpy(track_out + ((size_t)i * C + c) * F, e->mixbuf[c], (size_t)F * sizeof(float));
     if (e->n_buses && t->bus >= 0) {
       float* b[16];
       for (uint32_t c = 0; c < C; c++) b[c] = e->busbuf + ((size_t)t->bus * C + c) * F;

@@ -222,6 +222,9 @@ void wbo_engine_process_ex(wbo_engine* e, float* const* out, float* bus_out, int
 /* NOT in the reference: the same without clearing `out` first (engine.cpp:1598) — `out` holds the running un-clamped
  * sum of the tracks before this engine's; checker for wbx_set_master_init / WBX_DIST_CHAIN.  No sub-buses. */
 void wbo_engine_process_from(wbo_engine* e, float* const* out, int clamp);
+/* NOT in the reference: wbo_engine_process_ex, and each track's post-gain block buffer (Engine::mixing_buffer after
+ * Track::process, what the track loop adds into the output or its bus) in track_out [n_tracks][C][F] */
+void wbo_engine_process_tracks(wbo_engine* e, float* const* out, float* bus_out, int clamp, float* track_out);
 
 /* synthetic input generator (integer hash; input generation only, same bits as whitebox_amd/synth.py) */
 void wbo_synth_f32(float* dst, size_t frames, uint64_t key, float amp, size_t pad);

@@ -437,6 +437,18 @@ class OracleEngine:
                                      int(clamp))
         return np.stack(out), bus
 
+    def process_tracks(self, want_buses=False, clamp=True):
+        """process(), and each track's post-gain block buffer [n_tracks][C][F] (what the track loop adds into the output
+        or its bus): the inputs of tests/grouped_order.py's model"""
+        out = [np.zeros(self.F, dtype=np.float32) for _ in range(self.C)]
+        nb = self.e.contents.n_buses
+        bus = np.zeros((nb, self.C, self.F), dtype=np.float32) if (want_buses and nb) else None
+        tracks = np.zeros((self.e.contents.n_tracks, self.C, self.F), dtype=np.float32)
+        self.L.wbo_engine_process_tracks.argtypes = [C.POINTER(_Engine), c_f32pp, c_f32p, C.c_int, c_f32p]
+        self.L.wbo_engine_process_tracks(self.e, planar_ptrs(out), bus.ctypes.data_as(c_f32p) if bus is not None else None,
+                                         int(clamp), tracks.ctypes.data_as(c_f32p))
+        return np.stack(out), bus, tracks
+
     def process_from(self, running: np.ndarray, clamp=False) -> np.ndarray:
         """Engine::process continuing `running` ([C][F], the un-clamped sum of the tracks before this engine's) instead of
         the cleared output buffer — the checker for wbx_set_master_init / WBX_DIST_CHAIN."""

@@ -6,6 +6,7 @@ of the same engine configuration (bit-identical: same functions, same order of a
 import numpy as np
 import pytest
 
+import grouped_order as GO
 import oracle_ffi as O
 import whitebox_amd as W
 from whitebox_amd import synth
@@ -29,8 +30,7 @@ def oracle_rows(e, block):
             for (t, ds, ln, off, spd, g, smp) in e.seglog()]
 
 
-def callback_group(n):       # what a max_blocks = 1 engine picks (wbx_runtime.hip build_routing)
-    return 64 if n <= 16 else 1 if n <= 64 else 4 if n <= 256 else 8 if n <= 512 else 16
+callback_group = GO.callback_group       # what a max_blocks = 1 engine picks (wbx_runtime.hip build_routing)
 
 
 return_names = []      # the kernel names of the last run_callback call
@@ -50,7 +50,7 @@ def run_callback(spec, K, edits=None, check_plan=True, every_block_one_launch=Tr
     for b in range(K):
         if edits and b in edits:
             edits[b](e, eng)
-        om, _ = e.process()
+        om, _, tracks = e.process_tracks()
         eng.process(None, out, float(spec.sample_rate))
         m = np.stack(out.channel_buffers)
         names.append(eng.ctx.kernel_name())
@@ -59,6 +59,11 @@ def run_callback(spec, K, edits=None, check_plan=True, every_block_one_launch=Tr
         else:
             d = m.astype(np.float64) - om.astype(np.float64)
             assert float(np.sqrt(np.mean(d * d))) <= RMS_TOL, b
+        # ... and the grouped order itself, bit for bit (tests/grouped_order.py over the oracle's track buffers)
+        groups = GO.spec_partition(spec, callback_group(spec.n_tracks))
+        assert eng.ctx.render_order(1)[:2] == GO.shape_of(groups), b
+        em, _ = GO.grouped_sum(tracks, groups, spec.n_buses)
+        GO.assert_model(m, em, what=("callback", spec.n_tracks, b))
         _, pk, _ = eng.ctx.fetch(peaks=True)
         # (by value: a muted track's peak is -0.0 in the reference — math::abs(-0.0f) is -0.0f and math::max keeps it — and +0.0
         #  here, where magnitudes are compared as unsigned integers)
@@ -115,7 +120,7 @@ def test_one_launch_callback_with_sub_buses(n_tracks, n_buses):
     eng.play()
     per_bus = n_tracks // n_buses
     for b in range(K):
-        om, obus = e.process(want_buses=True)
+        om, obus, tracks = e.process_tracks(want_buses=True)
         eng.process(None, out, 48000.0)
         assert eng.ctx.kernel_name().startswith("wbx::callback_kernel<")
         m = np.stack(out.channel_buffers)
@@ -126,6 +131,8 @@ def test_one_launch_callback_with_sub_buses(n_tracks, n_buses):
         else:
             d = m.astype(np.float64) - om.astype(np.float64)
             assert float(np.sqrt(np.mean(d * d))) <= RMS_TOL
+        # ... and the spread sum's sub-bus branch in the grouped order itself: bus sums and master bit for bit
+        GO.assert_grouped(m, tracks, callback_group(n_tracks), n_buses, spec.track_bus, bus[0], what=("buses", n_tracks, b))
     e.close()
     eng.close()
 
@@ -215,12 +222,13 @@ def test_callback_grid_shrinks_from_more_than_the_device_to_a_spread_grid():
                 n -= 1
                 e.delete_track(n)
                 eng.delete_track(n)
-        om, _ = e.process()
+        om, _, tracks = e.process_tracks()
         eng.process(None, out, float(spec.sample_rate))
         assert eng.ctx.kernel_name().startswith("wbx::callback_kernel<"), b
         m = np.stack(out.channel_buffers)
         d = m.astype(np.float64) - om.astype(np.float64)
         assert float(np.sqrt(np.mean(d * d))) <= RMS_TOL, b
+        GO.assert_grouped(m, tracks, callback_group(n), what=("shrink", n, b))   # (the groups of the tracks that are left)
         _, pk, _ = eng.ctx.fetch(peaks=True)
         assert np.array_equal(pk[0][:n], e.peaks()[:n, :spec.channels]), b
     launches, spread, give_ups, off = eng.callback_stats()
@@ -243,11 +251,12 @@ def test_callback_give_up_at_the_spread_barrier_mixes_the_block_again(monkeypatc
     e.play()
     eng.play()
     for b in range(5):
-        om, _ = e.process()
+        om, _, tracks = e.process_tracks()
         eng.process(None, out, float(spec.sample_rate))
         m = np.stack(out.channel_buffers)
         d = m.astype(np.float64) - om.astype(np.float64)
         assert float(np.sqrt(np.mean(d * d))) <= RMS_TOL, b
+        GO.assert_grouped(m, tracks, callback_group(n_tracks), what=("give-up", n_tracks, b))   # (mixed again: the same groups)
         _, pk, _ = eng.ctx.fetch(peaks=True)
         assert np.array_equal(pk[0], e.peaks()[:, :spec.channels]), b
         if n_tracks <= 1025:
@@ -297,11 +306,12 @@ def test_callback_give_up_with_the_plan_counters_in_use(monkeypatch, n_tracks):
     e.play()
     eng.play()
     for b in range(4):
-        om, _ = e.process()
+        om, _, tracks = e.process_tracks()
         eng.process(None, out, float(spec.sample_rate))
         m = np.stack(out.channel_buffers)
         d = m.astype(np.float64) - om.astype(np.float64)
         assert float(np.sqrt(np.mean(d * d))) <= RMS_TOL, b
+        GO.assert_grouped(m, tracks, callback_group(n_tracks), what=("give-up", n_tracks, b))   # (mixed again: the same groups)
         _, pk, _ = eng.ctx.fetch(peaks=True)
         assert np.array_equal(pk[0], e.peaks()[:, :spec.channels]), b
         rows = oracle_rows(e, 0)

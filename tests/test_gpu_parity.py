@@ -18,6 +18,7 @@ import pytest
 
 import fuzz_util as FZ
 import golden_util as G
+import grouped_order as GO
 import oracle_ffi as O
 import whitebox_amd as W
 from whitebox_amd import synth
@@ -133,8 +134,19 @@ def check_against_oracle(spec, n_blocks, group_size=0, expect_exact=False, devic
             assert np.array_equal(bits(bus), bits(obus))
     else:
         assert r <= RMS_TOL, r
+    check_grouped_order(eng, spec, n_blocks, group_size, m, bus)
     eng.close()
     return r
+
+
+def check_grouped_order(eng, spec, n_blocks, group_size, m, bus):
+    """the render's master and bus sums, bit for bit, against tests/grouped_order.py's model of the order the render took
+    (wbx_render_order: the reference's, or groups of G) over the oracle's track buffers"""
+    order = eng.ctx.render_order(n_blocks)
+    groups = GO.render_partition(spec, order, group_size, n_blocks)
+    _, _, tracks = GO.oracle_tracks(spec, n_blocks)
+    em, ebus = GO.grouped_sum(tracks, groups, spec.n_buses)
+    GO.assert_model(m, em, bus, ebus if spec.n_buses else None, what=(spec.name, order))
 
 
 def test_config1_8_mono_unity():
@@ -224,6 +236,7 @@ def test_grouped_order_at_mix_bus_levels(name, kw, mult):
     eng.play()
     eng.render(K)
     m, pk, _ = eng.ctx.fetch(peaks=True)
+    groups = GO.render_partition(spec, eng.ctx.render_order(K), 0, K)
     eng.close()
     assert np.array_equal(pk, opk[..., :2])
     d = m.astype(np.float64) - om.astype(np.float64)
@@ -234,6 +247,10 @@ def test_grouped_order_at_mix_bus_levels(name, kw, mult):
         assert np.array_equal(bits(m), bits(om))
     else:
         assert r <= RMS_TOL, r
+    _, _, tracks = GO.oracle_tracks(spec, K)      # ... and exactly the order the render took (c3: 32 groups of 128 tracks)
+    assert len(groups) == (32 if name == "c3" else 64)
+    em, _ = GO.grouped_sum(tracks, groups, spec.n_buses)
+    GO.assert_model(m, em, what=(name, mult))
 
 
 @pytest.mark.parametrize("mult", [0.25, 1.0])
@@ -1158,10 +1175,11 @@ def test_layer1_submit_host_sequenced(src_rate, fmt, block):
     ctx = W.MixContext(spec.n_tracks, max_blocks=5, block=block, group_size=32)
     for i, s in enumerate(spec.samples):
         ctx.clip_upload(i, s.fmt, s.rate, [np.ascontiguousarray(a[:s.frames]) for a in spec.sample_data(i)])
-    segs, offs, gains, masters, peaks = [], [0], [], [], []
+    segs, offs, gains, masters, peaks, tracks = [], [0], [], [], [], []
     for b in range(5):
-        m, _ = e.process()
+        m, _, tb = e.process_tracks()
         masters.append(m)
+        tracks.append(tb)
         peaks.append(e.peaks())
         log = e.seglog()
         per_track = {}
@@ -1175,6 +1193,7 @@ def test_layer1_submit_host_sequenced(src_rate, fmt, block):
     m, pk, _ = ctx.fetch(peaks=True)
     assert np.array_equal(pk, np.stack(peaks))
     assert rms(m, np.stack(masters)) <= RMS_TOL
+    GO.assert_grouped(m, np.stack(tracks), 32, what="submit")      # ... and groups of 32, bit for bit
     ctx.close()
     e.close()
 
@@ -1468,6 +1487,10 @@ def test_config5_32768_tracks_sharded_8way_on_one_gpu():
         eng.render(K)
         part, pk, _ = eng.ctx.fetch(peaks=True)
         assert np.array_equal(pk, opk[:, first:first + count, :spec.channels])
+        sspec = _shard_spec(spec, first, count)                 # (one device's share: the grouped order, un-clamped, bit for bit)
+        _, _, tracks = GO.oracle_tracks(sspec, K, clamp_master=False)
+        groups = GO.render_partition(sspec, eng.ctx.render_order(K), 0, K)
+        GO.assert_model(part, GO.grouped_sum(tracks, groups, do_clamp=False)[0], what=("shard", rank))
         total = (total + part).astype(np.float32)          # fp32 sum in rank order
         eng.close()
     clamped = np.where(total > 1.0, np.float32(1.0), np.where(total < -1.0, np.float32(-1.0), total))
@@ -1545,10 +1568,12 @@ def test_random_sessions_rendered_in_random_pieces(seed, monkeypatch):
     else:
         spec, total = FZ.random_masked_session(seed, integer_unity=kind == "integer", lean16=kind == "lean16", everything=kind == "everything")
     total += 3                                          # (... and a few blocks past the end of the last clip)
-    if spec.n_tracks > 128:
-        pytest.skip("more tracks than one group: the grouped order is compared elsewhere")
     om, opk, obus, _, otr = run_oracle(spec, total, want_buses=bool(spec.n_buses))
-    eng = build_engine(spec, max_blocks=24, group_size=max(spec.n_tracks, 1))
+    G = min(max(spec.n_tracks, 1), 128)
+    if spec.n_tracks > G:   # more tracks than a workgroup's group: every path in groups of 128, against the grouped-order model
+        _, _, tracks = GO.oracle_tracks(spec, total)
+        om, obus = GO.grouped_sum(tracks, GO.spec_partition(spec, G), spec.n_buses)
+    eng = build_engine(spec, max_blocks=24, group_size=G)
     eng.play()
     out = W.AudioBuffer(spec.block, spec.channels)
     done = 0
@@ -1653,12 +1678,13 @@ def test_random_pieces_with_controls_and_renders_in_flight(seed, monkeypatch):
             trail.append(("delete", t))
         mode = int(rng.integers(0, 3))
         k = 1 if mode == 0 else int(rng.integers(1, 8)) if mode == 1 else int(rng.integers(8, 25))
-        oms, opks, obus = [], [], []
+        oms, opks, obus, tracks = [], [], [], []
         for _ in range(k):
-            om, bu = e.process(want_buses=bool(spec.n_buses))
+            om, bu, tb = e.process_tracks(want_buses=bool(spec.n_buses))
             oms.append(om)
             opks.append(e.peaks())
             obus.append(bu)
+            tracks.append(tb)
         done += k
         if mode == 0 and rng.random() < 0.5:              # the audio callback itself (waits for its block), amid whatever is in flight
             eng.process(None, cb_out, float(spec.sample_rate))
@@ -1676,6 +1702,9 @@ def test_random_pieces_with_controls_and_renders_in_flight(seed, monkeypatch):
             bad = [b for b in range(k) if not np.array_equal(bits(m[b]), bits(oms[b]))]
         else:
             bad = [b for b in range(k) if rms(m[b], oms[b]) > RMS_TOL]
+            # ... and the groups of 16 of the tracks as they are now, bit for bit
+            bad += [("model", b) for b in range(k) if not GO.same_bits(
+                m[b], GO.grouped_sum(tracks[b], GO.partition(tracks[b].shape[0], 16))[0]).all()]
         badpk = [b for b in range(k) if not np.array_equal(pk[b], opks[b][:, :spec.channels])]
         badbus = [b for b in range(k) if spec.n_buses and not np.array_equal(bits(bus[b]), bits(obus[b]))]
         assert not bad and not badpk and not badbus, (seed, bad, badpk, badbus, trail[-6:], spec.block, spec.channels, spec.n_tracks)
@@ -1820,6 +1849,8 @@ def test_pipelined_renders_large():
     got = np.stack([o.cpu().numpy().reshape(K, spec.channels, spec.block) for o in outs]).reshape(K * R, spec.channels, spec.block)
     assert rms(got, om) <= RMS_TOL
     assert np.abs(got - om).max() < 1e-5
+    _, em = GO.oracle_model(spec, K * R, GO.render_partition(spec, eng.ctx.render_order(K), 0, K))
+    GO.assert_model(got, em, what="pipelined")
     _, pk, _ = eng.ctx.fetch(peaks=True)
     assert np.array_equal(pk, opk[-K:, :, :spec.channels])
     eng.ctx.set_master_target(None)
@@ -1992,6 +2023,7 @@ def check_masked_session(spec, n_blocks, seed):
     check_against_oracle(spec, n_blocks, group_size=gs, expect_exact=one_group and not spec.n_buses)
     if seed % 3 == 0:
         om, opk, _, _, _ = run_oracle(spec, n_blocks)
+        _, _, tracks = GO.oracle_tracks(spec, n_blocks)
         eng = build_engine(spec, max_blocks=1, group_size=gs)
         eng.play()
         out = W.AudioBuffer(spec.block, spec.channels)
@@ -2002,6 +2034,7 @@ def check_masked_session(spec, n_blocks, seed):
                 assert np.array_equal(bits(m), bits(om[b])), b
             else:
                 assert rms(m, om[b]) <= RMS_TOL
+            GO.assert_grouped(m, tracks[b], GO.group_size_of(spec.n_tracks, gs, 1), spec.n_buses, spec.track_bus, what=("masked", b))
             _, pk, _ = eng.ctx.fetch(peaks=True)
             assert np.array_equal(pk[0], opk[b][:, :spec.channels]), b
         eng.close()

@@ -11,6 +11,7 @@ master bit for bit in the reference's order."""
 import numpy as np
 import pytest
 
+import grouped_order as GO
 import oracle_ffi as O
 import whitebox_amd as W
 from whitebox_amd import synth
@@ -101,7 +102,7 @@ def test_callback_at_a_device_period_is_one_launch(block, channels, n_tracks):
     eng.play()
     names = []
     for b in range(K):
-        om, _ = e.process()
+        om, _, tracks = e.process_tracks()
         eng.process(None, out, float(spec.sample_rate))
         names.append(eng.ctx.kernel_name())
         m = np.stack(out.channel_buffers)
@@ -109,6 +110,9 @@ def test_callback_at_a_device_period_is_one_launch(block, channels, n_tracks):
             assert np.array_equal(P.bits(m), P.bits(om)), b
         else:
             assert P.rms(m, om) <= P.RMS_TOL, b
+        # ... and the callback's grouped order itself, bit for bit
+        em, _ = GO.grouped_sum(tracks, GO.spec_partition(spec, GO.callback_group(n_tracks)), spec.n_buses)
+        GO.assert_model(m, em, what=("ragged", block, channels, n_tracks, b))
         _, pk, _ = eng.ctx.fetch(peaks=True)
         assert np.array_equal(pk[0], e.peaks()[:, :channels]), b
         if n_tracks <= 300:
