@@ -508,8 +508,9 @@ class OracleEngine:
     def sample_position(self): return self.e.contents.sample_position
 
 
-def build_oracle_engine(spec) -> OracleEngine:
-    """Build a wbo_engine from a whitebox_amd.synth.SessionSpec through the restated reference API."""
+def build_oracle_engine(spec, sample_data=None) -> OracleEngine:
+    """Build a wbo_engine from a whitebox_amd.synth.SessionSpec through the restated reference API.  `sample_data`: the
+    planar arrays of every sample (tests/sparse_clip.py's for clips too long to hold), else spec.sample_data(i)."""
     eng = OracleEngine(spec.channels, spec.block, spec.sample_rate)
     eng.set_bpm(spec.bpm)
     if spec.playhead_start:
@@ -518,7 +519,8 @@ def build_oracle_engine(spec) -> OracleEngine:
         eng.set_buses(spec.n_buses)
     ids = []
     for i, s in enumerate(spec.samples):
-        ids.append(eng.add_sample(s.fmt, s.channels, s.rate, s.frames, spec.sample_data(i)))
+        ids.append(eng.add_sample(s.fmt, s.channels, s.rate, s.frames,
+                                  spec.sample_data(i) if sample_data is None else sample_data[i]))
     for t in range(spec.n_tracks):
         eng.add_track()
         eng.set_volume(t, spec.volumes_db[t])

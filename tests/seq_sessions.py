@@ -47,7 +47,10 @@ def _clip_args(rng, t, si, resample_ok, pos, length, frames):
 
 def session_script(seed, kind):
     """kind: 'static' (clip layouts only), 'controls' (transport / parameter / track operations between blocks), 'edits' (clip
-    adds into free space, deletes aimed at the sounding clip, gains, moves), 'dense' (back-to-back clips, edges on block edges)"""
+    adds into free space, deletes aimed at the sounding clip, gains, moves), 'dense' (back-to-back clips, edges on block edges),
+    'far' (the session past timeline frame 2^31 / 2^32: far_session_script)"""
+    if kind == "far":
+        return far_session_script(seed)
     rng = np.random.default_rng([seed, {"static": 1, "controls": 2, "edits": 3, "dense": 4, "wild": 5}[kind]])
     wild = kind == "wild"           # the corners of what the API accepts, all at once; otherwise an 'edits' script
     out_ch = int(rng.choice([1, 2, 2, 2]))
@@ -154,5 +157,72 @@ def session_script(seed, kind):
                 s.op("move", t, int(rng.integers(0, 4)), float(rng.choice([-1, 1])) * total * float(rng.uniform(0.5, 3)))
             else:
                 s.op("seek", float(rng.uniform(0, total))); s.op("stop"); s.op("play")
+        s.op("clips")
+    return s
+
+
+FAR_FRAMES = [2**31, 2**32, 2**33, 2**31 + 2**30]
+
+
+def far_session_script(seed):
+    """Clips placed, and the playhead set, past timeline frame 2^31 and 2^32 (and 2^33), at several tempos and rates: the
+    transport, the block windows and the clip time -> frame conversions with large beat and sample positions.  Between runs:
+    seeks to other far landmarks (also just in front of a clip), tempo changes, stop / play, clip deletes, gains, adds far ahead
+    and moves.  Its own generator stream: the scripts of the other kinds do not change."""
+    global RATES, SPEEDS
+    RATES, SPEEDS = PLAIN_RATES, PLAIN_SPEEDS
+    rng = np.random.default_rng([seed, 6])
+    block = int(rng.choice([64, 128, 256, 512, 1000, 1024]))
+    rate = int(rng.choice([44100, 48000, 96000]))
+    bpm = float(rng.choice([120.0, 97.0, 140.5, 61.3, 174.0, 20.0, 999.0]))
+    s = R.Script(2, block, rate, bpm)
+    n_tracks = int(rng.integers(1, 6))
+    n_blocks = int(rng.integers(6, 20))
+    beat_frames = rate * 60.0 / bpm
+    unit = block / beat_frames
+    total = n_blocks * unit
+    resample_ok = _samples(rng, s, 0x5EA0000 + seed, n_tracks, rate, 2, stereo_only=True)
+    for t in range(n_tracks):
+        s.op("track")
+        s.op("vol", t, float(np.float32(rng.uniform(-30, 3))))
+        s.op("pan", t, float(np.float32(rng.uniform(-1, 1))))
+    # the landmark, a fraction of a block off it, as a beat position
+    base = (float(rng.choice(FAR_FRAMES)) + float(rng.uniform(-3, 3)) * block) / beat_frames
+    for t in range(n_tracks):
+        si = int(rng.integers(0, n_tracks))
+        frames = s.samples[si][3]
+        pos = base + total * float(rng.uniform(-0.2, 0.3))
+        for _ in range(int(rng.integers(1, 4))):
+            length = total * (0.02 + 0.5 * rng.random())
+            s.op(*_clip_args(rng, t, si, resample_ok[si], pos, length, frames))
+            pos += length + (0.0 if rng.random() < 0.3 else total * 0.1 * rng.random())
+    s.op("seek", base + float(rng.choice([0.0, -0.5 * unit, total * 0.1])))
+    s.op("play")
+    done = 0
+    while done < n_blocks:
+        k = int(rng.integers(1, 4))
+        s.op("run", k)
+        done += k
+        op = int(rng.integers(0, 8))
+        t = int(rng.integers(0, n_tracks))
+        if op == 0:          # to another landmark, just in front of the session's clips there
+            far = (float(rng.choice(FAR_FRAMES)) - float(rng.uniform(0, 2)) * block) / beat_frames
+            s.op("seek", float(rng.choice([far, base + total * float(rng.uniform(0, 0.5))])))
+        elif op == 1:
+            s.op("bpm", float(rng.choice([120.0, 90.0, 133.3, 200.0])))
+        elif op == 2:
+            s.op("stop"); s.op("play")
+        elif op == 3:
+            s.op("delclip", t, int(rng.integers(0, 3)))
+        elif op == 4:
+            s.op("gain", t, int(rng.integers(0, 3)), float(np.float32(rng.uniform(0.0, 1.5))))
+        elif op == 5:        # a clip far ahead: free space
+            si = int(rng.integers(0, n_tracks))
+            mn = base + total * float(rng.uniform(1.5, 3.0))
+            s.op(*_clip_args(rng, t, si, resample_ok[si], mn, unit * float(rng.uniform(0.3, 4)), s.samples[si][3]))
+        elif op == 6:
+            s.op("move", t, int(rng.integers(0, 3)), float(rng.choice([-1, 1])) * total * float(rng.uniform(0.5, 3)))
+        else:
+            s.op("seek", base + total * float(rng.uniform(0, 0.6)))
         s.op("clips")
     return s

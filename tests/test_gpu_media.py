@@ -192,3 +192,96 @@ def test_ingest_matches_the_reference_fixture():
         ctx.close()
         n += 1
     assert n == 36
+
+
+@pytest.mark.parametrize("fmt", ["i16", "f32"])
+def test_mipmaps_above_level_9(fmt):
+    """a 2^28+3-frame mono clip: 11 levels, both qualities, every level against the oracle — f32 salted with NaN, ±Inf and
+    values beyond [-1, 1] near its start, middle and end"""
+    frames = 2**28 + 3
+    a = make_pcm(fmt, frames, 1, 28 + len(fmt))
+    if fmt == "f32":
+        for at in (0, frames // 2, frames - 64):
+            a[at:at + 64, 0] = special_values(fmt, a[at:at + 64, 0].copy())[:64]
+            a[at + 30, 0] = -np.inf
+    ctx = W.MixContext(4)
+    try:
+        ctx.clip_upload_interleaved(0, fmt, 48000, a)
+        col = np.ascontiguousarray(a[:, 0])
+        del a
+        levels = ctx.L.wbx_mip_levels(frames)
+        assert levels == O.oracle_mip_levels(frames) == 11
+        for quality in (0, 1):
+            ctx.build_mipmaps(0, quality)
+            for lvl in range(levels):
+                got = ctx.fetch_mipmap(0, lvl, 1, frames, quality)[0]
+                exp = O.oracle_mip(fmt, col, lvl, quality)
+                assert np.array_equal(got, exp), (fmt, quality, lvl, np.flatnonzero(got != exp)[:8])
+    finally:
+        ctx.close()
+
+
+class _DeviceArray:
+    """a device allocation of the library's, seen by torch (__cuda_array_interface__) so that a slice of it can be copied"""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
+
+
+def device_level(ctx, clip, level, dtype):
+    """(torch view of mip-map level `level` on the device, element count): slices of a level without fetching all of it"""
+    import ctypes as C
+    import torch
+    p, n = C.c_void_p(), C.c_uint64()
+    assert ctx.L.wbx_clip_mipmap_device(ctx.h, clip, level, C.byref(p), C.byref(n)) == 0
+    return torch.as_tensor(_DeviceArray(p.value, n.value, np.dtype(dtype).str), device="cuda"), n.value
+
+
+@pytest.mark.parametrize("fmt", ["i16", "f32"])
+def test_mipmaps_of_the_longest_clip(fmt):
+    """a 2^31-17-frame mono clip (the longest the ABI accepts; made on the device): 13 levels, both qualities.  Too long for a
+    host oracle of every level: per level the pairs of the first 2^20 samples and of the last 2^20 (each stretch widened to a
+    whole chunk of the level, and the last one started on a chunk boundary so the chunks line up) against oracle_mip, every
+    level's length, and the ordered-merge property between levels 2..12 — a pair is the ordered merge of the four below it"""
+    import torch
+    from sparse_clip import CAP
+    seed, key, amp = 0x313, 2, 0.9
+    A = ((CAP - 2**20) >> 25) << 25                      # a chunk boundary of level 12 (2^25 samples a pair)
+    gen = synth.clip_channel if fmt == "f32" else synth.clip_channel_i16
+    kw = {"amp": amp} if fmt == "f32" else {}
+    head = gen(seed, key, 0, 2**25, first=0, **kw)
+    tail = gen(seed, key, 0, CAP - A, first=A, **kw)
+    ctx = W.MixContext(4)
+    try:
+        ctx.clip_synth(0, fmt, 1, 48000, CAP, seed, key, amp)
+        levels = ctx.L.wbx_mip_levels(CAP)
+        assert levels == O.oracle_mip_levels(CAP) == 13
+        for quality in (0, 1):
+            dt = np.int16 if quality else np.int8
+            ctx.build_mipmaps(0, quality)
+            torch.cuda.synchronize()
+            prev = None
+            for lvl in range(levels):
+                dev, n = device_level(ctx, 0, lvl, dt)
+                assert n == O.lib().wbo_mip_data_count(CAP, lvl)
+                chunk = 2 << (2 * lvl)                   # samples a pair of this level summarises
+                h = max(2**20, chunk)
+                a = ((CAP - 2**20) // chunk) * chunk
+                eh = O.oracle_mip(fmt, head[:h], lvl, quality)
+                et = O.oracle_mip(fmt, tail[a - A:], lvl, quality)
+                off = a >> (2 * lvl)
+                assert off + len(et) == n
+                assert np.array_equal(dev[:len(eh)].cpu().numpy(), eh), (fmt, quality, lvl, "head")
+                assert np.array_equal(dev[off:].cpu().numpy(), et), (fmt, quality, lvl, "tail")
+                if lvl >= 2:
+                    got = dev.cpu().numpy()
+                    if prev is not None:
+                        k = min(len(got) // 2, len(prev) // 8)
+                        lo = prev[:k * 8].reshape(k, 8)
+                        assert np.array_equal(got[:2 * k].reshape(k, 2).min(axis=1), lo.min(axis=1)), (fmt, quality, lvl)
+                        assert np.array_equal(got[:2 * k].reshape(k, 2).max(axis=1), lo.max(axis=1)), (fmt, quality, lvl)
+                    prev = got
+                del dev
+    finally:
+        ctx.close()
+        torch.cuda.empty_cache()

@@ -126,7 +126,7 @@ def test_product_equals_the_reference_recordings(batch):
     assert n >= 28 and blocks > 350, (n, blocks)
 
 
-@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild"])
+@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild", "far"])
 def test_product_equals_the_live_reference(kind):
     """the same comparison against the reference executable itself where it travelled with the tree (oracle/_ref/wbref_engine is a
     prebuilt test artefact like liboracle.so; nothing of /root/reference is read): fresh seeds, scripts of tests/seq_sessions.py

@@ -419,7 +419,7 @@ def test_host_sequencer_on_the_reference_recordings():
 
 
 @pytest.mark.ref
-@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild"])
+@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild", "far"])
 def test_host_sequencer_against_the_live_reference(kind):
     """the same against the reference executable itself (this container): fresh seeds of tests/seq_sessions.py.  WBX_REFSEQ_SEEDS
     widens the range."""

@@ -344,3 +344,123 @@ def test_perf_measurer_and_block_period_bit_exact(oracle, reflib):
     for rate in (8000, 11025, 22050, 32000, 44100, 48000, 88200, 96000, 176400, 192000):
         for size in range(4, 4097, 4):
             assert oracle.f64_bits(L.wbo_buffer_duration_ms(size, rate)) == oracle.f64_bits(reflib.ref_buffer_duration_ms(size, rate)), (size, rate)
+
+
+# ---- positions far into a clip: the sampler's index math up to the longest clip the ABI accepts --------------------------
+LANDMARKS = (2**24, 2**30, 2147483000)      # fp32-exact frame indices end; 2^30; classify's hot-path position bound
+
+
+def _ref_vs_oracle_calls(oracle, reflib, fmt, channels, count, data, start, speed, lengths, what):
+    """stream calls of `lengths` frames from `start` at playback speed `speed` (src rate == dst rate), oracle vs reference:
+    sample_offset_ bits after every call and every output sample's bits"""
+    s = oracle.OracleSampler(fmt, channels, 48000, count, data)
+    s.reset(start, speed, 48000)
+    ps, so = C.c_double(), C.c_double()
+    reflib.ref_sampler_reset(C.byref(ps), C.byref(so), start, speed, 48000.0, 48000.0)
+    assert (ps.value, so.value) == (s.state.playback_speed, s.state.sample_offset)
+    ptrs = O.void_ptrs(data)
+    outs = []
+    for it, n in enumerate(lengths):
+        played = _frames_played(count, s.state.sample_offset, s.state.playback_speed, n)
+        a = [np.zeros(max(n, 1), np.float32) for _ in range(channels)]
+        b = [np.zeros(max(n, 1), np.float32) for _ in range(channels)]
+        s.stream(a, n, 0, np.float32(0.75))
+        reflib.ref_sampler_stream(C.byref(ps), C.byref(so), O.FMT[fmt], channels, 48000, count, C.cast(ptrs, O.c_voidpp),
+                                  channels, n, 0, np.float32(0.75), O.planar_ptrs(b))
+        assert O.f64_bits(so.value) == O.f64_bits(s.state.sample_offset), (what, it)
+        for c in range(channels):
+            assert np.array_equal(a[c].view(np.uint32), b[c].view(np.uint32)), (what, it, c, np.flatnonzero(a[c] != b[c])[:8])
+            # both read the same sparse array: a read outside the filled stretch would show as zeros in both
+            assert np.count_nonzero(a[c][:played]) >= played - 2 and not a[c][played:n].any(), (what, it, c, played)
+        outs.append(a)
+    return outs
+
+
+def _frames_played(count, off, speed, n):
+    """min(num_samples, (uint32_t)ceil((count - offset) / speed)) (sampler.cpp:99-104), the low word of the quotient"""
+    import math
+    if off >= count:
+        return 0
+    q = math.ceil((count - off) / speed)
+    return min(n, q & 0xFFFFFFFF if q < 2**63 else 0)
+
+
+LARGE_SPEEDS = (1.0, 0.5, 44100 / 48000, 0.999999, 1.088, 1.3333333333333333, 1.75, 2.0, 3.7, 4096.0, 4097.0)
+
+
+def _large_starts(count, speed, F):
+    """just below / above each landmark (integer and fractional), and blocks that end at the clip's last frames — one whose
+    last frame's right tap is the first padding frame (ix + 1 == count), one cut short by the tail limit"""
+    out = []
+    for L in LANDMARKS:
+        if L + 8 < count:
+            out += [L - 1.0, L - 0.25, float(L), L + 0.5, L - F * speed - 0.75]
+    out += [count - 1.0 - (F - 1) * speed, count - 0.5 - (F - 1) * speed, count - (F // 2) * speed, count - 1.0]
+    return [x for x in out if 0.0 <= x < count]
+
+
+@pytest.mark.parametrize("fmt", ["f32", "i16", "i24", "i32"])
+def test_sampler_stream_bit_exact_at_large_positions(oracle, reflib, fmt):
+    """Sampler::stream of a mono clip of 2^31-17 frames — the longest the ABI accepts — against the reference's compiled
+    sampler at positions around 2^24, 2^30 and 2147483000 and at the clip's last frames, unity and linear paths, speeds up to
+    4097 frames per frame.  The clip is a sparse host array: only the stretch a case reads holds data, the rest reads 0, so
+    every played frame must come out non-zero; the resident memory the test adds stays small."""
+    from sparse_clip import CAP, clear, fill, rss_bytes, sparse_sample_data
+    rss0 = rss_bytes()
+    spec = synth.SampleSpec(seed_track=3, channels=1, rate=48000, frames=CAP, fmt=fmt, amp=0.7)
+    data = sparse_sample_data(0xABCD, spec, [])
+    F = 512
+    n_cases = 0
+    for speed in LARGE_SPEEDS:
+        for start in _large_starts(CAP, speed, F):
+            clear(data[0])
+            lo = int(start) - 2
+            hi = int(start + (2 * F + 1) * speed) + 3
+            fill(data[0], 0xABCD, spec, 0, [(lo, hi)])
+            assert data[0][CAP:].tolist() == [0] * 16
+            _ref_vs_oracle_calls(oracle, reflib, fmt, 1, CAP, data, start, speed, [F, F - 1, 3], (fmt, speed, start))
+            n_cases += 1
+    assert n_cases > 150
+    clear(data[0])
+    assert rss_bytes() - rss0 < 256 << 20
+
+
+def test_sampler_stream_bit_exact_stereo_i16_at_2_30(oracle, reflib):
+    """a 2^30+3-frame 16-bit stereo clip: both channels at positions past 2^30 and at the clip's end"""
+    from sparse_clip import clear, fill, sparse_sample_data
+    count = 2**30 + 3
+    spec = synth.SampleSpec(seed_track=5, channels=2, rate=48000, frames=count, fmt="i16")
+    data = sparse_sample_data(0x5151, spec, [])
+    for speed in (1.0, 44100 / 48000, 1.088, 4096.0):
+        for start in [2**30 - 600.0, 2**30 - 1.5, count - 1.0 - 511 * speed, count - 2.0]:
+            if start < 0:
+                continue
+            for c in range(2):
+                clear(data[c])
+                fill(data[c], 0x5151, spec, c, [(int(start) - 2, int(start + 1025 * speed) + 3)])
+            _ref_vs_oracle_calls(oracle, reflib, "i16", 2, count, data, start, speed, [512, 512], (speed, start))
+
+
+@pytest.mark.parametrize("fmt", ["f32", "i16", "i32"])
+@pytest.mark.parametrize("count,speed,k", [(5_000_000, 1e-3, 1), (5_000_000, 2.5e-4, 2), (5_000_000, 1e-4, 11),
+                                           (2**31 - 17, 1e-3, 1), (2**31 - 17, 2e-5, 24), (2**31 - 17, 0.25, 1)])
+def test_sampler_tail_quotient_crossing_2_32(oracle, reflib, fmt, count, speed, k):
+    """At a slow playback speed (count - offset) / speed passes k * 2^32 with an ordinary clip and offset, and
+    (uint32_t)std::ceil(...) (sampler.cpp:104) keeps its low word: a block whose quotient is k * 2^32 + r plays r frames
+    (silent at r = 0) and still advances by the whole block.  Crossings at frames 0, 1, F/2 and F-1 of the block, then the
+    blocks after it; whatever the compiled reference does is the answer."""
+    from long_sessions import offset_with_quotient
+    from sparse_clip import clear, fill, sparse_sample_data
+    F = 512
+    spec = synth.SampleSpec(seed_track=9, channels=1, rate=48000, frames=count, fmt=fmt, amp=0.6)
+    data = sparse_sample_data(0x2032, spec, [])
+    for r in (0, 1, F // 2, F - 1, F, F + 1):
+        start = offset_with_quotient(count, speed, k * 2**32 + r)
+        if not (0 <= start < count):
+            continue
+        clear(data[0])
+        fill(data[0], 0x2032, spec, 0, [(int(start) - 2, int(start + 4 * F * speed) + 3)])
+        outs = _ref_vs_oracle_calls(oracle, reflib, fmt, 1, count, data, start, speed, [F, F, F], (fmt, r))
+        # the first block plays r frames of it (the low word), or all F when r >= F
+        played = np.flatnonzero(outs[0][0])
+        assert (played.max() + 1 if played.size else 0) <= min(r, F)

@@ -42,7 +42,7 @@ def _differential(kind, seeds):
     return compared, wrapped, blocks
 
 
-@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild"])
+@pytest.mark.parametrize("kind", ["static", "controls", "edits", "dense", "wild", "far"])
 def test_oracle_sequencer_equals_the_reference(exe, kind):
     compared, wrapped, blocks = _differential(kind, range(FROM, FROM + N))
     assert compared >= N * (0.5 if kind in ("dense", "wild") else 0.8), (compared, wrapped)
