@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the whitebox mix path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
       N>1: either launched one rank per GPU by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the
       environment), or run plainly — bench.py then starts the N ranks itself.
 
 A "step" is one device pass of the hot path (clip sequencer + per-track render/gain/pan/resample +
 peaks + group/bus/master sum + clamp) over one batch of `--blocks` consecutive 512-frame blocks (default 2048: the
 tracks of every block are added in the reference's strictly sequential order) of a synthetic session that is already
-resident in HBM.  After the timed loop the head of one more step is checked against the CPU oracle (`verify`).  The default workload is BASELINE.json configs[2]
+resident in HBM.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line, nothing else.
+With --full the run goes on: the head of one more step is checked against the CPU oracle (`verify`), the K = 1 callback
+is timed (`latency_mode`), the other configurations run (`configs`) and the CPU baselines are timed (`cpu_baseline`);
+the --no-* options leave parts of that out.  The default workload is BASELINE.json configs[2]
 ("4096 stereo tracks, gain+pan + linear clip resample (44.1->48 kHz), 1 MI355X") — the configuration the
 metric "…4096 tracks @ 512-frame blocks" is quoted on.  With N GPUs every rank mixes its own 4096 tracks
 (weak scaling = configs[4]: 32768 tracks sharded 8-way) and the un-clamped partial masters are reduced
@@ -796,9 +799,14 @@ def main():
                     "are side measurements)")
     ap.add_argument("--session-blocks", type=int, default=0, help="length of the resident session in blocks "
                     "(0 = as long as the run needs, capped by memory); the transport rewinds at its end")
+    ap.add_argument("--full", action="store_true", help="after the headline run, everything else the line can report: the "
+                    "check of one more step against the CPU oracle, the K=1 latency mode, the short runs of the other "
+                    "configurations and the CPU baselines (a plain run does none of them; the --no-* options below and "
+                    "--latency-blocks 0 leave parts out)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--latency-blocks", type=int, default=800, help="K=1 Engine::process calls timed after the run (per session size)")
+    ap.add_argument("--latency-blocks", type=int, default=800, help="with --full: K=1 Engine::process calls timed after the run "
+                    "(per session size)")
     ap.add_argument("--force-dist-path", action="store_true",
                     help="run the multi-GPU code path (RCCL exchange + clamp on root) even with one rank")
     ap.add_argument("--dist-mode", default="auto", choices=["auto", "reduce", "ordered", "chain"],
@@ -808,10 +816,10 @@ def main():
                     "reduce / ordered add SHARD sums: within 1e-6 RMS up to about half of full scale (profiles/r03_level_probe.txt)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: BASELINE configs[4]'s 32768 tracks split over "
                     "the N ranks (default: weak scaling, 4096 tracks per GPU)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of the other single-GPU configurations "
-                    "(c2, c4, c3 cut into clips, i16r, the sustained run) that fill the line's `configs` object")
-    ap.add_argument("--no-verify", action="store_true", help="skip the check of the rendered step against the CPU oracle "
-                    "(after the timed loop, outside the timed region)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the short runs of the other single-GPU "
+                    "configurations (c2, c4, c3 cut into clips, i16r, the sustained run) that fill the line's `configs` object")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the check of the rendered step against the CPU "
+                    "oracle (after the timed loop, outside the timed region)")
     ap.add_argument("--no-verify-tail", action="store_true", help="compare only the first 8 blocks of the verified step with the "
                     "oracle (default: also one block per 256 and the last 8 — the oracle's tracks run sharded over the host's "
                     "cores between compared blocks, a few seconds per configuration)")
@@ -859,10 +867,11 @@ def main():
         os.environ["NCCL_DEBUG"] = "INFO"          # (whatever level the environment asked for: the connection lines are INFO)
         os.environ["NCCL_DEBUG_SUBSYS"] = "INIT,P2P,SHM,NET"
         os.environ["NCCL_DEBUG_FILE"] = rccl_log_path(rank)
+    # a plain run stops after the timed steps (and --dump-outputs); the check against the oracle and the latency mode are --full's
     r = run_workload(W, synth, args, args.workload, rank, world, n_tracks=n_tracks, K=K, steps=args.steps,
                      warmup=args.warmup, ramp=ramp, clip_blocks=args.clip_blocks, use_dist=use_dist,
-                     dist_mode=dist_mode, latency_blocks=args.latency_blocks, verify=not args.no_verify, verify_tail=not args.no_verify_tail,
-                     dump_dir=args.dump_outputs)
+                     dist_mode=dist_mode, latency_blocks=args.latency_blocks if args.full else 0,
+                     verify=args.full and not args.no_verify, verify_tail=not args.no_verify_tail, dump_dir=args.dump_outputs)
     # every rank says what it ran on (stderr: stdout carries rank 0's one JSON line).  One write of the whole line: the ranks
     # share the pipe, and an unbuffered stderr (PYTHONUNBUFFERED) would let print's separate newline interleave with another rank's
     sys.stderr.flush()
@@ -936,7 +945,7 @@ def main():
     # clips, the 16-bit resampled session, the round-2 operating point (256-block renders, grouped order) and a
     # sustained run: each with its own roofline from its own HIP-event kernel times, each checked against the oracle
     failed = [] if (ver is None or ver["ok"]) else ["headline"]
-    if world == 1 and not use_dist and not args.no_configs and args.workload == "c3" and not args.clip_blocks and F == 512:
+    if args.full and world == 1 and not use_dist and not args.no_configs and args.workload == "c3" and not args.clip_blocks and F == 512:
         subs = {}
         for name, wl, kw in (("c2", "c2", dict(n_tracks=256)), ("c4", "c4", dict(n_tracks=4096)),
                              ("c3_clips5.3", "c3", dict(n_tracks=4096, clip_blocks=5.3)),
@@ -962,7 +971,7 @@ def main():
         # the full entries: their own JSON line on stderr (tools/profile_round.sh keeps it); the stdout line carries the compact form
         print(json.dumps({"configs_full": subs}), file=sys.stderr, flush=True)
         line["configs"] = {k: compact_entry(v) for k, v in subs.items()}
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.workload, n_tracks, args.cpu_seconds)
     # the headline once more at the very END of the line: a reader that keeps only the tail of a long line still sees it
     rf = line["roofline"]

@@ -101,7 +101,7 @@ def test_bench_multi_gpu_launch_paths():
     for mode in ("reduce", "ordered", "chain"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--blocks", "64", "--steps", "6",
                             "--warmup", "1", "--ramp-steps", "4", "--force-dist-path", "--dist-mode", mode,
-                            "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, env=env, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, env=env, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1, r.stdout[-2000:]                  # ONE JSON line on stdout, nothing of RCCL's banner
@@ -122,7 +122,7 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
     lines = {}
     for name, warmup, steps in (("a", 1, 3), ("b", 2, 2)):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--blocks", "64", "--steps", str(steps),
-                            "--warmup", str(warmup), "--ramp-steps", "2", "--no-cpu-baseline", "--no-configs", "--latency-blocks", "0",
+                            "--warmup", str(warmup), "--ramp-steps", "2", "--full", "--no-cpu-baseline", "--no-configs", "--latency-blocks", "0",
                             "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines[name] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -133,6 +133,30 @@ def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
         assert np.array_equal(bits(a), bits(b)), f
     m = np.load(tmp_path / "a" / "master.npy")
     assert 0.0 < np.abs(m).max() <= 1.0 and np.abs(m).max() == lines["a"]["master_peak"]
+
+
+def test_a_plain_bench_run_stops_after_its_steps(tmp_path):
+    """bench.py without --full: the headline's line and --dump-outputs, none of the check against the oracle, the latency
+    mode or the CPU baseline; --full adds them after the same timed steps, which dump the same master and peaks"""
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--latency-blocks", "16", "--cpu-seconds", "0.5"])):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c2", "--blocks", "64", "--steps", "3",
+                            "--warmup", "1", "--ramp-steps", "2", "--dump-outputs", str(tmp_path / name)] + extra,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "ramp_steps"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["kernel_launches"] == 3
+    assert not {"verify", "latency_mode", "configs", "cpu_baseline"} & set(plain)
+    assert plain["headline"]["verify_ok"] is None and plain["headline"]["configs_failed"] == []
+    assert full["verify"]["ok"] and full["headline"]["verify_ok"] is True
+    assert full["latency_mode"]["calls"] == 16 and full["cpu_baseline"]["value"] > 0
+    for f in ("master", "peaks"):
+        assert np.array_equal(bits(np.load(tmp_path / "plain" / f"{f}.npy")), bits(np.load(tmp_path / "full" / f"{f}.npy"))), f
 
 
 @pytest.mark.parametrize("world", [2, 4])
@@ -149,7 +173,7 @@ def test_ranks_that_share_the_device_exchange_over_rccl(world):
     for mode in ("reduce", "ordered", "chain"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--dist-mode", mode, "--tracks", "1024",
                             "--blocks", "64", "--session-blocks", "256", "--steps", "4", "--warmup", "1", "--ramp-steps", "2",
-                            "--no-cpu-baseline", "--no-configs", "--latency-blocks", "0"]
+                            "--full", "--no-cpu-baseline", "--no-configs", "--latency-blocks", "0"]
                            # (a render of 64 blocks adds 128-track groups; one group per rank = the reference's order inside a rank)
                            + (["--group-size", "1024"] if mode == "chain" else []),
                            capture_output=True, text=True, env=env, timeout=600)

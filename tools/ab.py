@@ -4,7 +4,7 @@
     python tools/ab.py PRESET [-r REPEATS] [-o OUT.jsonl]
     python tools/ab.py run "<label>;<ENV=1 ENV2=2>;<bench args>" ...      ad-hoc cases
 
-Every case is one `python bench.py <args> --no-cpu-baseline --no-configs` (+ `--latency-blocks 0` unless the case
+Every case is one `python bench.py <args> --full --no-cpu-baseline --no-configs` (+ `--latency-blocks 0` unless the case
 measures the callback path) with the given environment; cases are interleaved REPEATS times (A B A B, not A A B B) so
 that drift of the box hits both sides.  One summary line per run; `-o` appends the raw bench lines (with the label).
 
@@ -120,7 +120,7 @@ def run_case(c, out):
     for kv in c["env"].split():
         k, v = kv.split("=", 1)
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + c["args"].split() + ["--no-cpu-baseline", "--no-configs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + c["args"].split() + ["--full", "--no-cpu-baseline", "--no-configs"]
     if "--verify" in cmd:
         cmd.remove("--verify")      # (a case may ask for the oracle check of the rendered head; sweeps skip it)
     else:

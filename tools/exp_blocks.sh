@@ -5,7 +5,7 @@
 # usage (GPU box): tools/exp_blocks.sh [tag] -> gpurun_out/<tag>/
 set -u
 O=gpurun_out/${1:-r05_blocks}; mkdir -p $O
-B="--no-cpu-baseline --no-configs --latency-blocks 0"
+B="--full --no-cpu-baseline --no-configs --latency-blocks 0"
 for F in 480 416 960 448 320 1440; do
   timeout 300 python bench.py --block-frames $F $B > $O/bench_c3_F$F.json 2>> $O/err.log
   timeout 300 python bench.py --block-frames $F --clip-blocks 5.3 $B > $O/bench_c3_F${F}_L5.3.json 2>> $O/err.log

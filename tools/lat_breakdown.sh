@@ -1,8 +1,9 @@
 #!/bin/bash
 # per-kernel durations of the one-block callback path for a given track-group size
 G=${1:-64}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp; export TMPDIR=/tmp; rm -rf /tmp/lat; mkdir -p /tmp/lat
-rocprofv3 --kernel-trace -d /tmp/lat -o lat -- python $GRAFT_REPO_ROOT/bench.py --group-size $G --steps 2 --warmup 1 --ramp-steps 2 --no-cpu-baseline --no-configs --latency-blocks 400 > /tmp/lat/bench.log 2>&1
+rocprofv3 --kernel-trace -d /tmp/lat -o lat -- python $R/bench.py --group-size $G --steps 2 --warmup 1 --ramp-steps 2 --full --no-cpu-baseline --no-configs --latency-blocks 400 > /tmp/lat/bench.log 2>&1
 grep "^{" /tmp/lat/bench.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('group=$G latency %.4f ms/block' % d['latency_mode']['ms_per_block'])"
 python - <<PY
 import sqlite3, glob, collections

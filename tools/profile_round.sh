@@ -12,8 +12,8 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 timeout 900 python -m pytest tests -m gpu -q -n 4 > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
-B="--no-cpu-baseline --no-configs"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
+B="--full --no-cpu-baseline --no-configs"
 for W in c4 c2 u4096 i16 i16r i24r d96 mixfmt mixr; do
   timeout 300 python bench.py --workload $W $B > $O/bench_$W.json 2>> $O/bench_default.err
 done
