@@ -407,9 +407,62 @@ wbx_status wbx_engine_process(wbx_engine* e, float* const* out_planar);
  * core/audio_format_conv.cpp:5-91): dst receives the block as F*C interleaved samples of `out_format` (WBX_OUT_*), the
  * conversion running as the epilogue of the sum kernel — one launch fewer than process + wbx_fetch_interleaved. */
 wbx_status wbx_engine_process_interleaved(wbx_engine* e, int out_format, void* dst);
+/* Engine::process(input_buffer, output_buffer, sample_rate) with its input buffer (engine.cpp:1576, the recorder tap
+ * :1638-1649): in_planar[c][0..F) for c < n_in_channels.  Without a take running the input is not read (no monitoring:
+ * engine.cpp:1625 leaves it out of the master); wbx_engine_process / _interleaved during a take record silence. */
+wbx_status wbx_engine_process_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels, float* const* out_planar);
+wbx_status wbx_engine_process_interleaved_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels,
+                                             int out_format, void* dst);
 /* K consecutive blocks in one device pass (render-ahead / offline): sequencing, mixing, summing and
- * clamping all on the device.  Asynchronous; results via wbx_fetch(wbx_engine_ctx(e), ...). */
+ * clamping all on the device.  Asynchronous; results via wbx_fetch(wbx_engine_ctx(e), ...).
+ * Refused (WBX_ERR_UNSUPPORTED) while recording. */
 wbx_status wbx_engine_render(wbx_engine* e, uint32_t n_blocks);
+
+/* ---- recording: Engine::record / stop_record / arm_track_recording / set_track_input (engine.cpp:95-200),
+ * Track::prepare_record / stop_record (track.cpp:234-246).  Takes live in HBM from the first frame: every played block's
+ * input is captured on the device into chunks of the clip pool, and stop_record gathers each take into one clip.
+ * TrackInputType (track_input.h:10-15); MIDI input is refused (WBX_ERR_UNSUPPORTED). */
+enum { WBX_INPUT_NONE = 0, WBX_INPUT_MIDI = 1, WBX_INPUT_EXTERNAL_STEREO = 2, WBX_INPUT_EXTERNAL_MONO = 3 };
+/* a take's status bits (wbx_record_info.status) */
+enum {
+  WBX_RECORD_OVERFLOW = 1,   /* some block found no room (or its staging slot busy): its frames are silence in the take */
+  WBX_RECORD_SILENCE = 2     /* some block came through a process call without (all of) the recorded input channels */
+};
+/* the input_channels argument of Engine::set_audio_channel_config (engine.cpp:43-48; num_input_channels): the highest
+ * input channel a track may record is input_channels - 1 (checked at wbx_engine_record).  Default 0. */
+wbx_status wbx_engine_set_input_channels(wbx_engine* e, uint32_t input_channels);
+/* Engine::set_track_input (engine.cpp:145-198).  ExternalMono index i records input channel i, ExternalStereo index i
+ * channels 2i and 2i+1 (engine.cpp:1642-1643); several tracks may share an input, each gets its own copy of the take.
+ * Changes during a take take effect at the next wbx_engine_record. */
+wbx_status wbx_track_set_input(wbx_engine* e, uint32_t track, int type, uint32_t index, int armed);
+wbx_status wbx_engine_arm_track_recording(wbx_engine* e, uint32_t track, int armed);   /* engine.cpp:140-143 */
+/* Engine::record (engine.cpp:95-105): nothing while recording and playing; otherwise recording starts and play() runs —
+ * every armed track with an input starts a take at playhead_start (the transport restarts from there also when it was
+ * already running, as in the reference).  WBX_ERR_UNSUPPORTED on a redirected master / multi-GPU context,
+ * WBX_ERR_INVALID when an armed track's input lies past wbx_engine_set_input_channels. */
+wbx_status wbx_engine_record(wbx_engine* e);
+/* Engine::stop_record (engine.cpp:107-138): each take becomes an F32 sample at the session rate (1 or 2 channels, the
+ * frames written) and a clip add_audio_clip(track, record_min_time, record_max_time, 0.0, sample, speed 1.0, gain 1.0f)
+ * puts on its track (overlap trimming included); a take of no frames adds nothing.  Playback continues.  Returns
+ * WBX_ERR_OVERFLOW (clips still made) when a take has WBX_RECORD_OVERFLOW.  wbx_engine_stop calls it first
+ * (engine.cpp:83-84).  Deleting a recording track (or wbx_engine_clear_all) discards its take. */
+wbx_status wbx_engine_stop_record(wbx_engine* e);
+wbx_status wbx_engine_is_recording(wbx_engine* e, int* recording);
+typedef struct wbx_record_info {
+  int32_t recording;          /* Track::input_attr.recording */
+  int32_t armed;              /* input_attr.armed */
+  int32_t input_type;         /* WBX_INPUT_* */
+  uint32_t input_index;
+  double min_time, max_time;  /* record_min_time / record_max_time (track.h:100-101; 0 when not recording) */
+  uint64_t frames;            /* frames written into the track's latest take (running or finished) */
+  uint32_t status;            /* WBX_RECORD_* of that take */
+  uint32_t _pad;
+} wbx_record_info;
+wbx_status wbx_engine_record_info(wbx_engine* e, uint32_t track, wbx_record_info* out);
+/* Take storage: chunks of `frames` frames (default 65536, audio_record_chunk_size / 4, engine.h:36); the engine's
+ * recorder thread keeps `spare_chunks` (default 2) chunks ahead of every take's write position (wbx_engine_record
+ * reserves the first ones).  Not while recording. */
+wbx_status wbx_engine_set_record_chunk(wbx_engine* e, uint32_t frames, uint32_t spare_chunks);
 /* Transport after the last process/render (engine.h:44-46), for bit-exact checks. */
 wbx_status wbx_engine_transport(wbx_engine* e, double* playhead, double* sample_position, int* playing);
 /* VUMeter::level per track/channel: max since the last call (vu_meter.h:20-40). levels: [n_tracks][C]. */

@@ -6,6 +6,8 @@
 //   wb::AudioBuffer<float>                         src/core/audio_buffer.h:14-175
 //   wb::Engine::set_audio_channel_config/set_bpm/add_track/add_audio_clip/play/stop/process
 //                                                   src/engine/engine.h:68-113,235-239
+//   wb::Engine::record/stop_record/arm_track_recording/set_track_input, wb::TrackInputType
+//                                                   src/engine/engine.cpp:95-200, track_input.h:10-15
 //   wb::Track::set_volume/set_pan/set_mute          src/engine/track.h:137-139
 // Compiles with any C++17 compiler (no HIP headers needed); link against libwbx.so.
 #pragma once
@@ -180,6 +182,10 @@ struct Track {   // track.h:110-139
   void set_mute(bool mute);
 };
 
+enum class TrackInputType : int {   // track_input.h:10-15 (= WBX_INPUT_*); Midi is refused by set_track_input
+  None = WBX_INPUT_NONE, Midi = WBX_INPUT_MIDI, ExternalStereo = WBX_INPUT_EXTERNAL_STEREO, ExternalMono = WBX_INPUT_EXTERNAL_MONO
+};
+
 struct AudioClip {   // clip.h:39-45: the asset is a sample id returned by Engine::add_sample
   uint32_t asset{};
   double speed = 1.0;
@@ -188,7 +194,7 @@ struct AudioClip {   // clip.h:39-45: the asset is a sample id returned by Engin
 
 struct Engine {
   wbx_engine* h{};
-  uint32_t num_output_channels = 0, audio_buffer_size = 0, audio_sample_rate = 0;
+  uint32_t num_input_channels = 0, num_output_channels = 0, audio_buffer_size = 0, audio_sample_rate = 0;
   std::vector<std::unique_ptr<Track>> tracks;
   // device-side limits, fixed when the engine is first configured (not part of the reference's surface)
   uint32_t max_tracks = 4096, max_blocks = 1;
@@ -211,7 +217,7 @@ struct Engine {
   // set_audio_channel_config(in, out, buffer_size, sample_rate), engine.cpp:43-57.  The first call creates the device
   // context; later calls (the audio backend was reconfigured) resize it in place — tracks and clips stay, as in the
   // reference.
-  void set_audio_channel_config(uint32_t /*input_channels*/, uint32_t output_channels, uint32_t buffer_size, uint32_t sample_rate) {
+  void set_audio_channel_config(uint32_t input_channels, uint32_t output_channels, uint32_t buffer_size, uint32_t sample_rate) {
     if (!h) {
       wbx_config cfg{};
       cfg.device = device;
@@ -224,6 +230,8 @@ struct Engine {
     } else {
       check(wbx_engine_set_audio_channel_config(h, output_channels, buffer_size, sample_rate), "set_audio_channel_config");
     }
+    check(wbx_engine_set_input_channels(h, input_channels), "set_audio_channel_config");
+    num_input_channels = input_channels;
     num_output_channels = output_channels;
     audio_buffer_size = buffer_size;
     audio_sample_rate = sample_rate;
@@ -280,13 +288,30 @@ struct Engine {
   }
   void play() { check(wbx_engine_play(h), "play"); }
   void stop() { check(wbx_engine_stop(h), "stop"); }
+  // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
+  // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
+  void record() { check(wbx_engine_record(h), "record"); }
+  void stop_record() { check(wbx_engine_stop_record(h), "stop_record"); }
+  void arm_track_recording(uint32_t slot, bool armed) { check(wbx_engine_arm_track_recording(h, slot, armed ? 1 : 0), "arm_track_recording"); }
+  void set_track_input(uint32_t slot, TrackInputType type, uint32_t index, bool armed) {
+    check(wbx_track_set_input(h, slot, static_cast<int>(type), index, armed ? 1 : 0), "set_track_input");
+  }
+  bool is_recording() const {
+    int r = 0;
+    check(wbx_engine_is_recording(h, &r), "is_recording");
+    return r != 0;
+  }
   // void Engine::process(const AudioBuffer<float>&, AudioBuffer<float>&, double), engine.h:235-239
   // Audio thread.  Never throws: on a failure the block is silence and process_status / process_error say why.
-  void process(const AudioBuffer<float>& /*input_buffer*/, AudioBuffer<float>& output_buffer, double sample_rate) noexcept {
+  // The input buffer is what a running take records (engine.cpp:1638-1649); it never reaches the output (no monitoring).
+  void process(const AudioBuffer<float>& input_buffer, AudioBuffer<float>& output_buffer, double sample_rate) noexcept {
     assert(output_buffer.n_samples == audio_buffer_size && output_buffer.n_channels == num_output_channels);
     assert(sample_rate == (double)audio_sample_rate);
     (void)sample_rate;
-    const wbx_status st = wbx_engine_process(h, output_buffer.channel_buffers);
+    const wbx_status st =
+        input_buffer.n_channels != 0
+            ? wbx_engine_process_in(h, input_buffer.channel_buffers, input_buffer.n_channels, output_buffer.channel_buffers)
+            : wbx_engine_process(h, output_buffer.channel_buffers);
     if (st != WBX_OK) {
       output_buffer.clear();
       process_error = wbx_engine_last_error(h);

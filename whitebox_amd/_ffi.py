@@ -42,6 +42,12 @@ class Plugin(C.Structure):
     _fields_ = [("userdata", C.c_void_p), ("process", C.c_void_p)]
 
 
+class RecordInfo(C.Structure):
+    _fields_ = [("recording", C.c_int32), ("armed", C.c_int32), ("input_type", C.c_int32), ("input_index", C.c_uint32),
+                ("min_time", C.c_double), ("max_time", C.c_double), ("frames", C.c_uint64), ("status", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -50,6 +56,8 @@ class PlanRecord(C.Structure):
 
 
 FMT = {"i16": 3, "i24": 5, "i32": 7, "f32": 9}
+# TrackInputType (track_input.h:10-15) -> WBX_INPUT_*
+INPUT_TYPE = {"none": 0, "midi": 1, "external_stereo": 2, "external_mono": 3}
 OUT_FMT = {"i16": 3, "i24": 5, "i24_x8": 6, "i32": 7, "f32": 9}
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
@@ -153,7 +161,17 @@ SYMBOLS = {
     "wbx_engine_stop": (C.c_int, [_vp]),
     "wbx_engine_process": (C.c_int, [_vp, _fpp]),
     "wbx_engine_process_interleaved": (C.c_int, [_vp, C.c_int, _vp]),
+    "wbx_engine_process_in": (C.c_int, [_vp, _fpp, _u32, _fpp]),
+    "wbx_engine_process_interleaved_in": (C.c_int, [_vp, _fpp, _u32, C.c_int, _vp]),
     "wbx_engine_render": (C.c_int, [_vp, _u32]),
+    "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
+    "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),
+    "wbx_engine_arm_track_recording": (C.c_int, [_vp, _u32, C.c_int]),
+    "wbx_engine_record": (C.c_int, [_vp]),
+    "wbx_engine_stop_record": (C.c_int, [_vp]),
+    "wbx_engine_is_recording": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "wbx_engine_record_info": (C.c_int, [_vp, _u32, C.POINTER(RecordInfo)]),
+    "wbx_engine_set_record_chunk": (C.c_int, [_vp, _u32, _u32]),
     "wbx_engine_transport": (C.c_int, [_vp, C.POINTER(_d), C.POINTER(_d), C.POINTER(C.c_int)]),
     "wbx_engine_levels": (C.c_int, [_vp, C.POINTER(_f), _u32]),
     "wbx_engine_thread_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u32]),

@@ -38,6 +38,18 @@ void launch_levels_take(uint32_t* levels, uint32_t* dst, uint32_t n, hipStream_t
 bool probe_xcd_layout(hipStream_t s, uint32_t* n_xcds);   // workgroup ids round-robin over 8 / 4 / 2 / 1 XCDs? (wbx_kernels.hip)
 void launch_deinterleave(const void* src, void* dst0, void* dst1, uint64_t frames, uint32_t channels, uint32_t elem,
                          hipStream_t s);
+// recording (wbx_record.hip): one staged input block -> the chunks of every take that records it
+struct RecChunk {
+  uint32_t* ch[2];             // the chunk's channel rows (F32 samples moved as words)
+};
+struct RecCaptureArgs {
+  const uint32_t* stage;       // pinned: [in_channels][frames] samples of the block
+  const uint32_t* desc;        // pinned, beside them: [n_takes] ch0 << 2 | channels, 0 = skip the take this block
+  const RecChunk* table;       // device: [n_takes][table_cap] chunk rows
+  uint64_t start;              // the takes' frame of the block's first frame
+  uint32_t frames, in_channels, n_takes, table_cap, chunk_frames;
+};
+void launch_record_capture(const RecCaptureArgs& a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -321,7 +333,8 @@ inline size_t fmt_bytes(int fmt) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-enum : int { CLIP_SRC_PLANAR = 0, CLIP_SRC_INTERLEAVED_HOST = 1, CLIP_SRC_INTERLEAVED_DEVICE = 2, CLIP_SRC_SYNTH = 3 };
+enum : int { CLIP_SRC_PLANAR = 0, CLIP_SRC_INTERLEAVED_HOST = 1, CLIP_SRC_INTERLEAVED_DEVICE = 2, CLIP_SRC_SYNTH = 3,
+             CLIP_SRC_ZERO = 4 /* every frame zero, asynchronous on `on` (take chunks, recorded clips before their gather) */ };
 struct ClipFill {           // where a new clip's audio comes from
   int kind;
   const void* const* planar;   // CLIP_SRC_PLANAR: host channel arrays

@@ -6,6 +6,8 @@
 // holding the editor lock for its host side, one UI thread whose edits take the same lock and whose
 // wbx_track_set_volume / _pan / _mute go through the per-track SPSC ring without it.
 #include <chrono>
+#include <condition_variable>
+#include <thread>
 
 #include "wbx_ctx.h"
 #include "wbx_host.h"
@@ -92,6 +94,36 @@ struct wbx_engine {
   hipStream_t last_plan_stream = nullptr;
   hipEvent_t plan_handover = nullptr;
   uint32_t* h_levels = nullptr;         // [max_tracks][2]
+
+  // ---- recording (wbx_engine_record ... ; semantics in wbx_host.h, HostSession::takes) ----
+  // A take is a table of chunks of the clip pool (F32, rec_chunk frames, zeroed when taken) in HBM.  The audio thread copies
+  // each played block's input into a pinned staging slot and launches record_capture_kernel on the upload stream, which
+  // writes it into the chunks by absolute frame; the engine's recorder thread keeps rec_spare chunks ahead of every take's
+  // write position; stop_record gathers the chunks into one clip.
+  static constexpr int kRecSlots = 8;
+  uint32_t rec_chunk = 65536, rec_spare = 2;   // wbx_engine_set_record_chunk (audio_record_chunk_size / 4, engine.h:36)
+  struct RecTake {
+    std::vector<ClipSlot> chunks;              // the recorder thread's while the take runs
+    uint32_t channels = 1;
+    std::atomic<uint32_t> ready{0};            // chunks whose table entry is enqueued ahead of any capture that uses it
+  };
+  std::unique_ptr<RecTake[]> rec_takes;
+  uint32_t rec_n = 0, rec_table_cap = 0, rec_in_ch = 0, rec_F = 0;
+  DevBuf<RecChunk> d_rec_table;                // [rec_n][rec_table_cap]
+  RecChunk* h_rec_table = nullptr;             // pinned source of the table writes, same shape
+  size_t h_rec_table_cap = 0;
+  uint32_t* h_rec_stage = nullptr;             // pinned [kRecSlots][rec_slot_words]: samples, then the take descriptors
+  size_t rec_slot_words = 0, h_rec_stage_cap = 0;
+  hipEvent_t rec_ev[kRecSlots] = {};           // the capture that read the slot last
+  bool rec_ev_valid[kRecSlots] = {};
+  uint32_t rec_slot = 0;
+  std::thread rec_thread;
+  std::atomic<bool> rec_run{false};
+  std::atomic<uint64_t> rec_written{0};        // frames of the takes the audio thread has dealt with (all takes alike)
+  std::mutex rec_mu;                           // (the recorder thread's sleep only)
+  std::condition_variable rec_cv;
+  std::atomic<wbx_status> rec_thread_err{WBX_OK};
+  uint64_t rec_captures = 0;                   // capture launches so far (diagnostic)
 };
 
 namespace {
@@ -185,8 +217,21 @@ extern "C" wbx_status wbx_engine_create(const wbx_config* cfg, wbx_engine** out)
   return WBX_OK;
 }
 
+namespace {
+void rec_release(wbx_engine* e);
+}
+
 extern "C" void wbx_engine_destroy(wbx_engine* e) {
   if (!e) return;
+  if (e->ctx) {
+    (void)hipSetDevice(e->ctx->cfg.device);
+    rec_release(e);   // a take still running is discarded
+  }
+  for (int i = 0; i < wbx_engine::kRecSlots; i++)
+    if (e->rec_ev[i]) (void)hipEventDestroy(e->rec_ev[i]);
+  if (e->h_rec_stage) (void)hipHostFree(e->h_rec_stage);
+  if (e->h_rec_table) (void)hipHostFree(e->h_rec_table);
+  e->d_rec_table.release();
   if (e->ctx) {
     (void)hipSetDevice(e->ctx->cfg.device);
     (void)hipStreamSynchronize(e->ctx->plan_stream);
@@ -236,6 +281,7 @@ extern "C" wbx_status wbx_engine_set_audio_channel_config(wbx_engine* e, uint32_
   wbx_ctx* c = e->ctx;
   if (c->cfg.channels == output_channels && c->cfg.block_frames == buffer_size && c->cfg.sample_rate == sample_rate) return WBX_OK;
   if (c->dist) return efail(e, WBX_ERR_UNSUPPORTED, "set_audio_channel_config: shut the multi-GPU exchange down first (its buffers have the old shape)");
+  if (e->hs.recording) return efail(e, WBX_ERR_UNSUPPORTED, "set_audio_channel_config: not while recording (stop_record first)");
   (void)hipSetDevice(c->cfg.device);
   WBX_EHIP(e, hipStreamSynchronize(c->plan_stream));
   WBX_EHIP(e, join_sum(c));
@@ -666,12 +712,17 @@ extern "C" wbx_status wbx_engine_play(wbx_engine* e) {   // engine.cpp:68-80
   return WBX_OK;
 }
 
+namespace {
+wbx_status stop_record_impl(wbx_engine* e);
+}
+
 extern "C" wbx_status wbx_engine_stop(wbx_engine* e) {   // engine.cpp:82-93, Track::stop track.cpp:249-256
   if (!e) return WBX_ERR_INVALID;
+  const wbx_status rs = stop_record_impl(e);   // engine.cpp:83-84 (an overflow is the take's status, not the stop's)
   LockGuard g(e->hs.editor_lock);
   e->hs.stop_locked();
   e->hs.note_edit_locked();
-  return WBX_OK;
+  return rs == WBX_ERR_OVERFLOW ? WBX_OK : rs;
 }
 
 namespace {
@@ -1057,16 +1108,369 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
 extern "C" wbx_status wbx_engine_render(wbx_engine* e, uint32_t K) {
   if (!e || K == 0) return WBX_ERR_INVALID;
   LockGuard g(e->hs.editor_lock);
+  if (e->hs.recording) return efail(e, WBX_ERR_UNSUPPORTED, "wbx_engine_render: not while recording (takes are captured per process call)");
   return render_locked(e, K);
 }
 
+// ---- recording ---------------------------------------------------------------------------------------------------------
+// Engine::record / stop_record / arm_track_recording / set_track_input (engine.cpp:95-200) and the recorder tap of
+// Engine::process (engine.cpp:1638-1649).  Who records what, record_min_time / record_max_time and the frame count are the
+// host session's (wbx_host.h); the audio lives in HBM from the first frame on:
+//   audio thread  copies the block's recorded input channels into a pinned staging slot (kRecSlots of them, each with the
+//                 event of the capture that read it last) and launches record_capture_kernel on the upload stream — never
+//                 the mix streams, and it does not wait for it;
+//   recorder      the engine's own thread: keeps rec_spare chunks (clip pool extents, zeroed) ahead of every take's write
+//                 position and enqueues their table entries on the same stream before it publishes them;
+//   stop_record   waits for that stream, gathers each take's chunks into one F32 clip (with the 16 zero frames of padding),
+//                 frees the chunks and adds the clip through the edit path (add_audio_clip, overlap trimming included).
+// A block that finds a chunk missing (the recorder fell behind, or the table is full) or its staging slot still being read
+// is not written: its frames stay silent (chunks start zeroed; missing chunks gather as zeros) and the take's status
+// latches WBX_RECORD_OVERFLOW.  The frame count and record_max_time advance all the same.
+
 namespace {
-wbx_status process_block(wbx_engine* e, float* const* out_planar, int out_format, void* out_il);
+
+uint32_t rec_chunks_needed(const wbx_engine* e, uint64_t written) {   // chunks the next block touches, plus the spare ones
+  const uint64_t need = (written + e->rec_F + e->rec_chunk - 1) / e->rec_chunk + e->rec_spare;
+  return (uint32_t)std::min<uint64_t>(need, e->rec_table_cap);
+}
+
+// take chunks from the clip pool until every take holds what `written` asks for (the recorder thread, and record())
+wbx_status rec_fill(wbx_engine* e, uint64_t written) {
+  wbx_ctx* c = e->ctx;
+  const uint32_t need = rec_chunks_needed(e, written);
+  for (uint32_t k = 0; k < e->rec_n; k++) {
+    wbx_engine::RecTake& t = e->rec_takes[k];
+    while (t.chunks.size() < need) {
+      ClipSlot s;
+      ClipFill f{};
+      f.kind = CLIP_SRC_ZERO;
+      const wbx_status st = clip_build(c, s, WBX_FMT_F32, t.channels, c->cfg.sample_rate, e->rec_chunk, f, c->upload_stream);
+      if (st != WBX_OK) return st;
+      const size_t i = (size_t)k * e->rec_table_cap + t.chunks.size();
+      e->h_rec_table[i].ch[0] = (uint32_t*)s.d.ch[0];
+      e->h_rec_table[i].ch[1] = (uint32_t*)s.d.ch[1];
+      if (hipMemcpyAsync(e->d_rec_table.p + i, e->h_rec_table + i, sizeof(RecChunk), hipMemcpyHostToDevice, c->upload_stream) !=
+          hipSuccess) {
+        clip_release(c, s);
+        return WBX_ERR_DEVICE;
+      }
+      t.chunks.push_back(std::move(s));
+      t.ready.store((uint32_t)t.chunks.size(), std::memory_order_release);   // (the entry's copy is enqueued: captures see it)
+    }
+  }
+  return WBX_OK;
+}
+
+void rec_thread_main(wbx_engine* e) {
+  (void)hipSetDevice(e->ctx->cfg.device);
+  while (e->rec_run.load(std::memory_order_acquire)) {
+    const wbx_status st = rec_fill(e, e->rec_written.load(std::memory_order_acquire));
+    if (st != WBX_OK) e->rec_thread_err.store(st, std::memory_order_relaxed);   // the blocks that find no room say overflow
+    std::unique_lock<std::mutex> lk(e->rec_mu);
+    e->rec_cv.wait_for(lk, std::chrono::milliseconds(st == WBX_OK ? 2 : 20));
+  }
+}
+
+// stop the recorder thread, wait for every capture, free what the takes hold (the UI thread; no take running)
+void rec_release(wbx_engine* e) {
+  if (e->rec_thread.joinable()) {
+    e->rec_run.store(false, std::memory_order_release);
+    e->rec_cv.notify_one();
+    e->rec_thread.join();
+  }
+  if (e->ctx->upload_stream) (void)hipStreamSynchronize(e->ctx->upload_stream);
+  for (uint32_t k = 0; k < e->rec_n; k++)
+    for (auto& s : e->rec_takes[k].chunks) clip_release(e->ctx, s);
+  e->rec_takes.reset();
+  e->rec_n = 0;
+}
+
+// the audio thread, editor lock held, after the block's launches: the recorder tap (engine.cpp:1638-1649)
+void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
+  HostSession& hs = e->hs;
+  if (!hs.capture_due()) return;
+  wbx_ctx* c = e->ctx;
+  const uint32_t F = e->rec_F;
+  const uint64_t start = hs.capture_block_locked(F, !in || n_in < e->rec_in_ch);
+  const uint32_t slot = e->rec_slot;
+  const bool slot_free = !e->rec_ev_valid[slot] || hipEventQuery(e->rec_ev[slot]) == hipSuccess;
+  uint32_t* stage = e->h_rec_stage + slot * e->rec_slot_words;
+  uint32_t* desc = stage + (size_t)e->rec_in_ch * F;
+  const uint64_t last_chunk = (start + F - 1) / e->rec_chunk;
+  bool any = false;
+  for (uint32_t k = 0; k < e->rec_n; k++) {
+    const Take& tk = hs.takes[k];
+    uint32_t d = 0;
+    if (tk.track) {
+      if (slot_free && e->rec_takes[k].ready.load(std::memory_order_acquire) > last_chunk)
+        d = tk.ch0 << 2 | tk.channels;
+      else
+        hs.take_status_locked(k, REC_OVERFLOW);
+    }
+    if (slot_free) desc[k] = d;
+    any |= d != 0u;
+  }
+  if (any) {
+    for (uint32_t ch = 0; ch < e->rec_in_ch; ch++) {
+      if (in && ch < n_in && in[ch])
+        std::memcpy(stage + (size_t)ch * F, in[ch], (size_t)F * sizeof(float));
+      else
+        std::memset(stage + (size_t)ch * F, 0, (size_t)F * sizeof(float));
+    }
+    RecCaptureArgs a{};
+    a.stage = stage;
+    a.desc = desc;
+    a.table = e->d_rec_table.p;
+    a.start = start;
+    a.frames = F;
+    a.in_channels = e->rec_in_ch;
+    a.n_takes = e->rec_n;
+    a.table_cap = e->rec_table_cap;
+    a.chunk_frames = e->rec_chunk;
+    launch_record_capture(a, c->upload_stream);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(e->rec_ev[slot], c->upload_stream) != hipSuccess) {
+      for (uint32_t k = 0; k < e->rec_n; k++) hs.take_status_locked(k, REC_OVERFLOW);
+    } else {
+      e->rec_ev_valid[slot] = true;
+      e->rec_slot = (slot + 1) % wbx_engine::kRecSlots;
+      e->rec_captures++;
+    }
+  }
+  e->rec_written.store(start + F, std::memory_order_release);
+  const uint32_t need = rec_chunks_needed(e, start + F);
+  for (uint32_t k = 0; k < e->rec_n; k++)
+    if (e->rec_takes[k].ready.load(std::memory_order_relaxed) < need) {
+      e->rec_cv.notify_one();
+      break;
+    }
+}
+
+// Engine::stop_record (engine.cpp:107-141); the UI thread
+wbx_status stop_record_impl(wbx_engine* e) {
+  wbx_ctx* c = e->ctx;
+  std::vector<FinishedTake> fin;
+  {
+    LockGuard g(e->hs.editor_lock);
+    if (!e->hs.recording) return WBX_OK;
+    fin = e->hs.stop_record_locked();   // recording ends with the block in progress; every track's stop_record
+    e->hs.note_edit_locked();
+  }
+  if (e->rec_thread.joinable()) {
+    e->rec_run.store(false, std::memory_order_release);
+    e->rec_cv.notify_one();
+    e->rec_thread.join();
+  }
+  (void)hipSetDevice(c->cfg.device);
+  wbx_status st = hipStreamSynchronize(c->upload_stream) == hipSuccess ? WBX_OK : WBX_ERR_DEVICE;
+  // gather: one F32 clip per take (a take that captured no frame adds no clip), chunk after chunk, device to device
+  std::vector<ClipSlot> built(fin.size());
+  for (size_t i = 0; i < fin.size() && st == WBX_OK; i++) {
+    const FinishedTake& f = fin[i];
+    if (f.frames == 0) continue;
+    if (f.frames >= 2147483632ull) {
+      st = efail(e, WBX_ERR_UNSUPPORTED, "stop_record: a take longer than 2^31-16 frames");
+      break;
+    }
+    ClipFill fill{};
+    fill.kind = CLIP_SRC_ZERO;
+    st = cfail(e, clip_build(c, built[i], WBX_FMT_F32, f.channels, c->cfg.sample_rate, f.frames, fill, c->upload_stream));
+    const wbx_engine::RecTake& t = e->rec_takes[f.take];
+    for (size_t j = 0; st == WBX_OK && j < t.chunks.size() && (uint64_t)j * e->rec_chunk < f.frames; j++) {
+      const uint64_t at = (uint64_t)j * e->rec_chunk;
+      const uint64_t n = std::min<uint64_t>(e->rec_chunk, f.frames - at);
+      for (uint32_t ch = 0; ch < f.channels && st == WBX_OK; ch++)
+        if (hipMemcpyAsync((char*)built[i].d.ch[ch] + at * sizeof(float), t.chunks[j].d.ch[ch], n * sizeof(float),
+                           hipMemcpyDeviceToDevice, c->upload_stream) != hipSuccess)
+          st = efail(e, WBX_ERR_DEVICE, "stop_record: gathering a take");
+    }
+  }
+  if (st == WBX_OK && hipStreamSynchronize(c->upload_stream) != hipSuccess) st = efail(e, WBX_ERR_DEVICE, "stop_record: gather");
+  rec_release(e);
+  LockGuard g(e->hs.editor_lock);
+  e->hs.note_edit_locked();
+  bool overflow = false;
+  for (size_t i = 0; i < fin.size(); i++) {
+    if (!built[i].used) continue;
+    const int32_t t = e->hs.track_index(fin[i].track);
+    if (st != WBX_OK || t < 0) {   // (the track went while the take was gathered: its take is discarded)
+      clip_release(c, built[i]);
+      continue;
+    }
+    // Sample from the take -> SampleAsset -> add_audio_clip(track, record_min_time, record_max_time, 0.0, {speed 1, gain 1})
+    const uint32_t id = (uint32_t)c->clips.size();
+    const wbx_status ps = clip_publish(c, id, built[i]);
+    if (ps != WBX_OK) {
+      st = cfail(e, ps);
+      continue;
+    }
+    e->hs.samples.resize(c->clips.size());
+    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, fin[i].channels, c->cfg.sample_rate, fin[i].frames, true};
+    e->hs.add_audio_clip_locked((uint32_t)t, fin[i].min_time, fin[i].max_time, 0.0, id, 1.0, 1.0f);
+    overflow |= (fin[i].status & REC_OVERFLOW) != 0u;
+  }
+  e->hs.takes.clear();
+  if (st == WBX_OK && overflow) return efail(e, WBX_ERR_OVERFLOW, "stop_record: a take lost blocks (no chunk was ready for them)");
+  return st;
+}
+
+}  // namespace
+
+// Engine::record (engine.cpp:95-105): the take list and its first chunks are made before the transport (re)starts, so
+// the first block already has room; the recorder thread runs until stop_record.
+extern "C" wbx_status wbx_engine_record(wbx_engine* e) {
+  if (!e) return WBX_ERR_INVALID;
+  wbx_ctx* c = e->ctx;
+  std::vector<uint32_t> widths;
+  uint32_t in_ch = 0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    if (e->hs.recording && e->hs.playing.load(std::memory_order_relaxed)) return WBX_OK;
+    if (c->master_target || c->dist)
+      return efail(e, WBX_ERR_UNSUPPORTED, "record: not with a redirected master / a multi-GPU exchange");
+    if (!e->hs.record_inputs_valid()) return efail(e, WBX_ERR_INVALID, "record: a track input lies past the input channel count");
+    for (auto& tp : e->hs.tracks) {
+      const TrackRecord& r = tp->rec;
+      if (!r.armed || r.in_type == INPUT_NONE) continue;
+      widths.push_back(HostSession::input_width(r.in_type));
+      in_ch = std::max(in_ch, HostSession::input_first_channel(r.in_type, r.in_index) + widths.back());
+    }
+  }
+  rec_release(e);   // (nothing is left of an earlier take; a no-op normally)
+  (void)hipSetDevice(c->cfg.device);
+  const uint32_t n = (uint32_t)widths.size();
+  if (n) {
+    const uint32_t F = c->cfg.block_frames;
+    e->rec_F = F;
+    e->rec_in_ch = in_ch;
+    // the table covers the longest clip the pool holds (2^31-17 frames), at most 65536 chunks per take
+    e->rec_table_cap = (uint32_t)std::min<uint64_t>(65536u, (2147483631ull + e->rec_chunk - 1) / e->rec_chunk + 1);
+    const size_t table = (size_t)n * e->rec_table_cap;
+    WBX_EHIP(e, e->d_rec_table.ensure(table));
+    if (e->h_rec_table_cap < table) {
+      if (e->h_rec_table) WBX_EHIP(e, hipHostFree(e->h_rec_table));
+      e->h_rec_table = nullptr;
+      WBX_EHIP(e, hipHostMalloc((void**)&e->h_rec_table, table * sizeof(RecChunk), hipHostMallocDefault));
+      e->h_rec_table_cap = table;
+    }
+    e->rec_slot_words = align_up((size_t)in_ch * F + n, 64);
+    const size_t stage = e->rec_slot_words * wbx_engine::kRecSlots;
+    if (e->h_rec_stage_cap < stage) {
+      if (e->h_rec_stage) WBX_EHIP(e, hipHostFree(e->h_rec_stage));
+      e->h_rec_stage = nullptr;
+      WBX_EHIP(e, hipHostMalloc((void**)&e->h_rec_stage, stage * sizeof(uint32_t), hipHostMallocDefault));
+      e->h_rec_stage_cap = stage;
+    }
+    for (int i = 0; i < wbx_engine::kRecSlots; i++) {
+      if (!e->rec_ev[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->rec_ev[i], hipEventDisableTiming));
+      e->rec_ev_valid[i] = false;
+    }
+    e->rec_slot = 0;
+    e->rec_takes.reset(new wbx_engine::RecTake[n]);
+    e->rec_n = n;
+    for (uint32_t k = 0; k < n; k++) e->rec_takes[k].channels = widths[k];
+    e->rec_written.store(0, std::memory_order_relaxed);
+    e->rec_thread_err.store(WBX_OK, std::memory_order_relaxed);
+    wbx_status st = rec_fill(e, 0);
+    if (st == WBX_OK && hipStreamSynchronize(c->upload_stream) != hipSuccess) st = WBX_ERR_DEVICE;
+    if (st != WBX_OK) {
+      rec_release(e);
+      return cfail(e, st);
+    }
+  }
+  LockGuard g(e->hs.editor_lock);
+  e->hs.note_edit_locked();
+  e->hs.record_locked();   // (the same take list: only this thread arms tracks or sets inputs)
+  if (n) {
+    e->rec_run.store(true, std::memory_order_release);
+    e->rec_thread = std::thread(rec_thread_main, e);
+  }
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_engine_stop_record(wbx_engine* e) {
+  if (!e) return WBX_ERR_INVALID;
+  return stop_record_impl(e);
+}
+
+extern "C" wbx_status wbx_engine_is_recording(wbx_engine* e, int* recording) {
+  if (!e || !recording) return WBX_ERR_INVALID;
+  LockGuard g(e->hs.editor_lock);
+  *recording = e->hs.recording ? 1 : 0;
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_engine_set_input_channels(wbx_engine* e, uint32_t input_channels) {
+  if (!e) return WBX_ERR_INVALID;
+  if (input_channels > 1024) return efail(e, WBX_ERR_INVALID, "set_input_channels: at most 1024");
+  LockGuard g(e->hs.editor_lock);
+  e->hs.input_channels = input_channels;
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_track_set_input(wbx_engine* e, uint32_t track, int type, uint32_t index, int armed) {
+  if (!e) return WBX_ERR_INVALID;
+  if (type == WBX_INPUT_MIDI) return efail(e, WBX_ERR_UNSUPPORTED, "set_track_input: MIDI input is not supported");
+  if (type != WBX_INPUT_NONE && type != WBX_INPUT_EXTERNAL_STEREO && type != WBX_INPUT_EXTERNAL_MONO)
+    return efail(e, WBX_ERR_INVALID, "set_track_input: input type");
+  if (index > 0xFFFFFFu) return efail(e, WBX_ERR_INVALID, "set_track_input: index above 2^24-1 (TrackInput::as_packed_u32)");
+  LockGuard g(e->hs.editor_lock);
+  if (!e->hs.valid_track(track)) return WBX_ERR_INVALID;
+  e->hs.set_track_input_locked(track, (uint32_t)type, index, armed != 0);
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_engine_arm_track_recording(wbx_engine* e, uint32_t track, int armed) {
+  if (!e) return WBX_ERR_INVALID;
+  LockGuard g(e->hs.editor_lock);
+  if (!e->hs.valid_track(track)) return WBX_ERR_INVALID;
+  const TrackRecord& r = e->hs.tracks[track]->rec;
+  e->hs.set_track_input_locked(track, r.in_type, r.in_index, armed != 0);
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_engine_record_info(wbx_engine* e, uint32_t track, wbx_record_info* out) {
+  if (!e || !out) return WBX_ERR_INVALID;
+  LockGuard g(e->hs.editor_lock);
+  if (!e->hs.valid_track(track)) return WBX_ERR_INVALID;
+  const TrackRecord& r = e->hs.tracks[track]->rec;
+  *out = wbx_record_info{};
+  out->recording = r.recording ? 1 : 0;
+  out->armed = r.armed ? 1 : 0;
+  out->input_type = (int32_t)r.in_type;
+  out->input_index = r.in_index;
+  out->min_time = r.min_time;
+  out->max_time = r.max_time;
+  out->frames = r.last_frames;
+  out->status = r.last_status;
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_engine_set_record_chunk(wbx_engine* e, uint32_t frames, uint32_t spare_chunks) {
+  if (!e) return WBX_ERR_INVALID;
+  if (frames < 1 || frames > (1u << 24) || spare_chunks > 4096)
+    return efail(e, WBX_ERR_INVALID, "set_record_chunk: 1 to 2^24 frames, at most 4096 spare chunks");
+  LockGuard g(e->hs.editor_lock);
+  if (e->hs.recording) return efail(e, WBX_ERR_UNSUPPORTED, "set_record_chunk: not while recording");
+  e->rec_chunk = frames;
+  e->rec_spare = spare_chunks;
+  return WBX_OK;
+}
+
+namespace {
+wbx_status process_block(wbx_engine* e, float* const* out_planar, int out_format, void* out_il, const float* const* in,
+                         uint32_t n_in);
 }
 
 extern "C" wbx_status wbx_engine_process(wbx_engine* e, float* const* out_planar) {   // engine.cpp:1576-1654
   if (!e || !out_planar) return WBX_ERR_INVALID;
-  return process_block(e, out_planar, 0, nullptr);
+  return process_block(e, out_planar, 0, nullptr, nullptr, 0);
+}
+
+// Engine::process(input_buffer, output_buffer, sample_rate) with its input buffer: in_planar[c][0..F) for c < n_in_channels
+extern "C" wbx_status wbx_engine_process_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels,
+                                            float* const* out_planar) {
+  if (!e || !in_planar || !out_planar) return WBX_ERR_INVALID;
+  return process_block(e, out_planar, 0, nullptr, in_planar, n_in_channels);
 }
 
 // Engine::process + the back end's conversion to the device format (audio_io_pulseaudio.cpp:419-461:
@@ -1078,28 +1482,42 @@ extern "C" wbx_status wbx_engine_process_interleaved(wbx_engine* e, int out_form
   if (out_format != WBX_OUT_I16 && out_format != WBX_OUT_I24 && out_format != WBX_OUT_I24_X8 && out_format != WBX_OUT_I32 &&
       out_format != WBX_OUT_F32)
     return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
-  return process_block(e, nullptr, out_format, dst);
+  return process_block(e, nullptr, out_format, dst, nullptr, 0);
+}
+
+// ... and with the input buffer of Engine::process (the recorder tap reads it, engine.cpp:1638-1649)
+extern "C" wbx_status wbx_engine_process_interleaved_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels,
+                                                        int out_format, void* dst) {
+  if (!e || !in_planar || !dst) return WBX_ERR_INVALID;
+  if (out_format != WBX_OUT_I16 && out_format != WBX_OUT_I24 && out_format != WBX_OUT_I24_X8 && out_format != WBX_OUT_I32 &&
+      out_format != WBX_OUT_F32)
+    return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
+  return process_block(e, nullptr, out_format, dst, in_planar, n_in_channels);
 }
 
 namespace {
 
-wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out_format, void* out_il);
+wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out_format, void* out_il, const float* const* in,
+                                uint32_t n_in);
 
-wbx_status process_block(wbx_engine* e, float* const* out_planar, int out_format, void* out_il) {
+wbx_status process_block(wbx_engine* e, float* const* out_planar, int out_format, void* out_il, const float* const* in,
+                         uint32_t n_in) {
   const auto t_in = std::chrono::steady_clock::now();   // ScopedPerformanceCounter, engine.cpp:1577
   LockGuard g(e->hs.editor_lock);   // held for the whole block, like editor_lock in Engine::process (engine.cpp:1587-1651)
-  const wbx_status st = process_block_locked(e, out_planar, out_format, out_il);
+  const wbx_status st = process_block_locked(e, out_planar, out_format, out_il, in, n_in);
   // perf_measurer.update(duration, audio_buffer_duration_ms), engine.cpp:1653 (there behind the unlock; one writer either way)
   e->hs.perf_update(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_in).count(), e->ctx->cfg.block_frames);
   return st;
 }
 
-wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out_format, void* out_il) {
+wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out_format, void* out_il, const float* const* in,
+                                uint32_t n_in) {
   wbx_ctx* c = e->ctx;
   if (c->master_target || c->dist) {   // the caller redirected the master: leave it there and fetch the ordinary way
     if (out_format) return efail(e, WBX_ERR_UNSUPPORTED, "wbx_engine_process_interleaved: not with a redirected master / a multi-GPU exchange");
     wbx_status st = render_locked(e, 1);
     if (st != WBX_OK) return st;
+    rec_capture_locked(e, in, n_in);
     return cfail(e, wbx_fetch(c, out_planar, nullptr, nullptr));
   }
   const int saved_format = c->master_format;
@@ -1122,6 +1540,9 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
   c->cb_launched = false;
   wbx_status st = render_locked(e, 1);
   e->in_process = false;
+  // the recorder tap, once per played block whichever path the block takes below (one launch, mixed again after a
+  // give-up, three launches): launched on the upload stream beside the block's kernels, not waited for
+  if (st == WBX_OK) rec_capture_locked(e, in, n_in);
   const bool one_launch = st == WBX_OK && c->cb_launched;
   if (st == WBX_OK && e->hs.n_tracks() != 0) {
     if (one_launch) {

@@ -117,6 +117,42 @@ struct SampleMeta {        // what the clip edits and the kernel-instance choice
   bool used = false;
 };
 
+// ---- recording: Engine::record / stop_record / arm_track_recording / set_track_input (engine.cpp:95-200), Track::
+//      prepare_record / stop_record (track.cpp:234-246), the record_max_time steps of process_event (track.cpp:281,342,448)
+//      and the recorder tap of Engine::process (engine.cpp:1638-1649).  Which frames go where is decided here; the frames
+//      themselves never touch the host (wbx_engine.hip: staging slot -> record_capture_kernel -> take chunks in HBM).
+enum : uint32_t { INPUT_NONE = 0, INPUT_MIDI = 1, INPUT_STEREO = 2, INPUT_MONO = 3 };   // TrackInputType, track_input.h:10-15
+enum : uint32_t { REC_OVERFLOW = 1, REC_SILENCE = 2 };   // a take's status bits (WBX_RECORD_*)
+
+struct HostTrack;
+
+struct TrackRecord {
+  uint32_t in_type = INPUT_NONE, in_index = 0;   // Track::input (track.h:95)
+  bool armed = false;                            // input_attr.armed
+  bool recording = false;                        // input_attr.recording
+  double min_time = 0.0, max_time = 0.0;         // record_min_time / record_max_time (track.h:100-101)
+  uint64_t last_frames = 0;                      // frames and status of this track's latest take (running or finished)
+  uint32_t last_status = 0;
+};
+
+// One take of the running recording: the routing is what the track's input was when record() started (the reference
+// sizes its queue from track_input_groups at record(), engine.cpp:99; later input / arm edits wait for the next record()).
+struct Take {
+  HostTrack* track = nullptr;   // null once the track was deleted: its take is discarded
+  uint32_t ch0 = 0, channels = 1;   // input channels ch0 .. ch0 + channels - 1 (engine.cpp:1642-1643)
+  uint64_t frames = 0;          // Track::num_samples_written
+  uint32_t status = 0;          // REC_*
+};
+
+// what stop_record hands to add_audio_clip (engine.cpp:119-137 -> :293-309), in track order
+struct FinishedTake {
+  uint32_t take = 0;            // index into the take list it came from
+  HostTrack* track = nullptr;
+  double min_time = 0.0, max_time = 0.0;
+  uint64_t frames = 0;
+  uint32_t channels = 1, status = 0;
+};
+
 struct HostTrack {
   std::vector<HostClip> clips;          // sorted by min_time (Track::update_clip_ordering, track.cpp:159-180)
   edit::ClipIds clip_ids;                   // Track::clip_allocator (track.h:105): which identity a new clip takes over
@@ -130,6 +166,7 @@ struct HostTrack {
   int32_t bus = -1;
   DPatch patch{};
   const void* plugin = nullptr;         // effect slot (Track::plugin_instance, track.h:124): always empty today
+  TrackRecord rec;
 };
 
 // Everything of a wbx_engine that is not device memory.  Methods named *_locked expect the caller to hold
@@ -165,6 +202,10 @@ struct HostSession {
   uint32_t next_clip_uid = 0;
   uint64_t edit_seq = 0;                // locked edits completed so far (UI thread, under the lock)
   uint64_t render_edit_seq = 0;         // edit_seq as the last process / render saw it
+  // recording (Engine::recording, num_input_channels, track_input_groups as of record(): engine.h:29, engine.cpp:95-105)
+  uint32_t input_channels = 0;
+  bool recording = false;
+  std::vector<Take> takes;
 
   // ---- the load figure of the audio thread: Engine::perf_measurer (engine.h:64; core/timing.h:54-67) ----
   // Engine::process starts a counter (engine.cpp:1577) and ends with perf_measurer.update(its duration in ms,
@@ -233,6 +274,10 @@ struct HostSession {
   void permute_tracks_locked(const std::vector<uint32_t>& order) {
     std::vector<std::unique_ptr<HostTrack>> moved(order.size());
     for (size_t i = 0; i < order.size(); i++) moved[i] = std::move(tracks[order[i]]);
+    for (auto& gone : tracks)   // a deleted track's take is discarded (delete_track, clear_all)
+      if (gone)
+        for (auto& tk : takes)
+          if (tk.track == gone.get()) tk.track = nullptr;
     tracks = std::move(moved);
     clips_dirty = gains_dirty = routing_dirty = true;
     recount_clips();
@@ -462,6 +507,11 @@ struct HostSession {
   }
 
   void play_locked() {   // engine.cpp:68-80
+    // prepare_record (track.cpp:234-240) for the tracks of the running take only: an arm / input change during a take takes
+    // effect at the next record() (the reference would prepare a track its recorder queue has no room for)
+    if (recording)
+      for (auto& tk : takes)
+        if (tk.track) prepare_record(*tk.track, playhead_start);
     for (auto& t : tracks) reset_playback_state(*t, playhead_start, false);
     sample_position = 0;
     playing.store(true, std::memory_order_relaxed);
@@ -476,6 +526,106 @@ struct HostSession {
       rate_flags_sticky = false;
       rederive_clip_flags();
     }
+  }
+
+  // ---- recording, under the lock ----
+  static void prepare_record(HostTrack& t, double time_pos) {   // track.cpp:234-240
+    t.rec.min_time = time_pos;
+    t.rec.max_time = time_pos;
+    t.rec.recording = true;
+  }
+  static void stop_record(HostTrack& t) {   // track.cpp:242-246
+    t.rec.min_time = 0.0;
+    t.rec.max_time = 0.0;
+    t.rec.recording = false;
+  }
+  static uint32_t input_width(uint32_t type) { return type == INPUT_STEREO ? 2u : 1u; }
+  static uint32_t input_first_channel(uint32_t type, uint32_t index) { return type == INPUT_STEREO ? 2u * index : index; }
+  // Engine::set_track_input / arm_track_recording (engine.cpp:145-198): the track's fields; the routing is taken at record()
+  void set_track_input_locked(uint32_t t, uint32_t type, uint32_t index, bool armed) {
+    tracks[t]->rec.in_type = type;
+    tracks[t]->rec.in_index = index;
+    tracks[t]->rec.armed = armed;
+  }
+  // would record() route a track to an input channel past the configured ones?  (the reference reads past its buffer)
+  bool record_inputs_valid() const {
+    for (auto& tp : tracks) {
+      const TrackRecord& r = tp->rec;
+      if (!r.armed || r.in_type == INPUT_NONE) continue;
+      if ((uint64_t)input_first_channel(r.in_type, r.in_index) + input_width(r.in_type) > input_channels) return false;
+    }
+    return true;
+  }
+  // Engine::record (engine.cpp:95-105).  Returns false when it does nothing (already recording and playing).  A new take
+  // list is made from every armed track with an input, in track order; play() prepares them (and restarts playback from
+  // playhead_start, also when the transport was already running — the reference's own behaviour).
+  bool record_locked() {
+    if (recording && playing.load(std::memory_order_relaxed)) return false;
+    takes.clear();
+    for (auto& tp : tracks) {
+      TrackRecord& r = tp->rec;
+      if (!r.armed || r.in_type == INPUT_NONE) continue;
+      Take tk;
+      tk.track = tp.get();
+      tk.ch0 = input_first_channel(r.in_type, r.in_index);
+      tk.channels = input_width(r.in_type);
+      takes.push_back(tk);
+      r.last_frames = 0;
+      r.last_status = 0;
+    }
+    recording = true;
+    play_locked();
+    return true;
+  }
+  bool capture_due() const { return recording && playing.load(std::memory_order_relaxed) && !takes.empty(); }
+  // the recorder tap of one played block (engine.cpp:1638-1649): every take of the list gets the block's F frames, starting
+  // at the frame returned.  `silence`: the caller had no input buffer for it; a take whose frames could not be stored
+  // gets REC_OVERFLOW from the caller.
+  uint64_t capture_block_locked(uint32_t F, bool silence) {
+    const uint64_t at = takes.empty() ? 0 : takes.front().frames;
+    for (auto& tk : takes) {
+      tk.frames += F;
+      if (silence) tk.status |= REC_SILENCE;
+      if (tk.track) {
+        tk.track->rec.last_frames = tk.frames;
+        tk.track->rec.last_status = tk.status;
+      }
+    }
+    return at;
+  }
+  void take_status_locked(size_t k, uint32_t bits) {
+    takes[k].status |= bits;
+    if (takes[k].track) takes[k].track->rec.last_status = takes[k].status;
+  }
+  // Engine::stop_record (engine.cpp:107-141), first half: recording ends with the block in progress; the takes that still
+  // have a track are returned in track order with the bounds add_audio_clip gets, and every track's record state is
+  // reset (Track::stop_record).  The caller turns each take into a sample and a clip (add_audio_clip_locked).
+  std::vector<FinishedTake> stop_record_locked() {
+    std::vector<FinishedTake> out;
+    if (!recording) return out;
+    recording = false;
+    for (auto& tp : tracks) {
+      for (size_t k = 0; k < takes.size(); k++) {
+        const Take& tk = takes[k];
+        if (tk.track != tp.get() || !tp->rec.recording) continue;
+        FinishedTake f;
+        f.take = (uint32_t)k;
+        f.track = tk.track;
+        f.min_time = tp->rec.min_time;
+        f.max_time = tp->rec.max_time;
+        f.frames = tk.frames;
+        f.channels = tk.channels;
+        f.status = tk.status;
+        out.push_back(f);
+      }
+      stop_record(*tp);
+    }
+    return out;
+  }
+  int32_t track_index(const HostTrack* t) const {
+    for (size_t i = 0; i < tracks.size(); i++)
+      if (tracks[i].get() == t) return (int32_t)i;
+    return -1;
   }
 
   bool sample_referenced(uint32_t sample) const {
@@ -616,6 +766,9 @@ struct HostSession {
       const double buffer_duration_in_beats = buffer_duration / bd;
       const double next_playhead_pos = ph + buffer_duration_in_beats;
       if (pl) {
+        if (recording)   // Track::process_event, track.cpp:281,342,448: every played block, whatever the clips did
+          for (auto& tk : takes)
+            if (tk.track && tk.track->rec.recording) tk.track->rec.max_time += buffer_duration_in_beats;
         const double sec = buffer_duration_in_beats * bd;       // beat_to_samples, core_math.h:209-212: two
         sp += sec * sample_rate;                                // separately rounded multiplies
         ph = next_playhead_pos;

@@ -1052,6 +1052,9 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
       }
       err = hipGetLastError();
       break;
+    case CLIP_SRC_ZERO:
+      for (uint32_t ch = 0; ch < channels && err == hipSuccess; ch++) err = hipMemsetAsync((char*)s.base + stride * ch, 0, stride, on);
+      break;
     case CLIP_SRC_INTERLEAVED_DEVICE:
       pad_tails();
       if (err == hipSuccess) {

@@ -98,6 +98,7 @@ class MixContext:
             self.h = _handle
         self.last = (0, 0)
         self.n_buses = 0
+        self.num_input_channels = 0
 
     def close(self):
         if self._owned and self.h:
@@ -326,6 +327,8 @@ class Engine:
         """Engine::set_audio_channel_config (engine.cpp:43-57) on the live engine: tracks and clips stay."""
         _check(self.L.wbx_engine_set_audio_channel_config(self.h, output_channels, buffer_size, sample_rate),
                "Engine::set_audio_channel_config", self.h, True)
+        _check(self.L.wbx_engine_set_input_channels(self.h, input_channels), "Engine::set_audio_channel_config", self.h, True)
+        self.num_input_channels = input_channels
         self.audio_buffer_size, self.audio_sample_rate, self.num_output_channels = buffer_size, sample_rate, output_channels
         self.ctx.block, self.ctx.channels, self.ctx.sample_rate = buffer_size, output_channels, sample_rate
 
@@ -473,10 +476,15 @@ class Engine:
         _check(self.L.wbx_engine_stop(self.h), "Engine::stop", self.h, True)
 
     def process(self, input_buffer: Optional[AudioBuffer], output_buffer: AudioBuffer, sample_rate: float):
-        """Engine::process(const AudioBuffer<float>&, AudioBuffer<float>&, double) — one block."""
+        """Engine::process(const AudioBuffer<float>&, AudioBuffer<float>&, double) — one block.  The input buffer (when
+        given) is what a running take records (engine.cpp:1638-1649); without one a take records silence."""
         assert output_buffer.n_samples == self.audio_buffer_size and output_buffer.n_channels == self.num_output_channels
         assert float(sample_rate) == float(self.audio_sample_rate)
-        st = self.L.wbx_engine_process(self.h, output_buffer._ptrs())
+        if input_buffer is not None and input_buffer.n_channels > 0:
+            assert input_buffer.n_samples >= self.audio_buffer_size
+            st = self.L.wbx_engine_process_in(self.h, input_buffer._ptrs(), input_buffer.n_channels, output_buffer._ptrs())
+        else:
+            st = self.L.wbx_engine_process(self.h, output_buffer._ptrs())
         if st != 0:
             _check(st, "Engine::process", self.h, True)
         self.ctx.last = (1, len(self.tracks))
@@ -489,6 +497,37 @@ class Engine:
                self.h, True)
         self.ctx.last = (1, len(self.tracks))
         return out
+
+    # ---- recording (engine.cpp:95-200) ----
+    def set_track_input(self, slot: int, type: str, index: int, armed: bool):
+        """Engine::set_track_input; type: "none", "external_stereo", "external_mono" ("midi" is refused)."""
+        _check(self.L.wbx_track_set_input(self.h, slot, _ffi.INPUT_TYPE[type], index, int(armed)), "Engine::set_track_input",
+               self.h, True)
+
+    def arm_track_recording(self, slot: int, armed: bool):
+        _check(self.L.wbx_engine_arm_track_recording(self.h, slot, int(armed)), "Engine::arm_track_recording", self.h, True)
+
+    def record(self):
+        _check(self.L.wbx_engine_record(self.h), "Engine::record", self.h, True)
+
+    def stop_record(self):
+        """Engine::stop_record; raises WbxError (status -8) when a take overflowed — its clip is made all the same."""
+        _check(self.L.wbx_engine_stop_record(self.h), "Engine::stop_record", self.h, True)
+
+    def is_recording(self) -> bool:
+        r = C.c_int()
+        _check(self.L.wbx_engine_is_recording(self.h, C.byref(r)), "wbx_engine_is_recording", self.h, True)
+        return bool(r.value)
+
+    def record_info(self, slot: int) -> dict:
+        ri = _ffi.RecordInfo()
+        _check(self.L.wbx_engine_record_info(self.h, slot, C.byref(ri)), "wbx_engine_record_info", self.h, True)
+        return {"recording": bool(ri.recording), "armed": bool(ri.armed), "input_type": ri.input_type,
+                "input_index": ri.input_index, "min_time": ri.min_time, "max_time": ri.max_time, "frames": ri.frames,
+                "status": ri.status}
+
+    def set_record_chunk(self, frames: int, spare_chunks: int):
+        _check(self.L.wbx_engine_set_record_chunk(self.h, frames, spare_chunks), "wbx_engine_set_record_chunk", self.h, True)
 
     def render(self, n_blocks: int):
         """K consecutive blocks in one device pass; fetch with self.ctx.fetch()."""
