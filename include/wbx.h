@@ -463,6 +463,49 @@ wbx_status wbx_engine_record_info(wbx_engine* e, uint32_t track, wbx_record_info
  * recorder thread keeps `spare_chunks` (default 2) chunks ahead of every take's write position (wbx_engine_record
  * reserves the first ones).  Not while recording. */
 wbx_status wbx_engine_set_record_chunk(wbx_engine* e, uint32_t frames, uint32_t spare_chunks);
+/* ---- bouncing: tracks, buses and the master into GPU-resident clips (stems, freeze, export; no reference counterpart —
+ * its export dialog, ui/export_audio_dlg.cpp / engine/export_prop.h, has nothing behind it).
+ * Render [min_time, max_time) (beats) offline and keep n_src signals of it as F32 samples of the session rate and channel
+ * count in the engine's clip pool; samples_out[i] is an engine sample id usable in wbx_engine_add_audio_clip,
+ * wbx_clip_download, wbx_clip_build_mipmaps, wbx_engine_delete_sample.  No host copy of the audio is made anywhere.
+ *   length    n_frames = (uint64_t)beat_to_samples(max_time - min_time, sample_rate, beat_duration) (core_math.h:209-212,
+ *             truncated as engine.cpp:1583 does) at the tempo in force at the call; ceil(n_frames / F) blocks are rendered,
+ *             the frames of the last block past n_frames are dropped; every sample has exactly n_frames frames (*frames_out,
+ *             may be NULL) plus the pool's 16 zero frames of padding
+ *   rendered  is, by definition, what   wbx_engine_set_playhead_position(min_time), wbx_engine_play, K blocks,
+ *             wbx_engine_stop, wbx_engine_set_playhead_position(the playhead before the call)   renders; the transport,
+ *             sampler and sequencer state, parameter rings and edit count afterwards are what that sequence leaves, and the
+ *             blocks of a bounce count into wbx_engine_levels like those of any render.  More blocks than
+ *             wbx_config.max_blocks are rendered in consecutive passes whose sampler state continues, like consecutive
+ *             wbx_engine_render calls; the samples do not depend on where the passes are cut
+ *   sources   WBX_BOUNCE_TRACK, post-fader: the block buffer Track::process leaves — the stream calls summed in order
+ *             (sampler.cpp:56,152), times fl(volume * pan_coeffs[c]) (track.cpp:728-731; 0 when muted: a negative sample
+ *             becomes -0.0f as in the reference); pre-fader: the same buffer before that multiplication.  WBX_BOUNCE_BUS:
+ *             the bus sum as wbx_fetch reports it.  WBX_BOUNCE_MASTER (index 0): the master as wbx_fetch reports it,
+ *             clamped.  The same signal may be named more than once; order and duplicates of src[] are kept
+ *   refusals  (nothing published, transport untouched, wbx_clip_pool_stats unchanged)  WBX_ERR_UNSUPPORTED while playing or
+ *             recording, on a redirected master (wbx_set_master_target, wbx_set_master_init; wbx_set_master_format when the
+ *             master is a source) or a multi-GPU context, and for a range of 2^31-16 frames or more; WBX_ERR_INVALID for n_src == 0, max_time <= min_time, a range of no
+ *             frame, a track or bus index out of range, a tap on a bus or the master; the pool's own status (WBX_ERR_OOM,
+ *             WBX_ERR_DEVICE) when it cannot hold n_src more samples — what had been allocated goes back to the pool
+ *             (bytes_live as before; slabs the pool took from the driver for it stay reserved, empty, until the context
+ *             goes — under wbx_clip_pool_limit none is taken); WBX_ERR_OVERFLOW when the pool's 2^24 sample ids would run out
+ * Takes the editor lock for its duration, like every other edit call.  A device error in the middle of the passes returns
+ * that error with the transport stopped at the playhead before the call and nothing published. */
+enum { WBX_BOUNCE_TRACK = 0, WBX_BOUNCE_BUS = 1, WBX_BOUNCE_MASTER = 2 };
+enum { WBX_TAP_POST_FADER = 0, WBX_TAP_PRE_FADER = 1 };   /* tracks only */
+typedef struct wbx_bounce_source {
+  int32_t kind;      /* WBX_BOUNCE_* */
+  uint32_t index;    /* track or bus; 0 for the master */
+  int32_t tap;       /* WBX_TAP_* */
+  uint32_t _pad;
+} wbx_bounce_source;
+wbx_status wbx_engine_bounce(wbx_engine* e, double min_time, double max_time, const wbx_bounce_source* src, uint32_t n_src,
+                             uint32_t* samples_out, uint64_t* frames_out);
+/* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
+ * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
+wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);
+
 /* Transport after the last process/render (engine.h:44-46), for bit-exact checks. */
 wbx_status wbx_engine_transport(wbx_engine* e, double* playhead, double* sample_position, int* playing);
 /* VUMeter::level per track/channel: max since the last call (vu_meter.h:20-40). levels: [n_tracks][C]. */

@@ -288,6 +288,16 @@ struct Engine {
   }
   void play() { check(wbx_engine_play(h), "play"); }
   void stop() { check(wbx_engine_stop(h), "stop"); }
+  // Bounce (no reference counterpart: its export dialog has nothing behind it): render [min_time, max_time) offline and
+  // keep the named signals — tracks post- or pre-fader, buses, the master — as sample ids usable in add_audio_clip
+  // (AudioClip::asset), wbx_clip_download and wbx_engine_delete_sample.  Returns the ids in the order of `sources`;
+  // *frames (optional) receives every sample's length.  Semantics and refusals: wbx_engine_bounce, wbx.h.
+  std::vector<uint32_t> bounce(double min_time, double max_time, const std::vector<wbx_bounce_source>& sources,
+                               uint64_t* frames = nullptr) {
+    std::vector<uint32_t> ids(sources.size());
+    check(wbx_engine_bounce(h, min_time, max_time, sources.data(), (uint32_t)sources.size(), ids.data(), frames), "bounce");
+    return ids;
+  }
   // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
   // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
   void record() { check(wbx_engine_record(h), "record"); }

@@ -48,6 +48,10 @@ class RecordInfo(C.Structure):
                 ("_pad", C.c_uint32)]
 
 
+class BounceSource(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("index", C.c_uint32), ("tap", C.c_int32), ("_pad", C.c_uint32)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -58,6 +62,8 @@ class PlanRecord(C.Structure):
 FMT = {"i16": 3, "i24": 5, "i32": 7, "f32": 9}
 # TrackInputType (track_input.h:10-15) -> WBX_INPUT_*
 INPUT_TYPE = {"none": 0, "midi": 1, "external_stereo": 2, "external_mono": 3}
+BOUNCE_KIND = {"track": 0, "bus": 1, "master": 2}     # WBX_BOUNCE_*
+BOUNCE_TAP = {"post": 0, "pre": 1}                      # WBX_TAP_*
 OUT_FMT = {"i16": 3, "i24": 5, "i24_x8": 6, "i32": 7, "f32": 9}
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
@@ -164,6 +170,8 @@ SYMBOLS = {
     "wbx_engine_process_in": (C.c_int, [_vp, _fpp, _u32, _fpp]),
     "wbx_engine_process_interleaved_in": (C.c_int, [_vp, _fpp, _u32, C.c_int, _vp]),
     "wbx_engine_render": (C.c_int, [_vp, _u32]),
+    "wbx_engine_bounce": (C.c_int, [_vp, _d, _d, C.POINTER(BounceSource), _u32, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
+    "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
     "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),
     "wbx_engine_arm_track_recording": (C.c_int, [_vp, _u32, C.c_int]),

@@ -50,6 +50,27 @@ struct RecCaptureArgs {
   uint32_t frames, in_channels, n_takes, table_cap, chunk_frames;
 };
 void launch_record_capture(const RecCaptureArgs& a, hipStream_t s);
+// bouncing (wbx_bounce.hip): the blocks of one render pass -> the destination clips of the signals asked for
+struct StemSrc {               // one signal of a bounce (32 B, read as eight broadcast dwords)
+  float* dst[2];               // the destination clip's channel rows (planar, frame 0); mono: dst[1] unused
+  uint32_t kind, index, tap;   // WBX_BOUNCE_* / track or bus index / WBX_TAP_*
+  uint32_t _pad;
+};
+static_assert(sizeof(StemSrc) == 32, "StemSrc must be 32 bytes");
+struct StemArgs {
+  const StemSrc* src;          // device: [n_src]
+  const DRow* rows;            // the pass's plan: [n_blocks][n_tracks] rows, their templates, the overflow pool
+  const DTrackBlock* tmpl;
+  const DSeg* pool;
+  const float* gains;          // device: [n_tracks][2] fl(volume * pan_coeffs[c]), the pass's gain row
+  const float* master;         // the pass's results: [n_blocks][C][F] (clamped), [n_blocks][n_buses][C][F]; null: silence
+  const float* buses;
+  uint64_t first_frame;        // destination frame of the pass's first block
+  uint64_t n_frames;           // frames of every destination clip: what lies past them is dropped
+  uint32_t n_src, n_blocks, n_tracks, n_buses, block_frames, channels;
+  uint32_t tmpl_cap, pool_chunks;
+};
+void launch_stem(const StemArgs& a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -130,6 +151,8 @@ struct wbx_ctx {
   std::vector<std::unique_ptr<ClipSlab>> slabs;   // clip storage (slab_mu: clips are built outside the editor lock)
   std::mutex slab_mu;
   std::atomic<uint32_t> slab_seq{0};  // clips placed so far (seeds the gap in front of the next one)
+  std::atomic<uint64_t> pool_limit{0};   // wbx_clip_pool_limit: bytes the pool may reserve from the driver, 0 = no bound
+  std::atomic<uint64_t> own_alloc_bytes{0};   // ... of which: clips with an allocation of their own
   DevBuf<DSample> d_samples;
   bool samples_dirty = true;
 
@@ -334,7 +357,8 @@ inline size_t fmt_bytes(int fmt) {
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 enum : int { CLIP_SRC_PLANAR = 0, CLIP_SRC_INTERLEAVED_HOST = 1, CLIP_SRC_INTERLEAVED_DEVICE = 2, CLIP_SRC_SYNTH = 3,
-             CLIP_SRC_ZERO = 4 /* every frame zero, asynchronous on `on` (take chunks, recorded clips before their gather) */ };
+             CLIP_SRC_ZERO = 4 /* every frame zero, asynchronous on `on` (take chunks, recorded clips before their gather) */,
+             CLIP_SRC_NONE = 5 /* only the padding is zeroed, asynchronous on `on`: a kernel writes every frame (bounced clips) */ };
 struct ClipFill {           // where a new clip's audio comes from
   int kind;
   const void* const* planar;   // CLIP_SRC_PLANAR: host channel arrays

@@ -1112,6 +1112,133 @@ extern "C" wbx_status wbx_engine_render(wbx_engine* e, uint32_t K) {
   return render_locked(e, K);
 }
 
+// ---- bouncing ----------------------------------------------------------------------------------------------------------
+// wbx_engine_bounce: the range is rendered by the ordinary passes (render_locked: sequencer, pre-render, mix, sum — the
+// levels and every bit of state are then those of the defining sequence, HostSession::bounce_locked), and behind each pass
+// stem_kernel (wbx_bounce.hip) writes the signals asked for into their destination clips from the pass's own plan and
+// result buffers.  The host waits for each pass: the plan buffers, the gain row and the result buffers a stem kernel reads
+// are then never handed to a later render before it is done, and the pass's plan status is looked at like wbx_fetch does.
+namespace {
+
+struct BounceDev {
+  wbx_engine* e;
+  const wbx_bounce_source* src;
+  uint32_t n_src;
+  std::vector<ClipSlot> slots;
+  DevBuf<StemSrc> d_src;
+  DevBuf<float> d_gains;
+  uint64_t n_frames = 0;
+  bool uploaded = false;
+
+  ~BounceDev() {
+    d_src.release();
+    d_gains.release();
+  }
+  wbx_status alloc(uint32_t i, uint64_t frames) {
+    wbx_ctx* c = e->ctx;
+    if (slots.empty()) slots.resize(n_src);
+    n_frames = frames;
+    ClipFill fill{};
+    fill.kind = CLIP_SRC_NONE;   // the stem kernel writes every frame; only the padding is cleared
+    return cfail(e, clip_build(c, slots[i], WBX_FMT_F32, c->cfg.channels, c->cfg.sample_rate, frames, fill, c->stream));
+  }
+  void release(uint32_t i) {
+    (void)sync_main(e->ctx);   // (nothing may still write the clip)
+    clip_release(e->ctx, slots[i]);
+  }
+  uint32_t publish(uint32_t i) {   // stop_record's path: the next free id of the pool, the session's sample table
+    wbx_ctx* c = e->ctx;
+    const uint32_t id = (uint32_t)c->clips.size();
+    const uint32_t channels = slots[i].d.channels;
+    (void)clip_publish(c, id, slots[i]);   // (a fresh id below 2^24 — wbx_engine_bounce checked the room for all of them — cannot fail)
+    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize((size_t)id + (n_src - i));   // once per bounce
+    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, channels, c->cfg.sample_rate, n_frames, true};
+    return id;
+  }
+  wbx_status pass(uint32_t first_block, uint32_t k) {
+    wbx_ctx* c = e->ctx;
+    const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
+    wbx_status st = render_locked(e, k);
+    if (st != WBX_OK) return st;
+    const uint32_t N = e->hs.n_tracks();
+    hipStream_t s = c->stream;
+    // the main stream behind this pass's sum (the event wbx_master_ready uses) and a mix on the alternate stream
+    WBX_EHIP(e, join_sum(c));
+    WBX_EHIP(e, join_alt(c));
+    if (!uploaded) {
+      std::vector<StemSrc> h(n_src);
+      for (uint32_t i = 0; i < n_src; i++) {
+        h[i].dst[0] = (float*)slots[i].d.ch[0];
+        h[i].dst[1] = (float*)slots[i].d.ch[1];
+        h[i].kind = (uint32_t)src[i].kind;
+        h[i].index = src[i].index;
+        h[i].tap = (uint32_t)src[i].tap;
+        h[i]._pad = 0;
+      }
+      WBX_EHIP(e, d_src.ensure(n_src));
+      WBX_EHIP(e, hipMemcpy(d_src.p, h.data(), h.size() * sizeof(StemSrc), hipMemcpyHostToDevice));
+      uploaded = true;
+    }
+    wbx_ctx::PlanBuf& B = PB(c);
+    StemArgs a{};
+    a.src = d_src.p;
+    a.first_frame = (uint64_t)first_block * F;
+    a.n_frames = n_frames;
+    a.n_src = n_src;
+    a.n_blocks = k;
+    a.n_tracks = N;
+    a.block_frames = F;
+    a.channels = C;
+    if (N) {   // (an empty session has no plan: its master is silence, it has no track to name)
+      WBX_EHIP(e, d_gains.ensure(std::max<size_t>((size_t)N * 2, 2)));
+      WBX_EHIP(e, hipMemcpyAsync(d_gains.p, e->h_gains[e->gains_slot], (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+      a.rows = B.prows.p;
+      a.tmpl = B.tmpl.p;
+      a.tmpl_cap = B.tmpl_cap;
+      a.pool = B.pool.p;
+      a.pool_chunks = B.pool_chunks;
+      a.gains = d_gains.p;
+      a.n_buses = c->n_buses;
+      a.buses = c->n_buses ? c->last_buses : nullptr;
+    }
+    a.master = c->last_master;
+    if ((uint64_t)n_src * k > 0x7FFFFFFFull) return efail(e, WBX_ERR_UNSUPPORTED, "bounce: more than 2^31 (source, block) pairs in one pass");
+    launch_stem(a, s);
+    WBX_EHIP(e, hipGetLastError());
+    WBX_EHIP(e, sync_main(c));
+    drain_events(c);
+    if (N) {
+      uint32_t pc[4] = {0, 0, 0, 0};
+      WBX_EHIP(e, hipMemcpy(pc, B.counters, sizeof(pc), hipMemcpyDeviceToHost));
+      st = plan_status_to_error(c, pc[1]);
+      if (st == WBX_OK) st = render_status(c);
+      if (st != WBX_OK) return cfail(e, st);
+    }
+    return WBX_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" wbx_status wbx_engine_bounce(wbx_engine* e, double min_time, double max_time, const wbx_bounce_source* src,
+                                        uint32_t n_src, uint32_t* samples_out, uint64_t* frames_out) {
+  if (!e) return WBX_ERR_INVALID;
+  wbx_ctx* c = e->ctx;
+  LockGuard g(e->hs.editor_lock);
+  tls_err.clear();
+  (void)hipSetDevice(c->cfg.device);
+  bool master_src = false;
+  for (uint32_t i = 0; src && i < n_src; i++) master_src |= src[i].kind == WBX_BOUNCE_MASTER;
+  const bool redirected = c->master_target || c->dist || c->master_init || (master_src && c->master_format);
+  if ((uint64_t)c->clips.size() + n_src > (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "bounce: the pool's sample ids (2^24) would run out");
+  BounceDev dev{e, src, n_src};
+  const char* why = "";
+  const wbx_status st = e->hs.bounce_locked(min_time, max_time, src, n_src, c->cfg.block_frames, c->cfg.max_blocks, redirected,
+                                            dev, samples_out, frames_out, &why);
+  if (st != WBX_OK && why[0]) return efail(e, st, why);
+  return st;
+}
+
 // ---- recording ---------------------------------------------------------------------------------------------------------
 // Engine::record / stop_record / arm_track_recording / set_track_input (engine.cpp:95-200) and the recorder tap of
 // Engine::process (engine.cpp:1638-1649).  Who records what, record_min_time / record_max_time and the frame count are the

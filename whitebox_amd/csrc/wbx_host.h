@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/wbx.h"
 #include "wbx_clip_edit.h"
 #include "wbx_dev.h"
 
@@ -753,6 +754,113 @@ struct HostSession {
     const size_t stranded = (size_t)((lanes > 1u ? 8u : template_reserve(K)) + (lanes > 1u ? 3u : 1u)) * n_tracks() * lanes;
     if (any_crawl_clip) return 2 * all + stranded;
     return std::min(2 * all, 2 * boundary_blocks_hint(K) + 3 * (size_t)n_tracks() + 64) + stranded;
+  }
+
+  // ---- bouncing (wbx_engine_bounce), under the lock ----
+  // A bounce renders [min_time, max_time) offline and keeps signals of it as samples.  What it renders and what it leaves
+  // behind are, by definition, those of  set_playhead_position(min_time), play(), K blocks, stop(),
+  // set_playhead_position(the playhead before the call)  through the ordinary calls: bounce_locked makes exactly these
+  // calls on the session, with the device work (destination clips, one render pass + stem kernel, publishing) behind `Dev`,
+  // so that the CPU-side harness (tests/cpp/bounce_sim.cpp) drives the product's own code.
+  //   length   n_frames = (uint64_t)(int64_t)beat_to_samples(max_time - min_time) at the tempo in force (core_math.h:209-212,
+  //            truncated like engine.cpp:1583); K = ceil(n_frames / F) blocks, the last one cut at n_frames
+  //   passes   consecutive renders of at most max_blocks blocks whose sampler state continues
+  //   refusals nothing allocated, transport untouched: playing / recording / redirected master -> UNSUPPORTED; no source,
+  //            an empty range, no frame, an index out of range, a tap on a bus or the master -> INVALID
+  static uint64_t bounce_frames(double min_time, double max_time, double sample_rate, double bd) {
+    const double sec = (max_time - min_time) * bd;      // beat_to_samples, core_math.h:209-212: two separately
+    const double samples = sec * sample_rate;           // rounded multiplies
+    if (!(samples >= 0.0)) return 0;
+    if (!(samples < 9.0e18)) return ~0ull;
+    return (uint64_t)(int64_t)samples;
+  }
+  struct BouncePlan {
+    uint64_t n_frames = 0;
+    uint32_t n_blocks = 0;
+  };
+  wbx_status bounce_check_locked(double min_time, double max_time, const wbx_bounce_source* src, uint32_t n_src,
+                                 uint32_t block_frames, bool redirected, BouncePlan* out, const char** why) const {
+    *why = "";
+    if (playing.load(std::memory_order_relaxed) || recording) {
+      *why = "bounce: not while playing or recording (a bounce is an offline operation)";
+      return WBX_ERR_UNSUPPORTED;
+    }
+    if (redirected) {
+      *why = "bounce: not with a redirected master / a multi-GPU exchange";
+      return WBX_ERR_UNSUPPORTED;
+    }
+    if (!src || n_src == 0) {
+      *why = "bounce: no source";
+      return WBX_ERR_INVALID;
+    }
+    if (!(max_time > min_time)) {
+      *why = "bounce: max_time <= min_time";
+      return WBX_ERR_INVALID;
+    }
+    for (uint32_t i = 0; i < n_src; i++) {
+      const wbx_bounce_source& b = src[i];
+      const bool ok = b.kind == WBX_BOUNCE_TRACK   ? (b.index < n_tracks() && (b.tap == WBX_TAP_POST_FADER || b.tap == WBX_TAP_PRE_FADER))
+                      : b.kind == WBX_BOUNCE_BUS   ? (b.index < n_buses && b.tap == WBX_TAP_POST_FADER)
+                      : b.kind == WBX_BOUNCE_MASTER ? (b.index == 0 && b.tap == WBX_TAP_POST_FADER)
+                                                    : false;
+      if (!ok) {
+        *why = "bounce: a source's kind, index or tap is out of range (taps are for tracks)";
+        return WBX_ERR_INVALID;
+      }
+    }
+    const uint64_t n = bounce_frames(min_time, max_time, (double)dst_rate, beat_duration.load(std::memory_order_relaxed));
+    if (n == 0) {
+      *why = "bounce: the range holds no frame";
+      return WBX_ERR_INVALID;
+    }
+    if (n >= 2147483632ull) {
+      *why = "bounce: a range longer than 2^31-16 frames";
+      return WBX_ERR_UNSUPPORTED;
+    }
+    out->n_frames = n;
+    out->n_blocks = (uint32_t)((n + block_frames - 1) / block_frames);
+    return WBX_OK;
+  }
+  // Dev:  wbx_status alloc(uint32_t i, uint64_t n_frames)      destination clip of source i
+  //       wbx_status pass(uint32_t first_block, uint32_t k)    render k blocks (advancing the transport) and keep the sources
+  //       uint32_t   publish(uint32_t i)                       -> engine sample id          void release(uint32_t i)
+  template <class Dev>
+  wbx_status bounce_locked(double min_time, double max_time, const wbx_bounce_source* src, uint32_t n_src,
+                           uint32_t block_frames, uint32_t max_blocks, bool redirected, Dev& dev, uint32_t* samples_out,
+                           uint64_t* frames_out, const char** why) {
+    BouncePlan p;
+    wbx_status st = bounce_check_locked(min_time, max_time, src, n_src, block_frames, redirected, &p, why);
+    if (st != WBX_OK) return st;
+    if (!samples_out || max_blocks == 0) return WBX_ERR_INVALID;
+    // every destination first: a pool that cannot hold them refuses before the transport moves
+    for (uint32_t i = 0; i < n_src; i++) {
+      st = dev.alloc(i, p.n_frames);
+      if (st != WBX_OK) {
+        for (uint32_t j = 0; j < i; j++) dev.release(j);
+        return st;
+      }
+    }
+    const double before = playhead;
+    set_playhead_position_locked(min_time);
+    note_edit_locked();
+    play_locked();
+    note_edit_locked();
+    for (uint32_t done = 0; done < p.n_blocks && st == WBX_OK;) {
+      const uint32_t k = std::min(max_blocks, p.n_blocks - done);
+      st = dev.pass(done, k);
+      done += k;
+    }
+    stop_locked();
+    note_edit_locked();
+    set_playhead_position_locked(before);
+    note_edit_locked();
+    if (st != WBX_OK) {
+      for (uint32_t i = 0; i < n_src; i++) dev.release(i);
+      return st;
+    }
+    for (uint32_t i = 0; i < n_src; i++) samples_out[i] = dev.publish(i);
+    if (frames_out) *frames_out = p.n_frames;
+    return WBX_OK;
   }
 
   // the transport advance of Engine::process for K blocks (engine.cpp:1578-1585, :1619-1623), the arithmetic the plan

@@ -913,7 +913,10 @@ extern "C" const char* wbx_last_error(const wbx_ctx* c) { return c ? c->err.c_st
 namespace wbx {
 
 void clip_release(wbx_ctx* c, ClipSlot& s) {
-  if (s.alloc) (void)hipFree(s.alloc);
+  if (s.alloc) {
+    (void)hipFree(s.alloc);
+    c->own_alloc_bytes.fetch_sub(s.stride * s.d.channels, std::memory_order_relaxed);
+  }
   if (s.slab) {
     std::lock_guard<std::mutex> g(c->slab_mu);
     ClipSlab& sl = *s.slab;
@@ -972,6 +975,12 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
     const uint32_t span = (uint32_t)std::min<size_t>(16, body / kGranule / 8 + 1);
     const size_t gap = jitter ? (size_t)((((c->slab_seq.fetch_add(1u, std::memory_order_relaxed) + 1u) * 2654435761u) >> 8) % span) * kGranule : 0;
     const size_t need = body + gap;
+    const uint64_t limit = c->pool_limit.load(std::memory_order_relaxed);   // wbx_clip_pool_limit
+    auto reserved_now = [&]() {   // (slab_mu held)
+      uint64_t r = c->own_alloc_bytes.load(std::memory_order_relaxed);
+      for (auto& sl : c->slabs) r += sl->size;
+      return r;
+    };
     if (use_slabs && need <= kSlab / 4) {   // (slab sizes grow 64 MiB, 256 MiB, 1 GiB, 1 GiB ...: small sessions stay small)
       std::lock_guard<std::mutex> g(c->slab_mu);
       ClipSlab* sl = nullptr;
@@ -996,7 +1005,12 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
         std::unique_ptr<ClipSlab> fresh(new (std::nothrow) ClipSlab());
         if (!fresh) return WBX_ERR_OOM;
         const size_t grown = c->slabs.size() >= 2 ? kSlab : ((size_t)64 << 20) << (2 * c->slabs.size());
-        const size_t sz = std::max(grown, need);
+        size_t sz = std::max(grown, need);
+        if (limit) {   // a bounded pool: the usual slab if it fits, else one just large enough, else none
+          const uint64_t have = reserved_now();
+          if (have + sz > limit) sz = need;
+          if (have + sz > limit) return fail(c, WBX_ERR_OOM, "clip pool limit reached (wbx_clip_pool_limit)");
+        }
         if (hipMalloc((void**)&fresh->mem, sz) == hipSuccess) {
           fresh->size = sz;
           c->slabs.push_back(std::move(fresh));
@@ -1019,8 +1033,13 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
       }
     }
     if (!s.slab) {
+      if (limit) {
+        std::lock_guard<std::mutex> g(c->slab_mu);
+        if (reserved_now() + stride * channels > limit) return fail(c, WBX_ERR_OOM, "clip pool limit reached (wbx_clip_pool_limit)");
+      }
       WBX_HIP(c, hipMalloc(&s.alloc, stride * channels));
       s.base = s.alloc;
+      c->own_alloc_bytes.fetch_add(stride * channels, std::memory_order_relaxed);
     }
   }
   s.d.ch[0] = s.base;
@@ -1054,6 +1073,9 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
       break;
     case CLIP_SRC_ZERO:
       for (uint32_t ch = 0; ch < channels && err == hipSuccess; ch++) err = hipMemsetAsync((char*)s.base + stride * ch, 0, stride, on);
+      break;
+    case CLIP_SRC_NONE:
+      pad_tails();
       break;
     case CLIP_SRC_INTERLEAVED_DEVICE:
       pad_tails();
@@ -1297,6 +1319,12 @@ extern "C" wbx_status wbx_clip_pool_stats(wbx_ctx* c, uint32_t* n_slabs, uint64_
   if (n_slabs) *n_slabs = (uint32_t)c->slabs.size();
   if (bytes_reserved) *bytes_reserved = reserved;
   if (bytes_live) *bytes_live = live;
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_clip_pool_limit(wbx_ctx* c, uint64_t max_bytes_reserved) {
+  if (!c) return WBX_ERR_INVALID;
+  c->pool_limit.store(max_bytes_reserved, std::memory_order_relaxed);
   return WBX_OK;
 }
 

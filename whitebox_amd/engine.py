@@ -145,6 +145,16 @@ class MixContext:
         _check(self.L.wbx_clip_synth(self.h, clip, _ffi.FMT[fmt], channels, rate, frames, seed, key_track,
                                      np.float32(amp)), "wbx_clip_synth", self.h)
 
+    def pool_stats(self):
+        """(slabs, bytes reserved from the driver, bytes held by live clips) of the clip pool"""
+        n, r, l = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(self.L.wbx_clip_pool_stats(self.h, C.byref(n), C.byref(r), C.byref(l)), "wbx_clip_pool_stats", self.h)
+        return n.value, r.value, l.value
+
+    def pool_limit(self, max_bytes_reserved: int):
+        """bound what the clip pool reserves from the driver (0: no bound); a clip past it fails with WBX_ERR_OOM"""
+        _check(self.L.wbx_clip_pool_limit(self.h, max_bytes_reserved), "wbx_clip_pool_limit", self.h)
+
     def set_routing(self, track_bus: Optional[Sequence[int]], n_buses: int, n_tracks: int):
         if track_bus is None or not n_buses:
             _check(self.L.wbx_set_routing(self.h, n_tracks, None, 0), "wbx_set_routing", self.h)
@@ -310,6 +320,7 @@ class Engine:
         self.ctx = MixContext(max_tracks, max_blocks, buffer_size, output_channels, sample_rate,
                               _handle=C.c_void_p(self.L.wbx_engine_ctx(h)))
         self.n_buses = 0
+        self.max_blocks = max_blocks
 
     def close(self):
         if self.h:
@@ -533,6 +544,30 @@ class Engine:
         """K consecutive blocks in one device pass; fetch with self.ctx.fetch()."""
         _check(self.L.wbx_engine_render(self.h, n_blocks), "wbx_engine_render", self.h, True)
         self.ctx.last = (n_blocks, len(self.tracks))
+
+    def bounce(self, min_time: float, max_time: float, sources: Sequence) -> tuple:
+        """wbx_engine_bounce: render [min_time, max_time) offline and keep signals of it as samples in the clip pool.
+        sources: ("track", index[, "post" | "pre"]), ("bus", index), ("master",) — or the raw (kind, index, tap) integers;
+        order and duplicates are kept.  Returns (sample ids, frames of each); the ids go into add_audio_clip,
+        bounce_download, ctx.build_mipmaps, delete_sample."""
+        arr = (_ffi.BounceSource * max(1, len(sources)))()
+        for i, s in enumerate(sources):
+            s = tuple(s)
+            kind = _ffi.BOUNCE_KIND.get(s[0], s[0])
+            index = s[1] if len(s) > 1 else 0
+            tap = s[2] if len(s) > 2 else 0
+            arr[i] = _ffi.BounceSource(kind, index, _ffi.BOUNCE_TAP.get(tap, tap), 0)
+        ids = (C.c_uint32 * max(1, len(sources)))()
+        frames = C.c_uint64()
+        _check(self.L.wbx_engine_bounce(self.h, min_time, max_time, arr, len(sources), ids, C.byref(frames)),
+               "wbx_engine_bounce", self.h, True)
+        K = -(-frames.value // self.audio_buffer_size)
+        self.ctx.last = (K % self.max_blocks or self.max_blocks, len(self.tracks))   # the last pass is what a fetch sees
+        return list(ids[:len(sources)]), frames.value
+
+    def bounce_download(self, sample: int, frames: int) -> np.ndarray:
+        """a bounced sample back on the host: [C][frames] fp32 (wbx_clip_download per channel)"""
+        return np.stack([self.ctx.clip_download(sample, c, frames, np.float32) for c in range(self.num_output_channels)])
 
     def transport(self):
         ph, sp, pl = C.c_double(), C.c_double(), C.c_int()
