@@ -16,6 +16,7 @@
 #include "../../include/wbx.h"
 #include "../../whitebox_amd/csrc/wbx_host.h"
 #include "../../whitebox_amd/csrc/wbx_seq.h"
+#include "../../whitebox_amd/csrc/wbx_shape.h"
 
 using namespace wbx;
 
@@ -331,6 +332,46 @@ int hsim_render(HostSim* s, uint32_t K) {
     for (uint32_t t = 0; t < N; t++) plan_track(a, t, times.data());
   }
   hs.advance_transport_locked(K, F, beat_duration);
+  return WBX_OK;
+}
+
+// The shape of a render of K blocks of this session (wbx_shape.h: the mix instance and what follows from it): the session's
+// facts as render_locked fills them (HostSession::shape_facts), the clip table's as upload_tables derives them, the group
+// size as wbx_create resolves it, the knobs read from the environment by the reader wbx_create calls.  The harness has no
+// routing: the caller says how many buses there are and how many tracks the longest member list holds.
+struct HsimShape {
+  char mix[64], callback[64];   // the instances' names as nm -C spells them
+  uint32_t family, masked_rows, walks_lists, chained, blocks_per_workgroup, mix_sb, cb_one_launch, cb_lane_span;
+};
+int hsim_render_shape(HostSim* s, uint32_t K, uint32_t group_size, uint32_t n_buses, uint32_t longest_list, int in_process, HsimShape* out) {
+  if (K == 0 || K > s->max_blocks) return WBX_ERR_INVALID;
+  LockGuard g(s->hs.editor_lock);
+  ShapeFacts f;
+  f.channels = s->channels;
+  f.block_frames = s->block_frames;
+  f.auto_group = group_size == 0;
+  f.group_size = group_size ? group_size : s->max_blocks == 1 ? kStage / 2 : kStage;
+  f.session = s->hs.shape_facts();
+  for (const DSample& d : s->samples) {
+    if (d.format != FMT_F32) f.integer_clips = true;
+    if (d.format != FMT_I16) f.non16_clips = true;
+  }
+  f.n_buses = n_buses;
+  f.longest_list = longest_list;
+  f.n_blocks = K;
+  f.n_tracks = s->hs.n_tracks();
+  f.callback = in_process != 0 && !s->hs.any_slow_clip;
+  const RenderShape r = choose_shape(ShapeKnobs::from_env(), f);
+  r.mix.name(out->mix, sizeof(out->mix));
+  r.cb.name(out->callback, sizeof(out->callback));
+  out->family = (uint32_t)r.family;
+  out->masked_rows = r.masked_rows;
+  out->walks_lists = r.walks_lists;
+  out->chained = r.chained;
+  out->blocks_per_workgroup = r.blocks_per_workgroup;
+  out->mix_sb = r.mix.SB;
+  out->cb_one_launch = r.cb_one_launch;
+  out->cb_lane_span = r.cb_lane_span;
   return WBX_OK;
 }
 

@@ -14,12 +14,18 @@ from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "host_sim.cpp")
-HDRS = [os.path.join(ROOT, "whitebox_amd", "csrc", h) for h in ("wbx_host.h", "wbx_seq.h", "wbx_clip_edit.h", "wbx_dev.h")]
+HDRS = [os.path.join(ROOT, "whitebox_amd", "csrc", h) for h in ("wbx_host.h", "wbx_seq.h", "wbx_clip_edit.h", "wbx_dev.h", "wbx_shape.h")]
 BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
 # no FMA contraction (the reference build has none), and the records are viewed as 16-B quads
 FLAGS = ["-std=c++20", "-ffp-contract=off", "-fno-fast-math", "-fno-strict-aliasing", "-Wall"]
 
 _lib = None
+
+
+class RenderShape(C.Structure):
+    """hsim_render_shape's result (tests/cpp/host_sim.cpp HsimShape)"""
+    _fields_ = [("mix", C.c_char * 64), ("callback", C.c_char * 64)] + [(n, C.c_uint32) for n in (
+        "family", "masked_rows", "walks_lists", "chained", "blocks_per_workgroup", "mix_sb", "cb_one_launch", "cb_lane_span")]
 
 
 def _stale(out: str) -> bool:
@@ -85,6 +91,7 @@ def lib() -> C.CDLL:
             "hsim_gains": [C.POINTER(C.c_float), C.c_uint32],
             "hsim_transport": [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int)],
             "hsim_thread_stats": [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32],
+            "hsim_render_shape": [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(RenderShape)],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -223,6 +230,13 @@ class HostSimEngine:
         ph, sp, pl = C.c_double(), C.c_double(), C.c_int()
         self._ok(self.L.hsim_transport(self.h, C.byref(ph), C.byref(sp), C.byref(pl)))
         return ph.value, sp.value, bool(pl.value)
+
+    def render_shape(self, k, group_size=0, n_buses=0, longest_list=0, in_process=False) -> RenderShape:
+        """the mix instance a render of k blocks takes and what follows from it (wbx_shape.h), the knobs as the environment
+        sets them now; in_process: the one-block callback of Engine::process"""
+        out = RenderShape()
+        self._ok(self.L.hsim_render_shape(self.h, k, group_size, n_buses, longest_list, int(in_process), C.byref(out)))
+        return out
 
     def thread_stats(self):
         n = len(self.tracks)

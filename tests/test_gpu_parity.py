@@ -2089,7 +2089,7 @@ INSTANCE_CASES = [
 @pytest.mark.parametrize("kw,block,expect", INSTANCE_CASES,
                          ids=[f"kw{i}-{block}-{instance_id(expect)}" for i, (_, block, expect) in enumerate(INSTANCE_CASES)])
 def test_instance_selection(kw, block, expect):
-    """Which mix_kernel instance a session takes (wbx_runtime.hip: mix_family, mix_two_channels_per_lane, launch_mix) — and
+    """Which mix_kernel instance a session takes (wbx_shape.h: choose_shape) — and
     that it renders the session like the oracle."""
     spec = synth.make_session("sel", 40, n_blocks=8, block=block, seed=0x5E1EC7, **kw)
     om, opk, _, _, _ = run_oracle(spec, 8)

@@ -81,6 +81,76 @@ def test_census_switches_are_read_by_the_sources():
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# CPU: the choice of the instance (whitebox_amd/csrc/wbx_shape.h), compiled with g++ into the host harness
+# ---------------------------------------------------------------------------------------------------------------------------
+def entry_shape(entry, block=None):
+    """what wbx_shape.h decides for the entry's session (the environment as it stands): the host harness holds the session and
+    fills the facts as the engine does; the routing's two facts come from the recipe"""
+    import host_sim as HS
+    e = IC.Entry(**{**entry.__dict__, "block": block or entry.block})
+    spec = IC.build_spec(e, salt=False)
+    K = 1 if e.callback else e.n_blocks
+    sim = HS.build_sim_engine(spec, max_blocks=K)
+    buses = list(spec.track_bus) if spec.n_buses else [-1] * spec.n_tracks
+    longest = max(sum(1 for b in buses if b == u) for u in range(-1, spec.n_buses))
+    sh = sim.render_shape(K, e.group_size, spec.n_buses, longest, in_process=e.callback)
+    out = {f: getattr(sh, f) for f, _ in sh._fields_}
+    out["mix"], out["callback"] = sh.mix.decode(), sh.callback.decode()
+    sim.close()
+    return out
+
+
+def check_entry_shape(entry):
+    """the function names the entry's instance for the entry's own recipe, and the blocks per workgroup the whole-list
+    threshold counted are the launched instance's own template argument"""
+    for block in ((128, 256, 512) if entry.callback else (entry.block,)):
+        sh = entry_shape(entry, block)
+        if entry.callback:
+            assert sh["cb_one_launch"] == 1 and sh["cb_lane_span"] == 256 // entry.channels, (entry.name, block, sh)
+            assert sh["callback"] == entry.name, (entry.name, block, sh)
+        else:
+            want = entry.mix if entry.name.startswith(IC.S) else entry.name
+            assert sh["mix"] == want, (entry.name, sh)
+            args = [a.strip() for a in want[want.index("<") + 1:-1].split(",")]
+            assert sh["mix_sb"] == int(args[4 if want.startswith(IC.M) else 3]), (entry.name, sh)
+        assert sh["blocks_per_workgroup"] == sh["mix_sb"], (entry.name, block, sh)
+    return sh
+
+
+@pytest.mark.parametrize("entry", IC.CENSUS, ids=[re.sub(r"[^0-9A-Za-z]+", "_", e.name.removeprefix("wbx::")).strip("_")
+                                                  for e in IC.CENSUS])
+def test_the_choice_names_every_entry_for_its_recipe(entry, monkeypatch):
+    assert entry.name.startswith(IC.KINDS) and (entry.mix or not entry.name.startswith(IC.S)), "an entry the check would leave out"
+    if entry.proc_env:   # (switches the library once read per process: a child process, as on the GPU)
+        env = dict(os.environ, **entry.proc_env, **entry.env)
+        code = ("import sys; sys.path[:0] = [%r, %r]; import instance_census as IC, test_instance_census as T; "
+                "T.check_entry_shape([x for x in IC.CENSUS if x.name == %r][0]); print('SHAPE ok')"
+                % (ROOT, os.path.join(ROOT, "tests"), entry.name))
+        r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "SHAPE ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+        return
+    for k, v in entry.env.items():
+        monkeypatch.setenv(k, v)
+    check_entry_shape(entry)
+
+
+def test_the_choice_follows_each_fact_of_a_recipe():
+    """one fact of a recipe flipped names another instance (each of them an entry of its own): the check is seen to look"""
+    base = [e for e in IC.CENSUS if e.name == IC.M + "2, true, 4, 0, 1, 1, 1, 256>"][0]   # fp32 resampled, one clip per track
+    flip = lambda **kw: entry_shape(IC.Entry(**{**base.__dict__, **kw}))
+    assert flip()["mix"] == base.name
+    assert flip(cut=True)["mix"] == IC.M + "2, true, 3, 0, 1, 1, 2, 128>"
+    assert flip(src_rate=48000)["mix"] == IC.M + "4, true, 3, 0, 1, 1, 1, 256>"
+    assert flip(block=256, n_blocks=9)["mix"] == IC.M + "2, true, 4, 0, 2, 1, 1, 256>"
+    assert flip(cut=True)["masked_rows"] == 1 and flip()["masked_rows"] == 1 and flip(block=256, n_blocks=9)["masked_rows"] == 0
+    # ... and the grouping: a long render of a long member list walks it, chained when its length keeps the pieces on one XCD
+    long_ = dict(n_tracks=131, group_size=0, n_blocks=2048, shared_samples=4)
+    assert (flip(**long_)["walks_lists"], flip(**long_)["chained"]) == (1, 1)
+    assert (flip(**{**long_, "n_blocks": 2050})["walks_lists"], flip(**{**long_, "n_blocks": 2050})["chained"]) == (1, 0)
+    assert flip(**{**long_, "group_size": 16})["walks_lists"] == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # GPU: render every entry
 # ---------------------------------------------------------------------------------------------------------------------------
 def _plan_rows(plan):

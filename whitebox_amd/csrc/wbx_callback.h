@@ -282,15 +282,31 @@ __global__ __launch_bounds__(256, 2) void callback_kernel(MixArgs a, PlanArgs p,
   }
 }
 
-#define WBX_CALLBACK(U, FAM)                                                                             \
-  {                                                                                                      \
-    name = "wbx::callback_kernel<" #U ", " #FAM ">";                                                     \
-    hipLaunchKernelGGL((callback_kernel<U, FAM>), dim3(1, a.n_groups, 1), dim3(256), 0, st, a, p, s, cb); \
-  }
+struct CallbackEntry {   // (as MixEntry, wbx_mix.h)
+  MixInstance inst;
+  const char* name;
+  void (*launch)(const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
+};
+#define WBX_CALLBACK(U, FAM)                                                                               \
+  {MixInstance::callback(U, FAM), "wbx::callback_kernel<" #U ", " #FAM ">",                                \
+   [](const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st) {     \
+     hipLaunchKernelGGL((callback_kernel<U, FAM>), dim3(1, a.n_groups, 1), dim3(256), 0, st, a, p, s, cb); \
+   }},
 
-// one per family (wbx_mix_fam<N>.hip); -> the instance's name
-const char* launch_callback_fam0(const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, bool window, hipStream_t st);
-const char* launch_callback_fam1(const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
-const char* launch_callback_fam2(const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
+template <size_t N>
+inline const char* launch_callback_from(const CallbackEntry (&table)[N], const MixInstance& inst, const MixArgs& a, const PlanArgs& p,
+                                        const SumArgs& s, const CallbackArgs& cb, hipStream_t st) {
+  for (const CallbackEntry& e : table)
+    if (e.inst.key() == inst.key()) {
+      e.launch(a, p, s, cb, st);
+      return e.name;
+    }
+  return nullptr;
+}
+
+// one per family (wbx_mix_fam<N>.hip); -> the instance's name, null: the file does not hold it
+const char* launch_callback_fam0(const MixInstance& inst, const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
+const char* launch_callback_fam1(const MixInstance& inst, const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
+const char* launch_callback_fam2(const MixInstance& inst, const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st);
 
 }  // namespace wbx

@@ -17,18 +17,19 @@
 
 #include "../../include/wbx.h"
 #include "wbx_dev.h"
+#include "wbx_shape.h"
 
 namespace wbx {
 void launch_plan(const PlanArgs& a, hipStream_t s);
 void launch_times_copy(const DBlockTime* host_pinned, DBlockTime* dev, uint32_t n_blocks, uint32_t* zero_counters, hipStream_t s);
 void launch_gen(const GenArgs& a, uint32_t max_grid, hipStream_t s);
 void launch_plan_segments(const PlanArgs& a, const SegArgs& g, bool beside, hipStream_t s);
-const char* launch_mix(const MixArgs& a, uint32_t n_blocks, int variant, int family, hipStream_t s, hipEvent_t t0 = nullptr,
-                       hipEvent_t t1 = nullptr);   // -> the instance's name
+const char* launch_mix(const MixInstance& inst, const MixArgs& a, uint32_t grid_z, hipStream_t s, hipEvent_t t0 = nullptr,
+                       hipEvent_t t1 = nullptr);   // -> the instance's name, null: not compiled in
 void launch_sum(const SumArgs& a, uint32_t n_blocks, hipStream_t s);
 // the one-block callback as one launch (wbx_callback.h): sequencer + mix + sum + completion flag -> the instance's name
-const char* launch_callback(const MixArgs& m, const PlanArgs& p, const SumArgs& s, uint32_t* done, uint32_t done_base, uint32_t done_base2, bool spread,
-                            uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, int family, bool window_rows, unsigned long long* dbg, hipStream_t st);
+const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s, uint32_t* done, uint32_t done_base, uint32_t done_base2,
+                            bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st);
 uint32_t callback_spread_limit();      // grids of at most this many workgroups are resident at once (the device's CU count)
 void launch_clamp(float* buf, size_t n, hipStream_t s);
 void launch_clamp_into(const float* src, float* dst, size_t n, int clamp, hipStream_t s);
@@ -83,7 +84,6 @@ constexpr int kEventRing = 64;
 constexpr int kRing = 3;
 constexpr uint32_t kPaceRing = 64;
 constexpr uint32_t kCbDoneWords = 2 * 16 * 64;   // wbx_ctx::d_cb_done: two counters of kCbLanes words, kCbStride apart (wbx_callback.h)
-constexpr uint32_t kOverlapMinBlocks = 8;   // renders shorter than this run plan, mix and sum on the main stream
 
 // Clip audio lives in slabs of 1 GiB carved up in order (64-KiB granules): a session of thousands of clips is a few
 // dozen large allocations, which the driver backs with large contiguous fragments (measured: the mix kernel's launch time
@@ -163,15 +163,11 @@ struct wbx_ctx {
   std::vector<DGroup> groups;         // member lists cut into pieces of group_size tracks (one workgroup per piece and block)
   std::vector<DGroup> groups_exact;   // the member lists whole: the reference's summation order (build_routing)
   bool buses_alias_exact = false;     // buses_alias_partials of groups_exact
-  bool whole_lists_now = false;       // the render being issued takes groups_exact (render_walks_whole_lists)
   uint32_t longest_list = 0;          // tracks in the longest member list
   mutable bool chain_broken = false;  // a chained render reported a failed hand-over (plan_status_to_error)
-  bool chain_now = false;             // ... as chained workgroup-sized pieces (render_chains_groups)
   uint32_t chain_epoch = 0;
   DevBuf<uint32_t> d_chain;           // chained renders: the "running sum is out" words
   uint32_t* d_sticky_status = nullptr;   // failure bits (32 | 64) of every chained render since the last report (render_status)
-  uint32_t exact_min_blocks = 1024;   // renders of at least this many blocks do, when the library picks the grouping
-                                      // (WBX_EXACT_MIN_BLOCKS; 0 = never)
   DevBuf<uint32_t> d_order;
   DevBuf<DGroup> d_groups;
   bool routing_dirty = true;
@@ -250,24 +246,21 @@ struct wbx_ctx {
   uint64_t cb_launches = 0, cb_spread_launches = 0;   // one-launch callbacks issued / ... with the spread sum
   bool seg_broken = false;            // plan_seg_kernel found its XCD layout broken (status bit 7): one lane per track from then on
   uint32_t cb_spin_bound = 40000;     // polls of the spread barrier before a workgroup gives up (~50 ms; WBX_CB_SPIN_BOUND, read at wbx_create)
-  // A/B switches read ONCE, at wbx_create (a test sets the variable and creates a new context): the audio callback never calls
-  // getenv, and what a context decides at plan time (masked rows, lane space) cannot disagree with what it launches
+  // Which mix instance a render takes and what follows from it (wbx_shape.h).  `shape` is assigned ONCE per render — by
+  // render_locked / wbx_submit, from the knobs, the session's facts and the context's state (render_shape) — and read by
+  // everything that launches for that render, the repeats of a callback block included.
+  ShapeKnobs knobs;                   // read once, at wbx_create
+  SessionFacts session;               // of the last render (a bare context: layer 1's "unknown, assume so")
+  RenderShape shape;
+  // further A/B switches, read ONCE at wbx_create like the knobs (the audio callback never calls getenv)
   uint32_t n_xcds = 0;                // the XCD layout probe of wbx_create: 8 / 4 / 2 / 1, or 0 — not round-robin: no chained pieces
                                       // (chain_broken), no segmented sequencer (seg_broken) from the start
-  bool knob_ragged_off = false;       // WBX_RAGGED=0: blocks between the instances' shapes take the general instance
-  bool knob_cb_any_off = false;       // WBX_CB_ANY=0: the one-launch callback only for blocks that are exactly one 256-lane workgroup
   bool knob_no_uniform = false;       // WBX_NO_UNIFORM=1: MixArgs::uniform_speed withheld (the one-ratio modes off)
-  bool knob_masked_rows_off = false;  // WBX_MASKED_ROWS=0: every clip boundary through the pre-render pass
-  bool knob_chain_off = false;        // WBX_CHAIN=0: long renders walk whole member lists instead of chaining 128-track pieces
-  bool knob_no_lean16 = false;        // WBX_NO_LEAN16: sessions of 16-bit PCM only through family 1
-  bool knob_no_fam3 = false;          // WBX_NO_FAM3: resampled-integer sessions through family 1
-  bool knob_no_cl2 = false;           // WBX_NO_CL2: never both channels of a frame in one lane
   bool knob_cb_fenced = false;        // WBX_CB_FENCED=1: release / acquire fences in the one-launch callback
   bool knob_partial_free_off = false; // WBX_PARTIAL_FREE=0: a partial buffer's next user waits for sum_done (behind the master's copy-out), as until round 5
   unsigned dev_event_flags = 0x2;     // hipEventDisableTiming [| hipEventReleaseToDevice]: events only other streams of this device wait for
   bool knob_mix_marker = false;       // WBX_MIX_MARKER=1: mix_done and the pace event as markers on the mix stream (as until round 5)
   bool knob_fast_partial_off = false; // WBX_FAST_PARTIAL=0: every partial stream call through the clamped masked arithmetic (as until round 5)
-  int knob_packed_x = -1;             // WBX_PACKED_X=0|1: the packed masked-row instances off / on for every shape (-1: the library's choice)
   bool cb_no_spread = false;          // a spread launch gave up waiting for the whole grid (not resident at once: a CU mask, a
                                       // device shared with another process): the context keeps to "the last workgroup adds"
   uint32_t cb_flags = 1;              // completion words the launch writes (one, or one per workgroup: cb_flag[0 .. cb_flags))
@@ -297,21 +290,9 @@ struct wbx_ctx {
   bool profiling = true;
   const char* mix_kernel_name = "";   // the instance launch_mix chose last (wbx_kernel_name)
   double last_uniform_speed = 0.0;    // MixArgs::uniform_speed of the last launch (wbx_render_uniform_speed)
-  int mix_unroll = 0;                 // WBX_MIX_VARIANT=10*U+W forces a kernel variant (results are identical);
-                                      // 0 = chosen per render: 24 when resampled or integer-PCM clips are present, else 43
-  bool has_window_clips = true;
   bool has_integer_clips = false;
   bool has_non16_clips = false;       // a clip asset that is not 16-bit PCM
-  bool has_lean16_clips = false;      // resampled clips exist and all of them are 16-bit PCM at speeds up to 0.999 (layer 2)
-  bool has_cut_tracks = true;         // some track holds more than one clip (layer 1: unknown, assume so)
-  bool force_g = false;
-  bool short_render_now = false;      // the render being issued is shorter than kOverlapMinBlocks (the callback path)
-  uint32_t render_blocks_now = 0;     // ... its length in blocks
-  bool has_taps_clips = true;         // ... rows read with per-frame taps (KIND_STRIDE) may occur: the instance must carry MODE_G
-  bool has_stride_clips = true;       // fp32 clips played at speed > 0.999, != 1 may occur (layer 1: unknown, assume so)
   bool auto_group = false;            // wbx_config.group_size was 0: the library picks the track-group size
-  uint32_t masked_rows = 0;           // the current plan holds partial-coverage rows / ROW_PAIRs for the hot loop (layer 2; PlanArgs level)
-  double uniform_speed = 0.0;         // MixArgs::uniform_speed of the next launch (layer 2; 0 for host-sequenced plans)
 
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -383,19 +364,12 @@ wbx_status ensure_result_buffers(wbx_ctx* c, uint32_t K, uint32_t N);
 wbx_status ensure_template_capacity(wbx_ctx* c, size_t n);
 wbx_status ensure_gen_capacity(wbx_ctx* c, size_t rows);
 wbx_status ensure_pool_slack(wbx_ctx* c);   // twice the default overflow pool (renders planned by segments; not when the host fixed max_segments)
-wbx_status launch_pre_render(wbx_ctx* c, uint32_t K, hipStream_t on);
+wbx_status launch_pre_render(wbx_ctx* c, hipStream_t on);
 wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N);
 wbx_status plan_status_to_error(wbx_ctx* c, uint32_t bits);
 wbx_status render_status(wbx_ctx* c);      // the latched hand-over failures of chained renders (the streams must be idle)
 float* begin_master(wbx_ctx* c, hipStream_t writer, hipError_t* err);
-bool render_walks_whole_lists(const wbx_ctx* c, uint32_t K);
-bool render_chains_groups(const wbx_ctx* c, uint32_t K);
-int mix_family(const wbx_ctx* c);
-bool mix_two_channels_per_lane(const wbx_ctx* c);
-uint32_t mix_takes_masked_rows(const wbx_ctx* c, bool window_clips, bool stride_clips);
-bool callback_is_one_launch(const wbx_ctx* c);
-inline uint32_t lane_span_of(const wbx_ctx* c) { return native_lane_span(c->cfg.channels, c->cfg.block_frames >> 2, c->knob_ragged_off); }
-uint32_t callback_lane_span(const wbx_ctx* c);   // lanes per channel of the one-launch callback's 256-lane workgroup, 0: three launches
+RenderShape render_shape(const wbx_ctx* c, uint32_t K, uint32_t N, bool callback);   // choose_shape over the context's facts
 
 // wbx_dist.hip
 float* dist_begin_render(wbx_ctx* c, hipStream_t sum_stream, hipError_t* err);

@@ -176,12 +176,6 @@ uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing
   return len < K ? len : 0u;
 }
 
-// A/B aid (WBX_FORCE_CUT=1): an uncut session through the instances a session cut into clips takes
-bool force_cut_instances() {
-  static const bool on = [] { const char* v = std::getenv("WBX_FORCE_CUT"); return v && v[0] == '1'; }();
-  return on;
-}
-
 bool sample_in_use_cb(void* owner, uint32_t sample) { return static_cast<wbx_engine*>(owner)->hs.sample_referenced(sample); }
 
 }  // namespace
@@ -878,24 +872,20 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   st = ensure_result_buffers(c, K, N);
   if (st != WBX_OK) return cfail(e, st);
 
+  // -- the mix instance of this render and what follows from it (wbx_shape.h): decided here, once, behind upload_tables (which
+  //    reads the clip table's formats) and in front of everything that plans or launches for this render
+  c->session = hs.shape_facts();
+  c->shape = render_shape(c, K, N, e->in_process && !hs.any_slow_clip);
+  const RenderShape& shape = c->shape;
+
   // -- rows for the track-blocks the hot loop cannot stream directly, and the plan's templates
-  c->has_window_clips = hs.any_window_clip;
-  c->has_stride_clips = hs.any_stride_clip;
-  c->has_taps_clips = hs.any_taps_clip;
-  c->has_lean16_clips = hs.any_win16_clip && !hs.any_other_window_clip;
-  c->has_cut_tracks = hs.cut_tracks != 0 || force_cut_instances();
-  c->short_render_now = K < kOverlapMinBlocks;
-  c->render_blocks_now = K;
-  c->whole_lists_now = render_walks_whole_lists(c, K);   // (enters the choice of the mix instance; reads the flags above)
-  c->chain_now = render_chains_groups(c, K);
-  c->masked_rows = mix_takes_masked_rows(c, hs.any_window_clip, hs.any_stride_clip);
   // the sequencer of this render: one lane per track, or — long renders of sessions cut into clips — per (track, segment)
   const uint32_t seg_len = plan_segment_length(e, K, N, playing);
   const uint32_t n_segs = seg_len ? (K + seg_len - 1u) / seg_len : 1u;
   // (segments: a track whose seam missed is planned again from there, and what its replaced segments queued / took from the
   //  pool / reserved stays allocated and unused — room for both versions of every row, so that a miss on a session that leans
   //  on the pre-render pass cannot turn into a capacity error)
-  st = ensure_gen_capacity(c, hs.gen_rows_hint(K, c->masked_rows, ((double)F / (double)c->cfg.sample_rate) / beat_duration) * (seg_len ? 2u : 1u));
+  st = ensure_gen_capacity(c, hs.gen_rows_hint(K, shape.masked_rows, ((double)F / (double)c->cfg.sample_rate) / beat_duration) * (seg_len ? 2u : 1u));
   if (st != WBX_OK) return cfail(e, st);
   if (seg_len) {
     st = ensure_pool_slack(c);
@@ -954,18 +944,8 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   a.clips_changed = hs.clips_edited ? 1u : 0u;
   a.flags_left = e->h_flags_left;
   hs.clips_edited = false;
-  c->short_render_now = K < kOverlapMinBlocks;
-  c->render_blocks_now = K;
-  c->whole_lists_now = render_walks_whole_lists(c, K);   // (enters the choice of the mix instance below)
-  c->chain_now = render_chains_groups(c, K);
   // clip boundaries inside a block stay in the hot loop when the mix instance of this render can take them
-  c->has_window_clips = hs.any_window_clip;
-  c->has_stride_clips = hs.any_stride_clip;
-  c->has_taps_clips = hs.any_taps_clip;
-  c->has_lean16_clips = hs.any_win16_clip && !hs.any_other_window_clip;
-  c->has_cut_tracks = hs.cut_tracks != 0 || force_cut_instances();
-  c->masked_rows = mix_takes_masked_rows(c, hs.any_window_clip, hs.any_stride_clip);
-  a.masked_rows = c->masked_rows;
+  a.masked_rows = shape.masked_rows;
   a.tmpl_reserve = HostSession::template_reserve(K);
   a.lanes = hs.plan_lanes(K);
   a.playhead = hs.playhead;
@@ -977,7 +957,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   //  2 / 1 tracks per wave 12-25 ms: every record look-up at a clip boundary is a memory round trip for its lane)
   static const bool lds_table_for_cut = [] { const char* v = std::getenv("WBX_PLAN_LDS_TABLE"); return !(v && v[0] == '0'); }();
   if (seg_len) a.tmpl_reserve = 8u;   // (a lane plans seg_len blocks, not K: a smaller reservation strands less)
-  if (seg_len || (plan_beside && (!c->has_cut_tracks || !lds_table_for_cut))) {
+  if (seg_len || (plan_beside && (!(hs.cut_tracks != 0 || c->knobs.force_cut) || !lds_table_for_cut))) {
     // Batch render of a session whose tracks are single clips (a steady run per track, a handful of look-ups): the transport
     // records live in device memory and the sequencer takes the register-capped instance — nothing in LDS, a wave no larger
     // than a mix wave, so it runs BESIDE the previous mix instead of in the drain at its end.  Sessions cut into clips
@@ -1016,10 +996,10 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   // looks at the queue counter afterwards and repeats pre-render + mix for the (rare) block that needed it.
   // (sessions whose boundary blocks do go through the pre-render pass take the same bet when the block can be one launch:
   //  a steady block — nearly all — wins two launches, a boundary block pays the repeat)
-  e->gen_skipped = e->in_process && !hs.any_slow_clip && (c->masked_rows || (K == 1u && callback_is_one_launch(c)));
+  e->gen_skipped = e->in_process && !hs.any_slow_clip && (shape.masked_rows || shape.cb_one_launch);
   // ... and then sequencer, mix and sum are ONE launch (wbx_callback.h): every mix workgroup plans its own tracks first, the
   // last one to finish sums the block and tells the host
-  const bool one_launch = e->gen_skipped && K == 1u && callback_is_one_launch(c);
+  const bool one_launch = shape.cb_one_launch;
   B.static_tmpl = one_launch;
   if (one_launch) a.tmpl_reserve = 0u;   // track t owns templates 2t, 2t + 1: no allocation round trip in the latency chain
   if (one_launch) {
@@ -1069,7 +1049,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     e->gains_valid[e->gains_slot] = true;
   }
   if (!e->gen_skipped) {
-    st = launch_pre_render(c, K, ps);
+    st = launch_pre_render(c, ps);
     if (st != WBX_OK) return cfail(e, st);
   }
   if (plan_event) WBX_EHIP(e, hipEventRecord(B.planned, ps));   // (plan and mix on one stream: the mix simply follows)
@@ -1077,11 +1057,6 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   // -- mix (main stream, or the alternate one for every other batch render) + sum, after the plan
   if (plan_event) WBX_EHIP(e, hipStreamWaitEvent(ms, B.planned, 0));
   c->levels_target = reinterpret_cast<uint32_t*>(e->d_levels.p);
-  c->has_window_clips = hs.any_window_clip;
-  c->has_stride_clips = hs.any_stride_clip;
-  c->has_taps_clips = hs.any_taps_clip;
-  c->has_lean16_clips = hs.any_win16_clip && !hs.any_other_window_clip;
-  c->uniform_speed = hs.uniform_window_speed();
   const int mix_parity = (int)(c->render_seq % kRing);
   c->cb_plan = one_launch ? &a : nullptr;
   if (one_launch) {
@@ -1729,7 +1704,7 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       // the block did queue records for the pre-render pass: run it now and mix again (the plan is untouched; the
       // first pass counted those records as silence, so the running levels hold nothing wrong)
       c->zero_status = false;
-      st = launch_pre_render(c, 1, c->stream);
+      st = launch_pre_render(c, c->stream);
       if (st == WBX_OK) st = launch_mix_sum(c, 1, e->hs.n_tracks());
       if (st == WBX_OK && sync_main(c) != hipSuccess) st = WBX_ERR_DEVICE;
       PB(c).counters_zero = false;

@@ -26,6 +26,7 @@
 #include "../../include/wbx.h"
 #include "wbx_clip_edit.h"
 #include "wbx_dev.h"
+#include "wbx_shape.h"
 
 namespace wbx {
 
@@ -237,6 +238,18 @@ struct HostSession {
   double perf_get_usage() const { return perf_clamped(perf_usage.load(std::memory_order_acquire)); }
 
   double uniform_window_speed() const { return window_speed > 0.0 ? window_speed : 0.0; }
+  // what the choice of a render's mix instance reads of the session (wbx_shape.h)
+  SessionFacts shape_facts() const {
+    SessionFacts f;
+    f.window_clips = any_window_clip;
+    f.stride_clips = any_stride_clip;
+    f.taps_clips = any_taps_clip;
+    f.lean16_clips = any_win16_clip && !any_other_window_clip;
+    f.cut_tracks = cut_tracks != 0;
+    f.host_sequenced = false;
+    f.uniform_speed = uniform_window_speed();
+    return f;
+  }
   uint32_t n_tracks() const { return (uint32_t)tracks.size(); }
   bool valid_track(uint32_t t) const { return t < tracks.size(); }
   bool valid_sample(uint32_t s) const { return s < samples.size() && samples[s].used; }

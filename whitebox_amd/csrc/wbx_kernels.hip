@@ -482,21 +482,17 @@ void launch_gen(const GenArgs& a, uint32_t max_grid, hipStream_t s) {
   hipLaunchKernelGGL(gen_kernel, dim3(grid * 4u), dim3(64), 0, s, a);   // (max_grid counts four-wave units)
 }
 
-// which instance of the hot kernel a render takes: the family's translation unit holds the instances
-// (family 0: fp32 + integer PCM at unity speed; 1: everything; 2: sessions of 16-bit PCM only)
-const char* launch_mix(const MixArgs& a, uint32_t n_blocks, int variant, int family, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
-  const uint32_t S4 = a.lane_span;          // (lanes per channel and block of the instance's lane space: F/4, or the next shape above it)
-  const uint32_t lanes = a.channels * S4;   // lanes one block needs
-  const bool full = (lanes % 256u == 0u) && (S4 % 64u == 0u);
-  if (family == 3) return launch_mix_fam3(a, n_blocks, variant, s, t0, t1);   // (falls back to family 1 for shapes it has no instance for)
-  // stereo 256-frame blocks with both channels per lane (families 0 and 2): one wave = one block
-  if (variant >= 1000 && family != 1 && a.channels == 2u && S4 == 64u)
-    return family == 2 ? launch_mix_fam2(a, n_blocks, variant, s, t0, t1) : launch_mix_fam0(a, n_blocks, variant, s, t0, t1);
-  // blocks shorter than a workgroup: the short-block instances exist for the everything family and the lean fp32 one
-  if (!full) return family != 0 ? launch_mix_fam1(a, n_blocks, s, t0, t1) : launch_mix_fam0(a, n_blocks, variant, s, t0, t1);
-  if (family == 1) return launch_mix_fam1(a, n_blocks, s, t0, t1);
-  if (family == 2) return launch_mix_fam2(a, n_blocks, variant, s, t0, t1);
-  return launch_mix_fam0(a, n_blocks, variant, s, t0, t1);
+// the instance the render's shape names (wbx_shape.h), launched: its family's translation unit holds it.  The grid comes from
+// the instance's own blocks per workgroup.  -> its name, null: no such instance is compiled in
+const char* launch_mix(const MixInstance& inst, const MixArgs& a, uint32_t grid_z, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+  const dim3 grid((a.n_blocks + inst.SB - 1u) / inst.SB, a.n_groups, grid_z);
+  switch (inst.FAM) {
+    case 0: return launch_mix_fam0(inst, a, grid, s, t0, t1);
+    case 1: return launch_mix_fam1(inst, a, grid, s, t0, t1);
+    case 2: return launch_mix_fam2(inst, a, grid, s, t0, t1);
+    case 3: return launch_mix_fam3(inst, a, grid, s, t0, t1);
+  }
+  return nullptr;
 }
 
 // The spread sum's ticket barrier needs every workgroup of the grid resident at once: at most one per CU the process may use.
@@ -521,16 +517,19 @@ uint32_t callback_spread_limit() {
   return no_spread ? 0u : (n_cus < 256u ? n_cus : 256u);
 }
 
-const char* launch_callback(const MixArgs& m, const PlanArgs& p, const SumArgs& s0, uint32_t* done, uint32_t done_base, uint32_t done_base2, bool spread,
-                            uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, int family, bool window_rows, unsigned long long* dbg, hipStream_t st) {
+const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s0, uint32_t* done, uint32_t done_base, uint32_t done_base2,
+                            bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st) {
   SumArgs s = s0;
   s.n_blocks = 1u;
   const bool fenced = m.partial_through == 0u;   // WBX_CB_FENCED=1 (A/B aid), as the context read it
   // (the election word: word 1 of the counter block — the counters' own words are multiples of kCbStride)
   CallbackArgs cb{done, spread ? 1u : 0u, done_base, done_base2, done + 1, gave_up, flag, seq, m.n_groups, fenced ? 1u : 0u, spin_bound, dbg};
-  if (family == 1 || family == 3) return launch_callback_fam1(m, p, s, cb, st);   // (3 = 1 without the per-frame taps: one instance serves both)
-  if (family == 2) return launch_callback_fam2(m, p, s, cb, st);
-  return launch_callback_fam0(m, p, s, cb, window_rows, st);
+  switch (inst.FAM) {
+    case 0: return launch_callback_fam0(inst, m, p, s, cb, st);
+    case 1: return launch_callback_fam1(inst, m, p, s, cb, st);
+    case 2: return launch_callback_fam2(inst, m, p, s, cb, st);
+  }
+  return nullptr;
 }
 
 void launch_sum(const SumArgs& a0, uint32_t n_blocks, hipStream_t s) {

@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "wbx_dev.h"
+#include "wbx_shape.h"
 
 namespace wbx {
 
@@ -1755,26 +1756,50 @@ __global__ __launch_bounds__(256, W) void mix_kernel_x(MixArgs a) {
   mix_body<U, true, FAM, SB, CW, 1, 256, X>(a);
 }
 
-// one instance, launched; t0 / t1 (optional): events that take the kernel's own start and end times (hipExtLaunchKernelGGL:
-// the time stamps of its dispatch packet — no event packets of their own in the stream).  -> the instance's name as
-// rocprofv3 prints it
-#define WBX_MIX(U, FULL, W, FAM, SB, CW, CL, T, GRID, BLOCK)                                                   \
-  {                                                                                                            \
-    name = "wbx::mix_kernel<" #U ", " #FULL ", " #W ", " #FAM ", " #SB ", " #CW ", " #CL ", " #T ">";          \
-    hipExtLaunchKernelGGL((mix_kernel<U, FULL, W, FAM, SB, CW, CL, T>), GRID, BLOCK, 0, s, t0, t1, 0, a);      \
-  }
-
+// One instance as its family's translation unit (wbx_mix_fam<N>.hip) holds it: the template arguments the render's shape names
+// it by (wbx_shape.h), the name as rocprofv3 prints it, the launch.  t0 / t1 (optional): events that take the kernel's own
+// start and end times (hipExtLaunchKernelGGL: the time stamps of its dispatch packet — no event packets of their own in the
+// stream).
+struct MixEntry {
+  MixInstance inst;
+  const char* name;
+  void (*launch)(const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+};
+#define WBX_MIX(U, FULL, W, FAM, SB, CW, CL, T)                                                                \
+  {MixInstance::mix(U, FULL, W, FAM, SB, CW, CL, T),                                                           \
+   "wbx::mix_kernel<" #U ", " #FULL ", " #W ", " #FAM ", " #SB ", " #CW ", " #CL ", " #T ">",                  \
+   [](const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {                              \
+     hipExtLaunchKernelGGL((mix_kernel<U, FULL, W, FAM, SB, CW, CL, T>), grid, dim3(T), 0, s, t0, t1, 0, a);   \
+   }},
 // a packed instance that takes masked rows (X = 1: half-length chunks)
-#define WBX_MIX_X(U, W, FAM, SB, CW, X, GRID)                                                                  \
-  {                                                                                                            \
-    name = "wbx::mix_kernel_x<" #U ", " #W ", " #FAM ", " #SB ", " #CW ", " #X ">";                            \
-    hipExtLaunchKernelGGL((mix_kernel_x<U, W, FAM, SB, CW, X>), GRID, dim3(256), 0, s, t0, t1, 0, a);          \
-  }
+#define WBX_MIX_X(U, W, FAM, SB, CW, X)                                                                        \
+  {MixInstance::mix_x(U, W, FAM, SB, CW, X), "wbx::mix_kernel_x<" #U ", " #W ", " #FAM ", " #SB ", " #CW ", " #X ">", \
+   [](const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {                              \
+     hipExtLaunchKernelGGL((mix_kernel_x<U, W, FAM, SB, CW, X>), grid, dim3(256), 0, s, t0, t1, 0, a);         \
+   }},
+// the short-block instances, which families 0 and 1 hold alike: the packed ones with masked rows, one block per workgroup (a
+// wave, or two) with them, 2 or 4 blocks per workgroup without
+#define WBX_MIX_SHORT(FAM)                                                                                     \
+  WBX_MIX_X(2, 4, FAM, 4, 2, 1) WBX_MIX_X(2, 4, FAM, 2, 1, 1) WBX_MIX_X(2, 4, FAM, 4, 1, 1)                    \
+  WBX_MIX(2, true, 3, FAM, 1, 2, 1, 64) WBX_MIX(2, true, 3, FAM, 1, 1, 1, 128) WBX_MIX(2, true, 3, FAM, 1, 1, 1, 64) \
+  WBX_MIX(2, true, 4, FAM, 4, 2, 1, 256) WBX_MIX(2, true, 4, FAM, 2, 1, 1, 256) WBX_MIX(2, true, 4, FAM, 4, 1, 1, 256)
 
-// the instances of one family (wbx_mix_fam<N>.hip); `variant`: 10 * U + W, or >= 1000 for both channels of a frame per lane
-const char* launch_mix_fam0(const MixArgs& a, uint32_t n_blocks, int variant, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
-const char* launch_mix_fam1(const MixArgs& a, uint32_t n_blocks, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
-const char* launch_mix_fam2(const MixArgs& a, uint32_t n_blocks, int variant, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
-const char* launch_mix_fam3(const MixArgs& a, uint32_t n_blocks, int variant, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+// -> the name of the launched instance, null: the table does not hold it
+template <size_t N>
+inline const char* launch_mix_from(const MixEntry (&table)[N], const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s,
+                                   hipEvent_t t0, hipEvent_t t1) {
+  for (const MixEntry& e : table)
+    if (e.inst.key() == inst.key()) {
+      e.launch(a, grid, s, t0, t1);
+      return e.name;
+    }
+  return nullptr;
+}
+
+// the instances of one family (wbx_mix_fam<N>.hip)
+const char* launch_mix_fam0(const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+const char* launch_mix_fam1(const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+const char* launch_mix_fam2(const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
+const char* launch_mix_fam3(const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1);
 
 }  // namespace wbx

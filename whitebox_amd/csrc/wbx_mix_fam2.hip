@@ -6,29 +6,21 @@
 
 namespace wbx {
 
-const char* launch_mix_fam2(const MixArgs& a, uint32_t n_blocks, int variant, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
-  const char* name = "";
-  const dim3 grid(n_blocks, a.n_groups, a.tiles), block(256);
-  const uint32_t S4 = a.lane_span;   // (the instance's lane space: F/4, or the next shape above it)
-  if (variant >= 1000 && a.channels == 2u && S4 == 64u)          // 256-frame stereo blocks: one wave = one block
-    WBX_MIX(2, true, 3, 2, 1, 1, 2, 64, grid, dim3(64))
-  else if (variant == 1042 && a.channels == 2u && S4 == 128u && a.tiles == 1u)
-    WBX_MIX(4, true, 2, 2, 1, 1, 2, 128, grid, dim3(128))
-  else if (variant == 1013 && a.channels == 2u && S4 == 128u && a.tiles == 1u)
-    WBX_MIX(1, true, 3, 2, 1, 1, 2, 128, grid, dim3(128))
-  else if (variant >= 1000 && a.channels == 2u && S4 == 128u && a.tiles == 1u)
-    WBX_MIX(2, true, 3, 2, 1, 1, 2, 128, grid, dim3(128))
-  else if (variant >= 1000 && a.channels == 2u && S4 == 256u)
-    WBX_MIX(2, true, 3, 2, 1, 1, 2, 256, dim3(n_blocks, a.n_groups, 1), dim3(256))
-  else
-    WBX_MIX(2, true, 4, 2, 1, 1, 1, 256, grid, block)
-  return name;
+static const MixEntry kMixFam2[] = {
+    WBX_MIX(2, true, 3, 2, 1, 1, 2, 64)
+    WBX_MIX(4, true, 2, 2, 1, 1, 2, 128) WBX_MIX(1, true, 3, 2, 1, 1, 2, 128) WBX_MIX(2, true, 3, 2, 1, 1, 2, 128)
+    WBX_MIX(2, true, 3, 2, 1, 1, 2, 256)
+    WBX_MIX(2, true, 4, 2, 1, 1, 1, 256)
+};
+
+const char* launch_mix_fam2(const MixInstance& inst, const MixArgs& a, dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1) {
+  return launch_mix_from(kMixFam2, inst, a, grid, s, t0, t1);
 }
 
-const char* launch_callback_fam2(const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st) {
-  const char* name = "";
-  WBX_CALLBACK(2, 2)
-  return name;
+static const CallbackEntry kCallbackFam2[] = {WBX_CALLBACK(2, 2)};
+
+const char* launch_callback_fam2(const MixInstance& inst, const MixArgs& a, const PlanArgs& p, const SumArgs& s, const CallbackArgs& cb, hipStream_t st) {
+  return launch_callback_from(kCallbackFam2, inst, a, p, s, cb, st);
 }
 
 }  // namespace wbx

@@ -69,7 +69,7 @@ void drain_events(wbx_ctx* c, int upto) {
 // run in.  Two group sets over it: `groups` cuts every member list into workgroup-sized pieces of group_size tracks
 // (the master is the in-order sum of the piece sums), `groups_exact` keeps every member list whole — one workgroup walks
 // all direct tracks of its block in track order, which IS the reference's summation (engine.cpp:1600-1617,
-// audio_buffer.h:73-82: bit-exact master).  Which set a render takes: render_walks_whole_lists().
+// audio_buffer.h:73-82: bit-exact master).  Which set a render takes: RenderShape::walks_lists (wbx_shape.h).
 void build_routing(wbx_ctx* c, uint32_t n_tracks) {
   uint32_t G = c->cfg.group_size;
   // the callback configuration: the one block's latency is a chain of dependent work per workgroup (≈0.4 us a track row), so
@@ -131,54 +131,26 @@ void build_routing(wbx_ctx* c, uint32_t n_tracks) {
   for (auto& g : c->groups_exact) c->longest_list = std::max(c->longest_list, g.count);
 }
 
-// Does a render of K blocks take `groups_exact` (one workgroup per member list and block)?  Only when the library
-// picks the grouping (wbx_config.group_size == 0) and the render is long enough to fill the device with one workgroup
-// per block: the parallelism that track groups give a short render comes from the K blocks of a long one.  Measured on
-// c3 (profiles/): from about a thousand blocks per render on, whole-list walks run at the grouped order's rate.
-// What counts is the number of workgroup COLUMNS, not of blocks: the instances for blocks shorter than a workgroup put 2 or 4
-// consecutive blocks into one, and a 1024-block render of 128-frame blocks through them is 256 columns — 256 chains, or 256
-// walks, on a device that holds a thousand workgroups (measured: 0.30 of the roofline instead of 0.60).
-// (-> blocks per workgroup; *resident: how many workgroups of that instance the device holds at once, in units of the 1024
-//  that the four-wave instances come to.  A chained piece waits for its predecessor while it occupies a slot: with fewer
-//  columns than resident workgroups several pieces of a block are resident TOGETHER and all but one of them wait — measured
-//  on the one-wave instances, 3072 resident: 0.25 of the roofline at 1024 columns, 0.45 at 2048, against 0.6 unchained)
-static uint32_t blocks_per_workgroup(const wbx_ctx* c, uint32_t K, uint32_t* resident) {
-  const uint32_t C = c->cfg.channels, S4 = lane_span_of(c), lanes = C * S4;   // (the instance's lane space)
-  *resident = 1u;
-  if ((lanes % 256u == 0u) && (S4 % 64u == 0u)) return 1u;
-  const bool short_ok = (C == 2u && S4 == 32u) || (S4 % 64u == 0u && lanes == 128u) || (S4 == 64u && lanes == 64u);
-  const uint32_t packed = (C == 2u && S4 == 32u) ? 4u : (S4 % 64u == 0u && (lanes == 128u || lanes == 64u)) ? 256u / lanes : 1u;
-  const int fam = mix_family(c);
-  if (short_ok && c->has_cut_tracks && !c->knob_masked_rows_off) {   // masked rows ...
-    if (!(fam == 2 && C == 2u && S4 == 64u) && packed_masked_variant(K, C == 2u && S4 == 32u, c->knob_packed_x)) return packed;   // ... in the packed instances
-    *resident = lanes <= 64u ? 3u : 2u;
-    return 1u;                                                   // ... in the one-block-per-workgroup instances
-  }
-  if (C == 2u && S4 == 64u && (fam == 0 || fam == 2) && (c->has_integer_clips || c->has_cut_tracks)) {   // one wave = one block
-    *resident = 3u;
-    return 1u;
-  }
-  return packed;
-}
-
-bool render_walks_whole_lists(const wbx_ctx* c, uint32_t K) {
-  uint32_t resident = 1u;
-  const uint32_t bpw = blocks_per_workgroup(c, K, &resident);
-  return c->auto_group && c->exact_min_blocks != 0u && K / bpw >= c->exact_min_blocks * resident;
-}
-
-// ... and of those, which chain the workgroup-sized pieces instead of walking a list in one workgroup: the same order of
-// additions, but scheduled like the grouped order (many short workgroups, dispatched dynamically) — a static assignment of
-// one long walk per workgroup ends when its slowest shader engine does (profiles/r03_wg_clocks.txt: 25-40 % behind the mean).
-// WBX_CHAIN=0: walk the lists whole.
-bool render_chains_groups(const wbx_ctx* c, uint32_t K) {
-  // (a reported hand-over failure: whole-list walks from then on.  WBX_MIX_ALT=1 runs two renders' mixes side by side, and
-  //  the words of both would share d_chain with only the epoch to tell them apart: render i+1's pieces overwrite words
-  //  render i's successors still poll — no chaining there)
-  const bool off = c->knob_chain_off || c->chain_broken || c->mix_alternate;
-  // (K a multiple of 32: every instance's grid then has an x extent that is a multiple of 8, which keeps the pieces of a
-  //  block on one XCD — what the chain's L2-level hand-over rests on; other lengths walk the lists whole)
-  return render_walks_whole_lists(c, K) && !off && c->longest_list > c->cfg.group_size && (K % 32u) == 0u;
+// the shape of a render of K blocks of N tracks (wbx_shape.h): the session's facts as the caller left them in the context, the
+// clip table's and the routing's as they stand
+RenderShape render_shape(const wbx_ctx* c, uint32_t K, uint32_t N, bool callback) {
+  ShapeFacts f;
+  f.channels = c->cfg.channels;
+  f.block_frames = c->cfg.block_frames;
+  f.group_size = c->cfg.group_size;
+  f.auto_group = c->auto_group;
+  f.session = c->session;
+  f.integer_clips = c->has_integer_clips;
+  f.non16_clips = c->has_non16_clips;
+  f.n_buses = c->n_buses;
+  f.longest_list = c->longest_list;
+  f.n_blocks = K;
+  f.n_tracks = N;
+  f.callback = callback;
+  f.chain_broken = c->chain_broken;
+  f.mix_alternate = c->mix_alternate;
+  f.dist = c->dist != nullptr;
+  return choose_shape(c->knobs, f);
 }
 
 wbx_status upload_tables(wbx_ctx* c, uint32_t n_tracks) {
@@ -290,7 +262,7 @@ wbx_status ensure_pool_slack(wbx_ctx* c) {
 }
 
 // pre-render of the queued generic records of the current plan buffer
-wbx_status launch_pre_render(wbx_ctx* c, uint32_t K, hipStream_t on) {
+wbx_status launch_pre_render(wbx_ctx* c, hipStream_t on) {
   const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
   GenArgs ga{};
   ga.tmpl = PB(c).tmpl.p;
@@ -302,102 +274,9 @@ wbx_status launch_pre_render(wbx_ctx* c, uint32_t K, hipStream_t on) {
   ga.gen_cap = PB(c).gen_cap;
   ga.block_frames = F;
   ga.channels = C;
-  // one wave per queued row, grid-stride: no more workgroups than the device holds at once (256 CUs x 6 workgroups at
-  // the kernel's register budget), or the surplus would start when the first ones have finished their whole share
-  // (a plan made for a masked-row mix instance queues only what is left over: blocks with three or more stream calls,
-  //  overlapping calls — a handful per render at most)
-  launch_gen(ga, K < kOverlapMinBlocks ? 64u * K : c->masked_rows ? 128u : 1536u, on);
+  launch_gen(ga, c->shape.gen_grid, on);
   WBX_HIP(c, hipGetLastError());
   return WBX_OK;
-}
-
-// which chunk modes the mix instance of the next launch carries (mix_kernel<.., FAM, ..>): 1 (everything) also holds the
-// pipelined modes for chunks that mix storage formats with resampled rows; 2: sessions of 16-bit PCM only, resampled at
-// speeds up to 0.999 or not at all
-int mix_family(const wbx_ctx* c) {
-  if (c->force_g) return 1;
-  if (c->has_lean16_clips && !c->has_non16_clips && !c->knob_no_lean16) return 2;
-  if (c->has_stride_clips || (c->has_window_clips && c->has_integer_clips))
-    return (c->has_taps_clips || c->knob_no_fam3) ? 1 : 3;   // (3 = 1 without the per-frame taps)
-  return 0;
-}
-
-// stereo sessions with integer-PCM clips or with tracks cut into several clips, blocks of 256 / 512 / 1024 frames: the
-// instances with both channels of a frame in one lane (position and masked-row arithmetic once per frame, one set of record
-// scalars for both channels).  Measured (tools/ab_cl2.sh, tools/ab_masked.sh, tools/ab_blocks.sh; slab-allocated sessions):
-// integer PCM +2-10 %, sessions cut into clips +5-11 % (2 x at 256 frames, where the other instances have no masked
-// rows), fp32 sessions of one clip per track 3-8 % slower (they fetch 1.06 x their bytes instead of 1.02 x) — those keep
-// one channel per wave.
-// fp32 sessions of one clip per track with resampled clips (c3), chained renders of 2048 blocks and more: the two-channels-per-
-// lane instance with ONE row per pipeline batch, <1,true,3,0,1,1,2,128>.  Round 2 measured these sessions 3 % slower through
-// the CL = 2 instances — at 256-block renders in the grouped order; at 2048 chained blocks, with the one-ratio modes taken
-// again, five alternating runs on one box (profiles/r05_ab_c3_instances.txt) read 0.711 of the roofline for it, 0.701 for
-// <2,true,3,..,2,128>, 0.694 for the one-channel-per-wave <2,true,4,..,1,256>; at 1024 and 256 blocks nothing to choose.
-bool mix_long_chained_window_render(const wbx_ctx* c) {
-  static const bool off = [] { const char* v = std::getenv("WBX_NO_LONG_CL2"); return v && v[0] == '1'; }();   // A/B aid
-  const uint32_t F = 4u * lane_span_of(c);
-  return !off && c->cfg.channels == 2u && F == 512u && c->chain_now && c->render_blocks_now >= 2048u && c->has_window_clips &&
-         !c->has_integer_clips && !c->has_cut_tracks && !c->has_stride_clips && !c->n_buses;
-}
-
-bool mix_two_channels_per_lane(const wbx_ctx* c) {
-  const uint32_t F = 4u * lane_span_of(c);   // (the block size of the instance's lane space)
-  if (c->mix_unroll) return c->mix_unroll >= 1000;   // WBX_MIX_VARIANT
-  if (c->cfg.channels != 2u || c->knob_no_cl2) return false;
-  if (!(F == 512u || F == 1024u || F == 256u)) return false;
-  // the callback path (a handful of workgroups, each a chain of dependent rows): a wave per channel half — four waves share
-  // the chain instead of two (measured, 4096 / 64 tracks: 16-bit resampled 53 -> 51 / 55 -> 49 us, cut into clips 63 -> 58 /
-  // 66 -> 58, 24-bit 55 -> 53 / 58 -> 53).  256-frame blocks keep the one-wave instances: only those take their masked rows.
-  if (c->short_render_now && F != 256u) return false;
-  // a render whose workgroups walk whole member lists of many staged chunks: the half-size workgroups of these instances
-  // put six of them on a CU, and the walk runs 15 % faster than through the four-wave ones (c3, 1024 blocks: 2.94 vs 3.43 ms)
-  if (c->whole_lists_now && !c->chain_now && c->longest_list > 2u * kStage) return true;
-  if (mix_long_chained_window_render(c)) return true;
-  return c->has_integer_clips || c->has_cut_tracks;
-}
-
-// Can the mix instance a render of this shape will launch take masked rows (partial-coverage records, ROW_PAIRs) in its
-// hot loop, and which (PlanArgs::masked_rows)?  Only the lean whole-workgroup-per-block instances do
-// (mix_kernel<U, true, W, false, 1, ...>): blocks of C*F/4 lanes a multiple of 256, sessions without per-frame-tap clips.
-// 1: fp32 rows, unity or resampled; 2: also integer PCM at unity speed — sessions whose integer clips all play at the
-// session rate and that hold no resampled clip (those take the instances with the mixed-format window modes).
-uint32_t mix_takes_masked_rows(const wbx_ctx* c, bool window_clips, bool stride_clips) {
-  const uint32_t S4 = lane_span_of(c), lanes = c->cfg.channels * S4;
-  bool full = (lanes % 256u == 0u) && (S4 % 64u == 0u);
-  // (256-frame stereo blocks: the one-wave instances with both channels per lane, the lean families only)
-  if (!full && c->cfg.channels == 2u && S4 == 64u && (mix_family(c) == 0 || mix_family(c) == 2) && mix_two_channels_per_lane(c)) full = true;
-  // short blocks — 128-frame stereo, 256-frame stereo in the families without that one-wave instance, 256 / 512-frame mono:
-  // one-block-per-workgroup instances (a wave or two) exist for families 0 and 1; a session with tracks cut into clips takes
-  // them, the others keep the instances that put 2 or 4 blocks into a workgroup
-  if (!full && c->has_cut_tracks &&
-      ((c->cfg.channels == 2u && S4 == 32u) || (S4 % 64u == 0u && lanes == 128u) || (S4 == 64u && lanes == 64u)))
-    full = true;
-  if (c->knob_masked_rows_off) return 0u;   // WBX_MASKED_ROWS=0, A/B aid: send every boundary row through the pre-render pass
-  if (!full) return 0u;
-  if (mix_family(c) == 1 || mix_family(c) == 3) return 4u;   // the everything family: every row kind it streams, also as a masked row
-  if (mix_family(c) == 2) return 3u;   // sessions of 16-bit PCM only: also their resampled rows
-  if (stride_clips) return 0u;
-  if (!c->has_integer_clips) return 1u;
-  return window_clips ? 0u : 2u;
-}
-
-// Does a one-block render of wbx_engine_process run as ONE launch (wbx_callback.h)?  Blocks that are exactly one 256-lane
-// workgroup (512-frame stereo, 1024-frame mono: the instances that exist), no multi-GPU exchange.  WBX_CALLBACK_FUSED=0: the
-// three launches of earlier rounds (A/B aid; results are identical).
-// (round 5) ... and every block that FITS one: the callback is a latency path — what counts is one dispatch instead of three, not
-// how many of the workgroup's lanes own frames — so a 128- or 256-frame stereo block (the low-latency settings of
-// ui/settings.cpp:22-24) runs through the same 256-lane instance with lane_span = 256 / C, its surplus lanes cloning the block's
-// last four frames (wbx_mix.h).  WBX_CB_ANY=0: only the shapes whose batch renders take a 256-lane workgroup per block.
-uint32_t callback_lane_span(const wbx_ctx* c) {
-  const uint32_t C = c->cfg.channels, S4 = c->cfg.block_frames >> 2;
-  const uint32_t nat = lane_span_of(c);
-  if (C * nat == 256u && (nat % 64u) == 0u) return nat;
-  if (c->knob_cb_any_off || c->knob_ragged_off) return 0u;
-  return C * S4 <= 256u ? 256u / C : 0u;
-}
-bool callback_is_one_launch(const wbx_ctx* c) {
-  static const bool off = [] { const char* v = std::getenv("WBX_CALLBACK_FUSED"); return v && v[0] == '0'; }();
-  return !off && !c->dist && callback_lane_span(c) != 0u && !c->mix_unroll;
 }
 
 // where the master of the render about to be issued goes; `writer` is the stream its last writer runs on
@@ -417,8 +296,9 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   m.pool = PB(c).pool.p;
   m.order = c->d_order.p;
   // the group set of this render: workgroup-sized pieces, or the whole member lists (the reference's summation order)
-  const bool chained = c->whole_lists_now && render_chains_groups(c, K);
-  const bool whole = c->whole_lists_now && !chained;
+  const RenderShape& sh = c->shape;
+  const bool chained = sh.chained;
+  const bool whole = sh.walks_lists && !chained;
   const DGroup* d_groups = c->d_groups.p + (whole ? c->groups.size() : 0);
   const uint32_t n_groups = (uint32_t)(whole ? c->groups_exact.size() : c->groups.size());
   const bool buses_alias = whole ? c->buses_alias_exact : c->buses_alias_partials;
@@ -458,16 +338,15 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   m.n_groups = n_groups;
   m.block_frames = F;
   m.channels = C;
-  m.lane_span = lane_span_of(c);
-  m.packed_x = c->knob_packed_x;
+  m.lane_span = sh.lane_span;
   m.fast_partial = c->knob_fast_partial_off ? 0u : 1u;
-  m.tiles = (C * m.lane_span + 255u) / 256u;
+  m.tiles = sh.tiles;
   m.n_blocks = K;
-  m.masked_rows = c->masked_rows ? 1u : 0u;
+  m.masked_rows = sh.masked_rows ? 1u : 0u;
   {   // one resampling ratio for every window row of this render (layer 2's word; MODE_WNU / WINU: the products fl(j * speed)
       // hoisted out of the track loop).  WBX_NO_UNIFORM=1: A/B aid.  [Round 3's split of this function lost this line: the
       // modes were carried but never taken until round 5 — SQ_INSTS_VALU_MUL_F64 of the r03-r05 PMC passes shows it.]
-    m.uniform_speed = c->knob_no_uniform ? 0.0 : c->uniform_speed;
+    m.uniform_speed = c->knob_no_uniform ? 0.0 : sh.uniform_speed;
     c->last_uniform_speed = m.uniform_speed;
   }
   // A short render of a session that is one group (the callback configuration up to 64 tracks; no sub-buses, planar fp32
@@ -520,9 +399,9 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   if (m.tiles > 1) WBX_HIP(c, hipMemsetAsync(m.peaks, 0, (size_t)K * N * C * sizeof(float), ms));
   // the kernel timer is for batch renders; the one-block callback path skips its three event records
   const bool timed = c->profiling && K > 1;
-  const bool one_launch = c->cb_plan != nullptr && K == 1u && m.n_groups != 0u && callback_is_one_launch(c);
+  const bool one_launch = c->cb_plan != nullptr && m.n_groups != 0u && sh.cb_one_launch;
   if (one_launch) {   // (the callback instance's own lane space: one 256-lane workgroup per block)
-    m.lane_span = callback_lane_span(c);
+    m.lane_span = sh.cb_lane_span;
     m.tiles = 1u;
   }
   c->cb_launched = false;
@@ -538,16 +417,10 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     // event packets between two mixes.  WBX_TIMER_PACKETS=1: the old way, an event record either side (A/B aid)
     static const bool packets = std::getenv("WBX_TIMER_PACKETS") != nullptr;
     if (timed && packets) WBX_HIP(c, hipEventRecord(c->ev[c->ev_pending][0], ms));
-    // (unity-speed fp32 sessions: four rows per pipeline batch at three waves per SIMD, <4,true,3,..> — round 2's choice at
-    //  256-block renders; in renders of >= 2048 blocks of large sessions two rows at four waves, <2,true,4,..>, is ahead:
-    //  c4 0.72-0.75 of the roofline against 0.67-0.69, u4096 0.755-0.777 against 0.746-0.763, one box, alternating
-    //  (profiles/r05_ab_c3_instances.txt); 256-track sessions: nothing to choose.  WBX_NO_LONG_24=1: the old choice)
-    static const bool no_long_24 = [] { const char* v = std::getenv("WBX_NO_LONG_24"); return v && v[0] == '1'; }();
-    const bool long_large = !no_long_24 && K >= 2048u && N >= 1024u;
-    c->mix_kernel_name = launch_mix(m, K, c->mix_unroll ? c->mix_unroll : mix_two_channels_per_lane(c) ? (mix_long_chained_window_render(c) ? 1013 : 1023)
-                                          : ((c->has_window_clips || c->has_integer_clips || long_large) ? 24 : 43),
-               mix_family(c), ms, (timed && !packets) ? c->ev[c->ev_pending][0] : nullptr,
-               (timed && !packets) ? c->ev[c->ev_pending][1] : nullptr);
+    const char* name = launch_mix(sh.mix, m, sh.grid_z, ms, (timed && !packets) ? c->ev[c->ev_pending][0] : nullptr,
+                                  (timed && !packets) ? c->ev[c->ev_pending][1] : nullptr);
+    if (!name) return fail(c, WBX_ERR_FAILED, "the render's mix instance is not compiled in");
+    c->mix_kernel_name = name;
     if (timed && packets) WBX_HIP(c, hipEventRecord(c->ev[c->ev_pending][1], ms));
     if (c->dist) WBX_HIP(c, dist_mix_issued(c, ms));
     // (round 6) When the kernel carries the timer's stop event and its sum runs on another stream, THAT event is what the sum
@@ -642,8 +515,9 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     // fit) and the engine's pinned block has a completion word for each of them
     const bool spread = !fused && !c->cb_no_spread && m.n_groups <= callback_spread_limit();
     c->cb_flags = 1u;
-    c->mix_kernel_name = launch_callback(m, *c->cb_plan, s, c->d_cb_done, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->cb_spin_bound, c->cb_flag, c->cb_seq, mix_family(c),
-                                         c->has_window_clips || c->has_integer_clips, cb_dbg, ms);
+    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
+    if (!name) return fail(c, WBX_ERR_FAILED, "the render's callback instance is not compiled in");
+    c->mix_kernel_name = name;
     // (a one-group block takes no ticket; a grid larger than the device — "the last workgroup adds everything" — only the
     //  first one: the second counter has a base of its own, or the first spread launch after such a block would wait for a
     //  count that wrapped)
@@ -734,9 +608,7 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
   // kernel's spread sum (by sum_kernel when the block shape takes the three-launch path).
   c->auto_group = c->cfg.group_size == 0;
   if (c->cfg.group_size == 0) c->cfg.group_size = c->cfg.max_blocks == 1 ? kStage / 2 : kStage;
-  if (const char* u = std::getenv("WBX_MIX_VARIANT")) c->mix_unroll = std::atoi(u);
-  if (const char* u = std::getenv("WBX_EXACT_MIN_BLOCKS")) c->exact_min_blocks = (uint32_t)std::atoi(u);   // 0: never
-  if (const char* u = std::getenv("WBX_FORCE_G")) c->force_g = std::atoi(u) != 0;   // A/B aid: always the G instances
+  c->knobs = ShapeKnobs::from_env();
   if (const char* u = std::getenv("WBX_KERNEL_TIMER")) c->profiling = std::atoi(u) != 0;   // 0: no HIP-event kernel timer
   // Events whose only waiters are other streams of this device (or a host that waits for "done" and reads nothing the device
   // wrote): released to the DEVICE — a marker's default release is to the system.  (No measurable effect by itself; the A/Bs
@@ -793,21 +665,13 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
     // measured (tools/ab_alt.sh): with consecutive mixes on alternating streams the two kernels share the device for
     // their whole length (each takes 1.05-1.2 ms instead of 0.74) and the step time does not move — off by default
     if (const char* sb = std::getenv("WBX_CB_SPIN_BOUND")) c->cb_spin_bound = (uint32_t)std::atoi(sb);   // (tests: 0 forces the give-up path)
-    {   // the A/B switches the render path consults (wbx_ctx.h: read once, here)
+    {   // the A/B switches the render path consults beside the shape's (wbx_ctx.h: read once, here)
       auto is = [](const char* name, char what) { const char* v = std::getenv(name); return v && v[0] == what; };
-      c->knob_ragged_off = is("WBX_RAGGED", '0');
-      c->knob_cb_any_off = is("WBX_CB_ANY", '0');
       c->knob_no_uniform = is("WBX_NO_UNIFORM", '1');
-      c->knob_masked_rows_off = is("WBX_MASKED_ROWS", '0');
-      c->knob_chain_off = is("WBX_CHAIN", '0');
-      c->knob_no_lean16 = std::getenv("WBX_NO_LEAN16") != nullptr;
-      c->knob_no_fam3 = std::getenv("WBX_NO_FAM3") != nullptr;
-      c->knob_no_cl2 = std::getenv("WBX_NO_CL2") != nullptr;
       c->knob_cb_fenced = is("WBX_CB_FENCED", '1');
       c->knob_partial_free_off = is("WBX_PARTIAL_FREE", '0');
       c->knob_mix_marker = is("WBX_MIX_MARKER", '1');
       c->knob_fast_partial_off = is("WBX_FAST_PARTIAL", '0');
-      if (const char* v = std::getenv("WBX_PACKED_X")) c->knob_packed_x = std::atoi(v) != 0 ? 1 : 0;
     }
     // the workgroup-id -> XCD layout the chained pieces and the segmented sequencer rest on, probed before anything relies on it
     // (WBX_XCD_PROBE_FAIL=1: tests take the fallback path)
@@ -1346,8 +1210,8 @@ extern "C" wbx_status wbx_set_routing(wbx_ctx* c, uint32_t n_tracks, const int32
 extern "C" wbx_status wbx_render_order(wbx_ctx* c, uint32_t n_blocks, uint32_t* n_groups, uint32_t* longest_group,
                                        int* reference_order) {
   if (!c || n_blocks == 0) return WBX_ERR_INVALID;
-  const bool chained = render_chains_groups(c, n_blocks);
-  const bool whole = render_walks_whole_lists(c, n_blocks) && !chained;
+  const RenderShape sh = render_shape(c, n_blocks, c->last_N, false);
+  const bool chained = sh.chained, whole = sh.walks_lists && !chained;
   const std::vector<DGroup>& gs = whole ? c->groups_exact : c->groups;
   uint32_t longest = 0;
   for (auto& g : gs) longest = std::max(longest, g.count);
@@ -1525,14 +1389,12 @@ extern "C" wbx_status wbx_submit(wbx_ctx* c, uint32_t K, uint32_t N, const wbx_s
   WBX_HIP(c, hipMemcpyAsync(PB(c).prows.p, c->h_rows.data(), c->h_rows.size() * sizeof(DRow), hipMemcpyHostToDevice, c->stream));
   if (!c->h_pool.empty())
     WBX_HIP(c, hipMemcpyAsync(PB(c).pool.p, c->h_pool.data(), c->h_pool.size() * sizeof(DSeg), hipMemcpyHostToDevice, c->stream));
-  c->short_render_now = K < kOverlapMinBlocks;
-  c->render_blocks_now = K;
-  c->whole_lists_now = render_walks_whole_lists(c, K);
-  c->chain_now = render_chains_groups(c, K);
   (void)pick_mix_stream(c, K, false);   // host-sequenced plans are uploaded on the main stream: their mix follows there
-  c->masked_rows = 0u;   // host-sequenced plans send every partial row through the pre-render pass
-  c->uniform_speed = 0.0;   // ... and make no promise about their playback speeds
-  st = launch_pre_render(c, K, c->stream);
+  // host-sequenced plans say nothing about their clips, send every partial row through the pre-render pass and make no
+  // promise about their playback speeds
+  c->session = SessionFacts{};
+  c->shape = render_shape(c, K, N, false);
+  st = launch_pre_render(c, c->stream);
   if (st != WBX_OK) return st;
   return launch_mix_sum(c, K, N);
 }
