@@ -313,8 +313,8 @@ def gen_sequencer():
     Track::process_event / Track::process / Engine::process and the session-building calls, cut out of the reference's sources
     where they lie and compiled unmodified — oracle/ref_engine_driver.cpp).  Per session: the script (JSON: operations with exact
     floats, clip audio as keys of whitebox_amd.synth's generator) and the driver's answer file byte for byte (per block: master,
-    playhead, sample_position, every track's AudioEvent list, sampler state and VU level; per operation whether the reference
-    took it; clip lists after edits)."""
+    playhead, sample_position, every track's AudioEvent list, sampler state and VU level; per operation its status; clip lists
+    after edits).  Edits that land on clips run through the reference's own reserve_track_region (engine_r3b.inc)."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import ref_engine as R
     import seq_sessions as S
@@ -341,6 +341,51 @@ def gen_sequencer():
             n += 1
     np.savez_compressed(os.path.join(OUT, "sequencer.npz"), **arrs)
     print("sequencer.npz:", n, "sessions")
+
+
+def gen_overlap():
+    """tests/golden/overlap.npz from the reference's own Engine::reserve_track_region under add_audio_clip / move_clip /
+    resize_clip / delete_region (oracle/_ref/wbref_engine, engine_r3b.inc): scripts of tests/seq_sessions.overlap_script and the
+    driver's answer files byte for byte, as sequencer.npz holds them — recorded data only.  Class scripts are taken seed by seed
+    while they add to a (caller, class) pair that fewer than 3 scripts reach yet (ref_engine.GRID less ref_engine.unreachable);
+    then 3 scripts of the inverted family (Q11: status 3)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_engine as R
+    import seq_sessions as S
+    if not R.available():
+        raise SystemExit("oracle/_ref/wbref_engine is not built (needs /root/reference)")
+    want = {p: set() for p in R.GRID if R.unreachable(*p) is None}
+    arrs, seed = {}, 2000
+
+    def record(name, s, raw):
+        arrs[f"{name}.script"] = np.frombuffer(R.script_to_json(s).encode(), np.uint8)
+        arrs[f"{name}.answer"] = np.frombuffer(raw, np.uint8)
+
+    while any(len(v) < 3 for v in want.values()):
+        seed += 1
+        assert seed < 2200, {p: len(v) for p, v in want.items() if len(v) < 3}
+        s = S.overlap_script(seed)
+        try:
+            orc = R.run_oracle(s)
+        except R.Wrapped:
+            continue
+        raw, ref = R.run_reference(s, want_raw=True)
+        assert R.compare(ref, orc, f"overlap {seed}") is None
+        got = {(c, k) for c, k, _tags, st, _p, _n in R.edit_classes(s, ref) if st == 1}
+        if len(raw) > 90000 or not any(len(want[p]) < 3 for p in got if p in want):
+            continue
+        for p in got:
+            if p in want:
+                want[p].add(seed)
+        record(f"classes_{seed}", s, raw)
+    for seed in (3001, 3002, 3003):
+        s = S.overlap_script(seed, "inverted")
+        raw, ref = R.run_reference(s, want_raw=True)
+        assert R.compare(ref, R.run_oracle(s), f"inverted {seed}") is None
+        record(f"inverted_{seed}", s, raw)
+    path = os.path.join(OUT, "overlap.npz")
+    np.savez_compressed(path, **arrs)
+    print("overlap.npz:", len(arrs) // 2, "sessions,", os.path.getsize(path), "bytes")
 
 
 BASELINE_REF_CASES = [   # (name, make_session kwargs, blocks) — BASELINE.json's configs and their seek variants (SURVEY 8(d))
@@ -410,17 +455,23 @@ def gen_cuts():
         with open(os.path.join(O.ORACLE_DIR, "_ref", inc)) as f:
             text = f.read()
         with open(os.path.join("/root/reference/src", src)) as f:
-            region = R.cut_region(text, f.read())
+            whole = f.read()
+        if inc in R.CUTS_LESS_ONE_LINE:          # the one cut that leaves a line out: the line's number is recorded, not its text
+            region = R.cut_region_less_one_line(text, whole, R.CUTS_LESS_ONE_LINE[inc])
+        else:
+            region = R.cut_region(text, whole)
         assert region is not None, (inc, "is not a verbatim region of", src)
         rec[inc] = {"src": src, "first": region[0], "last": region[1], "sha256": hashlib.sha256(text.encode()).hexdigest()}
+        if len(region) > 2:
+            rec[inc]["left_out"] = region[2]
     with open(os.path.join(OUT, "ref_cuts.json"), "w") as f:
         json.dump(rec, f, indent=1, sort_keys=True)
         f.write("\n")
     print("ref_cuts.json:", len(rec), "cuts")
 
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] in ("mip", "vu", "ingest", "sequencer", "baseline", "perf", "cuts"):     # (the other fixtures are untouched)
-        {"mip": gen_mip, "vu": gen_vu, "ingest": gen_ingest, "sequencer": gen_sequencer, "baseline": gen_baseline_ref, "perf": gen_perf,
+    if len(sys.argv) > 1 and sys.argv[1] in ("mip", "vu", "ingest", "sequencer", "overlap", "baseline", "perf", "cuts"):     # (the other fixtures are untouched)
+        {"mip": gen_mip, "vu": gen_vu, "ingest": gen_ingest, "sequencer": gen_sequencer, "overlap": gen_overlap, "baseline": gen_baseline_ref, "perf": gen_perf,
          "cuts": gen_cuts}[sys.argv[1]]()
     else:
         main()
@@ -428,5 +479,6 @@ if __name__ == "__main__":
         gen_vu()
         gen_ingest()
         gen_sequencer()
+        gen_overlap()
         gen_baseline_ref()
         gen_cuts()

@@ -8,30 +8,40 @@
 //
 // How it is built without third-party stand-ins (oracle/Makefile, target _ref/wbref_engine):
 //   * engine/track.cpp, engine/engine.cpp, engine/assets_table.cpp, engine/vu_meter.h, engine/audio_record.h include
-//     core/debug.h = third-party spdlog, absent from the image.  Nothing is written in spdlog's place.  The recipe cuts, at
-//     FUNCTION BOUNDARIES and out of the files where they lie, the regions of those sources that hold no `Log::` line (build
-//     outputs under _ref/eng/, git-ignored, never committed), and this file compiles those texts UNMODIFIED, in the reference's
-//     own order, against the reference's own headers.  track.cpp's per-function logging is behind its WB_DBG_LOG_* macros,
-//     which the file defines only `#ifndef _NDEBUG`: the build takes that configuration (-D_NDEBUG), so Track::process and
-//     process_event are whole.
+//     core/debug.h = third-party spdlog, absent from the image.  Nothing is written in spdlog's place.  THE CUT RULE: the recipe
+//     cuts, at FUNCTION BOUNDARIES and out of the files where they lie, contiguous regions of those sources that hold no `Log::`
+//     line (build outputs under _ref/eng/, git-ignored, never committed), and this file compiles those texts UNMODIFIED, in the
+//     reference's own order, against the reference's own headers.  ONE REFINEMENT of that rule, for one region: engine_r3b.inc
+//     = Engine::reserve_track_region (engine.cpp:478-569, overlap trimming: what a new, moved or resized clip and
+//     delete_region do to the clips they land on) is printed unmodified EXCEPT that the one line consisting wholly of a
+//     `Log::error("<string literal>");` statement (engine.cpp:505) is left out.  Nothing is defined in its place: no Log
+//     stand-in, no macro.  The recipe fails unless exactly one line of exactly that form was left out and no `Log::` remains.
+//     The line sits on the branch taken when track->clip_allocator.allocate() returns null; Pool<T>::allocate (core/memory.h:
+//     65-78) returns null only when _reserve_new_block's allocate_aligned fails (:97-100), i.e. when the host is out of
+//     memory — no script reaches it (a script's tracks hold a few dozen clips; one pool block holds 65536 / sizeof(Clip)), and
+//     the branch's own `return {};` is still there.
+//     track.cpp's per-function logging is behind its WB_DBG_LOG_* macros, which the file defines only `#ifndef _NDEBUG`: the
+//     build takes that configuration (-D_NDEBUG), so Track::process and process_event are whole.
 //   * What the cuts leave out, because an unconditional Log line sits inside the function: Engine::play / stop / record /
-//     stop_record, Engine::reserve_track_region (engine.cpp:478-569), add_plugin_to_track, Track::process_track_messages
-//     (track.cpp:773-813) and the plugin edit callbacks, SampleTable/MidiTable::shutdown.  Of these the path needs:
+//     stop_record, add_plugin_to_track, Track::process_track_messages (track.cpp:773-813) and the plugin edit callbacks,
+//     SampleTable/MidiTable::shutdown.  Of these the path needs:
 //       - play / stop: `harness_play` / `harness_stop` below restate their statements (engine.cpp:70-79, 83-91);
 //       - Track::process_track_messages: defined below with its ParamChange case only (track.cpp:777-779, one statement);
-//       - the plugin callbacks: their addresses are taken by track.h; defined below as traps (never reached: no plugin);
-//       - reserve_track_region: NOT provided.  An edit that would reach it (a clip landing on other clips) is REFUSED by the
-//         driver before the reference's code is entered (it asks the reference's own Track::query_clip_by_range), and the
-//         differential test skips that edit on the oracle side too.  Overlap trimming therefore stays KAT-pinned
-//         (tests/test_oracle_kat.py) with its arithmetic pinned through clip_edit.h (libwbref.so).
+//       - the plugin callbacks: their addresses are taken by track.h; defined below as traps (never reached: no plugin).
+//   * ONE edit is refused, with status 3: quirk Q11, on which the compiled reference dies.  An INVERTED range
+//     makes Track::query_clip_by_range answer first > last; in reserve_track_region's multi-clip branch, with last_clip == 0,
+//     the last clip not the ignored one and max < last->max_time, `last_clip--` (engine.cpp:547-552) wraps below zero and :556
+//     asks for 2^32 Clips.  `dies_in_reserve` below predicts exactly that from the reference's own query result and the clips'
+//     fields, before the reference is entered; tests/test_destroyed_clip.py defines the case for oracle and product.
 //   * Functions of the cut regions that call code from absent libraries (Sample::load_file -> libsndfile,
 //     WaveformVisual::create / ~WaveformVisual -> renderer, pm_close_plugin -> VST3 host, load_notes_from_file -> midi-parser,
 //     AudioRecordQueue's writer) are never reached by a script; their symbols stay UNRESOLVED in the executable
 //     (-Wl,--unresolved-symbols=ignore-all, lazy binding) rather than being given made-up bodies.
 //
 // Protocol: argv[1] = script (text, one operation per line), argv[2] = sample data (raw planar channels), argv[3] = result
-// file (binary records, layout in tests/ref_engine.py).  Every line is answered by one record, so the test knows which edits the
-// reference took and which the driver refused.
+// file (binary records, layout in tests/ref_engine.py).  Every line is answered by one record: status 1 = taken by the
+// reference's code, 2 = bad argument, 3 = Q11 (not entered).  The file opens with one record that answers no line: the layout
+// version of the records.
 #include <algorithm>
 #include <array>
 #include <atomic>
@@ -104,6 +114,7 @@ using namespace std::chrono_literals;
 #include "_ref/eng/engine_r1.inc"   // namespace wb { round_ppq, ~Engine, set_bpm, set_playhead_position, set_audio_channel_config, clear_all
 #include "_ref/eng/engine_r2.inc"   // arm_track_recording ... add_track, delete_track, move_track, solo_track
 #include "_ref/eng/engine_r3.inc"   // add_clip_from_file, add_audio_clip ... move_clip, resize_clip, delete_clip, add_to_cliplist, delete_region, query_clip_by_range
+#include "_ref/eng/engine_r3b.inc"  // reserve_track_region (less the one Log::error line: see the head of this file)
 #include "_ref/eng/engine_r4.inc"   // set_clip_gain
 #include "_ref/eng/engine_r5.inc"   // delete_plugin_from_track, get_song_length, update_audio_visualization, process
 #include "_ref/eng/engine_r6.inc"   // Engine g_engine; }
@@ -170,7 +181,8 @@ double now_s() {
   return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-// the clip list of a track (min, max, start_offset, speed, gain, asset index): what an edit left behind
+// the clip list of a track (min, max, start_offset, speed, gain, asset index, state: bit 0 active, bit 1 marked deleted): what an
+// edit left behind
 void dump_clips(Track* t) {
   put_u32((uint32_t)t->clips.size());
   for (auto c : t->clips) {
@@ -179,16 +191,24 @@ void dump_clips(Track* t) {
     uint32_t ai = 0xFFFFFFFFu;
     for (uint32_t i = 0; i < g_assets.size(); i++) if (g_assets[i] == c->audio.asset) ai = i;
     put_u32(ai);
+    put_u32((c->is_active() ? 1u : 0u) | (c->is_deleted() ? 2u : 0u));
   }
 }
-// would this [min, max) land on other clips (i.e. would the reference call reserve_track_region)?
-// add_to_cliplist (engine.cpp:409-461) reaches it only past its three early exits and a non-empty range query.
-bool add_needs_trim(Track* t, double min_time, double max_time) {
+// Q11: would reserve_track_region(first, last, min, max, ignore) wrap last_clip below zero?  The statement at engine.cpp:547 in
+// the multi-clip branch (first != last) with last_clip == 0, the last clip not the ignored one and max < last->max_time.
+bool dies_in_reserve(Track* t, double min_time, double max_time, Clip* ignore) {
+  auto q = t->query_clip_by_range(min_time, max_time);
+  if (!q || q->first == q->last || q->last != 0) return false;
+  Clip* last = t->clips[q->last];
+  return last != ignore && max_time < last->max_time;
+}
+// add_to_cliplist (engine.cpp:409-461) reaches its range query only past its three early exits
+bool add_dies(Track* t, double min_time, double max_time) {
   auto& clips = t->clips;
   if (clips.size() == 0) return false;
   if (clips.back()->max_time < min_time) return false;
   if (clips.front()->min_time > max_time) return false;
-  return t->query_clip_by_range(min_time, max_time).has_value();
+  return dies_in_reserve(t, min_time, max_time, nullptr);
 }
 }  // namespace
 
@@ -204,6 +224,9 @@ int main(int argc, char** argv) {
   std::vector<unsigned char> blob((size_t)data_size);
   if (data_size && std::fread(blob.data(), 1, (size_t)data_size, dataf) != (size_t)data_size) return 2;
 
+  // the answer file opens with the layout version of its records (2: a clip record ends in a state word).  An executable built
+  // from an earlier driver wrote no such record, and tests/ref_engine.py reads its clip records in the earlier layout.
+  put_u32(0x56455200u); put_u32(2u);
   // engines[0] = the reference's g_engine.  More engines exist only for the sub-bus composition (`bus` / `runbus` below): SURVEY
   // A13's oracle — "the same composition executed with the reference's AudioBuffer::mix on per-track buffers produced by the
   // reference Track::process" — is formed from whole Engine::process calls, one engine per bus.
@@ -217,7 +240,7 @@ int main(int argc, char** argv) {
   while (std::fgets(line, sizeof line, script)) {
     if (std::sscanf(line, "%31s", op) != 1 || op[0] == '#') continue;
     const char* a = line + std::strlen(op);
-    uint32_t status = 1;   // 1 = taken by the reference's code, 0 = refused (would need reserve_track_region), 2 = bad argument
+    uint32_t status = 1;   // 1 = taken by the reference's code, 2 = bad argument, 3 = Q11 (the reference would die: not entered)
     if (!std::strcmp(op, "cfg")) {
       unsigned c, f, r;
       std::sscanf(a, "%u %u %u", &c, &f, &r);
@@ -289,7 +312,7 @@ int main(int argc, char** argv) {
       unsigned t, si; double mn, mx, so, sp; float g;
       std::sscanf(a, "%u %la %la %la %u %la %a", &t, &mn, &mx, &so, &si, &sp, &g);
       Track* tr = E.tracks[t];
-      if (add_needs_trim(tr, mn, mx)) status = 0;
+      if (add_dies(tr, mn, mx)) status = 3;
       else E.add_audio_clip(tr, "c", mn, mx, so, AudioClip{ .asset = g_assets[si], .speed = sp, .gain = g });
     } else if (!std::strcmp(op, "delclip")) {  // delclip <track> <index>: Engine::delete_clip
       unsigned t, i; std::sscanf(a, "%u %u", &t, &i);
@@ -305,10 +328,24 @@ int main(int argc, char** argv) {
       else {
         Clip* c = tr->clips[i];
         auto [mn, mx] = calc_move_clip(c, rel);
-        // move_clip asks the track for [mn, mx) with the clip still in the list: any hit (the clip itself included) goes to
-        // reserve_track_region
-        if (rel != 0.0 && tr->query_clip_by_range(mn, mx).has_value()) status = 0; else E.move_clip(tr, c, rel);
+        if (rel != 0.0 && dies_in_reserve(tr, mn, mx, c)) status = 3; else E.move_clip(tr, c, rel);
       }
+    } else if (!std::strcmp(op, "resize")) {   // resize <track> <index> <rel> <resize_limit> <min_length> <left> <shift> <stretch>: Engine::resize_clip
+      unsigned t, i, left, shift, stretch; double rel, lim, ml;
+      std::sscanf(a, "%u %u %la %la %la %u %u %u", &t, &i, &rel, &lim, &ml, &left, &shift, &stretch);
+      Track* tr = E.tracks[t];
+      if (i >= tr->clips.size()) status = 2;
+      else {
+        Clip* c = tr->clips[i];
+        auto r = calc_resize_clip(c, rel, lim, ml, c->min_time, E.beat_duration, left != 0, shift != 0, stretch != 0);   // engine.cpp:377-378
+        if (rel != 0.0 && dies_in_reserve(tr, r.min, r.max, c)) status = 3;
+        else E.resize_clip(tr, c, rel, lim, ml, left != 0, shift != 0, stretch != 0);
+      }
+    } else if (!std::strcmp(op, "delregion")) {   // delregion <track> <min> <max>: Engine::delete_region
+      unsigned t; double mn, mx;
+      std::sscanf(a, "%u %la %la", &t, &mn, &mx);
+      Track* tr = E.tracks[t];
+      if (dies_in_reserve(tr, mn, mx, nullptr)) status = 3; else E.delete_region(tr, mn, mx);
     } else if (!std::strcmp(op, "query")) {    // query <track> <min> <max>: Track::query_clip_by_range (track.cpp:112-157) — what add / move /
       unsigned t; double mn, mx;               // resize / delete_region hand to reserve_track_region; answered with its own record
       std::sscanf(a, "%u %la %la", &t, &mn, &mx);

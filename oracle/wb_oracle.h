@@ -21,9 +21,16 @@
  *     into oracle/_ref/wbref_engine.  tests/test_ref_engine.py compares per block the master, transport, every track's
  *     AudioEvent list, sampler state and VU level, and the clip lists after edits (soak: 296 330 sessions / 4 570 895 blocks, 0
  *     divergences, profiles/r05_refseq_soak.txt); tests/golden/sequencer.npz carries its answers to 40 scripts everywhere.
- *     NOT in the cut (an unconditional Log:: line inside the function): Engine::reserve_track_region (overlap trimming:
- *     KAT-pinned, its arithmetic pinned through clip_edit.h), Engine::play / stop and Track::process_track_messages (a few
- *     statements each, restated by the driver and said so there).
+ *     THE CUT RULE: contiguous regions between function boundaries, printed unmodified — with ONE refinement: the region of
+ *     Engine::reserve_track_region (engine.cpp:478-569, overlap trimming) is printed unmodified except that the one
+ *     line consisting wholly of a Log::error("...") statement (engine.cpp:505, the null-allocator branch, which no script
+ *     reaches) is left out, nothing defined in its place (oracle/Makefile, engine_r3b.inc, with guards).  So overlap trimming
+ *     under add_audio_clip / move_clip / resize_clip / delete_region is pinned to reference-compiled code as well: the
+ *     `overlap` scripts reach every outcome class for every caller (tests/golden/overlap.npz; profiles/overlap_refseq_soak.txt:
+ *     1 500 sessions / 27 051 edits, 0 divergences).  The one edit that is NOT: Q11 (an inverted range on which the compiled
+ *     reference dies; the driver predicts it and answers status 3; tests/test_destroyed_clip.py defines it).
+ *     NOT in the cut (an unconditional Log:: line inside the function): Engine::play / stop and
+ *     Track::process_track_messages (a few statements each, restated by the driver and said so there).
  *
  * Build: gcc -O2 -ffp-contract=off -fno-fast-math  (no FMA contraction: the reference build has
  * none, CMakeLists.txt has no -march/-ffast-math).

@@ -226,3 +226,199 @@ def far_session_script(seed):
             s.op("seek", base + total * float(rng.uniform(0, 0.6)))
         s.op("clips")
     return s
+
+
+# ---- kind 'overlap': edits aimed at every outcome of Engine::reserve_track_region --------------------------------------------
+def _with(s: R.Script, extra):
+    t = R.Script(s.channels, s.block, s.rate)
+    t.ops, t.samples = list(s.ops) + list(extra), s.samples
+    return t
+
+
+def _candidates(rng, cl, t, ph, unit, n_samples, resample_ok, samples, family):
+    """aimed edits on track t whose clip list (floats) is cl: [(op tuple)], several per caller; which class each one is, the
+    reference says (overlap_script asks it)"""
+    out, n = [], len(cl)
+    under = [i for i, c in enumerate(cl) if c[0] <= ph < c[1]]
+
+    def pick():
+        return under[0] if under and rng.random() < 0.6 else int(rng.integers(0, n))
+
+    def before(i):          # a point not after clip i's start and not inside the clip in front of it: the edge itself, the neighbour's edge, the gap
+        c, lo = cl[i], (cl[i - 1][1] if i else max(cl[i][0] - 2 * unit, 0.0))
+        return float(rng.choice([c[0], lo, 0.5 * (lo + c[0])]))
+
+    def after(i):
+        c, hi = cl[i], (cl[i + 1][0] if i + 1 < n else cl[i][1] + 2 * unit)
+        return float(rng.choice([c[1], hi, 0.5 * (hi + c[1])]))
+
+    def inside(i):
+        c = cl[i]
+        return c[0] + (c[1] - c[0]) * float(rng.uniform(0.15, 0.85))
+
+    def a_range():
+        i = pick()
+        j = min(n - 1, i + int(rng.choice([0, 0, 1, 1, 2, 3])))
+        mn = inside(i) if rng.random() < 0.5 else before(i)
+        mx = inside(j) if rng.random() < 0.5 else after(j)
+        return (mn, mx) if mn < mx else None
+
+    for _ in range(6 if n else 0):
+        r = a_range()
+        if r:
+            si = int(rng.integers(0, n_samples))
+            out.append(_clip_args(rng, t, si, resample_ok[si], r[0], r[1] - r[0], samples[si][3]))
+        r = a_range()
+        if r:
+            out.append(("delregion", t, r[0], r[1]))
+    for _ in range(20 if n else 0):          # move: the new start aimed like a range's start, or so that the new END lies on an edge
+        m = pick() if rng.random() < 0.3 else int(rng.integers(0, n))
+        ln = cl[m][1] - cl[m][0]
+        i = int(rng.integers(0, n)) if rng.random() < 0.4 else min(n - 1, max(0, m + int(rng.choice([-2, -1, 1, 2]))))
+        to = float(rng.choice([inside(i), before(i), after(i) - ln, inside(i) - ln, cl[m][0] + ln * float(rng.uniform(-0.6, 0.6))]))
+        if to >= 0.0 and to != cl[m][0]:
+            out.append(("move", t, m, to - cl[m][0]))
+    for _ in range(10 if n else 0):          # resize: the moving edge aimed into gaps, onto edges, into and past the neighbours
+        m = pick() if rng.random() < 0.3 else int(rng.integers(0, n))
+        c, ln = cl[m], cl[m][1] - cl[m][0]
+        left = bool(rng.integers(0, 2))
+        shift = bool(rng.integers(0, 2))
+        stretch = bool(rng.integers(0, 2)) and resample_ok[c[5]]
+        if family == "inverted":             # the edge dragged past the clip's other edge (resize_limit 0: DESIGN Q11)
+            rel = (1 if left else -1) * ln * float(rng.uniform(1.05, 3.0))
+            out.append(("resize", t, m, rel, 0.0, 1.0 / 96.0, left, False, False))
+            continue
+        j = max(0, m - int(rng.choice([1, 1, 2, 3]))) if left else min(n - 1, m + int(rng.choice([1, 1, 2, 3])))
+        if rng.random() < 0.25 or j == m:
+            to = (c[0] + ln * float(rng.uniform(-0.5, 0.8))) if left else (c[1] - ln * float(rng.uniform(-0.5, 0.8)))
+        else:
+            to = float(rng.choice([inside(j), before(j), after(j)]))
+        rel = to - (c[0] if left else c[1])
+        if to < 0.0 or rel == 0.0 or (rel > 0.9 * ln if left else rel < -0.9 * ln):
+            continue
+        out.append(("resize", t, m, rel, 0.0, 1.0 / 96.0, left, shift, stretch))
+    return out
+
+
+def overlap_script(seed, family="classes"):
+    """Edits that land ON clips, aimed at every outcome class of Engine::reserve_track_region (ref_engine.classify) for every
+    caller.  The script is grown edit by edit WITH the reference executable: before an edit the reference is asked for the
+    track's clip list as it stands (a `clips` line after the script so far), some thirty candidate edits are aimed at it — range
+    edges inside clips, in the gaps, exactly on a clip's or a neighbour's edge (the values read back from the reference's list,
+    so equal bit for bit) — the reference answers a `query` line for each (the range from the reference's own clip_edit.h,
+    libwbref.so), and the candidate of the class this script still lacks most is taken.  In front of every edit stand a `clips`
+    and a `query` line, behind it a `clips` line: the comparison is per edit.  Sessions of 2-5 tracks, 10-40 blocks of 128-512
+    frames, every storage format, assets at and off the session rate, speeds 1 and != 1; mostly playing with the playhead
+    inside the clips (edits prefer the clip under it), sometimes stopped around the edits; runs of 1-4 edits between blocks;
+    deletes followed by splits on the same track (the split's right half takes over the freed Pool<Clip> chunk).
+    family 'inverted': ranges with min > max — a clip's right edge dragged left past its own start with resize_limit 0, what a
+    user interface can reach (a region handed to delete_region backwards is not: the reference asserts min <= max there,
+    track.cpp:113, and the product's wbx_engine_delete_region answers WBX_ERR_INVALID) — of which the Q11 ones answer status 3; the class scripts hold none.  Such an edit can leave a clip with max_time < min_time behind,
+    and the reference has no defined behaviour for PLAYING one (or for searching a list that holds one): these scripts stop
+    the engine first, never play again, and make at most one edit per track — status and clip lists are what they compare."""
+    global RATES, SPEEDS
+    RATES, SPEEDS = PLAIN_RATES, PLAIN_SPEEDS
+    ref = R.O.ref()
+    assert ref is not None and R.available(), "the overlap scripts are grown with the reference executable"
+    rng = np.random.default_rng([seed, 7 if family == "classes" else 8])
+    out_ch = int(rng.choice([1, 2, 2, 2]))
+    block = int(rng.choice([128, 128, 256, 384, 512]))
+    rate = int(rng.choice([44100, 48000, 48000, 96000]))
+    bpm = float(rng.choice([120.0, 97.0, 140.5, 174.0]))
+    s = R.Script(out_ch, block, rate, bpm)
+    n_tracks = int(rng.integers(2, 6))
+    n_blocks = int(rng.integers(10, 41 if block <= 256 else 21))
+    if family == "inverted":
+        n_blocks = n_tracks + 2
+    untouched = list(range(n_tracks))
+    beat_frames = rate * 60.0 / bpm
+    unit = block / beat_frames
+    resample_ok = _samples(rng, s, 0x5EB0000 + seed, n_tracks, rate, out_ch)
+    for t in range(n_tracks):
+        s.op("track")
+        s.op("vol", t, float(np.float32(rng.uniform(-20, 0))))
+        s.op("pan", t, float(np.float32(rng.uniform(-1, 1))))
+    for t in range(n_tracks):                # 4-7 clips per track, touching or with gaps, the first around the start
+        pos = unit * float(rng.uniform(0.0, 2.0))
+        for _ in range(int(rng.integers(4, 8))):
+            si = int(rng.integers(0, n_tracks))
+            length = unit * float(rng.choice([rng.uniform(0.3, 1.0), rng.uniform(1.0, 3.0), rng.uniform(3.0, 7.0)]))   # short between long
+            s.op(*_clip_args(rng, t, si, resample_ok[si], pos, length, s.samples[si][3]))
+            pos += length + (0.0 if rng.random() < 0.4 else unit * float(rng.uniform(0.1, 1.0)))
+    s.op("play")
+    playing, done, since = True, 0, 0       # since: the block at which play last started the playhead from 0
+    order = [p for p in R.GRID if R.unreachable(*p) is None]
+    rng.shuffle(order)
+    have = {}
+    while done < n_blocks:
+        k = int(rng.integers(1, 4))
+        s.op("run", k)
+        done += k
+        ph = (done - since) * unit
+        around = rng.random() < 0.25         # the engine stopped around this run of edits
+        if family == "inverted":
+            around = False
+            if playing:
+                s.op("stop")
+                playing = False
+            if not untouched:
+                continue
+        if around and playing:
+            s.op("stop")
+        for _ in range(int(rng.choice([1, 1, 2, 3, 4])) if family == "classes" else 1):
+            t = int(rng.integers(0, n_tracks)) if family == "classes" else untouched.pop(int(rng.integers(0, len(untouched))))
+            lists = R.records_clips(R.run_reference(_with(s, [("clips",)]))[-1][1])
+            cl = lists[t]
+            if len(cl) < 3 and family == "classes":                  # refill in free space behind the track's last clip
+                pos = (cl[-1][1] if cl else ph) + unit * float(rng.uniform(0.1, 1.0))
+                for _r in range(3):
+                    si = int(rng.integers(0, n_tracks))
+                    length = unit * float(rng.uniform(1.0, 4.0))
+                    s.op(*_clip_args(rng, t, si, resample_ok[si], pos, length, s.samples[si][3]))
+                    pos += length + unit * float(rng.choice([0.0, 0.5]))
+                continue
+            if rng.random() < 0.15 and family == "classes":          # a delete first: the next split on this track reuses the freed chunk (LIFO)
+                s.op("delclip", t, int(rng.integers(0, len(cl))))
+                lists = R.records_clips(R.run_reference(_with(s, [("clips",)]))[-1][1])
+                cl = lists[t]
+            cands = _candidates(rng, cl, t, ph, unit, n_tracks, resample_ok, s.samples, family)
+            ranges = []
+            for o in cands:
+                r = R.edit_range(ref, "ref", cl, s.samples, 60.0 / bpm, o)
+                if o[0] == "resize" and r is not None and o[8]:      # the stretched speed stays positive and sane (Q12)
+                    d = [R.O.C.c_double() for _ in range(4)]
+                    c = cl[o[2]]
+                    ref.ref_calc_resize_clip(c[0], c[1], c[2], c[3], float(s.samples[c[5]][2]), float(s.samples[c[5]][3]), o[3], o[4],
+                                             o[5], c[0], 60.0 / bpm, int(o[6]), int(o[7]), 1, 0, *[R.O.C.byref(x) for x in d])
+                    if not 0.05 < d[3].value < 16.0:
+                        r = None
+                ranges.append(r)
+            keep = [(o, r) for o, r in zip(cands, ranges) if r is not None]
+            if not keep:
+                continue
+            ans = [x[1] for x in R.run_reference(_with(s, [("query", t, r[0], r[1]) for _o, r in keep])) if x[0] == "query"][-len(keep):]
+            best, best_rank = None, None
+            for (o, r), q in zip(keep, ans):
+                cls = R.classify(cl, q, r[0], r[1], r[2])
+                caller = {"clip": "add", "move": "move", "delregion": "delregion"}.get(o[0]) or ("resize_left" if o[6] else "resize_right")
+                if family == "classes" and cls in ("q11", "inverted", "free"):
+                    continue
+                if family == "inverted" and cls not in ("q11", "inverted"):
+                    continue
+                rank = (have.get((caller, cls), 0), order.index((caller, cls)) if (caller, cls) in order else len(order))
+                if best_rank is None or rank < best_rank:
+                    best, best_rank = (o, r, caller, cls), rank
+            if best is None:
+                continue
+            o, r, caller, cls = best
+            have[(caller, cls)] = have.get((caller, cls), 0) + 1
+            s.op("clips")
+            s.op("query", t, r[0], r[1])
+            s.op(*o)
+            s.op("clips")
+        if around and playing:
+            s.op("play")
+            since = done                     # play restarts at playhead_start (engine.cpp:70-79)
+    s.op("run", 2)
+    s.op("clips")
+    return s

@@ -2,8 +2,10 @@
 Track::process / Engine::process of oracle/_ref/wbref_engine — the reference's code, cut out of its sources where they lie and
 compiled unmodified — answered to 40 session scripts; oracle/gen_golden.py sequencer).  Through the C ABI's Engine surface, as
 the audio callback (one wbx_engine_process per block) and as batch renders: master bit for bit, playhead / sample_position bit
-for bit, the running VU maxima, the clip lists after every edit.  Edits the reference's cut could not take (they need
-reserve_track_region) are skipped here exactly where the recording says they were refused."""
+for bit, the running VU maxima, the clip lists after every edit.  tests/golden/overlap.npz holds the same for scripts whose
+edits land ON clips — the reference's own Engine::reserve_track_region (overlap trimming) under add_audio_clip / move_clip /
+resize_clip / delete_region, aimed at every outcome class; there the plan rows of every block are compared too.  The one edit
+the compiled reference does not survive (Q11, status 3 in the recording) is skipped: tests/test_destroyed_clip.py defines it."""
 import numpy as np
 import pytest
 
@@ -19,7 +21,24 @@ def _cases():
     return [c for c in sequencer_golden_cases() if c[1].block % 4 == 0]
 
 
-def _replay(s, want, batch):
+def plan_rows(plan):
+    return [(b, t, bo, ns, O.f64_bits(off), O.f64_bits(spd), O.f32_bits(g), smp)
+            for (b, t, bo, ns, na, smp, off, spd, g, fl) in plan]
+
+
+def oracle_rows(e, block):
+    return [(block, t, ds, min(ln, 0xFFFF), O.f64_bits(off), O.f64_bits(spd), O.f32_bits(g), smp)
+            for (t, ds, ln, off, spd, g, smp) in e.seglog()]
+
+
+def _replay(s, want, batch, plan=False):
+    """plan: also the plan rows of every block (callback: wbx's fetch_plan after the block; batch: after the render) against the
+    oracle replaying the same script — the oracle is held to the same recording event for event on the CPU"""
+    import ref_engine as R
+    e = None
+    if plan:
+        e = O.OracleEngine(s.channels, s.block, s.rate)
+        e.enable_seglog()
     max_run = max([o[1] for o in s.ops if o[0] == "run"] + [1])
     eng = Engine(8, s.block, s.rate, s.channels, max_blocks=max_run if batch else 1)
     out = AudioBuffer(s.block, s.channels)
@@ -36,11 +55,21 @@ def _replay(s, want, batch):
             if batch:
                 eng.render(o[1])
                 m = eng.ctx.fetch()[0]          # [K][C][F]
+                if plan:
+                    rows = plan_rows(eng.fetch_plan())
+                    orows = []
+                    for b in range(o[1]):
+                        e.process()
+                        orows += oracle_rows(e, b)
+                    assert rows == orows, (rec[1][0]["block"], "plan rows")
             for b, br in enumerate(rec[1]):
                 if batch:
                     got = np.ascontiguousarray(m[b]).view(np.uint32)
                 else:
                     eng.process(None, out, float(rate_now[0]))
+                    if plan:
+                        e.process()
+                        assert [(0,) + r[1:] for r in plan_rows(eng.fetch_plan())] == oracle_rows(e, 0), (br["block"], "plan rows")
                     got = np.stack([out.get_write_pointer(c) for c in range(s.channels)]).view(np.uint32)
                     ph, sp, _pl = eng.transport()
                     assert (O.f64_bits(ph), O.f64_bits(sp)) == (br["playhead"], br["sample_position"]), (br["block"], ph, sp)
@@ -61,14 +90,14 @@ def _replay(s, want, batch):
             continue                # (a question to the reference's Track::query_clip_by_range: the oracle answers it, the engine has no such call)
         if k == "clips":
             assert rec[0] == "clips" and len(rec[1]) == len(eng.tracks)
-            for t, tr in enumerate(eng.tracks):
-                mine = [(O.f64_bits(c[0]), O.f64_bits(c[1]), O.f64_bits(c[2]), O.f64_bits(c[3]), O.f32_bits(c[4]), c[5])
-                        for c in eng.clips(tr)]
-                assert mine == rec[1][t], (t, mine, rec[1][t])
+            d = R.compare_clip_lists(rec[1], [R.clip_records(eng.clips(tr)) for tr in eng.tracks])
+            assert d is None, (wi - 1, d)
             continue
         assert rec[0] == "op"
         if rec[1] != 1:
-            continue                # refused by the reference's cut (needs reserve_track_region) or an index out of range
+            continue                # an index out of range (2) or Q11 (3)
+        if e is not None:
+            _on_oracle(e, s, o)
         if k in ("cfg",):
             pass
         elif k == "bpm":
@@ -82,7 +111,7 @@ def _replay(s, want, batch):
             eng.play()
         elif k == "stop":
             eng.stop()
-        elif k == "sample":
+        elif k in ("sample", "synth"):
             fmt, ch, rate, frames, data = s.samples[o[1]][:5]
             eng.add_sample(fmt, rate, [np.ascontiguousarray(d[:frames]) for d in data], frames)
         elif k == "track":
@@ -102,6 +131,10 @@ def _replay(s, want, batch):
             eng.set_clip_gain(eng.tracks[o[1]], o[2], o[3])
         elif k == "move":
             eng.move_clip(eng.tracks[o[1]], o[2], o[3])
+        elif k == "resize":
+            eng.resize_clip(eng.tracks[o[1]], *o[2:])
+        elif k == "delregion":
+            eng.delete_region(eng.tracks[o[1]], o[2], o[3])
         elif k == "deltrack":
             eng.delete_track(o[1])
         elif k == "movetrack":
@@ -111,7 +144,50 @@ def _replay(s, want, batch):
         else:
             raise AssertionError(k)
     eng.close()
+    if e is not None:
+        e.close()
     return blocks
+
+
+def _on_oracle(e, s, o):
+    """one taken operation of a script on the oracle (the plan rows' expectation)"""
+    k = o[0]
+    if k == "bpm": e.set_bpm(o[1])
+    elif k == "seek": e.set_playhead(o[1])
+    elif k == "rate": e.e.contents.sample_rate = int(o[1])
+    elif k == "play": e.play()
+    elif k == "stop": e.stop()
+    elif k in ("sample", "synth"): e.add_sample(*s.samples[o[1]][:5])
+    elif k == "track": e.add_track()
+    elif k == "vol": e.set_volume(o[1], o[2])
+    elif k == "pan": e.set_pan(o[1], o[2])
+    elif k == "mute": e.set_mute(o[1], o[2])
+    elif k == "clip": e.add_audio_clip(*o[1:])
+    elif k == "delclip": e.delete_clip(o[1], o[2])
+    elif k == "gain": e.set_clip_gain(o[1], o[2], o[3])
+    elif k == "move": e.move_clip(o[1], o[2], o[3])
+    elif k == "resize": e.resize_clip(*o[1:])
+    elif k == "delregion": e.delete_region(o[1], o[2], o[3])
+    elif k == "deltrack": e.delete_track(o[1])
+    elif k == "movetrack": e.move_track(o[1], o[2])
+    elif k == "solo": e.solo_track(o[1])
+    else: assert k == "cfg", k
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["callback", "render"])
+def test_product_equals_the_overlap_recordings(batch):
+    """tests/golden/overlap.npz on the device, once as one-block callbacks between the edits and once as batch renders between
+    them: master, transport (and VU maxima, callback) against the reference's recording bit for bit, after every edit the
+    track's whole clip list (wbx_engine_get_clip / clip_count) against the recording, and the plan rows of every block"""
+    from test_oracle_golden import overlap_golden_cases
+    n = blocks = 0
+    for name, s, want in overlap_golden_cases():
+        try:
+            blocks += _replay(s, want, batch, plan=True)
+        except AssertionError as e:
+            raise AssertionError(f"{name} ({'render' if batch else 'callback'}): {e}") from e
+        n += 1
+    assert n >= 12 and blocks > 200, (n, blocks)
 
 
 @pytest.mark.parametrize("batch", [False, True], ids=["callback", "render"])

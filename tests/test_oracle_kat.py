@@ -4,7 +4,9 @@ The numbers below are the outputs the survey recorded from the reference's own E
 Track::process / Sampler::stream compiled and run in the survey container (SURVEY.md §8(a) A8 and
 §8(c) "Seek-math KATs" / "Resampler KAT"), each asserted bit-for-bit.  Until round 5 they were the only pin the clip sequencer
 had; since then tests/test_ref_engine.py holds the oracle's sequencer to the reference's own compiled code (oracle/_ref/
-wbref_engine) — what stays KAT-pinned is Engine::reserve_track_region, which that build cannot hold.
+wbref_engine) — Engine::reserve_track_region (overlap trimming) included: its region is cut less the one whole-line Log::error
+statement (engine.cpp:505), and tests/golden/overlap.npz carries the reference's answers for every outcome of it.  The one
+edit not behind reference-compiled code is Q11 (the compiled reference dies on it: tests/test_destroyed_clip.py).
 """
 import ctypes as C
 
