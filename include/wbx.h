@@ -409,7 +409,9 @@ wbx_status wbx_engine_process(wbx_engine* e, float* const* out_planar);
 wbx_status wbx_engine_process_interleaved(wbx_engine* e, int out_format, void* dst);
 /* Engine::process(input_buffer, output_buffer, sample_rate) with its input buffer (engine.cpp:1576, the recorder tap
  * :1638-1649): in_planar[c][0..F) for c < n_in_channels.  Without a take running the input is not read (no monitoring:
- * engine.cpp:1625 leaves it out of the master); wbx_engine_process / _interleaved during a take record silence. */
+ * engine.cpp:1625 leaves it out of the master); wbx_engine_process / _interleaved during a take record silence, and so does
+ * a call whose n_in_channels is below the highest recorded channel + 1: the whole block is silence in every take, the
+ * channels the short buffer does hold included (WBX_RECORD_SILENCE). */
 wbx_status wbx_engine_process_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels, float* const* out_planar);
 wbx_status wbx_engine_process_interleaved_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels,
                                              int out_format, void* dst);
@@ -445,7 +447,8 @@ wbx_status wbx_engine_record(wbx_engine* e);
  * frames written) and a clip add_audio_clip(track, record_min_time, record_max_time, 0.0, sample, speed 1.0, gain 1.0f)
  * puts on its track (overlap trimming included); a take of no frames adds nothing.  Playback continues.  Returns
  * WBX_ERR_OVERFLOW (clips still made) when a take has WBX_RECORD_OVERFLOW.  wbx_engine_stop calls it first
- * (engine.cpp:83-84).  Deleting a recording track (or wbx_engine_clear_all) discards its take. */
+ * (engine.cpp:83-84).  Deleting a recording track (or wbx_engine_clear_all) discards its take: its storage goes back to the
+ * clip pool with the delete (wbx_clip_pool_stats), no later block is written into it, and stop_record makes no clip of it. */
 wbx_status wbx_engine_stop_record(wbx_engine* e);
 wbx_status wbx_engine_is_recording(wbx_engine* e, int* recording);
 typedef struct wbx_record_info {

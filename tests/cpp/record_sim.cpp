@@ -10,6 +10,12 @@
 //
 // Script lines (one call each):  tracks N | inputs N | bpm X | playhead X | input SLOT TYPE INDEX ARMED | arm SLOT ARMED |
 //                                record | stop_record | play | stop | block I (I < 0: no input) | delete SLOT | clear_all
+// Before the calls, optionally:  chunk N | capacity N   take storage in chunks of N frames, at most N of them per take.  The
+//                                device half decides which block is lost (rec_capture_locked: the block's last frame lies in a
+//                                chunk the take does not have); the harness restates that one comparison and hands the
+//                                verdict to the host session as the device half does (take_status_locked), so what is checked
+//                                here is what the HOST code makes of it: status latched, frames and record_max_time advancing,
+//                                stop_record's WBX_ERR_OVERFLOW with the clip still made.
 // Output: one "status S" line per call; for every clip stop_record makes:
 //   clip TRACK MIN_BITS MAX_BITS CH0 CHANNELS STATUS N_BLOCKS B0 B1 ...   (block -1: silence)
 #include <cinttypes>
@@ -36,6 +42,7 @@ uint64_t bits(double v) {
 struct RecordSim {
   HostSession hs;
   uint32_t F = 512;
+  uint64_t chunk = 65536, capacity = ~0ull;   // "chunk" / "capacity" lines
   // what lives in HBM in the product: which input block each block of every take holds (-1: silence)
   std::vector<std::vector<int64_t>> take_blocks;
 
@@ -82,9 +89,12 @@ struct RecordSim {
     hs.advance_transport_locked(1, F, hs.beat_duration.load());
     if (!hs.capture_due()) return WBX_OK;
     const uint64_t at = hs.capture_block_locked(F, input < 0);
-    for (auto& tb : take_blocks) {
+    const bool lost = (at + F - 1) / chunk >= capacity;
+    for (size_t k = 0; k < take_blocks.size(); k++) {
+      auto& tb = take_blocks[k];
       if (tb.size() * F != at) return WBX_ERR_FAILED;   // every take is written at the frame it has reached
-      tb.push_back(input);
+      if (lost && hs.takes[k].track) hs.take_status_locked(k, REC_OVERFLOW);
+      tb.push_back(lost ? -1 : input);
     }
     return WBX_OK;
   }
@@ -106,6 +116,12 @@ int main() {
       continue;
     } else if (op == "rate") {
       in >> hs.dst_rate;
+      continue;
+    } else if (op == "chunk") {
+      in >> sim.chunk;
+      continue;
+    } else if (op == "capacity") {
+      in >> sim.capacity;
       continue;
     } else if (op == "tracks") {
       int n;

@@ -10,7 +10,12 @@ Where the reference is undefined the library's documented choices (DESIGN.md "Re
     (play() during a take prepares the tracks of the running take only);
   * a process call without an input records silence (status REC_SILENCE);
   * deleting a recording track (or clear_all) discards its take; a take of no frames adds no clip;
-  * record() with an input past the configured input channel count is refused (INVALID), MIDI inputs are refused.
+  * record() with an input past the configured input channel count is refused (INVALID), MIDI inputs are refused;
+  * take storage is chunks of `chunk` frames and a take holds at most `capacity` of them (wbx_engine_set_record_chunk; the
+    chunk table's 65536 entries per take on the device): a block whose LAST frame lies in a chunk the take does not have is
+    lost whole — also its frames that lie in a chunk the take has —, it reads as silence, REC_OVERFLOW is latched, the frame
+    count and record_max_time advance as for any block, and stop_record returns OVERFLOW (-8) with the clip still made.
+    `capacity` is one number for every take or a list by position in the take list of a record() (None: no limit).
 
 A script is a list of tuples:
     ("tracks", n)                 n new tracks                 ("delete", slot) / ("clear_all",)
@@ -21,7 +26,7 @@ A script is a list of tuples:
     ("block", None)               one process call without an input
 run() returns the clips stop_record makes, in order: dict(track, args, blocks, ch0, channels, status) where args are the exact
 add_audio_clip arguments (track, min_time, max_time, start_offset 0.0, speed 1.0, gain 1.0) and blocks the input block index
-(None: silence) of every F frames of the take; take_frames() turns that into the take's samples.
+(None: silence, a lost block included) of every F frames of the take; take_frames() turns that into the take's samples.
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import numpy as np
 
 NONE, MIDI, STEREO, MONO = 0, 1, 2, 3          # TrackInputType, track_input.h:10-15
 REC_OVERFLOW, REC_SILENCE = 1, 2
-OK, UNSUPPORTED, INVALID = 0, -3, -4
+OK, UNSUPPORTED, INVALID, OVERFLOW = 0, -3, -4, -8
 
 
 class _Track:
@@ -39,14 +44,17 @@ class _Track:
 
 
 class _Take:
-    def __init__(self, track, ch0, channels):
+    def __init__(self, track, ch0, channels, capacity=None):
         self.track, self.ch0, self.channels = track, ch0, channels
         self.blocks, self.status = [], 0
+        self.capacity = capacity      # chunks this take can hold (None: as many as it needs)
 
 
 class RecordModel:
-    def __init__(self, block_frames: int = 512, sample_rate: int = 48000, bpm: float = 120.0):
+    def __init__(self, block_frames: int = 512, sample_rate: int = 48000, bpm: float = 120.0, chunk: int = 65536,
+                 capacity=None):
         self.F, self.sr = block_frames, sample_rate
+        self.chunk, self.capacity = chunk, capacity
         self.beat_duration = 60.0 / bpm
         self.tracks: list[_Track] = []
         self.input_channels = 0
@@ -87,7 +95,10 @@ class RecordModel:
         self.takes = []
         for t in self.tracks:
             if t.armed and t.type != NONE:
-                self.takes.append(_Take(t, 2 * t.index if t.type == STEREO else t.index, 2 if t.type == STEREO else 1))
+                cap = self.capacity
+                if isinstance(cap, (list, tuple)):
+                    cap = cap[len(self.takes)] if len(self.takes) < len(cap) else None
+                self.takes.append(_Take(t, 2 * t.index if t.type == STEREO else t.index, 2 if t.type == STEREO else 1, cap))
         self.recording = True
         self.play()
         return OK
@@ -103,7 +114,7 @@ class RecordModel:
                     self.clips.append(dict(track=slot, args=(slot, t.min_time, t.max_time, 0.0, 1.0, 1.0),
                                            blocks=list(tk.blocks), ch0=tk.ch0, channels=tk.channels, status=tk.status))
                     if tk.status & REC_OVERFLOW:
-                        st = -8
+                        st = OVERFLOW
             self._stop_record_track(t)
         self.takes = []
         return st
@@ -128,7 +139,11 @@ class RecordModel:
         self.playhead = self.playhead + buffer_duration_in_beats
         if self.recording and self.takes:
             for tk in self.takes:
-                tk.blocks.append(i)
+                last_chunk = (len(tk.blocks) * self.F + self.F - 1) // self.chunk     # the chunk of the block's last frame
+                lost = tk.capacity is not None and last_chunk >= tk.capacity
+                if lost and tk.track is not None:
+                    tk.status |= REC_OVERFLOW
+                tk.blocks.append(None if lost else i)
                 if i is None:
                     tk.status |= REC_SILENCE
         return OK
@@ -193,8 +208,8 @@ class RecordModel:
         return self.clips
 
 
-def run(script, block_frames=512, sample_rate=48000, bpm=120.0):
-    return RecordModel(block_frames, sample_rate, bpm).run(script)
+def run(script, block_frames=512, sample_rate=48000, bpm=120.0, chunk=65536, capacity=None):
+    return RecordModel(block_frames, sample_rate, bpm, chunk, capacity).run(script)
 
 
 def take_frames(clip: dict, inputs, block_frames: int) -> np.ndarray:

@@ -44,21 +44,31 @@ def input_blocks(rng, n, channels, F, special=True):
 
 
 class Rig:
-    """One script through the product engine, the model and the oracle engine side by side."""
+    """One script through the product engine, the model and the oracle engine side by side: every op of record_model.py's
+    script language.  `max_in`: the channel count of the buffer every process call hands over (the script's largest input
+    count, so that "block i is captured" holds whatever ("inputs", n) says at the time); `model`: a RecordModel made by the
+    caller (one with a capacity).  With `check_now` every take is checked the moment it is made — frames, placement, the
+    track's whole clip list against the oracle's, record_info — since a later take may trim or replace its clip.  A call the product refuses raises, as every engine call does; with `collect` its
+    status is kept instead (`statuses`, one per op, to be compared with the model's)."""
 
-    def __init__(self, spec, n_inputs, chunk, spare):
+    def __init__(self, spec, n_inputs, chunk, spare, max_in=None, spare_tracks=0, model=None, check_now=False,
+                 collect=False):
         self.spec, self.F = spec, spec.block
         self.e = O.build_oracle_engine(spec)
-        self.eng = build_engine(spec, max_blocks=1)
+        self.eng = build_engine(spec, max_blocks=1, spare_tracks=spare_tracks)
         self.eng.set_record_chunk(chunk, spare)
         self.eng.set_audio_channel_config(n_inputs, spec.channels, spec.block, spec.sample_rate)
-        self.m = RM.RecordModel(spec.block, spec.sample_rate, spec.bpm)
+        self.m = model or RM.RecordModel(spec.block, spec.sample_rate, spec.bpm)
         self.m.run([("tracks", spec.n_tracks), ("inputs", n_inputs)])
+        self.statuses = [0, 0]  # what the product returned for every call of the script (the two above: the constructor's)
         self.out = W.AudioBuffer(spec.block, spec.channels)
-        self.inb = W.AudioBuffer(spec.block, n_inputs)
+        self.inb = W.AudioBuffer(spec.block, n_inputs if max_in is None else max_in)
         self.inputs = []
         self.made = []          # (model clip, product sample id)
         self.masters, self.oracle_masters = [], []
+        self.check_now = check_now
+        self.collect = collect  # a call the product refuses: False — the error is raised, True — its status goes into statuses
+        self.process = None     # a stand-in for eng.process(inb or None, out): returns the block's master [C][F] or None
 
     def _oracle_takes(self, before):
         for c in self.m.clips[before:]:
@@ -69,72 +79,123 @@ class Rig:
             # the product's clip: the one on that track whose sample is new
             sids = [ci[5] for ci in self.eng.clips(self.eng.tracks[c["track"]])]
             self.made.append((c, max(sids)))
+            if self.check_now:
+                self.check_take(c, max(sids))
+                info = self.eng.record_info(c["track"])
+                assert (info["frames"], info["status"], info["recording"]) == (len(c["blocks"]) * self.F, c["status"], False), \
+                    (c["track"], info)
+        if self.check_now:
+            # every track's clip list is the oracle's after its trimming: no take but the model's was added anywhere
+            assert len(self.eng.tracks) == len(self.m.tracks)
+            for t in range(len(self.eng.tracks)):
+                got = [tuple(O.f64_bits(x) for x in ci[:4]) + (np.float32(ci[4]),) for ci in self.eng.clips(self.eng.tracks[t])]
+                want = [tuple(O.f64_bits(x) for x in ci[:4]) + (np.float32(ci[4]),) for ci in self.e.clips(t)]
+                assert got == want, ("clip list", t)
+
+    def _call(self, fn, *args):
+        try:
+            fn(*args)
+        except W.WbxError as ex:
+            if not self.collect:
+                raise
+            return ex.status
+        return 0
 
     def op(self, op, block=None, check=True):
         k = op[0]
         was_rec_playing = self.m.recording and self.m.playing
         n_clips = len(self.m.clips)
         self.m.run([op])
-        if k == "input":
-            self.eng.set_track_input(op[1], TYPE[op[2]], op[3], op[4])
+        st = 0
+        if k == "tracks":
+            for _ in range(op[1]):
+                st = st or self._call(self.eng.add_track)
+                self.e.add_track()
+        elif k == "inputs":     # the input count alone: set_audio_channel_config reconfigures the output, refused in a take
+            st = W.lib().wbx_engine_set_input_channels(self.eng.h, op[1])
+            assert st == 0 or self.collect, st
+        elif k == "delete":
+            st = self._call(self.eng.delete_track, op[1])
+            if st == 0:
+                self.e.delete_track(op[1])
+        elif k == "clear_all":
+            st = self._call(self.eng.clear_all)
+            for slot in range(self.e.e.contents.n_tracks - 1, -1, -1):
+                self.e.delete_track(slot)
+        elif k == "input":
+            st = self._call(self.eng.set_track_input, op[1], TYPE[op[2]], op[3], op[4])
         elif k == "arm":
-            self.eng.arm_track_recording(op[1], op[2])
+            st = self._call(self.eng.arm_track_recording, op[1], op[2])
         elif k == "record":
-            self.eng.record()
-            if not was_rec_playing:
+            st = self._call(self.eng.record)
+            if st == 0 and not was_rec_playing:
                 self.e.play()       # record() -> play() (engine.cpp:102)
         elif k == "play":
-            self.eng.play()
+            st = self._call(self.eng.play)
             self.e.play()
         elif k == "stop":
-            self.eng.stop()
+            st = self._call(self.eng.stop)
             self._oracle_takes(n_clips)
             self.e.stop()
         elif k == "stop_record":
-            self.eng.stop_record()
+            st = self._call(self.eng.stop_record)      # (-8: a take lost blocks; its clip is made all the same)
             self._oracle_takes(n_clips)
         elif k == "bpm":
-            self.eng.set_bpm(op[1])
+            st = self._call(self.eng.set_bpm, op[1])
             self.e.set_bpm(op[1])
         elif k == "playhead":
-            self.eng.set_playhead_position(op[1])
+            st = self._call(self.eng.set_playhead_position, op[1])
             self.e.set_playhead(op[1])
         elif k == "block":
-            if op[1] is None:
-                self.eng.process(None, self.out, float(self.spec.sample_rate))
-            else:
+            inb = None
+            if op[1] is not None:
                 for ch in range(self.inb.n_channels):
                     self.inb.channel_buffers[ch][:] = self.inputs[op[1]][ch]
-                self.eng.process(self.inb, self.out, float(self.spec.sample_rate))
+                inb = self.inb
+            if self.process is not None:
+                m = self.process(inb)
+            else:
+                self.eng.process(inb, self.out, float(self.spec.sample_rate))
+                m = np.stack(self.out.channel_buffers)
             om, _ = self.e.process()
-            m = np.stack(self.out.channel_buffers)
-            self.masters.append(m.copy())
             self.oracle_masters.append(om)
-            if check:
-                assert np.array_equal(bits(m), bits(om)), ("master", len(self.masters) - 1)
-                _, pk, _ = self.eng.ctx.fetch(peaks=True)
-                assert np.array_equal(pk[0], self.e.peaks()[:, :self.spec.channels]), ("peaks", len(self.masters) - 1)
+            if m is not None:       # (None: the stand-in kept the block in its own format)
+                self.masters.append(m.copy())
+                if check:
+                    self.check_block(m, om)
         else:
             raise ValueError(op)
+        self.statuses.append(st)
+
+    def check_block(self, m, om):
+        b = len(self.masters) - 1
+        assert np.array_equal(bits(m), bits(om)), ("master", b)
+        if len(self.eng.tracks):
+            _, pk, _ = self.eng.ctx.fetch(peaks=True)
+            assert np.array_equal(pk[0], self.e.peaks()[:, :self.spec.channels]), ("peaks", b)
 
     def run(self, script, check=True):
         for op in script:
             self.op(op, check=check)
 
+    def check_take(self, c, sid):
+        """the take equals the model's frames bit for bit, and its clip sits where the model's add_audio_clip put it"""
+        want = RM.take_frames(c, self.inputs, self.F)
+        for ch in range(c["channels"]):
+            got = self.eng.ctx.clip_download(sid, ch, want.shape[1], np.float32)
+            assert np.array_equal(bits(got), bits(want[ch])), (c["track"], ch)
+        infos = [ci for ci in self.eng.clips(self.eng.tracks[c["track"]]) if ci[5] == sid]
+        assert len(infos) == 1
+        mn, mx, so, spd, g, _ = infos[0]
+        t, wmn, wmx, wso, wspd, wg = c["args"]
+        assert (O.f64_bits(mn), O.f64_bits(mx), O.f64_bits(so), O.f64_bits(spd), np.float32(g)) == \
+            (O.f64_bits(wmn), O.f64_bits(wmx), O.f64_bits(wso), O.f64_bits(wspd), np.float32(wg))
+
     def check_takes(self):
-        """every take equals the model's frames bit for bit, and its clip sits where the model's add_audio_clip put it"""
+        """every take of the script, at its end (scripts whose takes do not cut into each other)"""
         assert len(self.made) == len(self.m.clips)
         for c, sid in self.made:
-            want = RM.take_frames(c, self.inputs, self.F)
-            for ch in range(c["channels"]):
-                got = self.eng.ctx.clip_download(sid, ch, want.shape[1], np.float32)
-                assert np.array_equal(bits(got), bits(want[ch])), (c["track"], ch)
-            infos = [ci for ci in self.eng.clips(self.eng.tracks[c["track"]]) if ci[5] == sid]
-            assert len(infos) == 1
-            mn, mx, so, spd, g, _ = infos[0]
-            t, wmn, wmx, wso, wspd, wg = c["args"]
-            assert (O.f64_bits(mn), O.f64_bits(mx), O.f64_bits(so), O.f64_bits(spd), np.float32(g)) == \
-                (O.f64_bits(wmn), O.f64_bits(wmx), O.f64_bits(wso), O.f64_bits(wspd), np.float32(wg))
+            self.check_take(c, sid)
 
     def close(self):
         self.eng.close()

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import record_model as RM
+import record_scripts as RS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, SR = 512, 48000
@@ -88,6 +89,75 @@ def test_arm_changes_wait_for_the_next_record_and_deleted_tracks_lose_their_take
     assert clips[0]["args"][1:3] == (0.0, chain(0.0, [BEATS(120.0)] * 2))   # play() prepared the take again
 
 
+def test_a_block_whose_last_frame_has_no_chunk_is_lost_whole():
+    """chunks of 700 frames, 3 of them: frames 0..2099 have room.  512-frame blocks 0-3 end at frame 2047 (chunk 2) and fit;
+    block 4 is frames 2048..2559: its first 52 frames lie in chunk 2, its last frame in chunk 3, which the take does not
+    have — the whole block is lost, and so is every later one."""
+    m = RM.RecordModel(F, SR, 120.0, chunk=700, capacity=3)
+    script = [("tracks", 1), ("inputs", 1), ("input", 0, RM.MONO, 0, True), ("playhead", 1.0), ("record",)]
+    script += [("block", b) for b in range(7)] + [("stop_record",)]
+    clips = m.run(script)
+    assert m.statuses[-1] == RM.OVERFLOW == -8 and len(clips) == 1
+    assert clips[0]["blocks"] == [0, 1, 2, 3, None, None, None]
+    assert clips[0]["status"] == RM.REC_OVERFLOW          # lost blocks are not "no input" blocks
+    assert clips[0]["args"] == (0, 1.0, chain(1.0, [BEATS(120.0)] * 7), 0.0, 1.0, 1.0)   # max_time advanced 7 times
+    inputs = [np.full((1, F), b + 1, np.float32) for b in range(7)]
+    fr = RM.take_frames(clips[0], inputs, F)
+    assert fr.shape == (1, 7 * F)
+    assert np.array_equal(fr[0, :4 * F], np.repeat(np.arange(1, 5, dtype=np.float32), F)) and not fr[0, 4 * F:].any()
+
+
+def test_a_block_that_ends_on_the_last_frame_of_the_last_chunk_fits():
+    # 4 chunks of 256 frames = 1024 frames = exactly two 512-frame blocks; the third is lost; 5 chunks of 205 = 1025 frames
+    # hold two blocks as well (the third block's last frame, 1535, is in chunk 7)
+    for chunk, cap in ((256, 4), (205, 5)):
+        m = RM.RecordModel(F, SR, 120.0, chunk=chunk, capacity=cap)
+        clips = m.run([("tracks", 1), ("inputs", 1), ("input", 0, RM.MONO, 0, True), ("record",), ("block", 0), ("block", 1),
+                       ("block", 2), ("stop",)])
+        assert clips[0]["blocks"] == [0, 1, None] and clips[0]["status"] == RM.REC_OVERFLOW
+    # one frame less room and the second block goes too; no capacity, or one that is never reached, loses nothing
+    assert RM.run([("tracks", 1), ("inputs", 1), ("input", 0, RM.MONO, 0, True), ("record",), ("block", 0), ("block", 1),
+                   ("stop_record",)], chunk=1023, capacity=1)[0]["blocks"] == [0, None]
+    m = RM.RecordModel(F, SR, 120.0, chunk=100, capacity=11)
+    clips = m.run([("tracks", 1), ("inputs", 1), ("input", 0, RM.MONO, 0, True), ("record",), ("block", 0), ("block", None),
+                   ("stop_record",)])
+    assert clips[0]["blocks"] == [0, None] and clips[0]["status"] == RM.REC_SILENCE and m.statuses[-1] == RM.OK
+
+
+def test_every_take_is_judged_by_its_own_capacity():
+    """two takes of one record(): the first has 2 chunks of 600 frames (two blocks and 176 frames of a third), the second
+    has room; a "no input" block after the limit sets REC_SILENCE on both; a later record() starts with empty takes"""
+    m = RM.RecordModel(F, SR, 120.0, chunk=600, capacity=[2, None])
+    script = [("tracks", 2), ("inputs", 3), ("input", 0, RM.STEREO, 0, True), ("input", 1, RM.MONO, 2, True), ("record",),
+              ("block", 0), ("block", 1), ("block", 2), ("block", None), ("stop_record",), ("record",), ("block", 4),
+              ("stop_record",)]
+    clips = m.run(script)
+    assert [(c["track"], c["blocks"], c["status"]) for c in clips] == [
+        (0, [0, 1, None, None], RM.REC_OVERFLOW | RM.REC_SILENCE), (1, [0, 1, 2, None], RM.REC_SILENCE),
+        (0, [4], 0), (1, [4], 0)]
+    assert m.statuses[9] == RM.OVERFLOW and m.statuses[-1] == RM.OK
+    assert clips[0]["args"][2] == clips[1]["args"][2] == chain(0.0, [BEATS(120.0)] * 4)
+
+
+def test_a_deleted_tracks_take_does_not_turn_stop_record_into_an_overflow():
+    m = RM.RecordModel(F, SR, 120.0, chunk=512, capacity=[1, None])
+    clips = m.run([("tracks", 2), ("inputs", 2), ("input", 0, RM.MONO, 0, True), ("input", 1, RM.MONO, 1, True), ("record",),
+                   ("block", 0), ("delete", 0), ("block", 1), ("stop_record",)])
+    assert [(c["track"], c["blocks"], c["status"]) for c in clips] == [(0, [0, 1], 0)] and m.statuses[-1] == RM.OK
+
+
+def test_the_device_scripts_do_something():
+    """the random scripts the device runs (tests/record_scripts.py): more clips than half the scripts in every configuration,
+    and among them a delete of a recording track, a record() that restarts a playing transport and an input-less block in a take"""
+    with_feature = np.zeros(4, dtype=int)
+    for block_frames, rate, chunk in RS.CONFIGS:
+        assert chunk % block_frames and block_frames % chunk
+        total, scripts_with = RS.census(block_frames, rate)
+        assert total[0] > RS.N_SCRIPTS // 2
+        with_feature += scripts_with
+    assert (with_feature[1:] >= 1).all(), with_feature
+
+
 # ---- the product's host code against the model -------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
@@ -101,8 +171,10 @@ def record_sim(tmp_path_factory):
     return exe
 
 
-def _script_text(script, block_frames, rate):
+def _script_text(script, block_frames, rate, chunk=None, capacity=None):
     lines = [f"frames {block_frames}", f"rate {rate}"]
+    if capacity is not None:
+        lines += [f"chunk {chunk}", f"capacity {capacity}"]
     for op in script:
         k = op[0]
         if k == "block":
@@ -118,8 +190,9 @@ def _bits(x):
     return struct.unpack("<Q", struct.pack("<d", x))[0]
 
 
-def run_sim(exe, script, block_frames=F, rate=SR):
-    r = subprocess.run([exe], input=_script_text(script, block_frames, rate), capture_output=True, text=True, timeout=60)
+def run_sim(exe, script, block_frames=F, rate=SR, chunk=None, capacity=None):
+    r = subprocess.run([exe], input=_script_text(script, block_frames, rate, chunk, capacity), capture_output=True, text=True,
+                       timeout=60)
     assert r.returncode == 0, r.stderr
     statuses, clips = [], []
     for ln in r.stdout.splitlines():
@@ -133,10 +206,10 @@ def run_sim(exe, script, block_frames=F, rate=SR):
     return statuses, clips
 
 
-def compare(exe, script, block_frames=F, rate=SR):
-    m = RM.RecordModel(block_frames, rate)
+def compare(exe, script, block_frames=F, rate=SR, chunk=None, capacity=None):
+    m = RM.RecordModel(block_frames, rate) if capacity is None else RM.RecordModel(block_frames, rate, 120.0, chunk, capacity)
     want = m.run(script)
-    statuses, got = run_sim(exe, script, block_frames, rate)
+    statuses, got = run_sim(exe, script, block_frames, rate, chunk, capacity)
     assert statuses == m.statuses
     assert len(got) == len(want)
     for g, w in zip(got, want):
@@ -150,6 +223,28 @@ def test_host_code_matches_the_hand_checked_cases(record_sim):
     compare(record_sim, [("tracks", 2), ("inputs", 4), ("input", 0, RM.MONO, 3, True), ("input", 1, RM.STEREO, 1, True),
                          ("playhead", 1.5), ("record",), ("block", 0), ("bpm", 133.7), ("block", None), ("block", 2),
                          ("record",), ("play",), ("block", 3), ("stop",)])
+
+
+@pytest.mark.parametrize("block_frames,rate,chunk,capacity", [(512, 48000, 700, 3), (480, 48000, 333, 7), (128, 44100, 64, 9),
+                                                              (512, 48000, 256, 4)])
+def test_host_code_carries_an_overflow_like_the_model(record_sim, block_frames, rate, chunk, capacity):
+    """the overflow extension through the product's host session: lost blocks, the latched status, frames and record_max_time
+    still advancing, stop_record's -8 with the clip made — a hand-written take past its capacity and 25 random scripts"""
+    script = [("tracks", 2), ("inputs", 4), ("input", 0, RM.MONO, 3, True), ("input", 1, RM.STEREO, 0, True), ("record",)]
+    script += [("block", b) for b in range(12)] + [("bpm", 90.0), ("block", None), ("stop_record",), ("record",), ("block", 13),
+                                                   ("stop",)]
+    m = RM.RecordModel(block_frames, rate, 120.0, chunk, capacity)
+    clips = m.run(script)
+    assert RM.OVERFLOW in m.statuses and all(c["status"] & RM.REC_OVERFLOW for c in clips[:2]) and clips[2]["status"] == 0
+    compare(record_sim, script, block_frames, rate, chunk, capacity)
+    rng = np.random.default_rng(0x0F10 + chunk)
+    overflows = 0
+    for _ in range(25):
+        script = RM.random_script(rng)
+        m = RM.RecordModel(block_frames, rate, 120.0, chunk, capacity)
+        overflows += any(c["status"] & RM.REC_OVERFLOW for c in m.run(script))
+        compare(record_sim, script, block_frames, rate, chunk, capacity)
+    assert overflows >= 3   # the random takes do run past the capacity
 
 
 @pytest.mark.parametrize("block_frames,rate", [(512, 48000), (128, 44100), (480, 48000)])

@@ -103,8 +103,9 @@ struct wbx_engine {
   static constexpr int kRecSlots = 8;
   uint32_t rec_chunk = 65536, rec_spare = 2;   // wbx_engine_set_record_chunk (audio_record_chunk_size / 4, engine.h:36)
   struct RecTake {
-    std::vector<ClipSlot> chunks;              // the recorder thread's while the take runs
+    std::vector<ClipSlot> chunks;              // the recorder thread's while the take runs (under rec_mu)
     uint32_t channels = 1;
+    bool discarded = false;                    // its track went (rec_discard_takes_locked): no chunks, none to come (under rec_mu)
     std::atomic<uint32_t> ready{0};            // chunks whose table entry is enqueued ahead of any capture that uses it
   };
   std::unique_ptr<RecTake[]> rec_takes;
@@ -120,7 +121,7 @@ struct wbx_engine {
   std::thread rec_thread;
   std::atomic<bool> rec_run{false};
   std::atomic<uint64_t> rec_written{0};        // frames of the takes the audio thread has dealt with (all takes alike)
-  std::mutex rec_mu;                           // (the recorder thread's sleep only)
+  std::mutex rec_mu;                           // the recorder thread's sleep, and every take's chunk list while that thread runs
   std::condition_variable rec_cv;
   std::atomic<wbx_status> rec_thread_err{WBX_OK};
   uint64_t rec_captures = 0;                   // capture launches so far (diagnostic)
@@ -213,6 +214,7 @@ extern "C" wbx_status wbx_engine_create(const wbx_config* cfg, wbx_engine** out)
 
 namespace {
 void rec_release(wbx_engine* e);
+void rec_discard_takes_locked(wbx_engine* e);
 }
 
 extern "C" void wbx_engine_destroy(wbx_engine* e) {
@@ -413,6 +415,7 @@ wbx_status permute_tracks_locked(wbx_engine* e, const std::vector<uint32_t>& ord
     e->state_tracks = new_n;
   }
   e->hs.permute_tracks_locked(order);
+  rec_discard_takes_locked(e);   // a recording track that went: its take's chunks go back to the pool now
   return WBX_OK;
 }
 
@@ -1242,7 +1245,9 @@ wbx_status rec_fill(wbx_engine* e, uint64_t written) {
   const uint32_t need = rec_chunks_needed(e, written);
   for (uint32_t k = 0; k < e->rec_n; k++) {
     wbx_engine::RecTake& t = e->rec_takes[k];
-    while (t.chunks.size() < need) {
+    while (true) {
+      std::lock_guard<std::mutex> lk(e->rec_mu);   // (per chunk: rec_discard_takes_locked never waits for a whole fill)
+      if (t.discarded || t.chunks.size() >= need) break;
       ClipSlot s;
       ClipFill f{};
       f.kind = CLIP_SRC_ZERO;
@@ -1273,6 +1278,29 @@ void rec_thread_main(wbx_engine* e) {
   }
 }
 
+// Deleting a recording track (or clear_all) discards its take: the host session has cut the take loose from its track
+// (permute_tracks_locked); here its chunks go back to the pool — once the captures in flight are through with them — and it
+// gets no more (rec_fill), so wbx_clip_pool_stats shows the discard at once and rec_capture_locked finds no chunk ready to
+// write the take's later blocks into.  The UI thread, editor lock held (no capture is being issued meanwhile).
+void rec_discard_takes_locked(wbx_engine* e) {
+  if (!e->hs.recording || !e->rec_n || e->hs.takes.size() != e->rec_n) return;
+  bool waited = false;
+  for (uint32_t k = 0; k < e->rec_n; k++) {
+    wbx_engine::RecTake& t = e->rec_takes[k];
+    if (e->hs.takes[k].track || t.discarded) continue;
+    {
+      std::lock_guard<std::mutex> lk(e->rec_mu);
+      t.discarded = true;
+      t.ready.store(0, std::memory_order_release);
+    }
+    if (!waited) (void)hipStreamSynchronize(e->ctx->upload_stream);   // captures and zero fills that still touch the chunks
+    waited = true;
+    std::lock_guard<std::mutex> lk(e->rec_mu);
+    for (auto& s : t.chunks) clip_release(e->ctx, s);
+    t.chunks.clear();
+  }
+}
+
 // stop the recorder thread, wait for every capture, free what the takes hold (the UI thread; no take running)
 void rec_release(wbx_engine* e) {
   if (e->rec_thread.joinable()) {
@@ -1293,7 +1321,10 @@ void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
   if (!hs.capture_due()) return;
   wbx_ctx* c = e->ctx;
   const uint32_t F = e->rec_F;
-  const uint64_t start = hs.capture_block_locked(F, !in || n_in < e->rec_in_ch);
+  // a call without (all of) the recorded input channels records silence in every take — the host session counts it as a
+  // silent block (REC_SILENCE), so no channel of it may be staged, the ones the short buffer does hold included
+  const bool silence = !in || n_in < e->rec_in_ch;
+  const uint64_t start = hs.capture_block_locked(F, silence);
   const uint32_t slot = e->rec_slot;
   const bool slot_free = !e->rec_ev_valid[slot] || hipEventQuery(e->rec_ev[slot]) == hipSuccess;
   uint32_t* stage = e->h_rec_stage + slot * e->rec_slot_words;
@@ -1303,18 +1334,17 @@ void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
   for (uint32_t k = 0; k < e->rec_n; k++) {
     const Take& tk = hs.takes[k];
     uint32_t d = 0;
-    if (tk.track) {
-      if (slot_free && e->rec_takes[k].ready.load(std::memory_order_acquire) > last_chunk)
-        d = tk.ch0 << 2 | tk.channels;
-      else
-        hs.take_status_locked(k, REC_OVERFLOW);
-    }
+    // (a discarded take — its track was deleted — holds no chunk and gets none: `ready` is 0, it is never written again)
+    if (slot_free && e->rec_takes[k].ready.load(std::memory_order_acquire) > last_chunk)
+      d = tk.ch0 << 2 | tk.channels;
+    else if (tk.track)
+      hs.take_status_locked(k, REC_OVERFLOW);
     if (slot_free) desc[k] = d;
     any |= d != 0u;
   }
   if (any) {
     for (uint32_t ch = 0; ch < e->rec_in_ch; ch++) {
-      if (in && ch < n_in && in[ch])
+      if (!silence && in[ch])   // (a null row of a full-width buffer stages zeros for that channel alone, without REC_SILENCE)
         std::memcpy(stage + (size_t)ch * F, in[ch], (size_t)F * sizeof(float));
       else
         std::memset(stage + (size_t)ch * F, 0, (size_t)F * sizeof(float));
@@ -1341,7 +1371,7 @@ void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
   e->rec_written.store(start + F, std::memory_order_release);
   const uint32_t need = rec_chunks_needed(e, start + F);
   for (uint32_t k = 0; k < e->rec_n; k++)
-    if (e->rec_takes[k].ready.load(std::memory_order_relaxed) < need) {
+    if (hs.takes[k].track && e->rec_takes[k].ready.load(std::memory_order_relaxed) < need) {
       e->rec_cv.notify_one();
       break;
     }

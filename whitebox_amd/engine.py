@@ -509,6 +509,18 @@ class Engine:
         self.ctx.last = (1, len(self.tracks))
         return out
 
+    def process_interleaved_in(self, input_buffer: AudioBuffer, fmt: str, n_in: Optional[int] = None) -> np.ndarray:
+        """process_interleaved with the input buffer of Engine::process: what an audio back end calls while a take runs.
+        `n_in`: how many of the buffer's channels to hand over (all of them by default)."""
+        assert input_buffer.n_samples >= self.audio_buffer_size
+        dt = {"i16": np.int16, "i24": np.uint8, "i24_x8": np.int32, "i32": np.int32, "f32": np.float32}[fmt]
+        out = np.zeros(self.audio_buffer_size * self.num_output_channels * (3 if fmt == "i24" else 1), dtype=dt)
+        n_in = input_buffer.n_channels if n_in is None else n_in
+        _check(self.L.wbx_engine_process_interleaved_in(self.h, input_buffer._ptrs(), n_in, _ffi.OUT_FMT[fmt], out.ctypes.data),
+               "Engine::process_interleaved_in", self.h, True)
+        self.ctx.last = (1, len(self.tracks))
+        return out
+
     # ---- recording (engine.cpp:95-200) ----
     def set_track_input(self, slot: int, type: str, index: int, armed: bool):
         """Engine::set_track_input; type: "none", "external_stereo", "external_mono" ("midi" is refused)."""
