@@ -141,6 +141,43 @@ wbx_status wbx_clip_ingest_device(wbx_ctx* ctx, uint32_t clip, int format, uint3
 /* planar clip audio back to the host (tests; also Sample::get_read_pointer's role for host-side tools) */
 wbx_status wbx_clip_download(wbx_ctx* ctx, uint32_t clip, uint32_t channel, void* dst);
 
+/* Export: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels (a take, a bounce, any
+ * uploaded F32 clip) as interleaved samples of a device format — the way into an audio file.  The counterpart of
+ * wbx_clip_upload_interleaved; the conversion is wbx_fetch_interleaved's (core/audio_format_conv.cpp:5-91: asymmetric
+ * scales, truncation, the x86 results out of range), run on the device in the pass that interleaves.
+ *   layout   sample i, channel c at index i*C + c in EVERY format.  WBX_OUT_I24 here is TRUE packed interleave: byte k of
+ *            the 24-bit sample at dst[(i*C + c)*3 + k].  This is deliberately NOT wbx_fetch_interleaved's WBX_OUT_I24,
+ *            which mirrors the reference writer's quirk (every channel overwrites bytes [0, 3F)): that is right for parity
+ *            of the audio callback and useless for a file, which needs every channel
+ *   flags    WBX_EXPORT_CLAMP: every sample first goes through the master's clamp, x > 1 ? 1 : (x < -1 ? -1 : x)
+ *            (engine.cpp:1627-1636; NaN passes).  Without it a post-fader stem beyond +-1.0 wraps as the reference's
+ *            conversion does (1.5 as 16-bit: -16386)
+ *   stats    (may be NULL) per channel, over the SOURCE values of this call's range, before any clamp: peak = max |x|
+ *            (a NaN never raises it; 0 for an all-NaN range), over = samples with x > 1 or x < -1, nans = NaN samples
+ *   dst      caller-owned host memory of wbx_export_bytes(out_format, channels, n_frames) bytes, pageable or from
+ *            wbx_host_alloc (then the copy engine writes it directly)
+ *   staging  the range goes in chunks through three pinned slots made at first use and freed with the context: device
+ *            and pinned memory used do not depend on the clip's length; the kernel and transfer of the next chunks run
+ *            while the host copies one out.  A long clip may be exported in several calls with advancing first_frame
+ *            (streaming into a file): the bytes are those of one call, the stats are per call
+ *   order    runs on a stream of its own (no mix or sum stream), ordered after everything enqueued so far on the
+ *            context's main and upload streams; returns when dst is complete
+ * WBX_ERR_INVALID: unknown clip, n_frames == 0, first_frame + n_frames > the clip's frames, dst NULL, flags other than
+ * WBX_EXPORT_CLAMP.  WBX_ERR_UNSUPPORTED: an unknown out_format, a clip whose storage format is not F32 (the reference
+ * has no integer-to-device-format path).  dst is untouched after a refusal. */
+enum { WBX_EXPORT_CLAMP = 1 };
+typedef struct wbx_export_stats {
+  float peak[2];
+  uint64_t over[2];
+  uint64_t nans[2];
+} wbx_export_stats;
+uint64_t wbx_export_bytes(int out_format, uint32_t channels, uint64_t n_frames);   /* 0 for an unknown format */
+wbx_status wbx_clip_export(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, int out_format,
+                           uint32_t flags, void* dst, wbx_export_stats* stats);
+/* Frames per staging chunk of later exports: a multiple of 8, 8 .. 2^24; 0 = the default (2^20).  For tests, which reach
+ * chunk seams with 1000-frame clips this way (cf. wbx_engine_set_record_chunk); results do not depend on it. */
+wbx_status wbx_set_export_chunk(wbx_ctx* ctx, uint32_t frames);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -505,6 +542,16 @@ typedef struct wbx_bounce_source {
 } wbx_bounce_source;
 wbx_status wbx_engine_bounce(wbx_engine* e, double min_time, double max_time, const wbx_bounce_source* src, uint32_t n_src,
                              uint32_t* samples_out, uint64_t* frames_out);
+/* wbx_clip_export of an engine sample (a take's, a bounce's, an uploaded F32 sample), for the editing thread — the audio
+ * thread may keep calling wbx_engine_process* meanwhile, playing or recording: an export touches no transport state.  The
+ * editor lock is held only to validate the sample, pin it and order the export's stream behind the work enqueued so
+ * far; never across a device wait or a chunk copy (the rule of wbx_engine_levels).  While the export is in flight
+ * wbx_engine_delete_sample refuses that sample (WBX_ERR_UNSUPPORTED, "sample is being exported"); the pin is dropped
+ * when the call returns.  (wbx_engine_clear_all removes tracks, not samples, and needs no such check.)  Allowed on a
+ * redirected master and a multi-GPU context: it reads the local clip pool only.  Arguments, refusals and results are
+ * wbx_clip_export's. */
+wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, int out_format,
+                                    uint32_t flags, void* dst, wbx_export_stats* stats);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -298,6 +298,18 @@ struct Engine {
     check(wbx_engine_bounce(h, min_time, max_time, sources.data(), (uint32_t)sources.size(), ids.data(), frames), "bounce");
     return ids;
   }
+  // Export a sample (a take's, a bounce's, any F32 sample) as interleaved samples of a device format (WBX_OUT_*) into
+  // `dst` — wbx_export_bytes(out_format, channels, n_frames) bytes of host memory — and return the range's statistics
+  // (peak, samples beyond +-1, NaNs per channel, of the source values).  Packed 24-bit is true interleave here (every
+  // channel, unlike the callback's writer).  Editing thread; the audio thread may keep calling process().  A long sample
+  // may be streamed into a file by calls with advancing first_frame.  Semantics and refusals: wbx_clip_export, wbx.h.
+  wbx_export_stats export_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, int out_format, void* dst,
+                                 bool clamp = true) {
+    wbx_export_stats stats{};
+    check(wbx_engine_export_sample(h, sample, first_frame, n_frames, out_format, clamp ? (uint32_t)WBX_EXPORT_CLAMP : 0u, dst, &stats),
+          "export_sample");
+    return stats;
+  }
   // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
   // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
   void record() { check(wbx_engine_record(h), "record"); }

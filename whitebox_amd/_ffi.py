@@ -52,6 +52,10 @@ class BounceSource(C.Structure):
     _fields_ = [("kind", C.c_int32), ("index", C.c_uint32), ("tap", C.c_int32), ("_pad", C.c_uint32)]
 
 
+class ExportStats(C.Structure):
+    _fields_ = [("peak", C.c_float * 2), ("over", C.c_uint64 * 2), ("nans", C.c_uint64 * 2)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -65,6 +69,8 @@ INPUT_TYPE = {"none": 0, "midi": 1, "external_stereo": 2, "external_mono": 3}
 BOUNCE_KIND = {"track": 0, "bus": 1, "master": 2}     # WBX_BOUNCE_*
 BOUNCE_TAP = {"post": 0, "pre": 1}                      # WBX_TAP_*
 OUT_FMT = {"i16": 3, "i24": 5, "i24_x8": 6, "i32": 7, "f32": 9}
+OUT_DTYPE = {"i16": "<i2", "i24": "u1", "i24_x8": "<i4", "i32": "<i4", "f32": "<f4"}   # numpy element of an exported buffer
+EXPORT_CLAMP = 1                                        # WBX_EXPORT_CLAMP
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
 _vp, _u32, _i32, _f, _d, _sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_double, C.c_size_t
@@ -84,6 +90,9 @@ SYMBOLS = {
     "wbx_clip_upload_interleaved": (C.c_int, [_vp, _u32, C.c_int, _u32, _u32, C.c_uint64, _vp]),
     "wbx_clip_ingest_device": (C.c_int, [_vp, _u32, C.c_int, _u32, _u32, C.c_uint64, _vp]),
     "wbx_clip_download": (C.c_int, [_vp, _u32, _u32, _vp]),
+    "wbx_export_bytes": (C.c_uint64, [C.c_int, _u32, C.c_uint64]),
+    "wbx_clip_export": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _vp, C.POINTER(ExportStats)]),
+    "wbx_set_export_chunk": (C.c_int, [_vp, _u32]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -171,6 +180,7 @@ SYMBOLS = {
     "wbx_engine_process_interleaved_in": (C.c_int, [_vp, _fpp, _u32, C.c_int, _vp]),
     "wbx_engine_render": (C.c_int, [_vp, _u32]),
     "wbx_engine_bounce": (C.c_int, [_vp, _d, _d, C.POINTER(BounceSource), _u32, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
+    "wbx_engine_export_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _vp, C.POINTER(ExportStats)]),
     "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
     "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),

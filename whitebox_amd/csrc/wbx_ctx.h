@@ -72,6 +72,15 @@ struct StemArgs {
   uint32_t tmpl_cap, pool_chunks;
 };
 void launch_stem(const StemArgs& a, hipStream_t s);
+// exporting (wbx_export.hip): one staging chunk of a planar F32 clip -> interleaved samples of a device format
+struct ExportArgs {
+  const float* src[2];         // the channel rows at the chunk's first frame (4-byte aligned; mono: src[1] unused)
+  void* dst;                   // the chunk's samples, 16-byte aligned: [n_frames][channels]
+  uint32_t* stats;             // device: peak bits [2], samples beyond +-1 [2], NaNs [2] — zero before the launch
+  uint32_t n_frames;           // <= kExportChunkMax
+  uint32_t channels, format, flags;   // 1 or 2 / WBX_OUT_* / WBX_EXPORT_*
+};
+void launch_export(const ExportArgs& a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -136,6 +145,29 @@ struct DevBuf {             // grow-only device array
 };
 
 struct DistState;   // wbx_dist.hip
+
+// wbx_clip_export's staging: a stream of its own and kExportSlots chunks, each a device buffer the kernel writes, a pinned
+// host buffer the copy engine moves it into and a block of statistics — made at first use, the same size for a clip of a
+// thousand frames and one of 2^31 (a chunk is at most 8 bytes per frame: two channels of 32 bits), freed with the context.
+constexpr int kExportSlots = 3;
+constexpr uint32_t kExportChunkDefault = 1u << 20, kExportChunkMax = 1u << 24;
+struct ExportStage {
+  hipStream_t stream = nullptr;
+  hipEvent_t after_main = nullptr, after_upload = nullptr;   // what last wrote the clip: the main and the upload stream
+  uint32_t chunk = 0;                     // frames the slots were made for
+  void* d_slot[kExportSlots] = {};
+  void* h_slot[kExportSlots] = {};        // pinned
+  uint32_t* d_stats[kExportSlots] = {};   // 8 words each (6 used)
+  uint32_t* h_stats = nullptr;            // pinned: [kExportSlots][8]
+  hipEvent_t done[kExportSlots] = {};
+};
+// a clip's storage as an export needs it (layer 2 copies it out of the pool under the editor lock)
+struct ExportSrc {
+  const void* base = nullptr;
+  size_t stride = 0;
+  uint32_t channels = 0, format = 0;
+  uint64_t frames = 0;
+};
 
 }  // namespace wbx
 
@@ -294,6 +326,12 @@ struct wbx_ctx {
   bool has_non16_clips = false;       // a clip asset that is not 16-bit PCM
   bool auto_group = false;            // wbx_config.group_size was 0: the library picks the track-group size
 
+  // wbx_clip_export / wbx_engine_export_sample: one export at a time (export_mu), on a stream that is no mix or sum stream
+  ExportStage exp;
+  std::mutex export_mu;
+  std::atomic<uint32_t> export_chunk{0};   // wbx_set_export_chunk: frames per staging chunk, 0 = kExportChunkDefault
+  bool knob_export_direct = false;     // WBX_EXPORT_DIRECT=1 (A/B aid, read at wbx_create): the kernel stores into the pinned slot itself
+
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
   hipEvent_t pace_ev[kPaceRing] = {};  // wbx_pace
@@ -354,6 +392,15 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
                       const ClipFill& f, hipStream_t on);
 wbx_status clip_publish(wbx_ctx* c, uint32_t clip, ClipSlot& s);
 void clip_release(wbx_ctx* c, ClipSlot& s);
+// exporting: argument checks (no device call), "order the export stream after what last wrote the pool" (enqueues only;
+// layer 2 calls it under the editor lock) and the chunk loop (no lock held; `why` gets the message of a failure)
+wbx_status export_check(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+                        const void* dst, const char** why);
+wbx_status export_prepare(wbx_ctx* c, std::string* why);   // stream, events and slots for the chunk size in force
+wbx_status export_order(wbx_ctx* c, std::string* why);
+wbx_status export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+                      void* dst, wbx_export_stats* stats, std::string* why);
+void export_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it

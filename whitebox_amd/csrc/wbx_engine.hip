@@ -125,6 +125,10 @@ struct wbx_engine {
   std::condition_variable rec_cv;
   std::atomic<wbx_status> rec_thread_err{WBX_OK};
   uint64_t rec_captures = 0;                   // capture launches so far (diagnostic)
+  // wbx_engine_export_sample: the sample an export in flight reads (under the editor lock; one export at a time,
+  // wbx_ctx::export_mu) — wbx_engine_delete_sample refuses it until the export is over
+  static constexpr uint32_t kNoExport = ~0u;
+  uint32_t export_pin = kNoExport;
 };
 
 namespace {
@@ -572,10 +576,48 @@ extern "C" wbx_status wbx_engine_delete_sample(wbx_engine* e, uint32_t sample) {
   e->hs.note_edit_locked();
   if (!e->hs.valid_sample(sample)) return efail(e, WBX_ERR_INVALID, "unknown sample");
   if (e->hs.sample_referenced(sample)) return efail(e, WBX_ERR_INVALID, "sample is still referenced by a clip (delete the clips first)");
+  if (e->export_pin == sample) return efail(e, WBX_ERR_UNSUPPORTED, "sample is being exported (wbx_engine_export_sample is still reading it)");
   const wbx_status st = wbx_clip_free(e->ctx, sample);
   if (st != WBX_OK) return cfail(e, st);
   e->hs.samples[sample] = SampleMeta{};
   return WBX_OK;
+}
+
+// An engine sample as interleaved device-format audio (wbx_clip_export; wbx.h).  Editing thread; the audio thread may be in
+// wbx_engine_process* all the while.  The editor lock covers validating the sample, copying its storage description out of
+// the pool (the pool's table may be reallocated by a later add_sample), pinning it against wbx_engine_delete_sample and
+// ordering the export stream behind what is enqueued — stream calls only; the staging slots are made before, the chunk
+// loop with its device waits and host copies runs after, both without the lock (the rule of wbx_engine_levels).
+extern "C" wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                               int out_format, uint32_t flags, void* dst, wbx_export_stats* stats) {
+  if (!e) return WBX_ERR_INVALID;
+  wbx_ctx* c = e->ctx;
+  std::lock_guard<std::mutex> one(c->export_mu);
+  (void)hipSetDevice(c->cfg.device);
+  std::string why;
+  ExportSrc src;
+  {
+    LockGuard g(e->hs.editor_lock);
+    if (!e->hs.valid_sample(sample) || sample >= c->clips.size() || !c->clips[sample].base) return efail(e, WBX_ERR_INVALID, "export: unknown sample");
+    const ClipSlot& s = c->clips[sample];
+    src = ExportSrc{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+    const char* msg = "";
+    const wbx_status st = export_check(src, first_frame, n_frames, out_format, flags, dst, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    e->export_pin = sample;
+  }
+  wbx_status st = export_prepare(c, &why);
+  if (st == WBX_OK) {
+    LockGuard g(e->hs.editor_lock);
+    st = export_order(c, &why);
+  }
+  if (st == WBX_OK) st = export_run(c, src, first_frame, n_frames, out_format, flags, dst, stats, &why);
+  {
+    LockGuard g(e->hs.editor_lock);
+    e->export_pin = wbx_engine::kNoExport;
+  }
+  if (st != WBX_OK) tls_err = why;
+  return st;
 }
 
 // Engine::add_audio_clip -> add_to_cliplist, engine.cpp:293-309, :409-461

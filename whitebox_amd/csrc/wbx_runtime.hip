@@ -672,6 +672,7 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
       c->knob_partial_free_off = is("WBX_PARTIAL_FREE", '0');
       c->knob_mix_marker = is("WBX_MIX_MARKER", '1');
       c->knob_fast_partial_off = is("WBX_FAST_PARTIAL", '0');
+      c->knob_export_direct = is("WBX_EXPORT_DIRECT", '1');
     }
     // the workgroup-id -> XCD layout the chained pieces and the segmented sequencer rest on, probed before anything relies on it
     // (WBX_XCD_PROBE_FAIL=1: tests take the fallback path)
@@ -715,6 +716,7 @@ extern "C" void wbx_destroy(wbx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   dist_destroy(c);
+  export_release(c);
   if (c->plan_stream) (void)hipStreamSynchronize(c->plan_stream);
   if (c->sum_stream) (void)hipStreamSynchronize(c->sum_stream);
   if (c->alt_stream) (void)hipStreamSynchronize(c->alt_stream);
@@ -1268,6 +1270,214 @@ extern "C" wbx_status wbx_set_master_format(wbx_ctx* c, int out_format) {
   if (out_format != 0 && out_format_bytes(out_format) == 0) return fail(c, WBX_ERR_UNSUPPORTED, "interleaved output format");
   c->master_format = out_format;
   return WBX_OK;
+}
+
+// ---- export: a resident F32 clip -> interleaved device-format samples in host memory (wbx.h "Export") ------------------
+// kernel: wbx_export.hip.  The range goes through kExportSlots staging chunks: chunk k's kernel writes the slot's device
+// buffer, the copy engine moves it into the slot's pinned buffer (or straight into a pinned dst), and while the host copies
+// chunk k out of its slot the kernels and transfers of chunks k+1 and k+2 are already enqueued.
+extern "C" uint64_t wbx_export_bytes(int out_format, uint32_t channels, uint64_t n_frames) {
+  return (uint64_t)out_format_bytes(out_format) * channels * n_frames;
+}
+
+extern "C" wbx_status wbx_set_export_chunk(wbx_ctx* c, uint32_t frames) {
+  if (!c) return WBX_ERR_INVALID;
+  if (frames && (frames < 8u || (frames & 7u) || frames > kExportChunkMax))
+    return fail(c, WBX_ERR_INVALID, "export chunk: a multiple of 8 frames, 8 .. 2^24 (0: the default)");
+  c->export_chunk.store(frames, std::memory_order_relaxed);
+  return WBX_OK;
+}
+
+wbx_status wbx::export_check(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+                             const void* dst, const char** why) {
+  *why = "";
+  if (!dst) return *why = "export: dst is NULL", WBX_ERR_INVALID;
+  if (flags & ~(uint32_t)WBX_EXPORT_CLAMP) return *why = "export: unknown flags", WBX_ERR_INVALID;
+  if (n_frames == 0) return *why = "export: no frames", WBX_ERR_INVALID;
+  if (first_frame > src.frames || n_frames > src.frames - first_frame) return *why = "export: the range ends past the clip", WBX_ERR_INVALID;
+  if (!out_format_bytes(out_format)) return *why = "export: unknown output format", WBX_ERR_UNSUPPORTED;
+  if (src.format != (uint32_t)WBX_FMT_F32) return *why = "export: the clip's storage format is not F32", WBX_ERR_UNSUPPORTED;
+  if (src.channels < 1 || src.channels > 2) return *why = "export: clip channel count (1 or 2)", WBX_ERR_UNSUPPORTED;
+  return WBX_OK;
+}
+
+static void export_free_slots(wbx_ctx* c) {
+  ExportStage& x = c->exp;
+  if (x.stream) (void)hipStreamSynchronize(x.stream);
+  for (int i = 0; i < kExportSlots; i++) {
+    if (x.d_slot[i]) (void)hipFree(x.d_slot[i]);
+    if (x.h_slot[i]) (void)hipHostFree(x.h_slot[i]);
+    if (x.d_stats[i]) (void)hipFree(x.d_stats[i]);
+    x.d_slot[i] = x.h_slot[i] = nullptr;
+    x.d_stats[i] = nullptr;
+  }
+  if (x.h_stats) (void)hipHostFree(x.h_stats);
+  x.h_stats = nullptr;
+  x.chunk = 0;
+}
+
+void wbx::export_release(wbx_ctx* c) {
+  ExportStage& x = c->exp;
+  export_free_slots(c);
+  for (auto& ev : x.done)
+    if (ev) (void)hipEventDestroy(ev);
+  if (x.after_main) (void)hipEventDestroy(x.after_main);
+  if (x.after_upload) (void)hipEventDestroy(x.after_upload);
+  if (x.stream) (void)hipStreamDestroy(x.stream);
+  x = ExportStage{};
+}
+
+static wbx_status export_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
+  if (why) {
+    *why = what;
+    if (e != hipSuccess) {
+      *why += ": ";
+      *why += hipGetErrorString(e);
+    }
+  }
+  return st;
+}
+
+wbx_status wbx::export_prepare(wbx_ctx* c, std::string* why) {
+  ExportStage& x = c->exp;
+  (void)hipSetDevice(c->cfg.device);
+  hipError_t e = hipSuccess;
+  if (!x.stream) {
+    e = hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_main, c->dev_event_flags);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_upload, c->dev_event_flags);
+    for (int i = 0; i < kExportSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      export_release(c);
+      return export_fail(why, WBX_ERR_DEVICE, "export: stream and events", e);
+    }
+  }
+  uint32_t want = c->export_chunk.load(std::memory_order_relaxed);
+  if (!want) want = kExportChunkDefault;
+  if (x.chunk != want) {
+    export_free_slots(c);
+    const size_t bytes = (size_t)want * 8u;   // two channels of 32 bits: the widest frame
+    for (int i = 0; i < kExportSlots && e == hipSuccess; i++) {
+      e = hipMalloc(&x.d_slot[i], bytes);
+      if (e == hipSuccess) e = hipHostMalloc(&x.h_slot[i], bytes, hipHostMallocDefault);
+      if (e == hipSuccess) e = hipMalloc((void**)&x.d_stats[i], 8 * sizeof(uint32_t));
+    }
+    if (e == hipSuccess) e = hipHostMalloc((void**)&x.h_stats, kExportSlots * 8 * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      export_free_slots(c);
+      return export_fail(why, WBX_ERR_OOM, "export: staging slots", e);
+    }
+    x.chunk = want;
+  }
+  return WBX_OK;
+}
+
+// the export stream behind everything enqueued so far on the streams that write the pool's clips: the main stream (with the
+// sum and the alternate mix joined to it, as sync_main does) and the upload stream.  Enqueues only: the host does not wait.
+wbx_status wbx::export_order(wbx_ctx* c, std::string* why) {
+  ExportStage& x = c->exp;
+  hipError_t e = join_sum(c);
+  if (e == hipSuccess) e = join_alt(c);
+  if (e == hipSuccess) e = hipEventRecord(x.after_main, c->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_main, 0);
+  if (e == hipSuccess && c->upload_stream) {
+    e = hipEventRecord(x.after_upload, c->upload_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_upload, 0);
+  }
+  return e == hipSuccess ? WBX_OK : export_fail(why, WBX_ERR_DEVICE, "export: ordering after the pool's writers", e);
+}
+
+static bool export_dst_is_pinned(const void* dst, size_t bytes) {
+  for (const char* p : {(const char*)dst, (const char*)dst + bytes - 1}) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (at.type != hipMemoryTypeHost) return false;
+  }
+  return true;
+}
+
+wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format,
+                           uint32_t flags, void* dst, wbx_export_stats* stats, std::string* why) {
+  ExportStage& x = c->exp;
+  const uint32_t C = src.channels;
+  const size_t fb = out_format_bytes(out_format) * C;          // bytes of a frame in dst
+  const uint64_t chunk = x.chunk, n_chunks = (n_frames + chunk - 1) / chunk;
+  const bool direct = c->knob_export_direct;
+  const bool to_dst = !direct && export_dst_is_pinned(dst, (size_t)n_frames * fb);   // the copy engine writes dst itself
+  wbx_export_stats acc{};
+  auto issue = [&](uint64_t k) -> hipError_t {
+    const int b = (int)(k % kExportSlots);
+    const uint64_t at = k * chunk;
+    const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n_frames - at);
+    hipError_t e = hipMemsetAsync(x.d_stats[b], 0, 8 * sizeof(uint32_t), x.stream);
+    if (e != hipSuccess) return e;
+    ExportArgs a{};
+    for (uint32_t ch = 0; ch < C; ch++)
+      a.src[ch] = reinterpret_cast<const float*>((const char*)src.base + src.stride * ch) + first_frame + at;
+    if (C == 1) a.src[1] = a.src[0];
+    a.dst = direct ? x.h_slot[b] : x.d_slot[b];
+    a.stats = x.d_stats[b];
+    a.n_frames = m;
+    a.channels = C;
+    a.format = (uint32_t)out_format;
+    a.flags = flags;
+    launch_export(a, x.stream);
+    e = hipGetLastError();
+    if (e == hipSuccess && !direct)
+      e = hipMemcpyAsync(to_dst ? (void*)((char*)dst + (size_t)at * fb) : x.h_slot[b], x.d_slot[b], (size_t)m * fb,
+                         hipMemcpyDeviceToHost, x.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats + 8 * b, x.d_stats[b], 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, x.stream);
+    if (e == hipSuccess) e = hipEventRecord(x.done[b], x.stream);
+    return e;
+  };
+  hipError_t e = hipSuccess;
+  for (uint64_t k = 0; k < std::min<uint64_t>(kExportSlots - 1, n_chunks) && e == hipSuccess; k++) e = issue(k);
+  for (uint64_t k = 0; k < n_chunks && e == hipSuccess; k++) {
+    const int b = (int)(k % kExportSlots);
+    e = hipEventSynchronize(x.done[b]);
+    if (e != hipSuccess) break;
+    const uint32_t* hs = x.h_stats + 8 * b;
+    for (uint32_t ch = 0; ch < C; ch++) {
+      float pk;
+      std::memcpy(&pk, hs + ch, sizeof(float));
+      if (pk > acc.peak[ch]) acc.peak[ch] = pk;
+      acc.over[ch] += hs[2 + ch];
+      acc.nans[ch] += hs[4 + ch];
+    }
+    if (k + kExportSlots - 1 < n_chunks) e = issue(k + kExportSlots - 1);   // (its slot was emptied one iteration ago)
+    if (!to_dst) {
+      const uint64_t at = k * chunk;
+      std::memcpy((char*)dst + (size_t)at * fb, x.h_slot[b], (size_t)std::min<uint64_t>(chunk, n_frames - at) * fb);
+    }
+  }
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(x.stream);   // nothing may still write a slot or dst
+    return export_fail(why, WBX_ERR_DEVICE, "export", e);
+  }
+  if (stats) *stats = acc;
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_clip_export(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, int out_format,
+                                      uint32_t flags, void* dst, wbx_export_stats* stats) {
+  if (!c) return WBX_ERR_INVALID;
+  if (clip >= c->clips.size() || !c->clips[clip].used || !c->clips[clip].base) return fail(c, WBX_ERR_INVALID, "export: unknown clip");
+  const ClipSlot& s = c->clips[clip];
+  const ExportSrc src{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+  const char* msg = "";
+  wbx_status st = export_check(src, first_frame, n_frames, out_format, flags, dst, &msg);
+  if (st != WBX_OK) return fail(c, st, msg);
+  std::lock_guard<std::mutex> g(c->export_mu);
+  std::string why;
+  st = export_prepare(c, &why);
+  if (st == WBX_OK) st = export_order(c, &why);
+  if (st == WBX_OK) st = export_run(c, src, first_frame, n_frames, out_format, flags, dst, stats, &why);
+  if (st != WBX_OK) c->err = why;
+  return st;
 }
 
 extern "C" wbx_status wbx_set_master_init(wbx_ctx* c, const void* device_buffer) {

@@ -76,6 +76,20 @@ def _check(st: int, where: str, handle=None, engine: bool = False):
         raise WbxError(st, where, detail or L.wbx_status_string(st).decode())
 
 
+def _export(fn, where, handle, engine, clip, fmt, channels, first_frame, n_frames, clamp, out):
+    L = _ffi.lib()
+    nbytes = L.wbx_export_bytes(_ffi.OUT_FMT[fmt], channels, n_frames)
+    if out is None:
+        out = np.zeros(max(nbytes, 1), dtype=np.uint8)[:nbytes].view(_ffi.OUT_DTYPE[fmt])
+    else:
+        assert out.nbytes >= nbytes and out.flags.c_contiguous and out.flags.writeable
+    st = _ffi.ExportStats()
+    _check(fn(handle, clip, first_frame, n_frames, _ffi.OUT_FMT[fmt], _ffi.EXPORT_CLAMP if clamp else 0, out.ctypes.data,
+              C.byref(st)), where, handle, engine)
+    return out, {"peak": [float(np.float32(st.peak[c])) for c in range(channels)],
+                 "over": [int(st.over[c]) for c in range(channels)], "nans": [int(st.nans[c]) for c in range(channels)]}
+
+
 def _config(device, max_tracks, max_blocks, block, channels, sample_rate, group_size, max_segments, stream):
     return _ffi.Config(device, max_tracks, max_blocks, block, channels, sample_rate, group_size, max_segments, stream)
 
@@ -130,6 +144,19 @@ class MixContext:
         out = np.empty(frames, dtype=dtype)
         _check(self.L.wbx_clip_download(self.h, clip, channel, out.ctypes.data), "wbx_clip_download", self.h)
         return out
+
+    def clip_export(self, clip: int, fmt: str, channels: int, first_frame: int, n_frames: int, clamp: bool = True,
+                    out: Optional[np.ndarray] = None):
+        """wbx_clip_export: frames [first_frame, first_frame + n_frames) of a resident F32 clip as interleaved samples of
+        `fmt` ("i16", "i24" — true packed interleave, bytes —, "i24_x8", "i32", "f32").  Returns (array, stats): the array
+        is typed by the format ([n_frames * channels], bytes * 3 for "i24") unless `out`, a writable buffer of
+        wbx_export_bytes bytes, is given; stats = {"peak", "over", "nans"}, one entry per channel."""
+        return _export(self.L.wbx_clip_export, "wbx_clip_export", self.h, False, clip, fmt, channels, first_frame, n_frames,
+                       clamp, out)
+
+    def set_export_chunk(self, frames: int):
+        """frames per staging chunk of later exports (a multiple of 8; 0: the default) — tests reach chunk seams with it"""
+        _check(self.L.wbx_set_export_chunk(self.h, frames), "wbx_set_export_chunk", self.h)
 
     def build_mipmaps(self, clip: int, quality: int):
         """WaveformVisual::create (gfx/waveform_visual.cpp:181-246): quality 0 = Low (int8), 1 = High (int16)."""
@@ -321,6 +348,7 @@ class Engine:
                               _handle=C.c_void_p(self.L.wbx_engine_ctx(h)))
         self.n_buses = 0
         self.max_blocks = max_blocks
+        self._sample_shape = {}   # sample id -> (frames, channels) of the samples made through this object (export_sample)
 
     def close(self):
         if self.h:
@@ -427,6 +455,7 @@ class Engine:
         sid = C.c_uint32()
         _check(self.L.wbx_engine_add_sample(self.h, _ffi.FMT[fmt], len(data), rate, frames, ptrs, C.byref(sid)),
                "wbx_engine_add_sample", self.h, True)
+        self._sample_shape[sid.value] = (frames, len(data))
         return sid.value
 
     def add_sample_interleaved(self, fmt: str, rate: int, frames_by_channels: np.ndarray) -> int:
@@ -435,16 +464,19 @@ class Engine:
         sid = C.c_uint32()
         _check(self.L.wbx_engine_add_sample_interleaved(self.h, _ffi.FMT[fmt], a.shape[1], rate, a.shape[0], a.ctypes.data,
                                                         C.byref(sid)), "wbx_engine_add_sample_interleaved", self.h, True)
+        self._sample_shape[sid.value] = (a.shape[0], a.shape[1])
         return sid.value
 
     def add_sample_synth(self, fmt: str, channels: int, rate: int, frames: int, seed: int, key_track: int, amp: float) -> int:
         sid = C.c_uint32()
         _check(self.L.wbx_engine_add_sample_synth(self.h, _ffi.FMT[fmt], channels, rate, frames, seed, key_track,
                                                   np.float32(amp), C.byref(sid)), "wbx_engine_add_sample_synth", self.h, True)
+        self._sample_shape[sid.value] = (frames, channels)
         return sid.value
 
     def delete_sample(self, sample: int):
         _check(self.L.wbx_engine_delete_sample(self.h, sample), "wbx_engine_delete_sample", self.h, True)
+        self._sample_shape.pop(sample, None)
 
     def add_audio_clip(self, track: Track, name: str, min_time: float, max_time: float, start_offset: float,
                        sample: int, speed: float = 1.0, gain: float = 1.0):
@@ -575,7 +607,26 @@ class Engine:
                "wbx_engine_bounce", self.h, True)
         K = -(-frames.value // self.audio_buffer_size)
         self.ctx.last = (K % self.max_blocks or self.max_blocks, len(self.tracks))   # the last pass is what a fetch sees
+        for i in ids[:len(sources)]:
+            self._sample_shape[i] = (frames.value, self.num_output_channels)
         return list(ids[:len(sources)]), frames.value
+
+    def export_sample(self, sample: int, out_format: str, first_frame: int = 0, n_frames: Optional[int] = None,
+                      clamp: bool = True, channels: Optional[int] = None, frames: Optional[int] = None,
+                      out: Optional[np.ndarray] = None):
+        """wbx_engine_export_sample: a sample (a take's, a bounce's, any F32 sample) as interleaved samples of `out_format`
+        — see MixContext.clip_export.  `n_frames` None: to the sample's end.  Length and channel count of samples made by
+        add_sample* / bounce are known here; for a take's sample (made inside stop_record) pass `frames`
+        (record_info()["frames"]) and `channels` (1 for a mono input).  May be called while another thread runs process();
+        delete_sample of the sample is refused meanwhile."""
+        known = self._sample_shape.get(sample, (None, self.num_output_channels))
+        frames = known[0] if frames is None else frames
+        channels = known[1] if channels is None else channels
+        if n_frames is None:
+            assert frames is not None, "export_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        return _export(self.L.wbx_engine_export_sample, "wbx_engine_export_sample", self.h, True, sample, out_format, channels,
+                       first_frame, n_frames, clamp, out)
 
     def bounce_download(self, sample: int, frames: int) -> np.ndarray:
         """a bounced sample back on the host: [C][frames] fp32 (wbx_clip_download per channel)"""
