@@ -178,6 +178,69 @@ wbx_status wbx_clip_export(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, ui
  * chunk seams with 1000-frame clips this way (cf. wbx_engine_set_record_chunk); results do not depend on it. */
 wbx_status wbx_set_export_chunk(wbx_ctx* ctx, uint32_t frames);
 
+/* Editing clips: measure a frame range of a resident F32 clip of 1 or 2 channels (the class of clip wbx_clip_export takes),
+ * or derive a NEW F32 clip from it — trim, reverse, channel mode, gain, fade-in, fade-out — without the samples leaving
+ * HBM.  No reference counterpart as a whole: dsp::find_abs_maximum and dsp::gain (dsp/dsp_ops.h:10-25) and Sample::resize
+ * (sample.cpp:69-110) are the pieces; AudioClip::fade_start / fade_end (engine/clip.h:41-42) are stored and read by nothing.
+ * Both calls run on a stream of their own (no mix or sum stream), ordered after everything enqueued so far on the
+ * context's main and upload streams, and return when the result is complete.
+ *
+ * wbx_clip_measure: per channel over [first_frame, first_frame + n_frames)
+ *   peak        max |x| taken by `a > peak` from 0: a NaN never raises it (the export's rule)
+ *   peak_frame  the smallest frame, relative to first_frame, whose |x| equals peak; 0 when peak is 0
+ *   min, max    signed, NaNs skipped, -0.0 below +0.0; +0.0 for both when no sample was counted
+ *   over, nans  samples with x > 1 or x < -1 / NaN samples
+ *   sum, sum_sq fp64 over the samples that are no NaN, every square formed in fp64
+ * Every field but sum and sum_sq is independent of the order of reduction, hence exact; those two are summed in an order
+ * that is not fixed: |error| <= (n - 1) * 2^-53 * sum |term|.
+ *
+ * wbx_clip_derive: dst_clip becomes a new F32 pool clip of n_frames frames (plus the pool's 16 zero frames of padding) at
+ * the source's sample rate; an existing dst_clip is replaced as wbx_clip_upload would replace it; dst_clip != src_clip.
+ * Output frame j in [0, n) of output channel c, with every operation a single IEEE fp32 round-to-nearest one:
+ *   source frame  s = first_frame + j, or first_frame + n - 1 - j with WBX_EDIT_REVERSE
+ *   channel       WBX_CH_KEEP      src[c][s]                     (mono or stereo)
+ *                 WBX_CH_SWAP      src[1 - c][s]                 (stereo)
+ *                 WBX_CH_LEFT / WBX_CH_RIGHT   that channel, mono result   (stereo)
+ *                 WBX_CH_MONO_MIX  fl(fl(L + R) * 0.5f), mono result       (stereo)
+ *                 WBX_CH_DUAL_MONO src[0][s] on both channels of a stereo result (mono)
+ *   gain          y = fl(x * gain), always multiplied (invert: gain = -1)
+ *   fade-in       j < fade_in:       t = (float)((double)j / (double)fade_in),               y = fl(y * w(t))
+ *   fade-out      j >= n - fade_out: t = (float)((double)(n - 1 - j) / (double)fade_out),    y = fl(y * w(t))   (after the fade-in)
+ *   w(t)          WBX_FADE_LINEAR t;  WBX_FADE_SQUARE fl(t*t);  WBX_FADE_SMOOTH fl(fl(t*t) * fl(3 - fl(2*t)))
+ *   NaN           a result that is a NaN is stored as 0x7FC00000, whatever its source's payload
+ * Frames outside both fades get no fade multiplication; the first frame of a fade-in and the last of a fade-out have
+ * weight 0, so a reversed edit with a fade-in is bit-equal to the reverse of the forward edit with that fade-out.
+ * stats_of_result (may be NULL): wbx_clip_measure of the whole result, taken in the same pass from the values stored.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: unknown source clip, NULL
+ * descriptor, n_frames == 0, a range past the clip, dst_clip == src_clip, an unknown flag, mode or shape, a fade longer
+ * than n_frames, a channel mode that does not fit the source's channel count; WBX_ERR_UNSUPPORTED: a source whose storage
+ * format is not F32.  WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated). */
+enum { WBX_EDIT_REVERSE = 1 };
+enum { WBX_CH_KEEP = 0, WBX_CH_SWAP = 1, WBX_CH_LEFT = 2, WBX_CH_RIGHT = 3, WBX_CH_MONO_MIX = 4, WBX_CH_DUAL_MONO = 5 };
+enum { WBX_FADE_LINEAR = 0, WBX_FADE_SQUARE = 1, WBX_FADE_SMOOTH = 2 };
+typedef struct wbx_clip_stats {   /* 104 bytes */
+  float peak[2];
+  float min[2];
+  float max[2];
+  uint64_t peak_frame[2];
+  uint64_t over[2];
+  uint64_t nans[2];
+  double sum[2];
+  double sum_sq[2];
+} wbx_clip_stats;
+typedef struct wbx_clip_edit_desc {   /* 56 bytes */
+  uint64_t first_frame, n_frames;
+  uint32_t flags;          /* WBX_EDIT_* */
+  int32_t channel_mode;    /* WBX_CH_* */
+  float gain;
+  uint32_t _pad;
+  uint64_t fade_in, fade_out;   /* frames, each <= n_frames */
+  int32_t fade_in_shape, fade_out_shape;   /* WBX_FADE_* */
+} wbx_clip_edit_desc;
+wbx_status wbx_clip_measure(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out);
+wbx_status wbx_clip_derive(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, const wbx_clip_edit_desc* d,
+                           wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -552,6 +615,23 @@ wbx_status wbx_engine_bounce(wbx_engine* e, double min_time, double max_time, co
  * wbx_clip_export's. */
 wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, int out_format,
                                     uint32_t flags, void* dst, wbx_export_stats* stats);
+/* wbx_clip_measure / wbx_clip_derive of engine samples, for the editing thread, under wbx_engine_export_sample's rules: the
+ * audio thread may keep calling wbx_engine_process* meanwhile, playing or recording; the calls touch no transport state
+ * and do not count as edits of the session.  The editor lock is held only to validate the sample, copy its storage
+ * description out, set or clear the pin, order the edit's stream and register the new sample; never across a device
+ * wait.  While a call is in flight wbx_engine_delete_sample refuses its source (WBX_ERR_UNSUPPORTED, "sample is being
+ * edited" — said before "still referenced by a clip": the pin passes by itself).  Arguments, results and refusals are wbx_clip_measure's and wbx_clip_derive's.
+ *   derive     *new_sample is a fresh sample id, registered as a bounce's results are: usable at once in
+ *              wbx_engine_add_audio_clip, wbx_engine_export_sample, wbx_clip_build_mipmaps, wbx_engine_delete_sample
+ *   normalize  measures [first_frame, first_frame + n_frames), takes gain = target_peak / max(peak[0], peak[1]) as ONE IEEE
+ *              fp32 division on the host (*gain_used, may be NULL) and derives that range with it (WBX_CH_KEEP, no fade).
+ *              The result's peak is fl(peak * gain), which may differ from target_peak by one ulp.  A silent range
+ *              (peak == 0) or one whose peak is not finite is WBX_ERR_INVALID and creates no sample */
+wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                     wbx_clip_stats* stats);
+wbx_status wbx_engine_derive_sample(wbx_engine* e, uint32_t sample, const wbx_clip_edit_desc* desc, uint32_t* new_sample);
+wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                       float target_peak, uint32_t* new_sample, float* gain_used);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -310,6 +310,24 @@ struct Engine {
           "export_sample");
     return stats;
   }
+  // Measure and edit samples where they live (wbx.h "Editing clips"): peak / RMS / DC material of a range; a NEW sample
+  // derived by trim, reverse, channel mode, gain and fades; a new sample normalized to a peak (*gain_used: the factor).
+  // Editing thread; the audio thread may keep calling process().  The ids go where a bounce's go.
+  wbx_clip_stats measure_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames) {
+    wbx_clip_stats stats{};
+    check(wbx_engine_measure_sample(h, sample, first_frame, n_frames, &stats), "measure_sample");
+    return stats;
+  }
+  uint32_t derive_sample(uint32_t sample, const wbx_clip_edit_desc& desc) {
+    uint32_t id = 0;
+    check(wbx_engine_derive_sample(h, sample, &desc, &id), "derive_sample");
+    return id;
+  }
+  uint32_t normalize_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, float target_peak, float* gain_used = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_normalize_sample(h, sample, first_frame, n_frames, target_peak, &id, gain_used), "normalize_sample");
+    return id;
+  }
   // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
   // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
   void record() { check(wbx_engine_record(h), "record"); }

@@ -6,4 +6,4 @@ CPU: `whitebox_amd.lib()` raises if the HIP library is missing, and engines cann
 without a gfx950 device.
 """
 from ._ffi import WbxError, lib, lib_path  # noqa: F401
-from .engine import AudioBuffer, Engine, MixContext, Track  # noqa: F401
+from .engine import AudioBuffer, Engine, MixContext, Track, edit_desc  # noqa: F401

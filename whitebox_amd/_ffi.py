@@ -56,6 +56,17 @@ class ExportStats(C.Structure):
     _fields_ = [("peak", C.c_float * 2), ("over", C.c_uint64 * 2), ("nans", C.c_uint64 * 2)]
 
 
+class ClipStats(C.Structure):          # wbx_clip_stats, 104 bytes
+    _fields_ = [("peak", C.c_float * 2), ("min", C.c_float * 2), ("max", C.c_float * 2), ("peak_frame", C.c_uint64 * 2),
+                ("over", C.c_uint64 * 2), ("nans", C.c_uint64 * 2), ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2)]
+
+
+class ClipEditDesc(C.Structure):       # wbx_clip_edit_desc, 56 bytes
+    _fields_ = [("first_frame", C.c_uint64), ("n_frames", C.c_uint64), ("flags", C.c_uint32), ("channel_mode", C.c_int32),
+                ("gain", C.c_float), ("_pad", C.c_uint32), ("fade_in", C.c_uint64), ("fade_out", C.c_uint64),
+                ("fade_in_shape", C.c_int32), ("fade_out_shape", C.c_int32)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -71,6 +82,10 @@ BOUNCE_TAP = {"post": 0, "pre": 1}                      # WBX_TAP_*
 OUT_FMT = {"i16": 3, "i24": 5, "i24_x8": 6, "i32": 7, "f32": 9}
 OUT_DTYPE = {"i16": "<i2", "i24": "u1", "i24_x8": "<i4", "i32": "<i4", "f32": "<f4"}   # numpy element of an exported buffer
 EXPORT_CLAMP = 1                                        # WBX_EXPORT_CLAMP
+EDIT_REVERSE = 1                                        # WBX_EDIT_REVERSE
+CH_MODE = {"keep": 0, "swap": 1, "left": 2, "right": 3, "mono_mix": 4, "dual_mono": 5}   # WBX_CH_*
+CH_MODE_OUT = {"swap": 2, "left": 1, "right": 1, "mono_mix": 1, "dual_mono": 2}          # channels of the result ("keep": the source's)
+FADE_SHAPE = {"linear": 0, "square": 1, "smooth": 2}    # WBX_FADE_*
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
 _vp, _u32, _i32, _f, _d, _sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_double, C.c_size_t
@@ -93,6 +108,8 @@ SYMBOLS = {
     "wbx_export_bytes": (C.c_uint64, [C.c_int, _u32, C.c_uint64]),
     "wbx_clip_export": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _vp, C.POINTER(ExportStats)]),
     "wbx_set_export_chunk": (C.c_int, [_vp, _u32]),
+    "wbx_clip_measure": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.POINTER(ClipStats)]),
+    "wbx_clip_derive": (C.c_int, [_vp, _u32, _u32, C.POINTER(ClipEditDesc), C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -181,6 +198,9 @@ SYMBOLS = {
     "wbx_engine_render": (C.c_int, [_vp, _u32]),
     "wbx_engine_bounce": (C.c_int, [_vp, _d, _d, C.POINTER(BounceSource), _u32, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
     "wbx_engine_export_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _vp, C.POINTER(ExportStats)]),
+    "wbx_engine_measure_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.POINTER(ClipStats)]),
+    "wbx_engine_derive_sample": (C.c_int, [_vp, _u32, C.POINTER(ClipEditDesc), C.POINTER(_u32)]),
+    "wbx_engine_normalize_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, C.POINTER(_u32), C.POINTER(_f)]),
     "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
     "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),

@@ -81,6 +81,23 @@ struct ExportArgs {
   uint32_t channels, format, flags;   // 1 or 2 / WBX_OUT_* / WBX_EXPORT_*
 };
 void launch_export(const ExportArgs& a, hipStream_t s);
+// editing clips (wbx_clipfx.hip): a frame range of a planar F32 clip measured, or derived into a new planar F32 clip
+struct ClipFxStats {           // the device's statistics block (80 B), per output channel
+  unsigned long long peak[2];  // (bits of max |x|) << 32 | ~(its first frame): one 64-bit integer max; 0: the peak is 0
+  double sum[2], sum_sq[2];    // over the samples that are no NaN
+  uint32_t mn[2], mx[2];       // order-preserving keys of the signed extremes; initially 0xFFFFFFFF / 0
+  uint32_t over[2], nans[2];
+};
+struct ClipFxArgs {
+  const float* src[2];         // the source's channel rows at the CLIP's frame 0, as the channel mode orders them
+  float* dst[2];               // the new clip's rows (256-B aligned); dst[0] null: measure only
+  ClipFxStats* stats;          // device, holding the initial image
+  uint32_t first_frame, n_frames;   // the range; n_frames < 2^31 - 16
+  uint32_t fade_in, fade_out, shape_in, shape_out;   // frames (<= n_frames) / WBX_FADE_*
+  float gain;
+  uint32_t reversed, src_channels, out_channels;   // src_channels: rows read (LEFT / RIGHT read one)
+};
+void launch_clipfx(const ClipFxArgs& a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -167,6 +184,15 @@ struct ExportSrc {
   size_t stride = 0;
   uint32_t channels = 0, format = 0;
   uint64_t frames = 0;
+};
+
+// wbx_clip_measure / wbx_clip_derive: a stream of their own, the events that order it and the statistics block (device,
+// and pinned: [0] the image a launch starts from, [1] what it left) — made at first use, freed with the context
+struct ClipFxStage {
+  hipStream_t stream = nullptr;
+  hipEvent_t after_main = nullptr, after_upload = nullptr;
+  ClipFxStats* d_stats = nullptr;
+  ClipFxStats* h_stats = nullptr;
 };
 
 }  // namespace wbx
@@ -332,6 +358,10 @@ struct wbx_ctx {
   std::atomic<uint32_t> export_chunk{0};   // wbx_set_export_chunk: frames per staging chunk, 0 = kExportChunkDefault
   bool knob_export_direct = false;     // WBX_EXPORT_DIRECT=1 (A/B aid, read at wbx_create): the kernel stores into the pinned slot itself
 
+  // wbx_clip_measure / wbx_clip_derive and layer 2's forms: one at a time (fx_mu), on a stream that is no mix or sum stream
+  ClipFxStage fx;
+  std::mutex fx_mu;
+
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
   hipEvent_t pace_ev[kPaceRing] = {};  // wbx_pace
@@ -401,6 +431,17 @@ wbx_status export_order(wbx_ctx* c, std::string* why);
 wbx_status export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
                       void* dst, wbx_export_stats* stats, std::string* why);
 void export_release(wbx_ctx* c);
+// editing clips (wbx_clipfx.hip), cut like the export: argument checks (no device call), the stream, its ordering behind the
+// pool's writers (enqueues only; layer 2 calls it under the editor lock) and the runs (no lock held; they wait for the device)
+wbx_status clipfx_check_range(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, const char** why);
+wbx_status clipfx_check_derive(const ExportSrc& src, const wbx_clip_edit_desc* d, uint32_t* out_channels, const char** why);
+wbx_status clipfx_prepare(wbx_ctx* c, std::string* why);
+wbx_status clipfx_order(wbx_ctx* c, std::string* why);
+wbx_status clipfx_measure_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out,
+                              std::string* why);
+wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
+                             uint32_t out_channels, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
+void clipfx_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it

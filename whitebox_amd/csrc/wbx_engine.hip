@@ -129,6 +129,9 @@ struct wbx_engine {
   // wbx_ctx::export_mu) — wbx_engine_delete_sample refuses it until the export is over
   static constexpr uint32_t kNoExport = ~0u;
   uint32_t export_pin = kNoExport;
+  // wbx_engine_measure_sample / derive_sample / normalize_sample: the source of the edit in flight (under the editor lock;
+  // one edit at a time, wbx_ctx::fx_mu), refused by wbx_engine_delete_sample in the same way
+  uint32_t edit_pin = kNoExport;
 };
 
 namespace {
@@ -575,6 +578,8 @@ extern "C" wbx_status wbx_engine_delete_sample(wbx_engine* e, uint32_t sample) {
   LockGuard g(e->hs.editor_lock);
   e->hs.note_edit_locked();
   if (!e->hs.valid_sample(sample)) return efail(e, WBX_ERR_INVALID, "unknown sample");
+  // the edit pin first: it passes by itself, and a caller told to delete the clips first would do so only to be refused again
+  if (e->edit_pin == sample) return efail(e, WBX_ERR_UNSUPPORTED, "sample is being edited (a measure, derive or normalize call is still reading it)");
   if (e->hs.sample_referenced(sample)) return efail(e, WBX_ERR_INVALID, "sample is still referenced by a clip (delete the clips first)");
   if (e->export_pin == sample) return efail(e, WBX_ERR_UNSUPPORTED, "sample is being exported (wbx_engine_export_sample is still reading it)");
   const wbx_status st = wbx_clip_free(e->ctx, sample);
@@ -618,6 +623,142 @@ extern "C" wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, u
   }
   if (st != WBX_OK) tls_err = why;
   return st;
+}
+
+// Measuring and editing engine samples (wbx_clip_measure / wbx_clip_derive; wbx.h "Editing clips").  Editing thread, under
+// wbx_engine_export_sample's rules: the editor lock covers validating the sample, copying its storage description out of the
+// pool, the pin, ordering the edit stream behind what is enqueued (stream calls only) and registering the new sample; the
+// stream's creation, the new clip's allocation, the kernel and the wait for it run without the lock.  Nothing here touches
+// the transport or counts as an edit (no note_edit_locked): a render sees the new sample only once a clip names it.
+namespace {
+
+struct EditPin {   // fx_mu held for its life; begin() validates and pins, the destructor drops the pin
+  wbx_engine* e;
+  std::lock_guard<std::mutex> one;
+  bool pinned = false;
+  ExportSrc src;
+  uint32_t rate = 0;
+  explicit EditPin(wbx_engine* e_) : e(e_), one(e_->ctx->fx_mu) { (void)hipSetDevice(e->ctx->cfg.device); }
+  ~EditPin() {
+    if (!pinned) return;
+    LockGuard g(e->hs.editor_lock);
+    e->edit_pin = wbx_engine::kNoExport;
+  }
+  // (editor lock held) the sample's storage, pinned against wbx_engine_delete_sample
+  wbx_status begin_locked(uint32_t sample, const char* what) {
+    wbx_ctx* c = e->ctx;
+    if (!e->hs.valid_sample(sample) || sample >= c->clips.size() || !c->clips[sample].base) return efail(e, WBX_ERR_INVALID, what);
+    const ClipSlot& s = c->clips[sample];
+    src = ExportSrc{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+    rate = s.d.sample_rate;
+    return WBX_OK;
+  }
+  void pin_locked(uint32_t sample) {
+    e->edit_pin = sample;
+    pinned = true;
+  }
+  wbx_status order(std::string* why) {   // the edit stream: made without the lock, ordered under it
+    wbx_status st = clipfx_prepare(e->ctx, why);
+    if (st != WBX_OK) return st;
+    LockGuard g(e->hs.editor_lock);
+    return clipfx_order(e->ctx, why);
+  }
+  wbx_status measure(uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out, std::string* why) {
+    wbx_status st = order(why);
+    if (st == WBX_OK) st = clipfx_measure_run(e->ctx, src, first_frame, n_frames, out, why);
+    return st;
+  }
+  wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
+    wbx_ctx* c = e->ctx;
+    wbx_status st = order(why);
+    ClipSlot slot;
+    if (st == WBX_OK) st = clipfx_derive_run(c, src, rate, d, out_channels, slot, nullptr, why);
+    if (st != WBX_OK) return st;
+    LockGuard g(e->hs.editor_lock);   // a bounce's publish: the next free id of the pool, the session's sample table
+    const uint32_t id = (uint32_t)c->clips.size();
+    st = clip_publish(c, id, slot);
+    if (st != WBX_OK) return *why = c->err, st;
+    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize(c->clips.size());
+    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, out_channels, rate, d.n_frames, true};
+    *new_sample = id;
+    return WBX_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                wbx_clip_stats* stats) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!stats) return efail(e, WBX_ERR_INVALID, "measure_sample: stats is NULL");
+  EditPin p(e);
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "measure_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = clipfx_check_range(p.src, first_frame, n_frames, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.measure(first_frame, n_frames, stats, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+extern "C" wbx_status wbx_engine_derive_sample(wbx_engine* e, uint32_t sample, const wbx_clip_edit_desc* desc, uint32_t* new_sample) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "derive_sample: new_sample is NULL");
+  EditPin p(e);
+  uint32_t out_channels = 0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "derive_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = clipfx_check_derive(p.src, desc, &out_channels, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "derive_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.derive(*desc, out_channels, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+extern "C" wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                  float target_peak, uint32_t* new_sample, float* gain_used) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "normalize_sample: new_sample is NULL");
+  EditPin p(e);
+  wbx_clip_edit_desc d{};
+  d.first_frame = first_frame;
+  d.n_frames = n_frames;
+  d.channel_mode = WBX_CH_KEEP;
+  uint32_t out_channels = 0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "normalize_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = clipfx_check_derive(p.src, &d, &out_channels, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "normalize_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  wbx_clip_stats m{};
+  wbx_status st = p.measure(first_frame, n_frames, &m, &why);
+  if (st != WBX_OK) return tls_err = why, st;
+  const float peak = out_channels > 1 && m.peak[1] > m.peak[0] ? m.peak[1] : m.peak[0];
+  if (!(peak > 0.0f) || !std::isfinite(peak)) return efail(e, WBX_ERR_INVALID, "normalize_sample: the range is silent, or its peak is not finite");
+  d.gain = target_peak / peak;   // one IEEE fp32 division (no fast-math in this build)
+  st = p.derive(d, out_channels, new_sample, &why);
+  if (st != WBX_OK) return tls_err = why, st;
+  if (gain_used) *gain_used = d.gain;
+  return WBX_OK;
 }
 
 // Engine::add_audio_clip -> add_to_cliplist, engine.cpp:293-309, :409-461

@@ -90,6 +90,21 @@ def _export(fn, where, handle, engine, clip, fmt, channels, first_frame, n_frame
                  "over": [int(st.over[c]) for c in range(channels)], "nans": [int(st.nans[c]) for c in range(channels)]}
 
 
+def edit_desc(first_frame: int, n_frames: int, reverse: bool = False, channel_mode="keep", gain: float = 1.0,
+              fade_in: int = 0, fade_out: int = 0, fade_in_shape="linear", fade_out_shape="linear", flags: Optional[int] = None):
+    """a wbx_clip_edit_desc; mode and shapes by name or as the raw integers, `flags` overrides `reverse`"""
+    return _ffi.ClipEditDesc(first_frame, n_frames, (_ffi.EDIT_REVERSE if reverse else 0) if flags is None else flags,
+                             _ffi.CH_MODE.get(channel_mode, channel_mode), gain, 0, fade_in, fade_out,
+                             _ffi.FADE_SHAPE.get(fade_in_shape, fade_in_shape), _ffi.FADE_SHAPE.get(fade_out_shape, fade_out_shape))
+
+
+def _clip_stats(st, channels: int) -> dict:
+    """wbx_clip_stats -> {"peak", "peak_frame", "min", "max", "over", "nans", "sum", "sum_sq"}, one entry per channel"""
+    f32 = ("peak", "min", "max")
+    return {k: [np.float32(getattr(st, k)[c]) if k in f32 else getattr(st, k)[c] for c in range(channels)]
+            for k in ("peak", "peak_frame", "min", "max", "over", "nans", "sum", "sum_sq")}
+
+
 def _config(device, max_tracks, max_blocks, block, channels, sample_rate, group_size, max_segments, stream):
     return _ffi.Config(device, max_tracks, max_blocks, block, channels, sample_rate, group_size, max_segments, stream)
 
@@ -153,6 +168,21 @@ class MixContext:
         wbx_export_bytes bytes, is given; stats = {"peak", "over", "nans"}, one entry per channel."""
         return _export(self.L.wbx_clip_export, "wbx_clip_export", self.h, False, clip, fmt, channels, first_frame, n_frames,
                        clamp, out)
+
+    def clip_measure(self, clip: int, channels: int, first_frame: int, n_frames: int) -> dict:
+        """wbx_clip_measure: peak, its first frame, signed extremes, overs, NaNs, fp64 sum and sum of squares per channel
+        of frames [first_frame, first_frame + n_frames) of a resident F32 clip, measured on the device"""
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_clip_measure(self.h, clip, first_frame, n_frames, C.byref(st)), "wbx_clip_measure", self.h)
+        return _clip_stats(st, channels)
+
+    def clip_derive(self, src_clip: int, dst_clip: int, desc, stats_channels: int = 0):
+        """wbx_clip_derive: `dst_clip` becomes a new F32 clip derived from `src_clip` by `desc` (edit_desc(...)); returns
+        the result's statistics when `stats_channels` (its channel count) is given, else None"""
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_clip_derive(self.h, src_clip, dst_clip, C.byref(desc) if desc is not None else None,
+                                      C.byref(st) if stats_channels else None), "wbx_clip_derive", self.h)
+        return _clip_stats(st, stats_channels) if stats_channels else None
 
     def set_export_chunk(self, frames: int):
         """frames per staging chunk of later exports (a multiple of 8; 0: the default) — tests reach chunk seams with it"""
@@ -627,6 +657,49 @@ class Engine:
             n_frames = frames - first_frame
         return _export(self.L.wbx_engine_export_sample, "wbx_engine_export_sample", self.h, True, sample, out_format, channels,
                        first_frame, n_frames, clamp, out)
+
+    def _shape_of(self, sample, frames, channels):
+        known = self._sample_shape.get(sample, (None, self.num_output_channels))
+        return (known[0] if frames is None else frames), (known[1] if channels is None else channels)
+
+    def measure_sample(self, sample: int, first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                       frames: Optional[int] = None) -> dict:
+        """wbx_engine_measure_sample — see MixContext.clip_measure; `frames` / `channels` as in export_sample.  May be
+        called while another thread runs process()."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "measure_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_engine_measure_sample(self.h, sample, first_frame, n_frames, C.byref(st)), "wbx_engine_measure_sample",
+               self.h, True)
+        return _clip_stats(st, channels)
+
+    def derive_sample(self, sample: int, desc, channels: Optional[int] = None) -> int:
+        """wbx_engine_derive_sample: a new sample derived from `sample` by `desc` (edit_desc(...)): trim, reverse, channel
+        mode, gain, fades — its id goes into add_audio_clip, export_sample, ctx.build_mipmaps, delete_sample.  `channels`:
+        the SOURCE's channel count when this object did not make it.  May be called while another thread runs process()."""
+        _, channels = self._shape_of(sample, None, channels)
+        new = C.c_uint32()
+        _check(self.L.wbx_engine_derive_sample(self.h, sample, C.byref(desc) if desc is not None else None, C.byref(new)),
+               "wbx_engine_derive_sample", self.h, True)
+        mode = {v: k for k, v in _ffi.CH_MODE.items()}.get(desc.channel_mode, "keep")
+        self._sample_shape[new.value] = (desc.n_frames, _ffi.CH_MODE_OUT.get(mode, channels))
+        return new.value
+
+    def normalize_sample(self, sample: int, target_peak: float, first_frame: int = 0, n_frames: Optional[int] = None,
+                         channels: Optional[int] = None, frames: Optional[int] = None) -> tuple:
+        """wbx_engine_normalize_sample: a new sample = the range times target_peak / (its peak), one fp32 division; returns
+        (new sample id, the gain used).  A silent range or a peak that is not finite raises WbxError (status -4)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "normalize_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        new, gain = C.c_uint32(), C.c_float()
+        _check(self.L.wbx_engine_normalize_sample(self.h, sample, first_frame, n_frames, target_peak, C.byref(new), C.byref(gain)),
+               "wbx_engine_normalize_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        return new.value, float(gain.value)
 
     def bounce_download(self, sample: int, frames: int) -> np.ndarray:
         """a bounced sample back on the host: [C][frames] fp32 (wbx_clip_download per channel)"""
