@@ -241,6 +241,59 @@ wbx_status wbx_clip_measure(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, u
 wbx_status wbx_clip_derive(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, const wbx_clip_edit_desc* d,
                            wbx_clip_stats* stats_of_result);
 
+/* Converting a clip's sample rate: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels
+ * become a NEW F32 clip at dst_rate through a band-limited (windowed-sinc, polyphase) filter, without the samples leaving
+ * HBM — a file conformed once to the session rate then plays at speed 1.0 through the mix's unity row mode instead of its
+ * per-block two-tap interpolation (Sampler::stream's sample_linear rows), and a bounce can leave at another rate than the
+ * session's.  No reference counterpart: Sampler::stream is its only resampler.  This text is the specification;
+ * tests/resample_model.py restates it in numpy and the device equals that BIT FOR BIT.
+ *   ratio     g = gcd(src_rate, dst_rate), L = dst_rate / g, M = src_rate / g.  Output frame j lies at source time j*M/L:
+ *             in 64-bit integers t = j*M, i = t div L, p = t mod L (the phase).  n source frames give
+ *             n_out = ceil(n*L / M) output frames
+ *   quality   WBX_SRC_FAST / GOOD / BEST: (Z, beta, frac) = (12, 7.0, 0.85) / (24, 10.0, 0.92) / (48, 14.0, 0.96).
+ *             rho = L < M ? (double)L / (double)M : 1.0; cutoff c = frac * rho; half width H = ceil(Z / rho) source frames
+ *             (in integers: ceil(Z*M / L) when L < M, else Z); T = 2H taps
+ *   table     fp64 on the host, for p in [0, L), k in [0, T):  d = (double)(k - (H-1)) - (double)p / (double)L,
+ *               h64[p][k] = ((c * sinc(c*d)) * I0(beta * sqrt(max(0, 1 - (d/H)*(d/H))))) / I0(beta)
+ *             each phase divided by the sum of its T values (added in ascending k), then rounded ONCE to fp32: h[p][k].
+ *             sinc(x) = x == 0 ? 1 : sinpi(x) / (pi*x) and I0 are built from + - * / floor sqrt alone in a fixed number of
+ *             steps (libm's sin differs between platforms in the last place):
+ *               sinpi(x)  a = |x|; r = a - 2*floor(a/2) (exact); r >= 1: r = r - 1, the sign flips; r > 1/2: r = 1 - r;
+ *                         y = pi*r (pi = 3.141592653589793); s = 1; for n = 13 .. 1: s = 1 - (s*(y*y)) / ((2n)(2n+1));
+ *                         result sign * (y*s)
+ *               I0(x)     h = x/2; t = s = 1; for k = 1 .. 39: t = (t*h)/k, s = s + t*t
+ *   output    channel c, frame j:  acc = 0.0 (fp64); for k = 0 .. T-1 ascending: acc = acc + (double)h[p][k] *
+ *             (double)x[c][i - (H-1) + k]  (the product of two fp32 values is exact in fp64);  y = (float)acc.
+ *             x is ZERO outside [first_frame, first_frame + n_frames), whatever the clip holds there — the range is
+ *             converted as if it were a whole file.  A NaN result is stored as 0x7FC00000 (wbx_clip_derive's rule).
+ *             Only the order of the T additions is fixed; output frames are independent of each other
+ * The filter is no identity at any ratio, so equal rates are refused rather than copied (wbx_clip_derive copies).
+ * wbx_resample_plan / _frames / _table are host-only and need no device: the plan's numbers, n_out (0 when refused: a rate
+ * of 0, equal rates, L > 1280, or n_out >= 2^31 - 16), and the table in phase order [p][k] (WBX_ERR_INVALID when cap_floats
+ * is below L*T; `out` untouched after any refusal).
+ * wbx_clip_resample: dst_clip becomes a new F32 pool clip of n_out frames (plus the pool's 16 zero frames of padding) at
+ * dst_rate with the source's channel count, replaced or allocated as wbx_clip_derive does it, on the same stream and
+ * behind the same ordering; one edit or conversion runs at a time.  stats_of_result (may be NULL): wbx_clip_measure of
+ * the whole result, a second pass over the output only.  The coefficient table is kept on the device per context and
+ * (L, M, quality) after its first use.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: unknown source clip,
+ * n_frames == 0, a range past the clip, dst_clip == src_clip, unknown quality, dst_rate == 0, dst_rate == the source's
+ * rate, n_out >= 2^31 - 16; WBX_ERR_UNSUPPORTED: a source whose storage format is not F32 (bounce a track pre-fader to get
+ * one) or with more than 2 channels, L > 1280 (22050 -> 192000 has 1280), T > 512 (192000 -> 32000 at BEST has 576).
+ * WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated). */
+enum { WBX_SRC_FAST = 0, WBX_SRC_GOOD = 1, WBX_SRC_BEST = 2 };
+typedef struct wbx_resample_info {   /* 24 bytes */
+  uint32_t L, M;             /* dst_rate / g, src_rate / g */
+  uint32_t half_width;       /* H */
+  uint32_t taps;             /* T = 2H */
+  uint64_t table_floats;     /* L * T */
+} wbx_resample_info;
+wbx_status wbx_resample_plan(uint32_t src_rate, uint32_t dst_rate, int quality, wbx_resample_info* out);
+uint64_t wbx_resample_frames(uint32_t src_rate, uint32_t dst_rate, uint64_t n_frames);
+wbx_status wbx_resample_table(uint32_t src_rate, uint32_t dst_rate, int quality, float* out, size_t cap_floats);
+wbx_status wbx_clip_resample(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                             uint32_t dst_rate, int quality, wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -632,6 +685,14 @@ wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, uint64_t fi
 wbx_status wbx_engine_derive_sample(wbx_engine* e, uint32_t sample, const wbx_clip_edit_desc* desc, uint32_t* new_sample);
 wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                        float target_peak, uint32_t* new_sample, float* gain_used);
+/* wbx_clip_resample of an engine sample, under wbx_engine_derive_sample's rules to the letter: editing thread, the audio
+ * thread may keep calling wbx_engine_process*; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin, never across a device wait; wbx_engine_delete_sample refuses the source meanwhile ("sample is being edited");
+ * no transport state is touched.  *new_sample is a fresh sample id registered with sample_rate = dst_rate and
+ * wbx_resample_frames(...) frames: placed by wbx_engine_add_audio_clip at speed 1.0 in a session of that rate it plays
+ * through the unity row mode.  Arguments and refusals are wbx_clip_resample's. */
+wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                      uint32_t dst_rate, int quality, uint32_t* new_sample);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

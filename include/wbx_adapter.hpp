@@ -328,6 +328,14 @@ struct Engine {
     check(wbx_engine_normalize_sample(h, sample, first_frame, n_frames, target_peak, &id, gain_used), "normalize_sample");
     return id;
   }
+  // A NEW sample holding the range converted to dst_rate by the band-limited filter of wbx.h "Converting a clip's sample
+  // rate" (quality: WBX_SRC_FAST / GOOD / BEST) — conform an imported file to the session rate once, or make the copy of a
+  // bounce that leaves at another rate.  Editing thread, like derive_sample; the id goes where a bounce's go.
+  uint32_t resample_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate, int quality = WBX_SRC_GOOD) {
+    uint32_t id = 0;
+    check(wbx_engine_resample_sample(h, sample, first_frame, n_frames, dst_rate, quality, &id), "resample_sample");
+    return id;
+  }
   // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
   // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
   void record() { check(wbx_engine_record(h), "record"); }

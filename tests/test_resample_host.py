@@ -1,0 +1,263 @@
+"""Converting a clip's sample rate, the part that needs no device: the symbols and the struct of include/wbx.h "Converting a
+clip's sample rate" exist and match their binding twins, the adapter's method compiles, the plan and the output length are the
+header's, the library's coefficient table equals the numpy twin (tests/resample_model.py) BIT FOR BIT and an independent
+np.sinc / np.i0 rendering within half an fp32 ulp — and the twin is a resampler, not merely self-consistent: in-band sines
+come out as the ideal sines at the new rate and out-of-band ones are gone, to the floors each quality promises."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import resample_model as M
+import whitebox_amd as W
+from whitebox_amd import _ffi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["wbx_resample_plan", "wbx_resample_frames", "wbx_resample_table", "wbx_clip_resample", "wbx_engine_resample_sample"]
+# (src_rate, dst_rate) -> (L, M, H at GOOD)
+PLANS = {(44100, 48000): (160, 147, 24), (48000, 44100): (147, 160, 27), (96000, 48000): (1, 2, 48), (48000, 96000): (2, 1, 24),
+         (48000, 32000): (2, 3, 36), (192000, 44100): (147, 640, 105), (44100, 96000): (320, 147, 24)}
+PAIRS = list(PLANS) + [(8000, 44100)]
+QUALITIES = (M.FAST, M.GOOD, M.BEST)
+
+
+def test_symbols_are_declared_exported_and_bound():
+    header = open(os.path.join(ROOT, "include", "wbx.h")).read()
+    L = W.lib()
+    for n in NEW:
+        assert re.search(r"\b%s\s*\(" % n, header), n
+        assert hasattr(L, n) and n in _ffi.SYMBOLS, n
+    assert callable(W.resample_plan) and callable(W.resample_frames) and callable(W.resample_table)
+    assert hasattr(W.MixContext, "clip_resample") and hasattr(W.Engine, "resample_sample")
+
+
+def test_struct_and_enums_equal_the_headers(tmp_path):
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "wbx.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu %d %d %d\\n", sizeof(wbx_resample_info), offsetof(wbx_resample_info, L),\n'
+                   '  offsetof(wbx_resample_info, M), offsetof(wbx_resample_info, half_width), offsetof(wbx_resample_info, taps),\n'
+                   '  offsetof(wbx_resample_info, table_floats), WBX_SRC_FAST, WBX_SRC_GOOD, WBX_SRC_BEST); return 0; }\n')
+    exe = str(tmp_path / "sizes")
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", str(src), "-I" + os.path.join(ROOT, "include"), "-o", exe])
+    got = [int(x) for x in subprocess.check_output([exe]).split()]
+    R = _ffi.ResampleInfo
+    assert got[:6] == [C.sizeof(R), R.L.offset, R.M.offset, R.half_width.offset, R.taps.offset, R.table_floats.offset]
+    assert got[0] == 24
+    assert got[6:] == [_ffi.SRC_QUALITY["fast"], _ffi.SRC_QUALITY["good"], _ffi.SRC_QUALITY["best"]] == [M.FAST, M.GOOD, M.BEST]
+
+
+def test_adapter_with_resample_sample_compiles(tmp_path):
+    """a translation unit that uses Engine::resample_sample (never run: it would need a device)"""
+    src = tmp_path / "adapter_resample.cpp"
+    src.write_text('#include "wbx_adapter.hpp"\n'
+                   'uint32_t conform(wbx::Engine& e, uint32_t file, uint64_t n) {\n'
+                   '  const uint32_t good = e.resample_sample(file, 0, n, 48000);\n'
+                   '  return e.resample_sample(good, 0, wbx_resample_frames(44100, 48000, n), 96000, WBX_SRC_BEST);\n}\n'
+                   'int main() { return sizeof(wbx_resample_info) == 24 ? 0 : 1; }\n')
+    exe = str(tmp_path / "adapter_resample")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", str(src), "-I" + os.path.join(ROOT, "include"),
+                           "-L" + os.path.join(ROOT, "whitebox_amd"), "-lwbx", "-Wl,-rpath," + os.path.join(ROOT, "whitebox_amd"),
+                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    assert subprocess.call([exe]) == 0
+
+
+def test_null_handles_are_refused_without_a_device():
+    L = W.lib()
+    st, new = _ffi.ClipStats(), C.c_uint32()
+    assert L.wbx_clip_resample(None, 0, 1, 0, 8, 48000, 1, C.byref(st)) == -4
+    assert L.wbx_engine_resample_sample(None, 0, 0, 8, 48000, 1, C.byref(new)) == -4
+    assert L.wbx_resample_plan(44100, 48000, 1, None) == -4
+    assert L.wbx_resample_table(44100, 48000, 1, None, 1 << 20) == -4
+
+
+# ---- the plan ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pair", list(PLANS), ids=lambda p: "%d-%d" % p)
+def test_plan_values(pair):
+    L, Mm, H = PLANS[pair]
+    for q, z in ((M.FAST, 12), (M.GOOD, 24), (M.BEST, 48)):
+        want_h = -(-z * Mm // L) if L < Mm else z               # H scales with Z
+        got = W.resample_plan(*pair, q)
+        assert got == dict(L=L, M=Mm, half_width=want_h, taps=2 * want_h, table_floats=L * 2 * want_h), (pair, q, got)
+        p = M.plan(*pair, q)
+        assert (p["L"], p["M"], p["H"], p["T"]) == (L, Mm, want_h, 2 * want_h)
+    assert W.resample_plan(*pair, "good")["half_width"] == H
+
+
+def test_plan_refusals():
+    L = W.lib()
+    info = _ffi.ResampleInfo(7, 7, 7, 7, 7)
+
+    def status(rs, rd, q):
+        st = L.wbx_resample_plan(rs, rd, q, C.byref(info))
+        try:
+            M.plan(rs, rd, q)
+            model = 0
+        except M.Refused as r:
+            model = r.status
+        assert st == model, (rs, rd, q, st, model)
+        buf = np.full(4, 7.0, dtype=np.float32)
+        if st:
+            assert L.wbx_resample_table(rs, rd, q, buf.ctypes.data, 1 << 30) == st and np.all(buf == 7.0)
+        return st
+
+    assert status(48000, 48000, 1) == -4 and status(0, 48000, 1) == -4 and status(48000, 0, 1) == -4
+    assert status(44100, 48000, 3) == -4 and status(44100, 48000, -1) == -4
+    assert (info.L, info.M, info.half_width, info.taps, info.table_floats) == (7, 7, 7, 7, 7)      # untouched by refusals
+    assert status(22050, 192000, 1) == 0 and info.L == 1280
+    assert status(11025, 192000, 1) == -3                       # L = 2560
+    assert status(192000, 32000, 2) == -3                       # T = 576
+    assert status(192000, 32000, 1) == 0 and info.taps == 288
+    assert L.wbx_resample_frames(11025, 192000, 100) == 0 and L.wbx_resample_frames(48000, 48000, 100) == 0
+    assert L.wbx_resample_frames(0, 48000, 100) == 0 and L.wbx_resample_frames(48000, 0, 100) == 0
+    small = np.zeros(160 * 48 - 1, dtype=np.float32)
+    assert L.wbx_resample_table(44100, 48000, 1, small.ctypes.data, small.size) == -4 and not small.any()
+
+
+def test_output_length():
+    top = (1 << 31) - 16
+    for rs, rd in PAIRS:
+        g = math.gcd(rs, rd)
+        L, Mm = rd // g, rs // g
+        edge = (top * Mm) // L                                  # around the first n whose n_out reaches 2^31 - 16
+        for n in [1, 2, 3, 147, 160, 441, 5003, (1 << 31) - 17, edge - 1, edge, edge + 1, edge + 2, 1 << 40, (1 << 64) - 1]:
+            want = -(-n * L // Mm)
+            want = want if want < top else 0
+            assert W.resample_frames(rs, rd, n) == want == M.out_frames(rs, rd, n), (rs, rd, n)
+        assert W.resample_frames(rs, rd, 0) == 0
+    assert W.resample_frames(44100, 48000, (1 << 31) - 17) == 0 and W.resample_frames(48000, 44100, (1 << 31) - 17) == -(-((1 << 31) - 17) * 147 // 160) == 1973000586
+
+
+# ---- the table --------------------------------------------------------------------------------------------------------------
+_tables = {}
+
+
+def tables(pair, q):
+    if (pair, q) not in _tables:
+        _tables[(pair, q)] = (W.resample_table(*pair, q), M.table(*pair, q))
+    return _tables[(pair, q)]
+
+
+@pytest.mark.parametrize("q", QUALITIES)
+@pytest.mark.parametrize("pair", PAIRS, ids=lambda p: "%d-%d" % p)
+def test_table_equals_the_model_bit_for_bit(pair, q):
+    got, want = tables(pair, q)
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    bad = np.flatnonzero(got.view(np.uint32).ravel() != want.view(np.uint32).ravel())
+    assert bad.size == 0, (pair, q, bad[:8], bad.size)
+
+
+@pytest.mark.parametrize("q", QUALITIES)
+@pytest.mark.parametrize("pair", PAIRS, ids=lambda p: "%d-%d" % p)
+def test_table_against_numpy_and_phase_sums(pair, q):
+    """coefficients are below 1 in magnitude, so half an fp32 ulp is at most 2^-25 and the two fp64 paths differ by ~1e-14:
+    2^-24 absolute holds whatever the series lengths"""
+    got, _ = tables(pair, q)
+    ref = M.table_numpy(*pair, q)
+    err = float(np.max(np.abs(got.astype(np.float64) - ref)))
+    sums = np.array([math.fsum(row) for row in got.astype(np.float64)])
+    print("table", pair, q, "max |h - numpy|", err, "max |sum - 1|", float(np.max(np.abs(sums - 1.0))))
+    assert np.max(np.abs(ref)) < 1.0 and err <= 2.0 ** -24
+    assert np.max(np.abs(sums - 1.0)) <= 1e-6
+
+
+def test_the_series_against_numpy():
+    x = np.linspace(-40.0, 40.0, 200001)
+    err = float(np.max(np.abs(M.sinpi(x) - np.sin(np.pi * x))))
+    print("max |sinpi - np.sin(pi x)| on [-40, 40]", err)
+    assert err <= 2e-14                                         # pi * x itself is off by 40 * pi * 2^-53 = 1.4e-14 in numpy's argument
+    assert np.all(M.sinpi(np.arange(-9.0, 10.0)) == 0.0)
+    assert np.max(np.abs(M.sinpi(np.array([0.5, -0.5, 1.5, -1.5, 2.5])) - np.array([1.0, -1.0, -1.0, 1.0, 1.0]))) <= 2.0 ** -52
+    b = np.linspace(0.0, 14.0, 1401)
+    rel = float(np.max(np.abs(M.i0(b) / np.i0(b) - 1.0)))
+    print("max relative |i0 - np.i0| on [0, 14]", rel)
+    assert rel <= 1e-14
+
+
+# ---- the model's own quality ------------------------------------------------------------------------------------------------
+FLOORS = {M.FAST: 70.0, M.GOOD: 96.0, M.BEST: 130.0}
+N_IN, AMP = 20000, 0.5
+
+
+def tone(freq, rate, n):
+    return (AMP * np.sin(2.0 * np.pi * freq * np.arange(n) / rate)).astype(np.float32)
+
+
+def db(signal_rms, noise_rms):
+    return 20.0 * math.log10(signal_rms / max(noise_rms, 1e-300))
+
+
+def component(y, freq, beside, rate, j):
+    """amplitude of the sinusoid of `freq` in y: least squares over sin / cos of `freq` AND of `beside`, the tone itself,
+    fitted jointly (projected alone, the tone would leak into the image at about 1 / len(j))"""
+    w, v = 2.0 * np.pi * freq * j / rate, 2.0 * np.pi * beside * j / rate
+    A = np.stack([np.sin(w), np.cos(w), np.sin(v), np.cos(v)], axis=1)
+    c, *_ = np.linalg.lstsq(A, y, rcond=None)
+    return float(np.hypot(c[0], c[1]))
+
+
+def quality_figures(pair, q):
+    rs, rd = pair
+    p = M.plan(rs, rd, q)
+    tab = tables(pair, q)[1]
+    n_out = M.out_frames(rs, rd, N_IN)
+    edge = int(math.ceil((p["H"] + 1) * rd / rs)) + 1            # outputs whose taps reach past the input's ends
+    j = np.arange(edge, n_out - edge)
+    snr = []
+    for f in (997.0, 0.30 * min(rs, rd)):
+        y = M.resample([tone(f, rs, N_IN)], 0, N_IN, rs, rd, q, tab=tab)[0].astype(np.float64)[j]
+        ideal = AMP * np.sin(2.0 * np.pi * f * j / rd)
+        snr.append(db(AMP / math.sqrt(2.0), float(np.sqrt(np.mean((y - ideal) ** 2)))))
+    rej = None
+    if rd < rs:                                                 # a tone just above the new band must be gone (it would alias)
+        f = 0.56 * rd
+        if f < rs / 2:
+            y = M.resample([tone(f, rs, N_IN)], 0, N_IN, rs, rd, q, tab=tab)[0].astype(np.float64)[j]
+            rej = db(AMP / math.sqrt(2.0), float(np.sqrt(np.mean(y ** 2))))
+    else:                                                       # a tone below the old Nyquist must leave no image above it
+        f = 0.45 * rs
+        y = M.resample([tone(f, rs, N_IN)], 0, N_IN, rs, rd, q, tab=tab)[0].astype(np.float64)[j]
+        rej = db(AMP, component(y, rs - f, f, rd, j))
+    return min(snr), rej
+
+
+@pytest.mark.parametrize("q", QUALITIES)
+def test_the_model_is_a_resampler(q):
+    worst_snr, worst_rej = math.inf, math.inf
+    for pair in PAIRS:
+        snr, rej = quality_figures(pair, q)
+        print("quality", q, pair, "min SNR %.1f dB" % snr, "rejection", "-" if rej is None else "%.1f dB" % rej)
+        worst_snr = min(worst_snr, snr)
+        if rej is not None:
+            worst_rej = min(worst_rej, rej)
+    print("quality", q, "worst SNR %.1f dB, worst rejection %.1f dB; floor %.0f dB" % (worst_snr, worst_rej, FLOORS[q]))
+    assert worst_snr >= FLOORS[q] and worst_rej >= FLOORS[q]
+
+
+def test_frames_outside_the_range_count_as_zero():
+    rng = np.random.default_rng(3)
+    x = rng.uniform(-1, 1, 700).astype(np.float32)
+    alone = M.resample([x[100:400].copy()], 0, 300, 44100, 48000, M.GOOD)[0]
+    inside = M.resample([x], 100, 300, 44100, 48000, M.GOOD)[0]
+    assert np.array_equal(alone.view(np.uint32), inside.view(np.uint32))
+    win = M.resample([x], 100, 300, 44100, 48000, M.GOOD, window=(17, 250))[0]
+    assert np.array_equal(win.view(np.uint32), inside[17:250].view(np.uint32))
+
+
+# ---- the host code under a sanitizer ----------------------------------------------------------------------------------------
+def test_table_generator_under_address_and_ub_sanitizers(tmp_path):
+    """tests/cpp/resample_table_main.cpp: wbx_resample.h alone, every table of the list, stand-alone (its own main)"""
+    exe = str(tmp_path / "resample_table_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "cpp", "resample_table_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = dict(l.rsplit(" ", 1) for l in out.stdout.strip().splitlines())
+    assert len(lines) == len(PAIRS) * 3 + 1 and lines.pop("refusals") == "ok"
+    for pair in PAIRS:
+        for q in QUALITIES:
+            want = int(np.bitwise_xor.reduce(tables(pair, q)[1].view(np.uint32).ravel() * np.uint32(2654435761) + np.arange(tables(pair, q)[1].size, dtype=np.uint32)))
+            assert int(lines["%d %d %d" % (pair[0], pair[1], q)], 16) == want, (pair, q)

@@ -67,6 +67,11 @@ class ClipEditDesc(C.Structure):       # wbx_clip_edit_desc, 56 bytes
                 ("fade_in_shape", C.c_int32), ("fade_out_shape", C.c_int32)]
 
 
+class ResampleInfo(C.Structure):       # wbx_resample_info, 24 bytes
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("half_width", C.c_uint32), ("taps", C.c_uint32),
+                ("table_floats", C.c_uint64)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -86,6 +91,7 @@ EDIT_REVERSE = 1                                        # WBX_EDIT_REVERSE
 CH_MODE = {"keep": 0, "swap": 1, "left": 2, "right": 3, "mono_mix": 4, "dual_mono": 5}   # WBX_CH_*
 CH_MODE_OUT = {"swap": 2, "left": 1, "right": 1, "mono_mix": 1, "dual_mono": 2}          # channels of the result ("keep": the source's)
 FADE_SHAPE = {"linear": 0, "square": 1, "smooth": 2}    # WBX_FADE_*
+SRC_QUALITY = {"fast": 0, "good": 1, "best": 2}         # WBX_SRC_*
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
 _vp, _u32, _i32, _f, _d, _sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_double, C.c_size_t
@@ -110,6 +116,10 @@ SYMBOLS = {
     "wbx_set_export_chunk": (C.c_int, [_vp, _u32]),
     "wbx_clip_measure": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.POINTER(ClipStats)]),
     "wbx_clip_derive": (C.c_int, [_vp, _u32, _u32, C.POINTER(ClipEditDesc), C.POINTER(ClipStats)]),
+    "wbx_resample_plan": (C.c_int, [_u32, _u32, C.c_int, C.POINTER(ResampleInfo)]),
+    "wbx_resample_frames": (C.c_uint64, [_u32, _u32, C.c_uint64]),
+    "wbx_resample_table": (C.c_int, [_u32, _u32, C.c_int, _vp, _sz]),
+    "wbx_clip_resample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -201,6 +211,7 @@ SYMBOLS = {
     "wbx_engine_measure_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.POINTER(ClipStats)]),
     "wbx_engine_derive_sample": (C.c_int, [_vp, _u32, C.POINTER(ClipEditDesc), C.POINTER(_u32)]),
     "wbx_engine_normalize_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, C.POINTER(_u32), C.POINTER(_f)]),
+    "wbx_engine_resample_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(_u32)]),
     "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
     "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),

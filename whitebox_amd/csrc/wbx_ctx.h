@@ -18,6 +18,7 @@
 #include "../../include/wbx.h"
 #include "wbx_dev.h"
 #include "wbx_shape.h"
+#include "wbx_resample.h"
 
 namespace wbx {
 void launch_plan(const PlanArgs& a, hipStream_t s);
@@ -98,6 +99,17 @@ struct ClipFxArgs {
   uint32_t reversed, src_channels, out_channels;   // src_channels: rows read (LEFT / RIGHT read one)
 };
 void launch_clipfx(const ClipFxArgs& a, hipStream_t s);
+// converting a clip's sample rate (wbx_resample.hip): a frame range of a planar F32 clip -> a new planar F32 clip
+struct ResampleArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const float* table;          // device: the coefficients in phase-visit order, [T][L]: row r holds phase (r * M) mod L
+  uint32_t n_in, n_out;        // frames of the range / of the result, both < 2^31 - 16
+  uint32_t L, M, H, T;         // the plan (wbx_resample.h)
+  uint32_t channels;           // 1 or 2
+  uint32_t tile, span, n_tiles;   // filled by launch_resample: outputs per tile, floats staged per channel and tile, tiles
+};
+void launch_resample(ResampleArgs a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -193,6 +205,15 @@ struct ClipFxStage {
   hipEvent_t after_main = nullptr, after_upload = nullptr;
   ClipFxStats* d_stats = nullptr;
   ClipFxStats* h_stats = nullptr;
+};
+
+// wbx_clip_resample's coefficient tables on the device, one per (L, M, quality) a context has converted with — made at
+// first use, freed with the context (192 B .. 2.6 MB each)
+struct ResampleTable {
+  uint32_t L = 0, M = 0;
+  int quality = 0;
+  float* d = nullptr;
+  std::vector<float> host;     // the upload's source, until the stream has been waited for
 };
 
 }  // namespace wbx
@@ -361,6 +382,7 @@ struct wbx_ctx {
   // wbx_clip_measure / wbx_clip_derive and layer 2's forms: one at a time (fx_mu), on a stream that is no mix or sum stream
   ClipFxStage fx;
   std::mutex fx_mu;
+  std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.stream)
 
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -442,6 +464,13 @@ wbx_status clipfx_measure_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_f
 wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
                              uint32_t out_channels, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
 void clipfx_release(wbx_ctx* c);
+// converting a clip's sample rate (wbx_resample.hip), cut the same way; it runs under fx_mu on the edit stream, behind
+// clipfx_prepare / clipfx_order, and measures its result through clipfx_measure_run
+wbx_status resample_check(const ExportSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,
+                          int quality, ResamplePlan* plan, uint64_t* n_out, const char** why);
+wbx_status resample_run(wbx_ctx* c, const ExportSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
+                        uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
+void resample_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it

@@ -683,6 +683,23 @@ struct EditPin {   // fx_mu held for its life; begin() validates and pins, the d
     *new_sample = id;
     return WBX_OK;
   }
+  // wbx_clip_resample's run (wbx_resample.hip), published the same way: a sample of n_out frames at dst_rate
+  wbx_status resample(const ResamplePlan& plan, int quality, uint64_t first_frame, uint64_t n_frames, uint64_t n_out, uint32_t dst_rate,
+                      uint32_t* new_sample, std::string* why) {
+    wbx_ctx* c = e->ctx;
+    wbx_status st = order(why);
+    ClipSlot slot;
+    if (st == WBX_OK) st = resample_run(c, src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, why);
+    if (st != WBX_OK) return st;
+    LockGuard g(e->hs.editor_lock);
+    const uint32_t id = (uint32_t)c->clips.size();
+    st = clip_publish(c, id, slot);
+    if (st != WBX_OK) return *why = c->err, st;
+    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize(c->clips.size());
+    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, src.channels, dst_rate, n_out, true};
+    *new_sample = id;
+    return WBX_OK;
+  }
 };
 
 }  // namespace
@@ -759,6 +776,32 @@ extern "C" wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample
   if (st != WBX_OK) return tls_err = why, st;
   if (gain_used) *gain_used = d.gain;
   return WBX_OK;
+}
+
+// wbx_clip_resample of an engine sample (wbx.h "Converting a clip's sample rate"), beside wbx_engine_derive_sample and under
+// its rules: the editor lock covers validating, the pin, ordering the stream and registering the new sample — at dst_rate —
+// and is never held across the device wait.  No transport state is touched, no edit is counted.
+extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                 uint32_t dst_rate, int quality, uint32_t* new_sample) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "resample_sample: new_sample is NULL");
+  EditPin p(e);
+  ResamplePlan plan;
+  uint64_t n_out = 0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "resample_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = resample_check(p.src, p.rate, first_frame, n_frames, dst_rate, quality, &plan, &n_out, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "resample_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.resample(plan, quality, first_frame, n_frames, n_out, dst_rate, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
 }
 
 // Engine::add_audio_clip -> add_to_cliplist, engine.cpp:293-309, :409-461

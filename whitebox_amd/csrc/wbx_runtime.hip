@@ -717,6 +717,7 @@ extern "C" void wbx_destroy(wbx_ctx* c) {
   (void)hipSetDevice(c->cfg.device);
   dist_destroy(c);
   export_release(c);
+  resample_release(c);
   clipfx_release(c);
   if (c->plan_stream) (void)hipStreamSynchronize(c->plan_stream);
   if (c->sum_stream) (void)hipStreamSynchronize(c->sum_stream);

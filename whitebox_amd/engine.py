@@ -98,6 +98,28 @@ def edit_desc(first_frame: int, n_frames: int, reverse: bool = False, channel_mo
                              _ffi.FADE_SHAPE.get(fade_in_shape, fade_in_shape), _ffi.FADE_SHAPE.get(fade_out_shape, fade_out_shape))
 
 
+def resample_plan(src_rate: int, dst_rate: int, quality="good") -> dict:
+    """wbx_resample_plan (host-only): {"L", "M", "half_width", "taps", "table_floats"} of a conversion; WbxError where the
+    library refuses it (status -4: a rate of 0, equal rates, unknown quality; -3: L > 1280 or more than 512 taps)"""
+    info = _ffi.ResampleInfo()
+    _check(_ffi.lib().wbx_resample_plan(src_rate, dst_rate, _ffi.SRC_QUALITY.get(quality, quality), C.byref(info)), "wbx_resample_plan")
+    return {k: int(getattr(info, k)) for k, _ in _ffi.ResampleInfo._fields_}
+
+
+def resample_frames(src_rate: int, dst_rate: int, n_frames: int) -> int:
+    """wbx_resample_frames (host-only): ceil(n_frames * L / M), the length of the converted range; 0 when refused"""
+    return int(_ffi.lib().wbx_resample_frames(src_rate, dst_rate, n_frames))
+
+
+def resample_table(src_rate: int, dst_rate: int, quality="good") -> np.ndarray:
+    """wbx_resample_table (host-only): the fp32 coefficients in phase order, [L][taps]"""
+    p = resample_plan(src_rate, dst_rate, quality)
+    out = np.zeros((p["L"], p["taps"]), dtype=np.float32)
+    _check(_ffi.lib().wbx_resample_table(src_rate, dst_rate, _ffi.SRC_QUALITY.get(quality, quality), out.ctypes.data, out.size),
+           "wbx_resample_table")
+    return out
+
+
 def _clip_stats(st, channels: int) -> dict:
     """wbx_clip_stats -> {"peak", "peak_frame", "min", "max", "over", "nans", "sum", "sum_sq"}, one entry per channel"""
     f32 = ("peak", "min", "max")
@@ -182,6 +204,17 @@ class MixContext:
         st = _ffi.ClipStats()
         _check(self.L.wbx_clip_derive(self.h, src_clip, dst_clip, C.byref(desc) if desc is not None else None,
                                       C.byref(st) if stats_channels else None), "wbx_clip_derive", self.h)
+        return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def clip_resample(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, dst_rate: int, quality="good",
+                      stats_channels: int = 0):
+        """wbx_clip_resample: `dst_clip` becomes a new F32 clip holding frames [first_frame, first_frame + n_frames) of
+        `src_clip` converted to `dst_rate` ("fast" / "good" / "best", or WBX_SRC_*), resample_frames(...) frames long;
+        returns the result's statistics when `stats_channels` (its channel count) is given, else None"""
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_clip_resample(self.h, src_clip, dst_clip, first_frame, n_frames, dst_rate,
+                                        _ffi.SRC_QUALITY.get(quality, quality), C.byref(st) if stats_channels else None),
+               "wbx_clip_resample", self.h)
         return _clip_stats(st, stats_channels) if stats_channels else None
 
     def set_export_chunk(self, frames: int):
@@ -379,6 +412,7 @@ class Engine:
         self.n_buses = 0
         self.max_blocks = max_blocks
         self._sample_shape = {}   # sample id -> (frames, channels) of the samples made through this object (export_sample)
+        self._sample_rate = {}    # sample id -> the sample's own rate where this object knows it (wav.write_sample)
 
     def close(self):
         if self.h:
@@ -486,6 +520,7 @@ class Engine:
         _check(self.L.wbx_engine_add_sample(self.h, _ffi.FMT[fmt], len(data), rate, frames, ptrs, C.byref(sid)),
                "wbx_engine_add_sample", self.h, True)
         self._sample_shape[sid.value] = (frames, len(data))
+        self._sample_rate[sid.value] = rate
         return sid.value
 
     def add_sample_interleaved(self, fmt: str, rate: int, frames_by_channels: np.ndarray) -> int:
@@ -495,6 +530,7 @@ class Engine:
         _check(self.L.wbx_engine_add_sample_interleaved(self.h, _ffi.FMT[fmt], a.shape[1], rate, a.shape[0], a.ctypes.data,
                                                         C.byref(sid)), "wbx_engine_add_sample_interleaved", self.h, True)
         self._sample_shape[sid.value] = (a.shape[0], a.shape[1])
+        self._sample_rate[sid.value] = rate
         return sid.value
 
     def add_sample_synth(self, fmt: str, channels: int, rate: int, frames: int, seed: int, key_track: int, amp: float) -> int:
@@ -502,11 +538,13 @@ class Engine:
         _check(self.L.wbx_engine_add_sample_synth(self.h, _ffi.FMT[fmt], channels, rate, frames, seed, key_track,
                                                   np.float32(amp), C.byref(sid)), "wbx_engine_add_sample_synth", self.h, True)
         self._sample_shape[sid.value] = (frames, channels)
+        self._sample_rate[sid.value] = rate
         return sid.value
 
     def delete_sample(self, sample: int):
         _check(self.L.wbx_engine_delete_sample(self.h, sample), "wbx_engine_delete_sample", self.h, True)
         self._sample_shape.pop(sample, None)
+        self._sample_rate.pop(sample, None)
 
     def add_audio_clip(self, track: Track, name: str, min_time: float, max_time: float, start_offset: float,
                        sample: int, speed: float = 1.0, gain: float = 1.0):
@@ -639,6 +677,7 @@ class Engine:
         self.ctx.last = (K % self.max_blocks or self.max_blocks, len(self.tracks))   # the last pass is what a fetch sees
         for i in ids[:len(sources)]:
             self._sample_shape[i] = (frames.value, self.num_output_channels)
+            self._sample_rate[i] = self.audio_sample_rate
         return list(ids[:len(sources)]), frames.value
 
     def export_sample(self, sample: int, out_format: str, first_frame: int = 0, n_frames: Optional[int] = None,
@@ -685,6 +724,8 @@ class Engine:
                "wbx_engine_derive_sample", self.h, True)
         mode = {v: k for k, v in _ffi.CH_MODE.items()}.get(desc.channel_mode, "keep")
         self._sample_shape[new.value] = (desc.n_frames, _ffi.CH_MODE_OUT.get(mode, channels))
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
         return new.value
 
     def normalize_sample(self, sample: int, target_peak: float, first_frame: int = 0, n_frames: Optional[int] = None,
@@ -699,7 +740,28 @@ class Engine:
         _check(self.L.wbx_engine_normalize_sample(self.h, sample, first_frame, n_frames, target_peak, C.byref(new), C.byref(gain)),
                "wbx_engine_normalize_sample", self.h, True)
         self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
         return new.value, float(gain.value)
+
+    def resample_sample(self, sample: int, dst_rate: int, quality="good", first_frame: int = 0, n_frames: Optional[int] = None,
+                        channels: Optional[int] = None, frames: Optional[int] = None, src_rate: Optional[int] = None) -> int:
+        """wbx_engine_resample_sample: a new sample = the range converted to `dst_rate` ("fast" / "good" / "best"),
+        registered at that rate — see MixContext.clip_resample; `frames` / `channels` as in export_sample.  The new
+        sample's length is known here when the source's rate is (`src_rate`, or a sample add_sample* made).  May be called
+        while another thread runs process()."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "resample_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        new = C.c_uint32()
+        _check(self.L.wbx_engine_resample_sample(self.h, sample, first_frame, n_frames, dst_rate,
+                                                 _ffi.SRC_QUALITY.get(quality, quality), C.byref(new)),
+               "wbx_engine_resample_sample", self.h, True)
+        src_rate = self._sample_rate.get(sample) if src_rate is None else src_rate
+        self._sample_shape[new.value] = (resample_frames(src_rate, dst_rate, n_frames) if src_rate else None, channels)
+        self._sample_rate[new.value] = dst_rate
+        return new.value
 
     def bounce_download(self, sample: int, frames: int) -> np.ndarray:
         """a bounced sample back on the host: [C][frames] fp32 (wbx_clip_download per channel)"""

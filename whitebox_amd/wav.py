@@ -67,7 +67,9 @@ def write_sample(engine, sample: int, path: str, bits: int = 16, float32: bool =
         raise ValueError("wav: give frames, the sample's length")
     total = {"peak": [0.0] * channels, "over": [0] * channels, "nans": [0] * channels}
     with open(path, "wb") as f:
-        f.write(header(channels, engine.audio_sample_rate, bits, frames, float32))
+        # the sample's own rate where the engine object knows it (an imported file, a converted sample), else the session's
+        rate = getattr(engine, "_sample_rate", {}).get(sample, engine.audio_sample_rate)
+        f.write(header(channels, rate, bits, frames, float32))
         done = 0
         while done < frames:
             n = min(piece_frames, frames - done)
