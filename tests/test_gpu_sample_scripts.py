@@ -1,0 +1,235 @@
+"""Sample life scripts on the device (tests/sample_scripts.py): uploads, derived, normalized and resampled samples, recorder
+takes, bounces and deletes chained at random in ONE clip pool, with placements, playback, measure, export and mip-maps in
+between.  Every feature's own test checks its own result; this one checks THE OTHERS: after every op every live sample is
+downloaded and compared bit for bit (uint32 views) with the model — an extent handed to two clips corrupts whoever was
+written first, which is never the clip a feature test looks at — and the padding behind every producer's result shows when a
+clip of another rate plays to its end against the oracle engine, whose copy of the sample is the model's planes + 16 zeros.
+The pool's three figures are checked after every op and are the starting ones at the end.
+
+Measured on an MI355X: 0.07 - 0.45 s per case, 2.2 - 2.5 s for the module's twelve cases (MEASUREMENTS.md "Sample life scripts");
+no time is asserted."""
+import numpy as np
+import pytest
+
+import bounce_util as BU
+import clipfx_model as FX
+import oracle_ffi as O
+import record_model as RM
+import sample_scripts as SS
+import whitebox_amd as W
+from whitebox_amd import synth
+from test_gpu_clipfx import check_stats
+from test_gpu_export import expected_bytes, expected_stats, same_stats
+from test_gpu_record import Rig, input_blocks
+
+pytestmark = pytest.mark.gpu
+DT = {"f32": np.float32, "i16": np.int16}
+
+
+class LifeRig(Rig):
+    """test_gpu_record.Rig (product engine, record model and oracle engine side by side) with the sample vocabulary on top:
+    a second oracle engine with every fader at unity for pre-fader bounces, the contents model, and product / oracle ids of
+    every script key."""
+
+    def __init__(self, seed):
+        self.spec = synth.make_session("life", SS.TRACKS, n_blocks=8, block=SS.F, sample_rate=SS.RATE, bpm=SS.BPM, seed=0x11FE00 + seed)
+        Rig.__init__(self, self.spec, SS.INPUTS, SS.CHUNK, SS.SPARE, check_now=True, collect=True)
+        self.tw = O.build_oracle_engine(BU.unity_twin(self.spec))
+        self.base = self.eng.ctx.pool_stats()              # right after build_engine
+        self.c = SS.Contents()
+        self.sid, self.osid, self.pids = {}, {}, {}
+        self.n_oracle = len(self.spec.samples)
+        for i, s in enumerate(self.spec.samples):           # the session's own samples: bystanders nobody may touch
+            self.sid[("base", i)] = sorted(self.eng._sample_shape)[i]
+            self.c.put(("base", i), s.fmt, s.rate, [a[:s.frames] for a in self.spec.sample_data(i)])
+        self.script_keys = []
+
+    # ---- ids
+    def oracle_id(self, key):
+        """the oracle engines' copy of a sample: the model's planes + the reference's 16 zero frames, made when first placed"""
+        if key not in self.osid:
+            fmt, rate, planes = self.c.s[key]
+            data = [np.concatenate([p, np.zeros(16, p.dtype)]) for p in planes]
+            ids = [e.add_sample(fmt, len(planes), rate, len(planes[0]), data) for e in (self.e, self.tw)]
+            assert ids == [self.n_oracle] * 2
+            self.n_oracle += 1
+            self.osid[key] = ids[0]
+        return self.osid[key]
+
+    def _oracle_takes(self, before):
+        Rig._oracle_takes(self, before)                     # (the take's sample and clip in self.e, and every check of a take)
+        for c in self.m.clips[before:]:
+            fr = RM.take_frames(c, self.inputs, self.F)
+            data = [np.concatenate([fr[ch], np.zeros(16, np.float32)]) for ch in range(c["channels"])]
+            assert self.tw.add_sample("f32", c["channels"], self.spec.sample_rate, fr.shape[1], data) == self.n_oracle
+            assert self.tw.add_audio_clip(c["track"], c["args"][1], c["args"][2], 0.0, self.n_oracle, 1.0, 1.0) == 0
+            self.n_oracle += 1
+
+    # ---- checks
+    def new_sample(self, key, sid, frames, channels, rate):
+        assert key in self.c.s and (len(self.c.s[key][2][0]), len(self.c.s[key][2]), self.c.s[key][1]) == (frames, channels, rate)
+        self.sid[key] = sid
+        self.script_keys.append(key)
+        self.check_sample(key)                              # the new sample itself, bit for bit
+        if sid in self.eng._sample_shape:                   # (a take's sample is made inside stop_record: not registered here)
+            assert self.eng._sample_shape[sid] == (frames, channels) and self.eng._sample_rate.get(sid, rate) == rate, (key, sid)
+        if self.c.s[key][0] == "f32":                       # registered length: the frame behind the last one does not exist
+            with pytest.raises(W.WbxError):
+                self.eng.measure_sample(sid, frames, 1, channels=channels, frames=frames + 1)
+
+    def check_sample(self, key):
+        fmt, _, planes = self.c.s[key]
+        for ch, want in enumerate(planes):
+            got = self.eng.ctx.clip_download(self.sid[key], ch, len(want), DT[fmt])
+            bad = np.flatnonzero(got.view(np.uint8) != want.view(np.uint8))
+            assert bad.size == 0, ("sample", key, "channel", ch, "first wrong byte", int(bad[0]), "of", want.nbytes)
+
+    def check_bystanders(self):
+        """EVERY live sample against the model, and the pool's figures"""
+        for key in self.c.s:
+            self.check_sample(key)
+        n, reserved, live = self.eng.ctx.pool_stats()
+        assert (n, reserved) == self.base[:2], "the pool grew"
+        bounds = [SS.pool_bounds(len(p[0]), len(p), fmt) for key, (fmt, _, p) in self.c.s.items() if not isinstance(key, tuple)]
+        lo, hi = self.base[2] + sum(b[0] for b in bounds), self.base[2] + sum(b[1] for b in bounds)
+        assert lo <= live <= hi, (lo, live, hi)             # (exact where no clip has 8 granules: lo == hi)
+
+    def clip_index(self, track, sid, lo):
+        got = [i for i, ci in enumerate(self.eng.clips(self.eng.tracks[track])) if ci[5] == sid and O.f64_bits(ci[0]) == O.f64_bits(lo)]
+        assert len(got) == 1, (track, sid, lo)
+        return got[0]
+
+    def same_clip_lists(self):
+        for t in range(len(self.eng.tracks)):
+            got = [tuple(O.f64_bits(x) for x in ci[:4]) for ci in self.eng.clips(self.eng.tracks[t])]
+            for e in (self.e, self.tw):
+                assert got == [tuple(O.f64_bits(x) for x in ci[:4]) for ci in e.clips(t)], ("clip list", t)
+
+    # ---- the ops
+    def life_op(self, op):
+        """-> the status the product returned"""
+        k, eng, c = op[0], self.eng, self.c
+        try:
+            if k == "add":
+                _, key, fmt, channels, rate, frames, interleaved, _ = op
+                c.apply(op)
+                planes = c.s[key][2]
+                sid = eng.add_sample_interleaved(fmt, rate, np.stack(planes, axis=1)) if interleaved else eng.add_sample(fmt, rate, planes)
+                self.new_sample(key, sid, frames, channels, rate)
+            elif k == "derive":
+                _, key, src, first, n, rev, mode, gain, fi, fo, si, so = op
+                c.apply(op)
+                sid = eng.derive_sample(self.sid[src], W.edit_desc(first, n, rev, mode, gain, fi, fo, si, so), channels=len(c.s[src][2]))
+                self.new_sample(key, sid, n, len(c.s[key][2]), c.s[src][1])
+            elif k == "normalize":
+                _, key, src, target, first, n = op
+                c.apply(op)
+                sid, gain = eng.normalize_sample(self.sid[src], target, first, n, channels=len(c.s[src][2]), frames=len(c.s[src][2][0]))
+                assert np.float32(gain).tobytes() == np.float32(c.gain).tobytes()
+                self.new_sample(key, sid, n, len(c.s[src][2]), c.s[src][1])
+            elif k == "resample":
+                _, key, src, dst, q, first, n = op
+                c.apply(op)
+                sid = eng.resample_sample(self.sid[src], dst, q, first, n, channels=len(c.s[src][2]), frames=len(c.s[src][2][0]),
+                                          src_rate=c.s[src][1])
+                self.new_sample(key, sid, len(c.s[key][2][0]), len(c.s[src][2]), dst)
+            elif k == "take":
+                _, key, track, kind, index, b0, n, beat = op
+                made = len(self.made)
+                self.run([("input", track, kind, index, True), ("playhead", beat), ("record",)] +
+                         [("block", b0 + b) for b in range(n)] + [("stop_record",), ("stop",), ("input", track, RM.NONE, 0, False)])
+                assert self.statuses[-(n + 6):] == [0] * (n + 6) == self.m.statuses[-(n + 6):]
+                assert len(self.made) == made + 1
+                clip, sid = self.made[-1]
+                c.put(key, "f32", SS.RATE, list(RM.take_frames(clip, self.inputs, self.F)))
+                self.osid[key] = self.n_oracle - 1           # (_oracle_takes made it, in both oracle engines)
+                self.pids[("take", key)] = (track, sid, clip["args"][1])
+                assert O.f64_bits(clip["args"][1]) == O.f64_bits(beat) and clip["channels"] == (2 if kind == RM.STEREO else 1)
+                self.new_sample(key, sid, n * self.F, clip["channels"], SS.RATE)
+            elif k == "bounce":
+                _, keys, lo, hi, sources = op
+                frames, post, master, _ = BU.oracle_sequence(self.e, self.spec, lo, hi)
+                _, pre, _, _ = BU.oracle_sequence(self.tw, self.spec, lo, hi)
+                ids, got_frames = eng.bounce(lo, hi, list(sources))
+                assert got_frames == frames == int((hi - lo) * (60.0 / SS.BPM) * SS.RATE)
+                for key, sid, s in zip(keys, ids, sources):
+                    want = master if s[0] == "master" else (pre if s[2] == "pre" else post)[s[1]]
+                    c.put(key, "f32", SS.RATE, list(want))
+                    self.new_sample(key, sid, frames, 2, SS.RATE)
+            elif k == "place":
+                _, pid, src, track, lo, hi, start = op
+                osid = self.oracle_id(src)
+                eng.add_audio_clip(eng.tracks[track], "life", lo, hi, start, self.sid[src], 1.0, 1.0)
+                for e in (self.e, self.tw):
+                    assert e.add_audio_clip(track, lo, hi, start, osid, 1.0, 1.0) == 0
+                self.pids[pid] = (track, self.sid[src], lo)
+                self.same_clip_lists()
+            elif k == "unplace":
+                track, sid, lo = self.pids.pop(op[1])
+                i = self.clip_index(track, sid, lo)
+                eng.delete_clip(eng.tracks[track], i)
+                for e in (self.e, self.tw):
+                    assert O.f64_bits(e.clips(track)[i][0]) == O.f64_bits(lo) and e.delete_clip(track, i) == 0
+                self.same_clip_lists()
+            elif k == "play":
+                self.run([("playhead", op[1]), ("play",)] + [("block", None)] * op[2] + [("stop",)])   # master and peaks: check_block
+            elif k == "measure":
+                _, src, first, n = op
+                planes = c.s[src][2]
+                got = eng.measure_sample(self.sid[src], first, n, channels=len(planes), frames=len(planes[0]))
+                check_stats(got, FX.measure(planes, first, n), n, ("measure", src))
+            elif k == "export":
+                _, src, fmt, clamp, first, n = op
+                planes = [p[first:first + n] for p in c.s[src][2]]
+                got, st = eng.export_sample(self.sid[src], fmt, first, n, clamp=clamp, channels=len(planes), frames=len(c.s[src][2][0]))
+                assert np.array_equal(got.view(np.uint8), expected_bytes(planes, fmt, clamp)), ("export", src, fmt)
+                assert same_stats(st, expected_stats(planes)), ("export stats", src)
+            elif k == "mip":
+                _, src, quality = op
+                fmt, _, planes = c.s[src]
+                frames = len(planes[0])
+                levels = O.oracle_mip_levels(frames)
+                assert levels >= 1 and eng.L.wbx_mip_levels(frames) == levels
+                eng.ctx.build_mipmaps(self.sid[src], quality)
+                for lv in range(levels):
+                    mip = eng.ctx.fetch_mipmap(self.sid[src], lv, len(planes), frames, quality)
+                    for ch, p in enumerate(planes):
+                        assert np.array_equal(mip[ch], O.oracle_mip(fmt, p, lv, quality)), ("mip", src, lv, ch)
+            elif k == "delete":
+                eng.delete_sample(self.sid[op[1]])
+                c.apply(op)
+                del self.sid[op[1]]
+            else:
+                raise ValueError(op)
+        except W.WbxError as ex:
+            return ex.status
+        return 0
+
+    def close(self):
+        Rig.close(self)
+        self.tw.close()
+
+
+@pytest.mark.parametrize("seed", SS.SEEDS)
+def test_every_sample_outlives_its_neighbours(seed):
+    ops, facts = SS.make_script(seed)
+    rig = LifeRig(seed)
+    rig.inputs = input_blocks(np.random.default_rng(0x11FE + seed), max(facts["input_blocks"], 1), SS.INPUTS, SS.F, special=False)
+    try:
+        rig.check_bystanders()
+        for i, op in enumerate(ops):
+            try:
+                status = rig.life_op(op)
+                assert status == (op[2] if op[0] == "delete" else 0), ("status", status)
+                rig.check_bystanders()
+            except AssertionError as ex:
+                raise AssertionError((seed, i, op[:3], ex.args)) from ex
+        # everything the script placed and made goes; the pool is what it was after build_engine
+        for pid in list(rig.pids):
+            assert rig.life_op(("unplace", pid)) == 0
+        for key in [k for k in rig.script_keys if k in rig.sid]:
+            assert rig.life_op(("delete", key, 0)) == 0
+            rig.check_bystanders()
+        assert rig.eng.ctx.pool_stats() == rig.base
+    finally:
+        rig.close()

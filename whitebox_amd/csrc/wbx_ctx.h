@@ -19,6 +19,7 @@
 #include "wbx_dev.h"
 #include "wbx_shape.h"
 #include "wbx_resample.h"
+#include "wbx_pool.h"
 
 namespace wbx {
 void launch_plan(const PlanArgs& a, hipStream_t s);
@@ -123,20 +124,7 @@ constexpr int kRing = 3;
 constexpr uint32_t kPaceRing = 64;
 constexpr uint32_t kCbDoneWords = 2 * 16 * 64;   // wbx_ctx::d_cb_done: two counters of kCbLanes words, kCbStride apart (wbx_callback.h)
 
-// Clip audio lives in slabs of 1 GiB carved up in order (64-KiB granules): a session of thousands of clips is a few
-// dozen large allocations, which the driver backs with large contiguous fragments (measured: the mix kernel's launch time
-// is bimodal from process to process with one allocation per clip, 3-5 % apart, and stays at the fast end with slabs,
-// tools/ab_arena.sh).  A slab's space is reused when the last clip in it has been freed; slabs go back to the
-// driver with the context.  Clips above 256 MiB get an allocation of their own.
-struct ClipSlab {
-  char* mem = nullptr;
-  size_t size = 0, used = 0;   // [0, used): handed out in order (bump); [used, size): untouched
-  uint32_t live = 0;           // clips inside
-  size_t live_bytes = 0;
-  // extents below `used` that released clips gave back, sorted by offset, neighbours merged: first-fit for the next clip
-  // that fits (replacing a clip again and again, or add / delete cycles beside a long-lived clip, stay inside the slab)
-  std::vector<std::pair<size_t, size_t>> holes;   // (offset, bytes)
-};
+// (ClipSlab, the clip pool's slabs and the policy that carves them up: wbx_pool.h)
 
 struct ClipSlot {
   void* alloc = nullptr;    // an allocation of its own (hipFree), or
@@ -227,7 +215,7 @@ struct wbx_ctx {
   std::string err;
 
   std::vector<ClipSlot> clips;
-  std::vector<std::unique_ptr<ClipSlab>> slabs;   // clip storage (slab_mu: clips are built outside the editor lock)
+  ClipSlabs slabs;   // clip storage (slab_mu: clips are built outside the editor lock)
   std::mutex slab_mu;
   std::atomic<uint32_t> slab_seq{0};  // clips placed so far (seeds the gap in front of the next one)
   std::atomic<uint64_t> pool_limit{0};   // wbx_clip_pool_limit: bytes the pool may reserve from the driver, 0 = no bound

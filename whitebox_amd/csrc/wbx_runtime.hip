@@ -787,29 +787,7 @@ void clip_release(wbx_ctx* c, ClipSlot& s) {
   }
   if (s.slab) {
     std::lock_guard<std::mutex> g(c->slab_mu);
-    ClipSlab& sl = *s.slab;
-    sl.live_bytes -= std::min(sl.live_bytes, s.slab_len);
-    if (sl.live && --sl.live == 0) {   // the whole slab is free again
-      sl.used = 0;
-      sl.holes.clear();
-    } else if (s.slab_off + s.slab_len == sl.used) {   // the newest extent: the bump pointer steps back (over a hole that ends there, too)
-      sl.used = s.slab_off;
-      if (!sl.holes.empty() && sl.holes.back().first + sl.holes.back().second == sl.used) {
-        sl.used = sl.holes.back().first;
-        sl.holes.pop_back();
-      }
-    } else {                           // a hole, merged with its neighbours
-      auto it = std::lower_bound(sl.holes.begin(), sl.holes.end(), std::make_pair(s.slab_off, (size_t)0));
-      it = sl.holes.insert(it, std::make_pair(s.slab_off, s.slab_len));
-      if (it + 1 != sl.holes.end() && it->first + it->second == (it + 1)->first) {
-        it->second += (it + 1)->second;
-        it = sl.holes.erase(it + 1) - 1;
-      }
-      if (it != sl.holes.begin() && (it - 1)->first + (it - 1)->second == it->first) {
-        (it - 1)->second += it->second;
-        sl.holes.erase(it);
-      }
-    }
+    pool_give(*s.slab, s.slab_off, s.slab_len);   // (wbx_pool.h)
   }
   if (s.mip) (void)hipFree(s.mip);
   s = ClipSlot{};
@@ -833,81 +811,39 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
   const size_t stride = align_up((frames + kPad) * eb, 256);   // (varying the distance between a clip's channel rows: no effect)
   {
     static const bool use_slabs = !(std::getenv("WBX_CLIP_ARENA") && std::getenv("WBX_CLIP_ARENA")[0] == '0');   // A/B aid
-    constexpr size_t kSlab = (size_t)1 << 30, kGranule = (size_t)64 << 10;   // (8-GiB slabs, 2-MiB granules: no difference)
-    // A pseudo-random gap of 0..15 granules in front of every clip (at most an eighth of the clip): a session of equally
-    // long clips has one clip-to-clip stride, and some strides alias in the HBM address hash — the workgroups in flight
-    // read the same offset of many clips at once (c4 with 9.06-MiB clips: 0.82 instead of 0.73 ms per launch;
-    // tools/ab_arena.sh).  WBX_SLAB_JITTER=0: A/B aid.
-    static const bool jitter = !(std::getenv("WBX_SLAB_JITTER") && std::getenv("WBX_SLAB_JITTER")[0] == '0');
-    const size_t body = align_up(stride * channels, kGranule);
-    const uint32_t span = (uint32_t)std::min<size_t>(16, body / kGranule / 8 + 1);
-    const size_t gap = jitter ? (size_t)((((c->slab_seq.fetch_add(1u, std::memory_order_relaxed) + 1u) * 2654435761u) >> 8) % span) * kGranule : 0;
-    const size_t need = body + gap;
-    const uint64_t limit = c->pool_limit.load(std::memory_order_relaxed);   // wbx_clip_pool_limit
-    auto reserved_now = [&]() {   // (slab_mu held)
-      uint64_t r = c->own_alloc_bytes.load(std::memory_order_relaxed);
-      for (auto& sl : c->slabs) r += sl->size;
-      return r;
-    };
-    if (use_slabs && need <= kSlab / 4) {   // (slab sizes grow 64 MiB, 256 MiB, 1 GiB, 1 GiB ...: small sessions stay small)
+    static const bool jitter = !(std::getenv("WBX_SLAB_JITTER") && std::getenv("WBX_SLAB_JITTER")[0] == '0');   // A/B aid (the gap: wbx_pool.h)
+    const PoolExtent ext = pool_extent(stride * channels, jitter ? c->slab_seq.fetch_add(1u, std::memory_order_relaxed) : 0u, jitter);
+    const size_t need = ext.body + ext.gap;
+    PoolTake where;
+    {   // where the clip goes is wbx_pool.h's decision; hipMalloc is the slabs' source
       std::lock_guard<std::mutex> g(c->slab_mu);
-      ClipSlab* sl = nullptr;
-      size_t at = 0;
-      bool in_hole = false;
-      for (auto it = c->slabs.rbegin(); it != c->slabs.rend() && !sl; ++it) {   // the newest slab first: a hole that fits, else its tail
-        for (auto h = (*it)->holes.begin(); h != (*it)->holes.end() && !sl; ++h)
-          if (h->second >= need) {
-            sl = it->get();
-            at = h->first;
-            in_hole = true;
-            if (h->second == need) {
-              sl->holes.erase(h);
-            } else {
-              h->first += need;
-              h->second -= need;
-            }
-          }
-        if (!sl && (*it)->size - (*it)->used >= need) sl = it->get();
-      }
-      if (!sl) {
-        std::unique_ptr<ClipSlab> fresh(new (std::nothrow) ClipSlab());
-        if (!fresh) return WBX_ERR_OOM;
-        const size_t grown = c->slabs.size() >= 2 ? kSlab : ((size_t)64 << 20) << (2 * c->slabs.size());
-        size_t sz = std::max(grown, need);
-        if (limit) {   // a bounded pool: the usual slab if it fits, else one just large enough, else none
-          const uint64_t have = reserved_now();
-          if (have + sz > limit) sz = need;
-          if (have + sz > limit) return fail(c, WBX_ERR_OOM, "clip pool limit reached (wbx_clip_pool_limit)");
-        }
-        if (hipMalloc((void**)&fresh->mem, sz) == hipSuccess) {
-          fresh->size = sz;
-          c->slabs.push_back(std::move(fresh));
-          sl = c->slabs.back().get();
-        } else {
-          (void)hipGetLastError();   // a device too full for another slab: this clip gets an allocation of its own below
-        }
-      }
-      if (sl) {
-        if (!in_hole) {
-          at = sl->used;
-          sl->used += need;
-        }
-        s.slab = sl;
-        s.slab_off = at;
-        s.slab_len = need;
-        s.base = sl->mem + at + gap;
-        sl->live++;
-        sl->live_bytes += need;
-      }
+      where = pool_take(c->slabs, need, stride * channels, c->pool_limit.load(std::memory_order_relaxed),
+                        c->own_alloc_bytes.load(std::memory_order_relaxed), use_slabs,
+                        [](void*, size_t bytes) -> char* {
+                          char* mem = nullptr;
+                          if (hipMalloc((void**)&mem, bytes) == hipSuccess) return mem;
+                          (void)hipGetLastError();   // a device too full for another slab: this clip gets an allocation of its own
+                          return nullptr;
+                        },
+                        nullptr);
     }
-    if (!s.slab) {
-      if (limit) {
-        std::lock_guard<std::mutex> g(c->slab_mu);
-        if (reserved_now() + stride * channels > limit) return fail(c, WBX_ERR_OOM, "clip pool limit reached (wbx_clip_pool_limit)");
+    switch (where.where) {
+      case POOL_IN_SLAB:
+        s.slab = where.slab;
+        s.slab_off = where.off;
+        s.slab_len = need;
+        s.base = where.slab->mem + where.off + ext.gap;
+        break;
+      case POOL_OWN: {
+        WBX_HIP(c, hipMalloc(&s.alloc, stride * channels));
+        s.base = s.alloc;
+        c->own_alloc_bytes.fetch_add(stride * channels, std::memory_order_relaxed);
+        break;
       }
-      WBX_HIP(c, hipMalloc(&s.alloc, stride * channels));
-      s.base = s.alloc;
-      c->own_alloc_bytes.fetch_add(stride * channels, std::memory_order_relaxed);
+      case POOL_LIMIT:
+        return fail(c, WBX_ERR_OOM, "clip pool limit reached (wbx_clip_pool_limit)");
+      default:
+        return WBX_ERR_OOM;
     }
   }
   s.d.ch[0] = s.base;
@@ -1174,17 +1110,15 @@ extern "C" wbx_status wbx_clip_free(wbx_ctx* c, uint32_t clip) {
 extern "C" wbx_status wbx_clip_pool_stats(wbx_ctx* c, uint32_t* n_slabs, uint64_t* bytes_reserved, uint64_t* bytes_live) {
   if (!c) return WBX_ERR_INVALID;
   std::lock_guard<std::mutex> g(c->slab_mu);
+  uint32_t n = 0;
   uint64_t reserved = 0, live = 0;
-  for (auto& sl : c->slabs) {
-    reserved += sl->size;
-    live += sl->live_bytes;
-  }
+  pool_slab_stats(c->slabs, &n, &reserved, &live);   // (wbx_pool.h)
   for (auto& s : c->clips)
     if (s.alloc) {
       reserved += s.stride * s.d.channels;
       live += s.stride * s.d.channels;
     }
-  if (n_slabs) *n_slabs = (uint32_t)c->slabs.size();
+  if (n_slabs) *n_slabs = n;
   if (bytes_reserved) *bytes_reserved = reserved;
   if (bytes_live) *bytes_live = live;
   return WBX_OK;
