@@ -473,3 +473,80 @@ def test_edits_beside_the_audio_thread():
         eng.measure_sample(big, channels=2, frames=FR)
     assert ex.value.status == -4
     eng.close()
+
+
+# ---- 7: an export and edits side by side ----------------------------------------------------------------------------------------
+def test_an_export_and_edits_run_side_by_side():
+    """wbx_engine_export_sample works on the export stream under export_mu, derive and resample on the edit stream under
+    fx_mu: one thread exports a sample (17 chunks of 4096 frames) while a second derives and then resamples the same sample
+    and the main thread renders a track that plays it.  Every call succeeds, and the exported bytes, both new samples and
+    the rendered blocks are, bit for bit, what the same calls give one after another on a fresh engine."""
+    FR, F, NB = (1 << 16) + 5, 128, 8
+    rng = np.random.default_rng(0x51DE)
+    planes = [rng.uniform(-1.3, 1.3, FR).astype(np.float32) for _ in range(2)]
+    desc = W.edit_desc(0, FR, True, "keep", 0.5, 100, 0)
+    n_rs = W.resample_frames(48000, 44100, FR)
+
+    def session():
+        eng = W.Engine(1, buffer_size=F, sample_rate=48000, max_blocks=1)
+        sid = eng.add_sample("f32", 48000, planes)
+        eng.add_audio_clip(eng.add_track("t"), "clip", 0.0, 4.0, 0.0, sid)
+        eng.ctx.set_export_chunk(4096)
+        eng.play()
+        return eng, sid
+
+    def export(eng, sid, r):
+        r["bytes"], r["stats"] = eng.export_sample(sid, "i16", clamp=True)
+
+    def edit(eng, sid, r):
+        r["derived"] = eng.derive_sample(sid, desc)
+        r["resampled"] = eng.resample_sample(sid, 44100, "fast")
+
+    def render(eng, r):
+        out = W.AudioBuffer(F, 2)
+        r["blocks"] = []
+        for _ in range(NB):
+            eng.process(None, out, 48000.0)
+            r["blocks"].append(np.stack(out.channel_buffers).copy())
+
+    def audio_of(eng, r):
+        r["derived_audio"] = np.stack(download(eng.ctx, r["derived"], 2, FR))
+        r["resampled_audio"] = np.stack(download(eng.ctx, r["resampled"], 2, n_rs))
+
+    want = {}
+    eng, sid = session()
+    export(eng, sid, want)
+    edit(eng, sid, want)
+    render(eng, want)
+    audio_of(eng, want)
+    eng.close()
+
+    got, errors = {}, []
+    eng, sid = session()
+    start = threading.Barrier(3)
+
+    def beside(fn):
+        def run():
+            try:
+                start.wait()
+                fn(eng, sid, got)
+            except Exception as ex:   # a status that is not WBX_OK raises WbxError
+                errors.append(ex)
+        return threading.Thread(target=run)
+
+    threads = [beside(export), beside(edit)]
+    for th in threads:
+        th.start()
+    start.wait()
+    render(eng, got)
+    for th in threads:
+        th.join()
+    assert not errors, errors
+    audio_of(eng, got)
+    eng.close()
+    assert got["bytes"].size == 2 * FR and np.array_equal(got["bytes"], want["bytes"]) and got["stats"] == want["stats"]
+    assert (got["derived"], got["resampled"]) == (want["derived"], want["resampled"])
+    for k in ("derived_audio", "resampled_audio"):
+        assert got[k].shape == want[k].shape and np.array_equal(bits(got[k]), bits(want[k])), k
+    assert any(b.any() for b in want["blocks"]) and len(got["blocks"]) == NB
+    assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(got["blocks"], want["blocks"]))

@@ -227,18 +227,7 @@ void launch_clipfx(const ClipFxArgs& a, hipStream_t s) {
 
 // ---- layer 1: checks (no device call), the stream and its ordering, the two runs ------------------------------------------
 
-static wbx_status fx_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
-  if (why) {
-    *why = what;
-    if (e != hipSuccess) {
-      *why += ": ";
-      *why += hipGetErrorString(e);
-    }
-  }
-  return st;
-}
-
-wbx_status clipfx_check_range(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, const char** why) {
+wbx_status clipfx_check_range(const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, const char** why) {
   if (n_frames == 0) return *why = "clip edit: no frames", WBX_ERR_INVALID;
   if (first_frame > src.frames || n_frames > src.frames - first_frame) return *why = "clip edit: the range ends past the clip", WBX_ERR_INVALID;
   if (src.format != (uint32_t)WBX_FMT_F32) return *why = "clip edit: the clip's storage format is not F32", WBX_ERR_UNSUPPORTED;
@@ -246,7 +235,7 @@ wbx_status clipfx_check_range(const ExportSrc& src, uint64_t first_frame, uint64
   return WBX_OK;
 }
 
-wbx_status clipfx_check_derive(const ExportSrc& src, const wbx_clip_edit_desc* d, uint32_t* out_channels, const char** why) {
+wbx_status clipfx_check_derive(const ClipSrc& src, const wbx_clip_edit_desc* d, uint32_t* out_channels, const char** why) {
   if (!d) return *why = "clip edit: the descriptor is NULL", WBX_ERR_INVALID;
   if (d->n_frames == 0) return *why = "clip edit: no frames", WBX_ERR_INVALID;
   if (d->first_frame > src.frames || d->n_frames > src.frames - d->first_frame) return *why = "clip edit: the range ends past the clip", WBX_ERR_INVALID;
@@ -274,12 +263,7 @@ wbx_status clipfx_check_derive(const ExportSrc& src, const wbx_clip_edit_desc* d
 
 void clipfx_release(wbx_ctx* c) {
   ClipFxStage& x = c->fx;
-  if (x.stream) {
-    (void)hipStreamSynchronize(x.stream);
-    (void)hipStreamDestroy(x.stream);
-  }
-  if (x.after_main) (void)hipEventDestroy(x.after_main);
-  if (x.after_upload) (void)hipEventDestroy(x.after_upload);
+  side_release(x.side);
   if (x.d_stats) (void)hipFree(x.d_stats);
   if (x.h_stats) (void)hipHostFree(x.h_stats);
   x = ClipFxStage{};
@@ -287,17 +271,15 @@ void clipfx_release(wbx_ctx* c) {
 
 wbx_status clipfx_prepare(wbx_ctx* c, std::string* why) {
   ClipFxStage& x = c->fx;
-  if (x.stream) return WBX_OK;
+  if (x.side.stream) return WBX_OK;
   (void)hipSetDevice(c->cfg.device);
-  hipError_t e = hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_main, c->dev_event_flags);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_upload, c->dev_event_flags);
+  hipError_t e = side_prepare(c, x.side);
   if (e == hipSuccess) e = hipMalloc((void**)&x.d_stats, sizeof(ClipFxStats));
   if (e == hipSuccess) e = hipHostMalloc((void**)&x.h_stats, 2 * sizeof(ClipFxStats), hipHostMallocDefault);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     clipfx_release(c);
-    return fx_fail(why, WBX_ERR_DEVICE, "clip edit: stream, events and statistics block", e);
+    return stage_fail(why, WBX_ERR_DEVICE, "clip edit: stream, events and statistics block", e);
   }
   ClipFxStats& init = x.h_stats[0];                          // what a launch starts from
   std::memset(&init, 0, sizeof(init));
@@ -305,18 +287,16 @@ wbx_status clipfx_prepare(wbx_ctx* c, std::string* why) {
   return WBX_OK;
 }
 
-// the edit stream behind everything enqueued so far on the streams that write the pool's clips (export_order's rule)
 wbx_status clipfx_order(wbx_ctx* c, std::string* why) {
-  ClipFxStage& x = c->fx;
-  hipError_t e = join_sum(c);
-  if (e == hipSuccess) e = join_alt(c);
-  if (e == hipSuccess) e = hipEventRecord(x.after_main, c->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_main, 0);
-  if (e == hipSuccess && c->upload_stream) {
-    e = hipEventRecord(x.after_upload, c->upload_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_upload, 0);
-  }
-  return e == hipSuccess ? WBX_OK : fx_fail(why, WBX_ERR_DEVICE, "clip edit: ordering after the pool's writers", e);
+  const hipError_t e = side_order(c, c->fx.side);
+  return e == hipSuccess ? WBX_OK : stage_fail(why, WBX_ERR_DEVICE, "clip edit: ordering after the pool's writers", e);
+}
+
+wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, const char* unknown_src, const char* same) {
+  if (!find_clip(c, src_clip)) return fail(c, WBX_ERR_INVALID, unknown_src);
+  if (dst_clip == src_clip) return fail(c, WBX_ERR_INVALID, same);
+  if (dst_clip >= (1u << 24)) return fail(c, WBX_ERR_INVALID, "clip id");
+  return WBX_OK;
 }
 
 static float key_to_float(uint32_t key) {
@@ -330,12 +310,13 @@ static float key_to_float(uint32_t key) {
 // statistics, asked for or not — instances without them would double the eight that store.)
 static hipError_t fx_launch(wbx_ctx* c, const ClipFxArgs& a, uint32_t channels, uint64_t n_frames, wbx_clip_stats* out) {
   ClipFxStage& x = c->fx;
-  hipError_t e = hipMemcpyAsync(x.d_stats, &x.h_stats[0], sizeof(ClipFxStats), hipMemcpyHostToDevice, x.stream);
+  const hipStream_t on = x.side.stream;
+  hipError_t e = hipMemcpyAsync(x.d_stats, &x.h_stats[0], sizeof(ClipFxStats), hipMemcpyHostToDevice, on);
   if (e != hipSuccess) return e;
-  launch_clipfx(a, x.stream);
+  launch_clipfx(a, on);
   e = hipGetLastError();
-  if (e == hipSuccess && out) e = hipMemcpyAsync(&x.h_stats[1], x.d_stats, sizeof(ClipFxStats), hipMemcpyDeviceToHost, x.stream);
-  const hipError_t w = hipStreamSynchronize(x.stream);       // (also after a failure: nothing may still write the new clip)
+  if (e == hipSuccess && out) e = hipMemcpyAsync(&x.h_stats[1], x.d_stats, sizeof(ClipFxStats), hipMemcpyDeviceToHost, on);
+  const hipError_t w = hipStreamSynchronize(on);             // (also after a failure: nothing may still write the new clip)
   if (e == hipSuccess) e = w;
   if (e != hipSuccess || !out) return e;
   const ClipFxStats& r = x.h_stats[1];
@@ -356,28 +337,27 @@ static hipError_t fx_launch(wbx_ctx* c, const ClipFxArgs& a, uint32_t channels, 
   return hipSuccess;
 }
 
-wbx_status clipfx_measure_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out,
+wbx_status clipfx_measure_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out,
                               std::string* why) {
   ClipFxArgs a{};
-  for (uint32_t ch = 0; ch < 2; ch++) a.src[ch] = reinterpret_cast<const float*>((const char*)src.base + src.stride * (ch % src.channels));
+  for (uint32_t ch = 0; ch < 2; ch++) a.src[ch] = clip_row(src, ch);
   a.stats = c->fx.d_stats;
   a.first_frame = (uint32_t)first_frame;
   a.n_frames = (uint32_t)n_frames;
   a.src_channels = a.out_channels = src.channels;
   const hipError_t e = fx_launch(c, a, src.channels, n_frames, out);
-  return e == hipSuccess ? WBX_OK : fx_fail(why, WBX_ERR_DEVICE, "clip measure", e);
+  return e == hipSuccess ? WBX_OK : stage_fail(why, WBX_ERR_DEVICE, "clip measure", e);
 }
 
 // `slot` becomes the new clip (built on the edit stream; complete when this returns WBX_OK, released otherwise)
-wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
+wbx_status clipfx_derive_run(wbx_ctx* c, const ClipSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
                              uint32_t out_channels, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
   ClipFill fill{};
   fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, out_channels, sample_rate, d.n_frames, fill, c->fx.stream);
+  wbx_status st = clip_build(c, slot, WBX_FMT_F32, out_channels, sample_rate, d.n_frames, fill, c->fx.side.stream);
   if (st != WBX_OK) return *why = c->err, st;
   ClipFxArgs a{};
-  const float* row[2];
-  for (uint32_t ch = 0; ch < 2; ch++) row[ch] = reinterpret_cast<const float*>((const char*)src.base + src.stride * (ch % src.channels));
+  const float* row[2] = {clip_row(src, 0), clip_row(src, 1)};
   switch (d.channel_mode) {
     case WBX_CH_SWAP: a.src[0] = row[1], a.src[1] = row[0]; break;
     case WBX_CH_RIGHT: a.src[0] = a.src[1] = row[1]; break;
@@ -400,7 +380,7 @@ wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_r
   const hipError_t e = fx_launch(c, a, out_channels, d.n_frames, stats);
   if (e != hipSuccess) {
     clip_release(c, slot);
-    return fx_fail(why, WBX_ERR_DEVICE, "clip derive", e);
+    return stage_fail(why, WBX_ERR_DEVICE, "clip derive", e);
   }
   return WBX_OK;
 }
@@ -410,9 +390,9 @@ wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_r
 extern "C" wbx_status wbx_clip_measure(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out) {
   if (!c) return WBX_ERR_INVALID;
   if (!out) return fail(c, WBX_ERR_INVALID, "clip measure: out is NULL");
-  if (clip >= c->clips.size() || !c->clips[clip].used || !c->clips[clip].base) return fail(c, WBX_ERR_INVALID, "clip measure: unknown clip");
-  const ClipSlot& s = c->clips[clip];
-  const ExportSrc src{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+  const ClipSlot* s = find_clip(c, clip);
+  if (!s) return fail(c, WBX_ERR_INVALID, "clip measure: unknown clip");
+  const ClipSrc src = clip_src(*s);
   const char* msg = "";
   wbx_status st = clipfx_check_range(src, first_frame, n_frames, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
@@ -428,22 +408,15 @@ extern "C" wbx_status wbx_clip_measure(wbx_ctx* c, uint32_t clip, uint64_t first
 extern "C" wbx_status wbx_clip_derive(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, const wbx_clip_edit_desc* d,
                                       wbx_clip_stats* stats_of_result) {
   if (!c) return WBX_ERR_INVALID;
-  if (src_clip >= c->clips.size() || !c->clips[src_clip].used || !c->clips[src_clip].base) return fail(c, WBX_ERR_INVALID, "clip derive: unknown source clip");
-  if (dst_clip == src_clip) return fail(c, WBX_ERR_INVALID, "clip derive: the result may not replace its source");
-  if (dst_clip >= (1u << 24)) return fail(c, WBX_ERR_INVALID, "clip id");
-  const ClipSlot& s = c->clips[src_clip];
-  const ExportSrc src{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
-  const uint32_t rate = s.d.sample_rate;
+  wbx_status st = clipfx_check_ids(c, src_clip, dst_clip, "clip derive: unknown source clip", "clip derive: the result may not replace its source");
+  if (st != WBX_OK) return st;
+  const ClipSrc src = clip_src(c->clips[src_clip]);
+  const uint32_t rate = c->clips[src_clip].d.sample_rate;
   const char* msg = "";
   uint32_t out_channels = 0;
-  wbx_status st = clipfx_check_derive(src, d, &out_channels, &msg);
+  st = clipfx_check_derive(src, d, &out_channels, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  ClipSlot slot;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = clipfx_derive_run(c, src, rate, *d, out_channels, slot, stats_of_result, &why);
-  if (st != WBX_OK) return c->err = why, st;
-  return clip_publish(c, dst_clip, slot);   // (may reallocate the pool's table: `s` is dead from here)
+  return clipfx_into_clip(c, dst_clip, [&](ClipSlot& slot, std::string* why) {
+    return clipfx_derive_run(c, src, rate, *d, out_channels, slot, stats_of_result, why);
+  });
 }

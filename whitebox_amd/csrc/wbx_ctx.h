@@ -163,14 +163,21 @@ struct DevBuf {             // grow-only device array
 
 struct DistState;   // wbx_dist.hip
 
-// wbx_clip_export's staging: a stream of its own and kExportSlots chunks, each a device buffer the kernel writes, a pinned
+// A side stream: what an editing-thread call that reads or creates pool clips beside the renders works on.  A stream of the
+// call's own (no mix or sum stream) and the two events that order it behind what last wrote the pool: the main and the
+// upload stream.  Export and the clip edits each own one; side_prepare / side_order / side_release (wbx_runtime.hip).
+struct SideStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t after_main = nullptr, after_upload = nullptr;
+};
+
+// wbx_clip_export's staging: a side stream and kExportSlots chunks, each a device buffer the kernel writes, a pinned
 // host buffer the copy engine moves it into and a block of statistics — made at first use, the same size for a clip of a
 // thousand frames and one of 2^31 (a chunk is at most 8 bytes per frame: two channels of 32 bits), freed with the context.
 constexpr int kExportSlots = 3;
 constexpr uint32_t kExportChunkDefault = 1u << 20, kExportChunkMax = 1u << 24;
 struct ExportStage {
-  hipStream_t stream = nullptr;
-  hipEvent_t after_main = nullptr, after_upload = nullptr;   // what last wrote the clip: the main and the upload stream
+  SideStream side;
   uint32_t chunk = 0;                     // frames the slots were made for
   void* d_slot[kExportSlots] = {};
   void* h_slot[kExportSlots] = {};        // pinned
@@ -178,19 +185,18 @@ struct ExportStage {
   uint32_t* h_stats = nullptr;            // pinned: [kExportSlots][8]
   hipEvent_t done[kExportSlots] = {};
 };
-// a clip's storage as an export needs it (layer 2 copies it out of the pool under the editor lock)
-struct ExportSrc {
+// a clip's storage as a side call needs it (layer 2 copies it out of the pool under the editor lock)
+struct ClipSrc {
   const void* base = nullptr;
   size_t stride = 0;
   uint32_t channels = 0, format = 0;
   uint64_t frames = 0;
 };
 
-// wbx_clip_measure / wbx_clip_derive: a stream of their own, the events that order it and the statistics block (device,
-// and pinned: [0] the image a launch starts from, [1] what it left) — made at first use, freed with the context
+// wbx_clip_measure / wbx_clip_derive: a side stream and the statistics block (device, and pinned: [0] the image a launch
+// starts from, [1] what it left) — made at first use, freed with the context
 struct ClipFxStage {
-  hipStream_t stream = nullptr;
-  hipEvent_t after_main = nullptr, after_upload = nullptr;
+  SideStream side;
   ClipFxStats* d_stats = nullptr;
   ClipFxStats* h_stats = nullptr;
 };
@@ -370,7 +376,7 @@ struct wbx_ctx {
   // wbx_clip_measure / wbx_clip_derive and layer 2's forms: one at a time (fx_mu), on a stream that is no mix or sum stream
   ClipFxStage fx;
   std::mutex fx_mu;
-  std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.stream)
+  std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.side.stream)
 
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -386,15 +392,20 @@ namespace wbx {
 
 inline wbx_ctx::PlanBuf& PB(wbx_ctx* c) { return c->pb[c->cur]; }
 
-inline wbx_status fail(wbx_ctx* c, wbx_status s, const char* what, hipError_t e = hipSuccess) {
-  if (c) {
-    c->err = what;
+// a failure's text, `what[: the HIP error]`, into *why (the side calls' messages) ...
+inline wbx_status stage_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
+  if (why) {
+    *why = what;
     if (e != hipSuccess) {
-      c->err += ": ";
-      c->err += hipGetErrorString(e);
+      *why += ": ";
+      *why += hipGetErrorString(e);
     }
   }
-  return s;
+  return st;
+}
+// ... or into the context's error string
+inline wbx_status fail(wbx_ctx* c, wbx_status s, const char* what, hipError_t e = hipSuccess) {
+  return stage_fail(c ? &c->err : nullptr, s, what, e);
 }
 
 #define WBX_HIP(ctx, call)                                                       \
@@ -432,31 +443,59 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
                       const ClipFill& f, hipStream_t on);
 wbx_status clip_publish(wbx_ctx* c, uint32_t clip, ClipSlot& s);
 void clip_release(wbx_ctx* c, ClipSlot& s);
-// exporting: argument checks (no device call), "order the export stream after what last wrote the pool" (enqueues only;
-// layer 2 calls it under the editor lock) and the chunk loop (no lock held; `why` gets the message of a failure)
-wbx_status export_check(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+// side streams: side_prepare makes the stream and its events (at once if they exist; after a failure the struct is zeroed
+// again), side_order puts the stream behind everything enqueued so far on the streams that write the pool's clips (enqueues
+// only; layer 2 calls it under the editor lock), side_release waits for the stream and destroys all three
+hipError_t side_prepare(wbx_ctx* c, SideStream& s);
+hipError_t side_order(wbx_ctx* c, SideStream& s);
+void side_release(SideStream& s);
+// a pool clip as the side calls see it: the slot of a clip that exists (or null), its storage, a channel's row (ch % channels)
+inline const ClipSlot* find_clip(const wbx_ctx* c, uint32_t id) {
+  return id < c->clips.size() && c->clips[id].used && c->clips[id].base ? &c->clips[id] : nullptr;
+}
+inline ClipSrc clip_src(const ClipSlot& s) { return ClipSrc{s.base, s.stride, s.d.channels, s.d.format, s.d.count}; }
+inline const float* clip_row(const ClipSrc& src, uint32_t ch) {
+  return reinterpret_cast<const float*>((const char*)src.base + src.stride * (ch % src.channels));
+}
+// exporting: argument checks (no device call), the side stream with its slots, its ordering and the chunk loop (no lock
+// held; `why` gets the message of a failure)
+wbx_status export_check(const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
                         const void* dst, const char** why);
-wbx_status export_prepare(wbx_ctx* c, std::string* why);   // stream, events and slots for the chunk size in force
-wbx_status export_order(wbx_ctx* c, std::string* why);
-wbx_status export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+wbx_status export_prepare(wbx_ctx* c, std::string* why);   // side stream, events and slots for the chunk size in force
+wbx_status export_order(wbx_ctx* c, std::string* why);     // side_order of exp.side
+wbx_status export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
                       void* dst, wbx_export_stats* stats, std::string* why);
 void export_release(wbx_ctx* c);
-// editing clips (wbx_clipfx.hip), cut like the export: argument checks (no device call), the stream, its ordering behind the
-// pool's writers (enqueues only; layer 2 calls it under the editor lock) and the runs (no lock held; they wait for the device)
-wbx_status clipfx_check_range(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, const char** why);
-wbx_status clipfx_check_derive(const ExportSrc& src, const wbx_clip_edit_desc* d, uint32_t* out_channels, const char** why);
+// editing clips (wbx_clipfx.hip), cut like the export: argument checks (no device call), the side stream with its statistics
+// block, its ordering and the runs (no lock held; they wait for the device)
+wbx_status clipfx_check_range(const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, const char** why);
+wbx_status clipfx_check_derive(const ClipSrc& src, const wbx_clip_edit_desc* d, uint32_t* out_channels, const char** why);
 wbx_status clipfx_prepare(wbx_ctx* c, std::string* why);
-wbx_status clipfx_order(wbx_ctx* c, std::string* why);
-wbx_status clipfx_measure_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out,
+wbx_status clipfx_order(wbx_ctx* c, std::string* why);     // side_order of fx.side
+wbx_status clipfx_measure_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out,
                               std::string* why);
-wbx_status clipfx_derive_run(wbx_ctx* c, const ExportSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
+wbx_status clipfx_derive_run(wbx_ctx* c, const ClipSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
                              uint32_t out_channels, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
 void clipfx_release(wbx_ctx* c);
+// layer 1's calls that make clip dst_clip out of clip src_clip on the edit stream (wbx_clip_derive, wbx_clip_resample): the
+// test of the two ids with the caller's messages, and "prepare, order, run(slot, why), publish" under fx_mu
+wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, const char* unknown_src, const char* same);
+template <class Run>
+wbx_status clipfx_into_clip(wbx_ctx* c, uint32_t dst_clip, Run run) {
+  std::lock_guard<std::mutex> g(c->fx_mu);
+  std::string why;
+  ClipSlot slot;
+  wbx_status st = clipfx_prepare(c, &why);
+  if (st == WBX_OK) st = clipfx_order(c, &why);
+  if (st == WBX_OK) st = run(slot, &why);
+  if (st != WBX_OK) return c->err = why, st;
+  return clip_publish(c, dst_clip, slot);   // (may reallocate the pool's table: references into it are dead from here)
+}
 // converting a clip's sample rate (wbx_resample.hip), cut the same way; it runs under fx_mu on the edit stream, behind
 // clipfx_prepare / clipfx_order, and measures its result through clipfx_measure_run
-wbx_status resample_check(const ExportSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,
+wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,
                           int quality, ResamplePlan* plan, uint64_t* n_out, const char** why);
-wbx_status resample_run(wbx_ctx* c, const ExportSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
+wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
 void resample_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);

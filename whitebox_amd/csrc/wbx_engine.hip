@@ -588,127 +588,110 @@ extern "C" wbx_status wbx_engine_delete_sample(wbx_engine* e, uint32_t sample) {
   return WBX_OK;
 }
 
-// An engine sample as interleaved device-format audio (wbx_clip_export; wbx.h).  Editing thread; the audio thread may be in
+// Side calls on engine samples: wbx_engine_export_sample (wbx_clip_export; wbx.h), and measuring and editing them
+// (wbx_clip_measure / wbx_clip_derive; wbx.h "Editing clips").  Editing thread; the audio thread may be in
 // wbx_engine_process* all the while.  The editor lock covers validating the sample, copying its storage description out of
-// the pool (the pool's table may be reallocated by a later add_sample), pinning it against wbx_engine_delete_sample and
-// ordering the export stream behind what is enqueued — stream calls only; the staging slots are made before, the chunk
-// loop with its device waits and host copies runs after, both without the lock (the rule of wbx_engine_levels).
-extern "C" wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
-                                               int out_format, uint32_t flags, void* dst, wbx_export_stats* stats) {
-  if (!e) return WBX_ERR_INVALID;
-  wbx_ctx* c = e->ctx;
-  std::lock_guard<std::mutex> one(c->export_mu);
-  (void)hipSetDevice(c->cfg.device);
-  std::string why;
-  ExportSrc src;
-  {
-    LockGuard g(e->hs.editor_lock);
-    if (!e->hs.valid_sample(sample) || sample >= c->clips.size() || !c->clips[sample].base) return efail(e, WBX_ERR_INVALID, "export: unknown sample");
-    const ClipSlot& s = c->clips[sample];
-    src = ExportSrc{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
-    const char* msg = "";
-    const wbx_status st = export_check(src, first_frame, n_frames, out_format, flags, dst, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    e->export_pin = sample;
-  }
-  wbx_status st = export_prepare(c, &why);
-  if (st == WBX_OK) {
-    LockGuard g(e->hs.editor_lock);
-    st = export_order(c, &why);
-  }
-  if (st == WBX_OK) st = export_run(c, src, first_frame, n_frames, out_format, flags, dst, stats, &why);
-  {
-    LockGuard g(e->hs.editor_lock);
-    e->export_pin = wbx_engine::kNoExport;
-  }
-  if (st != WBX_OK) tls_err = why;
-  return st;
-}
-
-// Measuring and editing engine samples (wbx_clip_measure / wbx_clip_derive; wbx.h "Editing clips").  Editing thread, under
-// wbx_engine_export_sample's rules: the editor lock covers validating the sample, copying its storage description out of the
-// pool, the pin, ordering the edit stream behind what is enqueued (stream calls only) and registering the new sample; the
-// stream's creation, the new clip's allocation, the kernel and the wait for it run without the lock.  Nothing here touches
-// the transport or counts as an edit (no note_edit_locked): a render sees the new sample only once a clip names it.
+// the pool (the pool's table may be reallocated by a later add_sample), pinning it against wbx_engine_delete_sample,
+// ordering the call's side stream behind what is enqueued (stream calls only), dropping the pin and registering a new
+// sample; the stream's and the staging slots' creation, a new clip's allocation, the kernels, the device waits and the
+// host copies run without the lock (the rule of wbx_engine_levels).  Nothing here touches the transport or counts as an
+// edit (no note_edit_locked): a render sees a new sample only once a clip names it.
 namespace {
 
-struct EditPin {   // fx_mu held for its life; begin() validates and pins, the destructor drops the pin
+// (editor lock held) `slot` becomes the pool's next sample, an F32 one, known to the session's sample table
+wbx_status register_sample_locked(wbx_engine* e, ClipSlot& slot, uint32_t channels, uint32_t rate, uint64_t frames, uint32_t* id) {
+  wbx_ctx* c = e->ctx;
+  const uint32_t next = (uint32_t)c->clips.size();
+  const wbx_status st = clip_publish(c, next, slot);
+  if (st != WBX_OK) return st;
+  if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize(c->clips.size());
+  e->hs.samples[next] = SampleMeta{WBX_FMT_F32, channels, rate, frames, true};
+  *id = next;
+  return WBX_OK;
+}
+
+// `mu` (export_mu or fx_mu) held for its life; begin_locked() validates, pin_locked() writes the pin word (export_pin or
+// edit_pin), the destructor clears it
+struct SamplePin {
+  using Step = wbx_status(wbx_ctx*, std::string*);
   wbx_engine* e;
   std::lock_guard<std::mutex> one;
+  uint32_t wbx_engine::* word;
   bool pinned = false;
-  ExportSrc src;
+  ClipSrc src;
   uint32_t rate = 0;
-  explicit EditPin(wbx_engine* e_) : e(e_), one(e_->ctx->fx_mu) { (void)hipSetDevice(e->ctx->cfg.device); }
-  ~EditPin() {
+  SamplePin(wbx_engine* e_, std::mutex& mu, uint32_t wbx_engine::* word_) : e(e_), one(mu), word(word_) {
+    (void)hipSetDevice(e->ctx->cfg.device);
+  }
+  ~SamplePin() {
     if (!pinned) return;
     LockGuard g(e->hs.editor_lock);
-    e->edit_pin = wbx_engine::kNoExport;
+    e->*word = wbx_engine::kNoExport;
   }
-  // (editor lock held) the sample's storage, pinned against wbx_engine_delete_sample
+  // (editor lock held) the sample's storage
   wbx_status begin_locked(uint32_t sample, const char* what) {
-    wbx_ctx* c = e->ctx;
-    if (!e->hs.valid_sample(sample) || sample >= c->clips.size() || !c->clips[sample].base) return efail(e, WBX_ERR_INVALID, what);
-    const ClipSlot& s = c->clips[sample];
-    src = ExportSrc{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
-    rate = s.d.sample_rate;
+    const ClipSlot* s = e->hs.valid_sample(sample) ? find_clip(e->ctx, sample) : nullptr;
+    if (!s) return efail(e, WBX_ERR_INVALID, what);
+    src = clip_src(*s);
+    rate = s->d.sample_rate;
     return WBX_OK;
   }
   void pin_locked(uint32_t sample) {
-    e->edit_pin = sample;
+    e->*word = sample;
     pinned = true;
   }
-  wbx_status order(std::string* why) {   // the edit stream: made without the lock, ordered under it
-    wbx_status st = clipfx_prepare(e->ctx, why);
+  wbx_status order(Step* prepare, Step* order_side, std::string* why) {   // the side stream: made without the lock, ordered under it
+    const wbx_status st = prepare(e->ctx, why);
     if (st != WBX_OK) return st;
     LockGuard g(e->hs.editor_lock);
-    return clipfx_order(e->ctx, why);
+    return order_side(e->ctx, why);
+  }
+  wbx_status publish(ClipSlot& slot, uint32_t channels, uint32_t new_rate, uint64_t frames, uint32_t* new_sample, std::string* why) {
+    LockGuard g(e->hs.editor_lock);
+    const wbx_status st = register_sample_locked(e, slot, channels, new_rate, frames, new_sample);
+    if (st != WBX_OK) *why = e->ctx->err;
+    return st;
   }
   wbx_status measure(uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out, std::string* why) {
-    wbx_status st = order(why);
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
     if (st == WBX_OK) st = clipfx_measure_run(e->ctx, src, first_frame, n_frames, out, why);
     return st;
   }
   wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
-    wbx_ctx* c = e->ctx;
-    wbx_status st = order(why);
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
     ClipSlot slot;
-    if (st == WBX_OK) st = clipfx_derive_run(c, src, rate, d, out_channels, slot, nullptr, why);
-    if (st != WBX_OK) return st;
-    LockGuard g(e->hs.editor_lock);   // a bounce's publish: the next free id of the pool, the session's sample table
-    const uint32_t id = (uint32_t)c->clips.size();
-    st = clip_publish(c, id, slot);
-    if (st != WBX_OK) return *why = c->err, st;
-    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize(c->clips.size());
-    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, out_channels, rate, d.n_frames, true};
-    *new_sample = id;
-    return WBX_OK;
-  }
-  // wbx_clip_resample's run (wbx_resample.hip), published the same way: a sample of n_out frames at dst_rate
-  wbx_status resample(const ResamplePlan& plan, int quality, uint64_t first_frame, uint64_t n_frames, uint64_t n_out, uint32_t dst_rate,
-                      uint32_t* new_sample, std::string* why) {
-    wbx_ctx* c = e->ctx;
-    wbx_status st = order(why);
-    ClipSlot slot;
-    if (st == WBX_OK) st = resample_run(c, src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, why);
-    if (st != WBX_OK) return st;
-    LockGuard g(e->hs.editor_lock);
-    const uint32_t id = (uint32_t)c->clips.size();
-    st = clip_publish(c, id, slot);
-    if (st != WBX_OK) return *why = c->err, st;
-    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize(c->clips.size());
-    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, src.channels, dst_rate, n_out, true};
-    *new_sample = id;
-    return WBX_OK;
+    if (st == WBX_OK) st = clipfx_derive_run(e->ctx, src, rate, d, out_channels, slot, nullptr, why);
+    return st == WBX_OK ? publish(slot, out_channels, rate, d.n_frames, new_sample, why) : st;
   }
 };
 
 }  // namespace
 
+extern "C" wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                               int out_format, uint32_t flags, void* dst, wbx_export_stats* stats) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->export_mu, &wbx_engine::export_pin);
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "export: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = export_check(p.src, first_frame, n_frames, out_format, flags, dst, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  wbx_status st = p.order(export_prepare, export_order, &why);
+  if (st == WBX_OK) st = export_run(e->ctx, p.src, first_frame, n_frames, out_format, flags, dst, stats, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
 extern "C" wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                 wbx_clip_stats* stats) {
   if (!e) return WBX_ERR_INVALID;
   if (!stats) return efail(e, WBX_ERR_INVALID, "measure_sample: stats is NULL");
-  EditPin p(e);
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
   {
     LockGuard g(e->hs.editor_lock);
     wbx_status st = p.begin_locked(sample, "measure_sample: unknown sample");
@@ -727,7 +710,7 @@ extern "C" wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, 
 extern "C" wbx_status wbx_engine_derive_sample(wbx_engine* e, uint32_t sample, const wbx_clip_edit_desc* desc, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "derive_sample: new_sample is NULL");
-  EditPin p(e);
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
   uint32_t out_channels = 0;
   {
     LockGuard g(e->hs.editor_lock);
@@ -749,7 +732,7 @@ extern "C" wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample
                                                   float target_peak, uint32_t* new_sample, float* gain_used) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "normalize_sample: new_sample is NULL");
-  EditPin p(e);
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
   wbx_clip_edit_desc d{};
   d.first_frame = first_frame;
   d.n_frames = n_frames;
@@ -785,7 +768,7 @@ extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample,
                                                  uint32_t dst_rate, int quality, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "resample_sample: new_sample is NULL");
-  EditPin p(e);
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
   ResamplePlan plan;
   uint64_t n_out = 0;
   {
@@ -799,7 +782,10 @@ extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample,
     p.pin_locked(sample);
   }
   std::string why;
-  const wbx_status st = p.resample(plan, quality, first_frame, n_frames, n_out, dst_rate, new_sample, &why);
+  ClipSlot slot;
+  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = resample_run(e->ctx, p.src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, &why);
+  if (st == WBX_OK) st = p.publish(slot, p.src.channels, dst_rate, n_out, new_sample, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }
@@ -1350,13 +1336,9 @@ struct BounceDev {
     (void)sync_main(e->ctx);   // (nothing may still write the clip)
     clip_release(e->ctx, slots[i]);
   }
-  uint32_t publish(uint32_t i) {   // stop_record's path: the next free id of the pool, the session's sample table
-    wbx_ctx* c = e->ctx;
-    const uint32_t id = (uint32_t)c->clips.size();
-    const uint32_t channels = slots[i].d.channels;
-    (void)clip_publish(c, id, slots[i]);   // (a fresh id below 2^24 — wbx_engine_bounce checked the room for all of them — cannot fail)
-    if (e->hs.samples.size() < c->clips.size()) e->hs.samples.resize((size_t)id + (n_src - i));   // once per bounce
-    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, channels, c->cfg.sample_rate, n_frames, true};
+  uint32_t publish(uint32_t i) {
+    uint32_t id = 0;   // (a fresh id below 2^24 — wbx_engine_bounce checked the room for all of them — cannot fail)
+    (void)register_sample_locked(e, slots[i], slots[i].d.channels, e->ctx->cfg.sample_rate, n_frames, &id);
     return id;
   }
   wbx_status pass(uint32_t first_block, uint32_t k) {
@@ -1655,14 +1637,12 @@ wbx_status stop_record_impl(wbx_engine* e) {
       continue;
     }
     // Sample from the take -> SampleAsset -> add_audio_clip(track, record_min_time, record_max_time, 0.0, {speed 1, gain 1})
-    const uint32_t id = (uint32_t)c->clips.size();
-    const wbx_status ps = clip_publish(c, id, built[i]);
+    uint32_t id = 0;
+    const wbx_status ps = register_sample_locked(e, built[i], fin[i].channels, c->cfg.sample_rate, fin[i].frames, &id);
     if (ps != WBX_OK) {
       st = cfail(e, ps);
       continue;
     }
-    e->hs.samples.resize(c->clips.size());
-    e->hs.samples[id] = SampleMeta{WBX_FMT_F32, fin[i].channels, c->cfg.sample_rate, fin[i].frames, true};
     e->hs.add_audio_clip_locked((uint32_t)t, fin[i].min_time, fin[i].max_time, 0.0, id, 1.0, 1.0f);
     overflow |= (fin[i].status & REC_OVERFLOW) != 0u;
   }

@@ -113,18 +113,7 @@ void launch_resample(ResampleArgs a, hipStream_t s) {
 
 // ---- layer 1: checks (no device call), the table, the run ------------------------------------------------------------------
 
-static wbx_status rs_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
-  if (why) {
-    *why = what;
-    if (e != hipSuccess) {
-      *why += ": ";
-      *why += hipGetErrorString(e);
-    }
-  }
-  return st;
-}
-
-wbx_status resample_check(const ExportSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,
+wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,
                           int quality, ResamplePlan* plan, uint64_t* n_out, const char** why) {
   if (n_frames == 0) return *why = "resample: no frames", WBX_ERR_INVALID;
   if (first_frame > src.frames || n_frames > src.frames - first_frame) return *why = "resample: the range ends past the clip", WBX_ERR_INVALID;
@@ -164,7 +153,7 @@ static hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int q
   }
   hipError_t e = hipMalloc((void**)&t.d, n * sizeof(float));
   if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(t.d, t.host.data(), n * sizeof(float), hipMemcpyHostToDevice, c->fx.stream);
+  e = hipMemcpyAsync(t.d, t.host.data(), n * sizeof(float), hipMemcpyHostToDevice, c->fx.side.stream);
   if (e != hipSuccess) {
     (void)hipFree(t.d);
     return e;
@@ -176,28 +165,28 @@ static hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int q
 }
 
 // `slot` becomes the new clip (built on the edit stream; complete when this returns WBX_OK, released otherwise)
-wbx_status resample_run(wbx_ctx* c, const ExportSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
+wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
   ClipFill fill{};
   fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, dst_rate, n_out, fill, c->fx.stream);
+  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, dst_rate, n_out, fill, c->fx.side.stream);
   if (st != WBX_OK) return *why = c->err, st;
   ResampleArgs a{};
   bool fresh = false;
   hipError_t e = resample_table_device(c, p, quality, &a.table, &fresh);
   if (e == hipSuccess) {
     for (uint32_t ch = 0; ch < 2; ch++) {
-      a.src[ch] = reinterpret_cast<const float*>((const char*)src.base + src.stride * (ch % src.channels)) + first_frame;
+      a.src[ch] = clip_row(src, ch) + first_frame;
       a.dst[ch] = (float*)slot.d.ch[ch % src.channels];
     }
     a.n_in = (uint32_t)n_frames;
     a.n_out = (uint32_t)n_out;
     a.L = p.L, a.M = p.M, a.H = p.H, a.T = p.T;
     a.channels = src.channels;
-    launch_resample(a, c->fx.stream);
+    launch_resample(a, c->fx.side.stream);
     e = hipGetLastError();
   }
-  const hipError_t w = hipStreamSynchronize(c->fx.stream);     // (also after a failure: nothing may still write the new clip)
+  const hipError_t w = hipStreamSynchronize(c->fx.side.stream);     // (also after a failure: nothing may still write the new clip)
   if (e == hipSuccess) e = w;
   if (fresh) std::vector<float>().swap(c->rs_tables.back().host);   // uploaded (or never will be)
   if (e != hipSuccess) {
@@ -206,11 +195,10 @@ wbx_status resample_run(wbx_ctx* c, const ExportSrc& src, const ResamplePlan& p,
       c->rs_tables.pop_back();
     }
     clip_release(c, slot);
-    return rs_fail(why, WBX_ERR_DEVICE, "clip resample", e);
+    return stage_fail(why, WBX_ERR_DEVICE, "clip resample", e);
   }
   if (stats) {                                                 // the measure pass over the result, on the same stream
-    const ExportSrc res{slot.base, slot.stride, src.channels, (uint32_t)WBX_FMT_F32, n_out};
-    st = clipfx_measure_run(c, res, 0, n_out, stats, why);
+    st = clipfx_measure_run(c, clip_src(slot), 0, n_out, stats, why);
     if (st != WBX_OK) clip_release(c, slot);
   }
   return st;
@@ -248,22 +236,15 @@ extern "C" wbx_status wbx_resample_table(uint32_t src_rate, uint32_t dst_rate, i
 extern "C" wbx_status wbx_clip_resample(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                                         uint32_t dst_rate, int quality, wbx_clip_stats* stats_of_result) {
   if (!c) return WBX_ERR_INVALID;
-  if (src_clip >= c->clips.size() || !c->clips[src_clip].used || !c->clips[src_clip].base) return fail(c, WBX_ERR_INVALID, "clip resample: unknown source clip");
-  if (dst_clip == src_clip) return fail(c, WBX_ERR_INVALID, "clip resample: the result may not replace its source");
-  if (dst_clip >= (1u << 24)) return fail(c, WBX_ERR_INVALID, "clip id");
-  const ClipSlot& s = c->clips[src_clip];
-  const ExportSrc src{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+  wbx_status st = clipfx_check_ids(c, src_clip, dst_clip, "clip resample: unknown source clip", "clip resample: the result may not replace its source");
+  if (st != WBX_OK) return st;
+  const ClipSrc src = clip_src(c->clips[src_clip]);
   const char* msg = "";
   ResamplePlan plan;
   uint64_t n_out = 0;
-  wbx_status st = resample_check(src, s.d.sample_rate, first_frame, n_frames, dst_rate, quality, &plan, &n_out, &msg);
+  st = resample_check(src, c->clips[src_clip].d.sample_rate, first_frame, n_frames, dst_rate, quality, &plan, &n_out, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  ClipSlot slot;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = resample_run(c, src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, stats_of_result, &why);
-  if (st != WBX_OK) return c->err = why, st;
-  return clip_publish(c, dst_clip, slot);   // (may reallocate the pool's table: `s` is dead from here)
+  return clipfx_into_clip(c, dst_clip, [&](ClipSlot& slot, std::string* why) {
+    return resample_run(c, src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, stats_of_result, why);
+  });
 }

@@ -1224,7 +1224,7 @@ extern "C" wbx_status wbx_set_export_chunk(wbx_ctx* c, uint32_t frames) {
   return WBX_OK;
 }
 
-wbx_status wbx::export_check(const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
+wbx_status wbx::export_check(const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format, uint32_t flags,
                              const void* dst, const char** why) {
   *why = "";
   if (!dst) return *why = "export: dst is NULL", WBX_ERR_INVALID;
@@ -1239,7 +1239,7 @@ wbx_status wbx::export_check(const ExportSrc& src, uint64_t first_frame, uint64_
 
 static void export_free_slots(wbx_ctx* c) {
   ExportStage& x = c->exp;
-  if (x.stream) (void)hipStreamSynchronize(x.stream);
+  if (x.side.stream) (void)hipStreamSynchronize(x.side.stream);
   for (int i = 0; i < kExportSlots; i++) {
     if (x.d_slot[i]) (void)hipFree(x.d_slot[i]);
     if (x.h_slot[i]) (void)hipHostFree(x.h_slot[i]);
@@ -1257,36 +1257,53 @@ void wbx::export_release(wbx_ctx* c) {
   export_free_slots(c);
   for (auto& ev : x.done)
     if (ev) (void)hipEventDestroy(ev);
-  if (x.after_main) (void)hipEventDestroy(x.after_main);
-  if (x.after_upload) (void)hipEventDestroy(x.after_upload);
-  if (x.stream) (void)hipStreamDestroy(x.stream);
+  side_release(x.side);
   x = ExportStage{};
 }
 
-static wbx_status export_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
-  if (why) {
-    *why = what;
-    if (e != hipSuccess) {
-      *why += ": ";
-      *why += hipGetErrorString(e);
-    }
+// ---- side streams (wbx_ctx.h SideStream) ------------------------------------------------------------------------------
+hipError_t wbx::side_prepare(wbx_ctx* c, SideStream& s) {
+  if (s.stream) return hipSuccess;
+  hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_main, c->dev_event_flags);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_upload, c->dev_event_flags);
+  if (e != hipSuccess) side_release(s);
+  return e;
+}
+
+// the stream behind everything enqueued so far on the streams that write the pool's clips: the main stream (with the sum
+// and the alternate mix joined to it, as sync_main does) and the upload stream.  Enqueues only: the host does not wait.
+hipError_t wbx::side_order(wbx_ctx* c, SideStream& s) {
+  hipError_t e = join_sum(c);
+  if (e == hipSuccess) e = join_alt(c);
+  if (e == hipSuccess) e = hipEventRecord(s.after_main, c->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, s.after_main, 0);
+  if (e == hipSuccess && c->upload_stream) {
+    e = hipEventRecord(s.after_upload, c->upload_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s.stream, s.after_upload, 0);
   }
-  return st;
+  return e;
+}
+
+void wbx::side_release(SideStream& s) {
+  if (s.stream) {
+    (void)hipStreamSynchronize(s.stream);
+    (void)hipStreamDestroy(s.stream);
+  }
+  if (s.after_main) (void)hipEventDestroy(s.after_main);
+  if (s.after_upload) (void)hipEventDestroy(s.after_upload);
+  s = SideStream{};
 }
 
 wbx_status wbx::export_prepare(wbx_ctx* c, std::string* why) {
   ExportStage& x = c->exp;
   (void)hipSetDevice(c->cfg.device);
-  hipError_t e = hipSuccess;
-  if (!x.stream) {
-    e = hipStreamCreateWithFlags(&x.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_main, c->dev_event_flags);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&x.after_upload, c->dev_event_flags);
-    for (int i = 0; i < kExportSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming);
-    if (e != hipSuccess) {
-      export_release(c);
-      return export_fail(why, WBX_ERR_DEVICE, "export: stream and events", e);
-    }
+  hipError_t e = side_prepare(c, x.side);
+  for (int i = 0; i < kExportSlots && e == hipSuccess; i++)
+    if (!x.done[i]) e = hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming);
+  if (e != hipSuccess) {
+    export_release(c);
+    return stage_fail(why, WBX_ERR_DEVICE, "export: stream and events", e);
   }
   uint32_t want = c->export_chunk.load(std::memory_order_relaxed);
   if (!want) want = kExportChunkDefault;
@@ -1302,26 +1319,16 @@ wbx_status wbx::export_prepare(wbx_ctx* c, std::string* why) {
     if (e != hipSuccess) {
       (void)hipGetLastError();
       export_free_slots(c);
-      return export_fail(why, WBX_ERR_OOM, "export: staging slots", e);
+      return stage_fail(why, WBX_ERR_OOM, "export: staging slots", e);
     }
     x.chunk = want;
   }
   return WBX_OK;
 }
 
-// the export stream behind everything enqueued so far on the streams that write the pool's clips: the main stream (with the
-// sum and the alternate mix joined to it, as sync_main does) and the upload stream.  Enqueues only: the host does not wait.
 wbx_status wbx::export_order(wbx_ctx* c, std::string* why) {
-  ExportStage& x = c->exp;
-  hipError_t e = join_sum(c);
-  if (e == hipSuccess) e = join_alt(c);
-  if (e == hipSuccess) e = hipEventRecord(x.after_main, c->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_main, 0);
-  if (e == hipSuccess && c->upload_stream) {
-    e = hipEventRecord(x.after_upload, c->upload_stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(x.stream, x.after_upload, 0);
-  }
-  return e == hipSuccess ? WBX_OK : export_fail(why, WBX_ERR_DEVICE, "export: ordering after the pool's writers", e);
+  const hipError_t e = side_order(c, c->exp.side);
+  return e == hipSuccess ? WBX_OK : stage_fail(why, WBX_ERR_DEVICE, "export: ordering after the pool's writers", e);
 }
 
 static bool export_dst_is_pinned(const void* dst, size_t bytes) {
@@ -1336,9 +1343,10 @@ static bool export_dst_is_pinned(const void* dst, size_t bytes) {
   return true;
 }
 
-wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format,
+wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, int out_format,
                            uint32_t flags, void* dst, wbx_export_stats* stats, std::string* why) {
   ExportStage& x = c->exp;
+  const hipStream_t on = x.side.stream;
   const uint32_t C = src.channels;
   const size_t fb = out_format_bytes(out_format) * C;          // bytes of a frame in dst
   const uint64_t chunk = x.chunk, n_chunks = (n_frames + chunk - 1) / chunk;
@@ -1349,11 +1357,10 @@ wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_fram
     const int b = (int)(k % kExportSlots);
     const uint64_t at = k * chunk;
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n_frames - at);
-    hipError_t e = hipMemsetAsync(x.d_stats[b], 0, 8 * sizeof(uint32_t), x.stream);
+    hipError_t e = hipMemsetAsync(x.d_stats[b], 0, 8 * sizeof(uint32_t), on);
     if (e != hipSuccess) return e;
     ExportArgs a{};
-    for (uint32_t ch = 0; ch < C; ch++)
-      a.src[ch] = reinterpret_cast<const float*>((const char*)src.base + src.stride * ch) + first_frame + at;
+    for (uint32_t ch = 0; ch < C; ch++) a.src[ch] = clip_row(src, ch) + first_frame + at;
     if (C == 1) a.src[1] = a.src[0];
     a.dst = direct ? x.h_slot[b] : x.d_slot[b];
     a.stats = x.d_stats[b];
@@ -1361,13 +1368,13 @@ wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_fram
     a.channels = C;
     a.format = (uint32_t)out_format;
     a.flags = flags;
-    launch_export(a, x.stream);
+    launch_export(a, on);
     e = hipGetLastError();
     if (e == hipSuccess && !direct)
       e = hipMemcpyAsync(to_dst ? (void*)((char*)dst + (size_t)at * fb) : x.h_slot[b], x.d_slot[b], (size_t)m * fb,
-                         hipMemcpyDeviceToHost, x.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats + 8 * b, x.d_stats[b], 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, x.stream);
-    if (e == hipSuccess) e = hipEventRecord(x.done[b], x.stream);
+                         hipMemcpyDeviceToHost, on);
+    if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats + 8 * b, x.d_stats[b], 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, on);
+    if (e == hipSuccess) e = hipEventRecord(x.done[b], on);
     return e;
   };
   hipError_t e = hipSuccess;
@@ -1391,8 +1398,8 @@ wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_fram
     }
   }
   if (e != hipSuccess) {
-    (void)hipStreamSynchronize(x.stream);   // nothing may still write a slot or dst
-    return export_fail(why, WBX_ERR_DEVICE, "export", e);
+    (void)hipStreamSynchronize(on);   // nothing may still write a slot or dst
+    return stage_fail(why, WBX_ERR_DEVICE, "export", e);
   }
   if (stats) *stats = acc;
   return WBX_OK;
@@ -1401,9 +1408,9 @@ wbx_status wbx::export_run(wbx_ctx* c, const ExportSrc& src, uint64_t first_fram
 extern "C" wbx_status wbx_clip_export(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, int out_format,
                                       uint32_t flags, void* dst, wbx_export_stats* stats) {
   if (!c) return WBX_ERR_INVALID;
-  if (clip >= c->clips.size() || !c->clips[clip].used || !c->clips[clip].base) return fail(c, WBX_ERR_INVALID, "export: unknown clip");
-  const ClipSlot& s = c->clips[clip];
-  const ExportSrc src{s.base, s.stride, s.d.channels, s.d.format, s.d.count};
+  const ClipSlot* s = find_clip(c, clip);
+  if (!s) return fail(c, WBX_ERR_INVALID, "export: unknown clip");
+  const ClipSrc src = clip_src(*s);
   const char* msg = "";
   wbx_status st = export_check(src, first_frame, n_frames, out_format, flags, dst, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
