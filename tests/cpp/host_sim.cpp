@@ -375,6 +375,17 @@ int hsim_render_shape(HostSim* s, uint32_t K, uint32_t group_size, uint32_t n_bu
   return WBX_OK;
 }
 
+// ShapeKnobs::from_env() as the environment stands now (wbx_knobs.h), field by field in the struct's order
+struct HsimKnobs {
+  int32_t ragged_off, cb_any_off, masked_rows_off, chain_off, no_lean16, no_fam3, no_cl2, callback_unfused, force_cut, force_g,
+      packed_x, mix_variant, cb_u, exact_min_blocks;
+};
+void hsim_shape_knobs(HsimKnobs* out) {
+  const ShapeKnobs k = ShapeKnobs::from_env();
+  *out = HsimKnobs{k.ragged_off, k.cb_any_off, k.masked_rows_off, k.chain_off, k.no_lean16, k.no_fam3, k.no_cl2, k.callback_unfused,
+                   k.force_cut, k.force_g, k.packed_x, k.mix_variant, k.cb_u, (int32_t)k.exact_min_blocks};
+}
+
 // plan status bits of the last render (PlanArgs::status) and the number of templates / pre-render rows it used
 int hsim_plan_counters(HostSim* s, uint32_t* out4) {
   std::memcpy(out4, s->counters, sizeof(s->counters));
@@ -495,6 +506,92 @@ int main() {
     if (s->hs.tracks[t]->volume != db_to_linear(last_db[t])) ok = false;
   hsim_destroy(s);
   std::printf(ok ? "host_tsan ok\n" : "host_tsan FAILED\n");
+  return ok ? 0 : 1;
+}
+#endif
+
+#ifdef HOST_SIM_KNOBS_MAIN
+// wbx_knobs.h and wbx_shape.h stand-alone, for a build with -fsanitize=address,undefined: every reader with the environment
+// empty and with each switch set, and choose_shape over a sweep of sessions and render lengths under each setting.
+#include <array>
+#include <cstdlib>
+#include <iterator>
+int main() {
+  static const char* const kShape[][2] = {{"WBX_RAGGED", "0"}, {"WBX_CB_ANY", "0"}, {"WBX_MASKED_ROWS", "0"}, {"WBX_CHAIN", "0"},
+      {"WBX_NO_LEAN16", "1"}, {"WBX_NO_FAM3", "1"}, {"WBX_NO_CL2", "1"}, {"WBX_CALLBACK_FUSED", "0"}, {"WBX_FORCE_CUT", "1"},
+      {"WBX_FORCE_G", "1"}, {"WBX_PACKED_X", "1"}, {"WBX_MIX_VARIANT", "1023"}, {"WBX_CB_U", "8"}, {"WBX_EXACT_MIN_BLOCKS", "0"}};
+  static const char* const kOther[][2] = {{"WBX_OVERLAP", "0"}, {"WBX_SUM_OVERLAP", "0"}, {"WBX_MIX_ALT", "1"}, {"WBX_KERNEL_TIMER", "0"},
+      {"WBX_CB_SPIN_BOUND", "0"}, {"WBX_NO_UNIFORM", "1"}, {"WBX_CB_FENCED", "1"}, {"WBX_FAST_PARTIAL", "0"}, {"WBX_XCD_PROBE_FAIL", "1"},
+      {"WBX_DBG_CLOCK", "1"}, {"WBX_CB_DBG", "1"}, {"HSA_CU_MASK", "0:0-7"}, {"WBX_PLAN_SEG", "-5"}, {"WBX_PLAN_LANES", "16"},
+      {"WBX_DIST_INIT_TIMEOUT_S", "2.5"}};
+  for (auto& kv : kShape) unsetenv(kv[0]);
+  for (auto& kv : kOther) unsetenv(kv[0]);
+  unsetenv("ROC_GLOBAL_CU_MASK");
+  bool ok = true;
+  auto flat = [] {
+    HsimKnobs h;
+    hsim_shape_knobs(&h);
+    return h;
+  };
+  const HsimKnobs d = flat();
+  ok = ok && std::memcmp(&d, std::array<int32_t, 14>{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0, 0, 1024}.data(), sizeof d) == 0;
+  uint64_t shapes = 0;
+  auto sweep = [&] {   // choose_shape over sessions x block shapes x render lengths, the knobs as the environment sets them
+    const ShapeKnobs k = ShapeKnobs::from_env();
+    for (uint32_t bits = 0; bits < 64u; bits++)
+      for (uint32_t F : {128u, 256u, 480u, 512u, 1024u})
+        for (uint32_t C : {1u, 2u})
+          for (uint32_t K : {1u, 8u, 256u, 2048u}) {
+            ShapeFacts f;
+            f.channels = C;
+            f.block_frames = F;
+            f.auto_group = true;
+            f.group_size = K == 1u ? kStage / 2 : kStage;
+            f.session.window_clips = bits & 1u;
+            f.session.stride_clips = bits & 2u;
+            f.session.taps_clips = bits & 2u;
+            f.session.lean16_clips = bits & 4u;
+            f.session.cut_tracks = bits & 8u;
+            f.session.host_sequenced = false;
+            f.integer_clips = bits & 16u;
+            f.non16_clips = !(bits & 4u);
+            f.n_buses = (bits & 32u) ? 2u : 0u;
+            f.longest_list = 4096u;
+            f.n_blocks = K;
+            f.n_tracks = 4096u;
+            f.callback = K == 1u;
+            char name[96];
+            const RenderShape r = choose_shape(k, f);
+            r.mix.name(name, sizeof name);
+            r.cb.name(name, sizeof name);
+            shapes += r.mix.key() != 0u;
+          }
+  };
+  sweep();
+  for (size_t i = 0; i < std::size(kShape); i++) {   // each switch flips its own field and no other
+    setenv(kShape[i][0], kShape[i][1], 1);
+    const HsimKnobs h = flat();
+    for (size_t j = 0; j < 14; j++) {
+      const bool same = reinterpret_cast<const int32_t*>(&h)[j] == reinterpret_cast<const int32_t*>(&d)[j];
+      if (same != (i != j)) ok = false, std::printf("%s: field %zu\n", kShape[i][0], j);
+    }
+    sweep();
+    unsetenv(kShape[i][0]);
+  }
+  const CtxKnobs c0 = CtxKnobs::from_env();
+  const EngineKnobs e0 = EngineKnobs::from_env();
+  ok = ok && c0.overlap && c0.sum_overlap && !c0.mix_alternate && c0.profiling && c0.cb_spin_bound == 40000u && !c0.no_uniform &&
+       !c0.cb_fenced && !c0.fast_partial_off && !c0.xcd_probe_fail && !c0.dbg_clock && !c0.cb_dbg && !c0.cu_mask;
+  ok = ok && e0.plan_seg == -1 && e0.plan_lanes == 0u && dist_init_timeout_s() == 60.0;
+  for (auto& kv : kOther) setenv(kv[0], kv[1], 1);
+  const CtxKnobs c1 = CtxKnobs::from_env();
+  const EngineKnobs e1 = EngineKnobs::from_env();
+  ok = ok && !c1.overlap && !c1.sum_overlap && c1.mix_alternate && !c1.profiling && c1.cb_spin_bound == 0u && c1.no_uniform &&
+       c1.cb_fenced && c1.fast_partial_off && c1.xcd_probe_fail && c1.dbg_clock && c1.cb_dbg && c1.cu_mask;
+  ok = ok && e1.plan_seg == 0 && e1.plan_lanes == 16u && dist_init_timeout_s() == 2.5;   // (WBX_PLAN_SEG: max(0, atoi))
+  setenv("WBX_PLAN_LANES", "3", 1);
+  ok = ok && EngineKnobs::from_env().plan_lanes == 0u;   // (not a power of two up to 64: ignored)
+  std::printf(ok ? "host_knobs ok %llu\n" : "host_knobs FAILED %llu\n", (unsigned long long)shapes);
   return ok ? 0 : 1;
 }
 #endif

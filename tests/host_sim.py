@@ -14,7 +14,7 @@ from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "host_sim.cpp")
-HDRS = [os.path.join(ROOT, "whitebox_amd", "csrc", h) for h in ("wbx_host.h", "wbx_seq.h", "wbx_clip_edit.h", "wbx_dev.h", "wbx_shape.h")]
+HDRS = [os.path.join(ROOT, "whitebox_amd", "csrc", h) for h in ("wbx_host.h", "wbx_seq.h", "wbx_clip_edit.h", "wbx_dev.h", "wbx_shape.h", "wbx_knobs.h")]
 BUILD = os.path.join(ROOT, "tests", "cpp", "_build")
 # no FMA contraction (the reference build has none), and the records are viewed as 16-B quads
 FLAGS = ["-std=c++20", "-ffp-contract=off", "-fno-fast-math", "-fno-strict-aliasing", "-Wall"]
@@ -26,6 +26,13 @@ class RenderShape(C.Structure):
     """hsim_render_shape's result (tests/cpp/host_sim.cpp HsimShape)"""
     _fields_ = [("mix", C.c_char * 64), ("callback", C.c_char * 64)] + [(n, C.c_uint32) for n in (
         "family", "masked_rows", "walks_lists", "chained", "blocks_per_workgroup", "mix_sb", "cb_one_launch", "cb_lane_span")]
+
+
+class ShapeKnobs(C.Structure):
+    """hsim_shape_knobs's result (tests/cpp/host_sim.cpp HsimKnobs): ShapeKnobs of wbx_knobs.h, field by field"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "ragged_off", "cb_any_off", "masked_rows_off", "chain_off", "no_lean16", "no_fam3", "no_cl2", "callback_unfused", "force_cut",
+        "force_g", "packed_x", "mix_variant", "cb_u", "exact_min_blocks")]
 
 
 def _stale(out: str) -> bool:
@@ -55,6 +62,20 @@ def build_tsan() -> str:
     return out
 
 
+def build_knobs_main(out: str) -> str:
+    """host_sim.cpp's stand-alone reader / choose_shape sweep (its own main), under ASan and UBSan"""
+    subprocess.check_call(["g++", *FLAGS, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-DHOST_SIM_KNOBS_MAIN", SRC, "-o", out, "-lpthread"])
+    return out
+
+
+def shape_knobs() -> dict:
+    """ShapeKnobs::from_env() as this process's environment stands now"""
+    k = ShapeKnobs()
+    lib().hsim_shape_knobs(C.byref(k))
+    return {n: getattr(k, n) for n, _ in ShapeKnobs._fields_}
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
@@ -70,6 +91,8 @@ def lib() -> C.CDLL:
         L.hsim_set_segments.argtypes = [C.c_void_p, C.c_uint32]
         L.hsim_segment_stats.restype = None
         L.hsim_segment_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.hsim_shape_knobs.restype = None
+        L.hsim_shape_knobs.argtypes = [C.POINTER(ShapeKnobs)]
         sig = {
             "hsim_set_bpm": [C.c_double], "hsim_set_playhead_position": [C.c_double],
             "hsim_add_track": [C.POINTER(C.c_uint32)],

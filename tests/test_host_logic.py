@@ -118,3 +118,100 @@ def test_perf_measurer_arithmetic_matches_oracle_random(oracle):
         assert O.f64_bits(L.wbx_calc_perf_usage(u)) == O.f64_bits(Lo.wbo_perf_get_usage(u))
         b, r = int(rng.integers(1, 8193)) * 4, int(rng.choice([8000, 22050, 44100, 48000, 96000, 192000]))
         assert O.f64_bits(L.wbx_calc_buffer_period_ms(b, r)) == O.f64_bits(Lo.wbo_buffer_duration_ms(b, r))
+
+
+# ---- the environment switches: one header reads them, DESIGN.md lists them ------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "whitebox_amd", "csrc")
+# the A/B switches whose losing arm was deleted (measurements: EXPERIMENTS.md, MEASUREMENTS.md, profiles/)
+DELETED_SWITCHES = (
+    "WBX_COUNTERS_MEMSET", "WBX_PLAN_LDS_TABLE", "WBX_FUSE_SUM", "WBX_TIMER_PACKETS", "WBX_MIX_MARKER", "WBX_HOST_MASTER_DIRECT",
+    "WBX_PARTIAL_FREE", "WBX_EVENT_SCOPE", "WBX_PLAN_PRIO", "WBX_SUM_PRIO", "WBX_PLAN_BESIDE", "WBX_CB_SPREAD", "WBX_EXPORT_DIRECT",
+    "WBX_CLIP_ARENA", "WBX_SLAB_JITTER", "WBX_NO_LONG_24", "WBX_NO_LONG_CL2")
+
+
+def _text(path):
+    with open(path, encoding="utf-8", errors="replace") as f:
+        return f.read()
+
+
+def _files(top):
+    for d, dirs, names in os.walk(top):
+        dirs[:] = [x for x in dirs if x not in ("__pycache__", "_build", "_obj", "golden")]
+        for n in names:
+            if not n.endswith((".so", ".o", ".pyc", ".npz", ".a")):
+                yield os.path.join(d, n)
+
+
+def test_one_header_reads_the_environment():
+    """getenv occurs under whitebox_amd/csrc/ in wbx_knobs.h and nowhere else"""
+    assert len(DELETED_SWITCHES) == 17
+    users = sorted(os.path.basename(p) for p in _files(CSRC) if "getenv" in _text(p))
+    assert users == ["wbx_knobs.h"]
+
+
+def test_switches_read_are_the_switches_documented():
+    """the WBX_* names wbx_knobs.h reads == the names in the first column of DESIGN.md's table of switches"""
+    import re
+    read = set(re.findall(r'"(WBX_[A-Z0-9_]+)"', _text(os.path.join(CSRC, "wbx_knobs.h"))))
+    design = _text(os.path.join(ROOT, "DESIGN.md"))
+    head = design.index("| switch | what it does | read by | used by a test |")
+    rows = []
+    for line in design[head:].splitlines()[2:]:
+        if not line.startswith("|"):
+            break
+        rows.append(line)
+    listed = [re.fullmatch(r"`(WBX_[A-Z0-9_]+)`", r.split("|")[1].strip()) for r in rows]
+    assert all(listed), "a row of the table does not start with one switch's name"
+    listed = [m.group(1) for m in listed]
+    assert len(listed) == len(set(listed)) == 28
+    assert set(listed) == read
+    assert {r.split("|")[3].strip() for r in rows} == {"`ShapeKnobs`", "`CtxKnobs`", "`EngineKnobs`", "`dist_init_timeout_s`"}
+    assert not set(DELETED_SWITCHES) & read
+
+
+def test_deleted_switches_are_named_nowhere():
+    """none of the 17 deleted names under whitebox_amd/, tools/, tests/, include/ or in bench.py (this file lists them)"""
+    me = os.path.abspath(__file__)
+    paths = [os.path.join(ROOT, "bench.py")]
+    for top in ("whitebox_amd", "tools", "tests", "include"):
+        paths += [p for p in _files(os.path.join(ROOT, top)) if os.path.abspath(p) != me]
+    hits = [(os.path.relpath(p, ROOT), name) for p in paths for t in [_text(p)] for name in DELETED_SWITCHES if name in t]
+    assert not hits, hits
+
+
+SHAPE_SWITCHES = (   # (variable, its active value, the ShapeKnobs field, what the field reads then)
+    ("WBX_RAGGED", "0", "ragged_off", 1), ("WBX_CB_ANY", "0", "cb_any_off", 1), ("WBX_MASKED_ROWS", "0", "masked_rows_off", 1),
+    ("WBX_CHAIN", "0", "chain_off", 1), ("WBX_NO_LEAN16", "1", "no_lean16", 1), ("WBX_NO_FAM3", "1", "no_fam3", 1),
+    ("WBX_NO_CL2", "1", "no_cl2", 1), ("WBX_CALLBACK_FUSED", "0", "callback_unfused", 1), ("WBX_FORCE_CUT", "1", "force_cut", 1),
+    ("WBX_FORCE_G", "1", "force_g", 1), ("WBX_PACKED_X", "0", "packed_x", 0), ("WBX_MIX_VARIANT", "1022", "mix_variant", 1022),
+    ("WBX_CB_U", "4", "cb_u", 4), ("WBX_EXACT_MIN_BLOCKS", "0", "exact_min_blocks", 0))
+SHAPE_DEFAULTS = dict(ragged_off=0, cb_any_off=0, masked_rows_off=0, chain_off=0, no_lean16=0, no_fam3=0, no_cl2=0, callback_unfused=0,
+                      force_cut=0, force_g=0, packed_x=-1, mix_variant=0, cb_u=0, exact_min_blocks=1024)
+
+
+def test_shape_knobs_from_env(monkeypatch):
+    """ShapeKnobs::from_env (wbx_knobs.h, through tests/cpp/host_sim.cpp): the defaults with the environment empty; each kept
+    shape switch at its active value flips exactly its own field"""
+    import host_sim as HS
+    for name, *_ in SHAPE_SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+    assert HS.shape_knobs() == SHAPE_DEFAULTS
+    assert sorted(f for _, _, f, _ in SHAPE_SWITCHES) == sorted(SHAPE_DEFAULTS)
+    for name, value, field, want in SHAPE_SWITCHES:
+        assert SHAPE_DEFAULTS[field] != want
+        monkeypatch.setenv(name, value)
+        assert HS.shape_knobs() == dict(SHAPE_DEFAULTS, **{field: want}), name
+        monkeypatch.delenv(name)
+    assert HS.shape_knobs() == SHAPE_DEFAULTS
+
+
+def test_knobs_and_shape_under_address_and_ub_sanitizers(tmp_path):
+    """wbx_knobs.h and wbx_shape.h stand-alone (host_sim.cpp's second main): every reader with the environment empty and with
+    each switch set, choose_shape over a sweep of sessions under each shape switch — built with ASan and UBSan, run directly"""
+    import subprocess
+    import host_sim as HS
+    exe = HS.build_knobs_main(str(tmp_path / "host_knobs"))
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.startswith("host_knobs ok ")

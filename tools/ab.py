@@ -59,8 +59,6 @@ def presets(other_lib=None):
                            f"--workload c2 --group-size {g} --steps 20 --warmup 3 --ramp-steps 60")
                       for g in (128, 64, 32) for v in (43, 24)]
     P["alt"] = [case(f"{w} alt={a}", f"WBX_MIX_ALT={a}", f"--workload {w} {STD}") for w in ("c3", "c4") for a in (1, 0)]
-    P["arena"] = [case(f"{w} {'per-clip allocations' if a else 'slabs'}", "WBX_CLIP_ARENA=0" if a else "",
-                       f"--workload {w} {STD}") for w in ("c3", "c4") for a in (0, 1)]
     P["blocks"] = [case(f"F={f} {w} L={l} {v or 'default'}", v,
                         f"--workload {w} --block-frames {f} {'--clip-blocks %s' % l if l else ''} {STD}")
                    for f in (256, 1024) for w in ("c3", "i16") for l in (0, 5.3) for v in ("", "WBX_NO_CL2=1")]
@@ -80,11 +78,9 @@ def presets(other_lib=None):
     P["masked"] = [case(f"{w} L={l} {'pre-render' if m else 'hot loop'}", "WBX_MASKED_ROWS=0" if m else "",
                         f"--workload {w} {'--clip-blocks %s' % l if l else ''} {STD}")
                    for w in ("c3", "i16") for l in (5.3, 20, 0) for m in (0, 1)]
-    P["planprio"] = [case(f"L={l} plan_prio={p}", f"WBX_PLAN_PRIO={p}", f"--clip-blocks {l} --steps 10 --warmup 2 --ramp-steps 30")
-                     for l in (5.3, 20) for p in ("hi", "lo")]
     P["ramp"] = [case(f"ramp={r}", "", f"--steps 20 --warmup 3 --ramp-steps {r}") for r in (40, 150, 400)]
     P["timer"] = [case(f"{w} {v or 'default (dispatch packet)'}", v, f"--workload {w} {STD}")
-                  for w in ("c2", "c3") for v in ("", "WBX_TIMER_PACKETS=1", "WBX_KERNEL_TIMER=0")]
+                  for w in ("c2", "c3") for v in ("", "WBX_KERNEL_TIMER=0")]
     P["uniform"] = [case(f"{w} no_uniform={nu}", "WBX_NO_UNIFORM=1" if nu else "", f"--workload {w} {STD}")
                     for w in ("c3", "i16r") for nu in (0, 1)]
     P["formats"] = [case(w, "", f"--workload {w} {STD}") for w in ("i16r", "i24r", "mixr", "mixfmt", "i16", "d96")]

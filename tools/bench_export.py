@@ -13,8 +13,7 @@ for I16, packed I24 and F32.  One process; per format, after a warm-up, `--repea
 then pinned inside each B), the yardstick behind each round; median and spread (min .. max) per figure, and the ratios B / A
 and B / Y of the medians.  The export's kernel time comes from a run of its own under
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_export.py --repeats 1 --no-host-route
-WBX_EXPORT_DIRECT=1 (the kernel stores into the pinned staging slot itself instead of device staging + copy engine) and
---chunk (frames per staging chunk) are the A/B aids of EXPERIMENTS.md."""
+--chunk (frames per staging chunk) is the A/B aid of EXPERIMENTS.md."""
 import argparse
 import ctypes as C
 import json
@@ -117,7 +116,7 @@ def main():
         del pinned
         assert L.wbx_host_free(p) == 0
     out = {"frames": n, "channels": ch, "source_bytes": n * ch * 4, "chunk_frames": a.chunk or (1 << 20),
-           "direct_stores": os.environ.get("WBX_EXPORT_DIRECT", "") == "1", "device": ctx.device_info(), "formats": res}
+           "device": ctx.device_info(), "formats": res}
     ctx.close()
     print(json.dumps(out))
 

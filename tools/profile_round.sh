@@ -48,11 +48,9 @@ for M in reduce ordered chain; do
   timeout 300 python bench.py --force-dist-path --dist-mode $M $B > $O/bench_dist1_$M.json 2>> $O/bench_default.err
 done
 timeout 300 python tools/longrun_probe.py c3 2048 4 > $O/longrun_probe.txt 2>&1
-# round 6: a 256-track session over 200 steps (a step is 0.4 ms: over 20 the one drain at the end is 4 % of the measurement), and
-# what releasing the internal events to the device instead of the system is worth there (alternating)
+# round 6: a 256-track session over 200 steps (a step is 0.4 ms: over 20 the one drain at the end is 4 % of the measurement)
 for rep in 1 2 3; do
   timeout 200 python bench.py --workload c2 --steps 200 $B > $O/bench_c2_steps200_$rep.json 2>> $O/bench_default.err
-  WBX_EVENT_SCOPE=system timeout 200 python bench.py --workload c2 --steps 200 $B > $O/bench_c2_steps200_sysscope_$rep.json 2>> $O/bench_default.err
 done
 cd /tmp
 kt() {   # name, bench args...

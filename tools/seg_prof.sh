@@ -1,7 +1,6 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/segprof; rm -rf $O; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-for V in beside roomy; do
-  E=""; [ $V = roomy ] && E="WBX_PLAN_BESIDE=0"
-  env $E timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$V -o run -- python $R/bench.py --block-frames 128 --clip-blocks 5.3 --steps 10 --warmup 2 --ramp-steps 10 --no-cpu-baseline --no-configs --no-verify --latency-blocks 0 > $O/$V.json 2> $O/$V.err
+for V in beside; do
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$V -o run -- python $R/bench.py --block-frames 128 --clip-blocks 5.3 --steps 10 --warmup 2 --ramp-steps 10 --no-cpu-baseline --no-configs --no-verify --latency-blocks 0 > $O/$V.json 2> $O/$V.err
   echo "== $V"; python - "$O/$V" <<'PY'
 import csv, glob, sys, json
 out=sys.argv[1]

@@ -32,7 +32,7 @@ void launch_sum(const SumArgs& a, uint32_t n_blocks, hipStream_t s);
 // the one-block callback as one launch (wbx_callback.h): sequencer + mix + sum + completion flag -> the instance's name
 const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s, uint32_t* done, uint32_t done_base, uint32_t done_base2,
                             bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st);
-uint32_t callback_spread_limit();      // grids of at most this many workgroups are resident at once (the device's CU count)
+uint32_t callback_spread_limit(uint32_t n_cus, bool cu_mask);   // grids of at most this many workgroups are resident at once
 void launch_clamp(float* buf, size_t n, hipStream_t s);
 void launch_clamp_into(const float* src, float* dst, size_t n, int clamp, hipStream_t s);
 void launch_convert(const float* master, void* dst, uint32_t n_blocks, uint32_t F, uint32_t C, int fmt, hipStream_t s);
@@ -122,6 +122,11 @@ constexpr int kEventRing = 64;
 // track plan kernel is starved for CU slots while a mix runs, so it needs that much slack to stay off the critical path.
 constexpr int kRing = 3;
 constexpr uint32_t kPaceRing = 64;
+// Events whose only waiters are other streams of this device (or a host that waits for "done" and reads nothing the device
+// wrote) are released to the DEVICE — a marker's default release is to the system.  (No measurable effect by itself; the A/Bs
+// that seemed to show one were reading the copy engine's two speeds: EXPERIMENTS.md.)  Results leave through sum_done and the
+// callback's own system-scope stores, which keep the system scope.
+constexpr unsigned kDevEventFlags = hipEventDisableTiming | hipEventReleaseToDevice;
 constexpr uint32_t kCbDoneWords = 2 * 16 * 64;   // wbx_ctx::d_cb_done: two counters of kCbLanes words, kCbStride apart (wbx_callback.h)
 
 // (ClipSlab, the clip pool's slabs and the policy that carves them up: wbx_pool.h)
@@ -268,21 +273,19 @@ struct wbx_ctx {
   } pb[kRing];
   int cur = 0;
   hipStream_t plan_stream = nullptr;
-  bool overlap = true;
   DevBuf<float> d_zero;               // zero page (F+8 floats)
   uint32_t* levels_target = nullptr;  // [N][C] running per-track maxima (VUMeter::level), or null
   DevBuf<float> d_partial2[kRing];    // group partials, one per render in flight (a sum may still read an older one)
   DevBuf<float> d_master, d_buses, d_gains;
   DevBuf<float> d_peaks[2];           // per-track-block peaks: one buffer per mix stream (two mixes may be in flight)
   float* last_peaks = nullptr;        // where the last render / submit put its peaks
-  // WBX_MIX_ALT=1 (experiment, off by default): consecutive batch renders of layer 2 alternate between the main stream
+  // WBX_MIX_ALT=1 (CtxKnobs::mix_alternate; experiment, off by default): consecutive batch renders of layer 2 alternate between the main stream
   // and `alt_stream`, so that nothing orders mix i+1 after mix i and the head of one can fill the CUs the tail of the
   // other leaves idle.  Everything else stays on the main stream, which joins the alternate one (join_alt) wherever it
   // joins the sum stream.  Measured: no gain in step time, each kernel's own interval grows by ~45 %.
   hipStream_t alt_stream = nullptr;
   hipStream_t cur_mix_stream = nullptr;   // the stream of the mix about to be / last launched
   int alt_pending = -1;                   // partial-buffer index of a mix on alt_stream the main stream has not joined
-  bool mix_alternate = false;             // WBX_MIX_ALT=1
   // The sum of render i runs on its own stream beside the mix of render i+1 (it is PCIe-bound when the master goes to
   // host memory and needs few CUs).  sum_pending: a sum has been issued that the main stream has not waited for yet.
   hipStream_t sum_stream = nullptr;
@@ -295,7 +298,6 @@ struct wbx_ctx {
   int sum_pending = -1;
   uint32_t render_seq = 0;
   bool partial_wait_done = false;     // the caller already ordered this render after the sum of two renders ago
-  bool sum_overlap = true;            // WBX_SUM_OVERLAP=0: sum on the main stream
   DevBuf<uint8_t> d_conv;
   DevBuf<unsigned long long> d_dbg;   // diagnostic (WBX_DBG_CLOCK=1): per-workgroup start / end times of the last mix
   size_t dbg_wgs = 0;
@@ -318,22 +320,16 @@ struct wbx_ctx {
   uint32_t cb_base2 = 0;              // ... the second one (only launches whose workgroups each add a share of the master)
   uint64_t cb_launches = 0, cb_spread_launches = 0;   // one-launch callbacks issued / ... with the spread sum
   bool seg_broken = false;            // plan_seg_kernel found its XCD layout broken (status bit 7): one lane per track from then on
-  uint32_t cb_spin_bound = 40000;     // polls of the spread barrier before a workgroup gives up (~50 ms; WBX_CB_SPIN_BOUND, read at wbx_create)
   // Which mix instance a render takes and what follows from it (wbx_shape.h).  `shape` is assigned ONCE per render — by
   // render_locked / wbx_submit, from the knobs, the session's facts and the context's state (render_shape) — and read by
   // everything that launches for that render, the repeats of a callback block included.
-  ShapeKnobs knobs;                   // read once, at wbx_create
+  ShapeKnobs knobs;                   // the switches, read once at wbx_create (wbx_knobs.h): those that enter the shape ...
+  CtxKnobs ck;                        // ... and the others the context consults
   SessionFacts session;               // of the last render (a bare context: layer 1's "unknown, assume so")
   RenderShape shape;
-  // further A/B switches, read ONCE at wbx_create like the knobs (the audio callback never calls getenv)
   uint32_t n_xcds = 0;                // the XCD layout probe of wbx_create: 8 / 4 / 2 / 1, or 0 — not round-robin: no chained pieces
                                       // (chain_broken), no segmented sequencer (seg_broken) from the start
-  bool knob_no_uniform = false;       // WBX_NO_UNIFORM=1: MixArgs::uniform_speed withheld (the one-ratio modes off)
-  bool knob_cb_fenced = false;        // WBX_CB_FENCED=1: release / acquire fences in the one-launch callback
-  bool knob_partial_free_off = false; // WBX_PARTIAL_FREE=0: a partial buffer's next user waits for sum_done (behind the master's copy-out), as until round 5
-  unsigned dev_event_flags = 0x2;     // hipEventDisableTiming [| hipEventReleaseToDevice]: events only other streams of this device wait for
-  bool knob_mix_marker = false;       // WBX_MIX_MARKER=1: mix_done and the pace event as markers on the mix stream (as until round 5)
-  bool knob_fast_partial_off = false; // WBX_FAST_PARTIAL=0: every partial stream call through the clamped masked arithmetic (as until round 5)
+  uint32_t n_cus = 0;                 // the device's CU count (wbx_create), what callback_spread_limit starts from
   bool cb_no_spread = false;          // a spread launch gave up waiting for the whole grid (not resident at once: a CU mask, a
                                       // device shared with another process): the context keeps to "the last workgroup adds"
   uint32_t cb_flags = 1;              // completion words the launch writes (one, or one per workgroup: cb_flag[0 .. cb_flags))
@@ -360,7 +356,6 @@ struct wbx_ctx {
   uint64_t gap_count = 0;
   double tail_ms_total = 0.0;          // mix end -> sum end (launch gap + sum kernel incl. its PCIe stores)
   uint64_t mix_launches = 0;
-  bool profiling = true;
   const char* mix_kernel_name = "";   // the instance launch_mix chose last (wbx_kernel_name)
   double last_uniform_speed = 0.0;    // MixArgs::uniform_speed of the last launch (wbx_render_uniform_speed)
   bool has_integer_clips = false;
@@ -371,7 +366,6 @@ struct wbx_ctx {
   ExportStage exp;
   std::mutex export_mu;
   std::atomic<uint32_t> export_chunk{0};   // wbx_set_export_chunk: frames per staging chunk, 0 = kExportChunkDefault
-  bool knob_export_direct = false;     // WBX_EXPORT_DIRECT=1 (A/B aid, read at wbx_create): the kernel stores into the pinned slot itself
 
   // wbx_clip_measure / wbx_clip_derive and layer 2's forms: one at a time (fx_mu), on a stream that is no mix or sum stream
   ClipFxStage fx;

@@ -305,8 +305,7 @@ extern "C" wbx_status wbx_dist_init(wbx_ctx* c, const wbx_dist_id* id, uint32_t 
     job->done = true;
     job->cv.notify_all();
   }).detach();
-  double limit = 60.0;
-  if (const char* t = std::getenv("WBX_DIST_INIT_TIMEOUT_S")) limit = std::atof(t);
+  const double limit = dist_init_timeout_s();   // (WBX_DIST_INIT_TIMEOUT_S: wbx_knobs.h)
   {
     std::unique_lock<std::mutex> lk(job->m);
     if (limit > 0.0) {

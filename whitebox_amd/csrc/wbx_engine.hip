@@ -18,7 +18,7 @@ using namespace wbx;
 struct wbx_engine {
   wbx_ctx* ctx = nullptr;
   HostSession hs;
-  int knob_plan_seg = -1;               // WBX_PLAN_SEG, read once at wbx_engine_create: 0 off, n > 0 segments of n blocks, -1 unset
+  EngineKnobs knobs;                    // WBX_PLAN_SEG / WBX_PLAN_LANES, read once at wbx_engine_create (wbx_knobs.h)
   // pinned host buffers the plan kernel reads in place (one 16-B / 8-B read per lane): state patches and per-track
   // gains reach the device without a copy and, above all, without a stream synchronisation that would drain the
   // renders the audio thread has run ahead by.  Rings of three; a buffer is refilled only after the plan kernel that
@@ -169,8 +169,8 @@ wbx_status cfail(wbx_engine* e, wbx_status s) {
 // r04_ab_seglen.txt: 256 tracks best at 32-64 blocks — 16 and 128 are 9-15 % slower —, 4096 tracks x 2048 short blocks at 512).
 // WBX_PLAN_SEG=0: off; =<n>: segments of n blocks (A/B aid, tests).
 uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing) {
-  if (e->knob_plan_seg == 0) return 0u;   // (WBX_PLAN_SEG as wbx_engine_create read it: the audio thread never calls getenv)
-  const uint32_t forced = e->knob_plan_seg > 0 ? (uint32_t)e->knob_plan_seg : 0u;
+  if (e->knobs.plan_seg == 0) return 0u;   // (WBX_PLAN_SEG as wbx_engine_create read it)
+  const uint32_t forced = e->knobs.plan_seg > 0 ? (uint32_t)e->knobs.plan_seg : 0u;
   if (e->table_flags && e->h_flags_left && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left) == 0u)
     e->table_flags = false;   // every flag of the table has been cleared by a plan that is over
   if (!playing || e->table_flags || e->in_process || N == 0u || e->ctx->seg_broken) return 0u;
@@ -202,15 +202,12 @@ extern "C" wbx_status wbx_engine_create(const wbx_config* cfg, wbx_engine** out)
   e->ctx = c;
   e->hs.max_tracks = cfg->max_tracks;
   e->hs.dst_rate = cfg->sample_rate;
-  if (const char* v = std::getenv("WBX_PLAN_SEG")) e->knob_plan_seg = std::max(0, std::atoi(v));
-  if (const char* v = std::getenv("WBX_PLAN_LANES")) {   // tuning knob; measured on c3 cut into clips of 5.3 / 20 blocks:
-    const int n = std::atoi(v);                          // 64, 32, 16 and 8 tracks per wave within 2 % of each other
-    if (n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 32 || n == 64) e->hs.plan_lanes_knob = (uint32_t)n;
-  }
+  e->knobs = EngineKnobs::from_env();
+  e->hs.plan_lanes_knob = e->knobs.plan_lanes;
   c->owner = e;
   c->sample_in_use = sample_in_use_cb;
   if (hipStreamCreateWithFlags(&e->levels_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->levels_ev, e->ctx->dev_event_flags) != hipSuccess ||
+      hipEventCreateWithFlags(&e->levels_ev, kDevEventFlags) != hipSuccess ||
       hipHostMalloc((void**)&e->h_levels, (size_t)cfg->max_tracks * 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
     wbx_engine_destroy(e);
     return WBX_ERR_OOM;
@@ -954,8 +951,8 @@ wbx_status ensure_pinned_tables(wbx_engine* e, uint32_t N) {
     e->patch_cap[i] = cap;
     e->patch_valid[i] = false;
     e->gains_valid[i] = false;
-    if (!e->patch_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->patch_done[i], e->ctx->dev_event_flags));
-    if (!e->gains_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->gains_done[i], e->ctx->dev_event_flags));
+    if (!e->patch_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->patch_done[i], kDevEventFlags));
+    if (!e->gains_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->gains_done[i], kDevEventFlags));
   }
   e->gains_cap = cap;
   e->gains_slot = -1;
@@ -1113,7 +1110,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   //    while the mix of the previous render is still busy on the main stream
   c->cur = (c->cur + 1) % kRing;
   wbx_ctx::PlanBuf& B = PB(c);
-  const bool plan_beside = c->overlap && K >= kOverlapMinBlocks;
+  const bool plan_beside = c->ck.overlap && K >= kOverlapMinBlocks;
   hipStream_t ps = plan_beside ? c->plan_stream : s;
   hipStream_t ms = pick_mix_stream(c, K, true);   // main stream, or the alternate one for every other batch render
   const bool plan_event = ps != ms;               // the mix runs on another stream than its plan
@@ -1121,7 +1118,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   {
     const int pp = (int)(c->render_seq % kRing);
     if (plan_beside && c->sum_valid[pp]) {   // ... and the sum that read the partial buffer this render's mix will write
-      WBX_EHIP(e, hipStreamWaitEvent(ps, c->knob_partial_free_off ? c->sum_done[pp] : c->partial_free[pp], 0));   // (the sum KERNEL: not the copy-out of its master behind it)
+      WBX_EHIP(e, hipStreamWaitEvent(ps, c->partial_free[pp], 0));   // (the sum KERNEL: not the copy-out of its master behind it)
       c->partial_wait_done = true;
     }
   }
@@ -1167,12 +1164,11 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   a.sample_position = hs.sample_position;
   a.beat_duration = beat_duration;
   a.times = nullptr;
-  // (WBX_PLAN_LDS_TABLE=0: A/B aid — the device-memory table for cut sessions too.  Measured again in round 4, with the run
-  //  end estimated instead of searched: plan of c3 cut into 5.3-block clips 5.4 ms from LDS, 10.9 ms from device memory, 4 /
-  //  2 / 1 tracks per wave 12-25 ms: every record look-up at a clip boundary is a memory round trip for its lane)
-  static const bool lds_table_for_cut = [] { const char* v = std::getenv("WBX_PLAN_LDS_TABLE"); return !(v && v[0] == '0'); }();
+  // (cut sessions keep the LDS table.  Measured again in round 4, with the run end estimated instead of searched: plan of c3
+  //  cut into 5.3-block clips 5.4 ms from LDS, 10.9 ms from device memory, 4 / 2 / 1 tracks per wave 12-25 ms: every record
+  //  look-up at a clip boundary is a memory round trip for its lane)
   if (seg_len) a.tmpl_reserve = 8u;   // (a lane plans seg_len blocks, not K: a smaller reservation strands less)
-  if (seg_len || (plan_beside && (!(hs.cut_tracks != 0 || c->knobs.force_cut) || !lds_table_for_cut))) {
+  if (seg_len || (plan_beside && !(hs.cut_tracks != 0 || c->knobs.force_cut))) {
     // Batch render of a session whose tracks are single clips (a steady run per track, a handful of look-ups): the transport
     // records live in device memory and the sequencer takes the register-capped instance — nothing in LDS, a wave no larger
     // than a mix wave, so it runs BESIDE the previous mix instead of in the drain at its end.  Sessions cut into clips
@@ -1188,11 +1184,10 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
       WBX_EHIP(e, hipHostMalloc((void**)&e->h_times[ts], (size_t)K * sizeof(DBlockTime), hipHostMallocDefault));
       e->times_cap[ts] = K;
     }
-    if (!e->times_done[ts]) WBX_EHIP(e, hipEventCreateWithFlags(&e->times_done[ts], e->ctx->dev_event_flags));
+    if (!e->times_done[ts]) WBX_EHIP(e, hipEventCreateWithFlags(&e->times_done[ts], kDevEventFlags));
     block_times(a, e->h_times[ts]);   // wbx_seq.h: the source the device compiles
-    static const bool by_memset = [] { const char* v = std::getenv("WBX_COUNTERS_MEMSET"); return v && v[0] == '1'; }();   // A/B aid
-    launch_times_copy(e->h_times[ts], B.times.p, K, (need_zero && !by_memset) ? B.counters : nullptr, ps);
-    if (!by_memset) need_zero = false;
+    launch_times_copy(e->h_times[ts], B.times.p, K, need_zero ? B.counters : nullptr, ps);
+    need_zero = false;
     WBX_EHIP(e, hipEventRecord(e->times_done[ts], ps));
     e->times_valid[ts] = true;
   }
@@ -1201,7 +1196,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     // (found by the random-pieces test once it left renders unfetched: a batch render's plan, on the idle plan stream,
     //  overtook the plan of a short render still queued on the main stream behind earlier mixes and read the state before
     //  that one had written it)
-    if (!e->plan_handover) WBX_EHIP(e, hipEventCreateWithFlags(&e->plan_handover, e->ctx->dev_event_flags));
+    if (!e->plan_handover) WBX_EHIP(e, hipEventCreateWithFlags(&e->plan_handover, kDevEventFlags));
     WBX_EHIP(e, hipEventRecord(e->plan_handover, e->last_plan_stream));
     WBX_EHIP(e, hipStreamWaitEvent(ps, e->plan_handover, 0));
   }
@@ -1229,7 +1224,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     // one lane per (track, segment); the lane that completes a track checks its seams; the seam states live in one buffer
     const size_t per = (size_t)N * n_segs;
     if (e->seam_stream && e->seam_stream != ps) {   // (its last user ran on the other stream)
-      if (!e->seam_done) WBX_EHIP(e, hipEventCreateWithFlags(&e->seam_done, e->ctx->dev_event_flags));
+      if (!e->seam_done) WBX_EHIP(e, hipEventCreateWithFlags(&e->seam_done, kDevEventFlags));
       WBX_EHIP(e, hipEventRecord(e->seam_done, e->seam_stream));
       WBX_EHIP(e, hipStreamWaitEvent(ps, e->seam_done, 0));
     }

@@ -457,8 +457,7 @@ void launch_times_copy(const DBlockTime* host_pinned, DBlockTime* dev, uint32_t 
 
 void launch_plan(const PlanArgs& a, hipStream_t s) {
   const uint32_t nb = (a.n_tracks + a.lanes - 1u) / a.lanes;
-  static const bool roomy = [] { const char* v = std::getenv("WBX_PLAN_BESIDE"); return v && v[0] == '0'; }();   // A/B aid
-  if (a.times && !roomy)
+  if (a.times)
     hipLaunchKernelGGL(plan_kernel_beside, dim3(nb), dim3(64), 0, s, a);
   else
     hipLaunchKernelGGL(plan_kernel, dim3(nb), dim3(64), a.times ? 0 : a.n_blocks * sizeof(DBlockTime), s, a);
@@ -468,8 +467,7 @@ void launch_plan_segments(const PlanArgs& a, const SegArgs& g, bool beside, hipS
   const uint32_t n_groups = (a.n_tracks + 63u) / 64u;
   const dim3 grid(8u * ((n_groups + 7u) / 8u) * g.n_segs);   // (the kernel decodes: id mod 8 = track group mod 8)
   const size_t lds = (size_t)(g.seg_len + 2u * kSegMargin) * sizeof(DBlockTime);
-  static const bool roomy = [] { const char* v = std::getenv("WBX_PLAN_BESIDE"); return v && v[0] == '0'; }();   // A/B aid
-  if (beside && !roomy)
+  if (beside)
     hipLaunchKernelGGL(plan_seg_kernel_beside, grid, dim3(64), lds, s, a, g);
   else
     hipLaunchKernelGGL(plan_seg_kernel, grid, dim3(64), lds, s, a, g);
@@ -499,23 +497,8 @@ const char* launch_mix(const MixInstance& inst, const MixArgs& a, uint32_t grid_
 // A CU mask (HSA_CU_MASK / ROC_GLOBAL_CU_MASK) takes CUs away without the attribute saying so: no spreading then.  (A device
 // shared with another process can still hold workgroups back; the barrier's wait is bounded, a give-up is reported and the
 // block is mixed again through three launches — wbx_engine_process — and the context stops spreading.)
-uint32_t callback_spread_limit() {
-  static const uint32_t n_cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    return (uint32_t)(n > 0 ? n : 0);
-  }();
-  static const bool no_spread = [] {
-    const char* v = std::getenv("WBX_CB_SPREAD");   // A/B aid
-    if (v && v[0] == '0') return true;
-    for (const char* name : {"HSA_CU_MASK", "ROC_GLOBAL_CU_MASK"}) {
-      const char* m = std::getenv(name);
-      if (m && m[0]) return true;
-    }
-    return false;
-  }();
-  return no_spread ? 0u : (n_cus < 256u ? n_cus : 256u);
-}
+// `n_cus`, `cu_mask`: the device's CU count and CtxKnobs::cu_mask, as wbx_create found them.
+uint32_t callback_spread_limit(uint32_t n_cus, bool cu_mask) { return cu_mask ? 0u : (n_cus < 256u ? n_cus : 256u); }
 
 const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s0, uint32_t* done, uint32_t done_base, uint32_t done_base2,
                             bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st) {

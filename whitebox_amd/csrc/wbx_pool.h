@@ -72,8 +72,9 @@ inline uint64_t pool_slab_bytes(const ClipSlabs& slabs) {
 // An extent of `need` bytes (whole granules, the gap included): the newest slab first — its lowest hole that fits, else
 // its tail — then the older ones; else a new slab (64 MiB, 256 MiB, 1 GiB, 1 GiB ...: small sessions stay small).
 // `limit` (0: none) bounds slabs + own_reserved, the bytes of the clips that have an allocation of their own: the usual
-// slab if it fits, else one just large enough, else none.  A clip above kPoolSlabbed, any clip with use_slabs off
-// (WBX_CLIP_ARENA=0) and a clip that needs a new slab the driver cannot give get an allocation of own_bytes.
+// slab if it fits, else one just large enough, else none.  A clip above kPoolSlabbed, any clip with use_slabs off (the
+// pool model's other arm: the library passes true) and a clip that needs a new slab the driver cannot give get an allocation
+// of own_bytes.
 inline PoolTake pool_take(ClipSlabs& slabs, size_t need, size_t own_bytes, uint64_t limit, uint64_t own_reserved, bool use_slabs,
                           PoolAlloc alloc, void* user) {
   PoolTake t;

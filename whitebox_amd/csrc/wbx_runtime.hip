@@ -36,7 +36,7 @@ hipError_t sync_main(wbx_ctx* c) {
 
 // which stream the next mix runs on: batch renders of layer 2 alternate (see wbx_ctx::alt_stream)
 hipStream_t pick_mix_stream(wbx_ctx* c, uint32_t K, bool alternate) {
-  const bool alt = alternate && c->mix_alternate && c->alt_stream && K >= kOverlapMinBlocks && c->cur_mix_stream == c->stream;
+  const bool alt = alternate && c->ck.mix_alternate && c->alt_stream && K >= kOverlapMinBlocks && c->cur_mix_stream == c->stream;
   c->cur_mix_stream = alt ? c->alt_stream : c->stream;
   return c->cur_mix_stream;
 }
@@ -148,7 +148,7 @@ RenderShape render_shape(const wbx_ctx* c, uint32_t K, uint32_t N, bool callback
   f.n_tracks = N;
   f.callback = callback;
   f.chain_broken = c->chain_broken;
-  f.mix_alternate = c->mix_alternate;
+  f.mix_alternate = c->ck.mix_alternate;
   f.dist = c->dist != nullptr;
   return choose_shape(c->knobs, f);
 }
@@ -309,7 +309,7 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   if (!c->cur_mix_stream) c->cur_mix_stream = c->stream;
   hipStream_t ms = c->cur_mix_stream;             // the main stream, or the alternate one (pick_mix_stream)
   const int pk = ms == c->stream ? 0 : 1;         // its peaks buffer
-  if (c->sum_valid[pp] && !c->partial_wait_done) WBX_HIP(c, hipStreamWaitEvent(ms, c->knob_partial_free_off ? c->sum_done[pp] : c->partial_free[pp], 0));
+  if (c->sum_valid[pp] && !c->partial_wait_done) WBX_HIP(c, hipStreamWaitEvent(ms, c->partial_free[pp], 0));
   c->partial_wait_done = false;
   m.partial = c->d_partial2[pp].p;
   m.peaks = c->d_peaks[pk].p;
@@ -317,7 +317,7 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   m.levels = c->levels_target;
   // short renders (the one-block callback path above all) keep everything on the main stream: the cross-stream
   // hand-overs cost more than the few microseconds of overlap they could buy
-  const bool sum_beside = c->sum_overlap && K >= kOverlapMinBlocks;
+  const bool sum_beside = c->ck.sum_overlap && K >= kOverlapMinBlocks;
   hipStream_t ss = sum_beside ? c->sum_stream : c->stream;
   // (argument checks first: once dist_mix_init has posted this render's receive, a failure would leave it unmatched)
   if (c->master_format && c->dist) return fail(c, WBX_ERR_UNSUPPORTED, "wbx_set_master_format: a multi-GPU partial master stays planar fp32");
@@ -339,14 +339,14 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   m.block_frames = F;
   m.channels = C;
   m.lane_span = sh.lane_span;
-  m.fast_partial = c->knob_fast_partial_off ? 0u : 1u;
+  m.fast_partial = c->ck.fast_partial_off ? 0u : 1u;
   m.tiles = sh.tiles;
   m.n_blocks = K;
   m.masked_rows = sh.masked_rows ? 1u : 0u;
   {   // one resampling ratio for every window row of this render (layer 2's word; MODE_WNU / WINU: the products fl(j * speed)
-      // hoisted out of the track loop).  WBX_NO_UNIFORM=1: A/B aid.  [Round 3's split of this function lost this line: the
+      // hoisted out of the track loop).  WBX_NO_UNIFORM=1 withholds it.  [Round 3's split of this function lost this line: the
       // modes were carried but never taken until round 5 — SQ_INSTS_VALU_MUL_F64 of the r03-r05 PMC passes shows it.]
-    m.uniform_speed = c->knob_no_uniform ? 0.0 : sh.uniform_speed;
+    m.uniform_speed = c->ck.no_uniform ? 0.0 : sh.uniform_speed;
     c->last_uniform_speed = m.uniform_speed;
   }
   // A short render of a session that is one group (the callback configuration up to 64 tracks; no sub-buses, planar fp32
@@ -356,19 +356,15 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   // buffers, and the late one would overwrite the head of the short render's blocks.  (Found by the edit scripts once they
   // stopped fetching every render: nobody had made the main stream wait, because a fetch in between always had.)
   if (ss == c->stream) WBX_HIP(c, join_sum(c));
-  bool fused = false;
-  {
-    static const bool off = [] { const char* v = std::getenv("WBX_FUSE_SUM"); return v && v[0] == '0'; }();   // A/B aid
-    fused = !off && K < kOverlapMinBlocks && n_groups == 1u && c->n_buses == 0u && m.tiles == 1u && !c->master_format && !c->dist &&
-            !m.init && !chained;
-    m.fused_master = nullptr;
-    if (fused) {
-      m.fused_master = master_dst;
-      m.fused_clamp = c->clamp ? 1u : 0u;
-      m.fused_status_src = c->status_dst ? PB(c).counters : nullptr;
-      m.fused_status_dst = c->status_dst;
-      m.fused_zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
-    }
+  const bool fused = K < kOverlapMinBlocks && n_groups == 1u && c->n_buses == 0u && m.tiles == 1u && !c->master_format && !c->dist &&
+                     !m.init && !chained;
+  m.fused_master = nullptr;
+  if (fused) {
+    m.fused_master = master_dst;
+    m.fused_clamp = c->clamp ? 1u : 0u;
+    m.fused_status_src = c->status_dst ? PB(c).counters : nullptr;
+    m.fused_status_dst = c->status_dst;
+    m.fused_zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
   }
   m.chain = nullptr;
   m.chain_status = nullptr;
@@ -387,47 +383,39 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     m.chain_status = PB(c).counters + 1;
     m.chain_sticky = c->d_sticky_status;
   }
-  {
-    static const bool dbg = std::getenv("WBX_DBG_CLOCK") != nullptr;   // diagnostic: per-workgroup start / end times of the mix
-    m.dbg_clock = nullptr;
-    if (dbg) {
-      c->dbg_wgs = (size_t)K * n_groups * m.tiles;
-      WBX_HIP(c, c->d_dbg.ensure(4 * c->dbg_wgs));
-      m.dbg_clock = c->d_dbg.p;
-    }
+  m.dbg_clock = nullptr;
+  if (c->ck.dbg_clock) {   // diagnostic: per-workgroup start / end times of the mix
+    c->dbg_wgs = (size_t)K * n_groups * m.tiles;
+    WBX_HIP(c, c->d_dbg.ensure(4 * c->dbg_wgs));
+    m.dbg_clock = c->d_dbg.p;
   }
   if (m.tiles > 1) WBX_HIP(c, hipMemsetAsync(m.peaks, 0, (size_t)K * N * C * sizeof(float), ms));
   // the kernel timer is for batch renders; the one-block callback path skips its three event records
-  const bool timed = c->profiling && K > 1;
+  const bool timed = c->ck.profiling && K > 1;
   const bool one_launch = c->cb_plan != nullptr && m.n_groups != 0u && sh.cb_one_launch;
   if (one_launch) {   // (the callback instance's own lane space: one 256-lane workgroup per block)
     m.lane_span = sh.cb_lane_span;
     m.tiles = 1u;
   }
   c->cb_launched = false;
+  // (round 6) When the kernel carries the timer's stop event and its sum runs on the sum stream, THAT event is what the sum
+  // stream waits for, and mix_done — what later plans wait for — is recorded over there: no marker packet behind the mix on
+  // its own stream, where the next mix queues (every packet between two mixes is a round trip of the command processor to
+  // the queue in host memory, behind whatever the copy engine is posting; what the marker cost: EXPERIMENTS.md, round 6).
   bool by_kernel_event = false;
   if (m.n_groups && !one_launch) {
-    if (timed) {
-      if (c->ev_pending == kEventRing) {   // the older half: 32 launches behind the newest, over long ago
-        WBX_HIP(c, hipEventSynchronize(c->ev[kEventRing / 2 - 1][2]));
-        drain_events(c, kEventRing / 2);
-      }
+    if (timed && c->ev_pending == kEventRing) {   // the older half: 32 launches behind the newest, over long ago
+      WBX_HIP(c, hipEventSynchronize(c->ev[kEventRing / 2 - 1][2]));
+      drain_events(c, kEventRing / 2);
     }
     // the timer's two events ride on the kernel's own dispatch packet (start / end time stamps of the kernel itself): no
-    // event packets between two mixes.  WBX_TIMER_PACKETS=1: the old way, an event record either side (A/B aid)
-    static const bool packets = std::getenv("WBX_TIMER_PACKETS") != nullptr;
-    if (timed && packets) WBX_HIP(c, hipEventRecord(c->ev[c->ev_pending][0], ms));
-    const char* name = launch_mix(sh.mix, m, sh.grid_z, ms, (timed && !packets) ? c->ev[c->ev_pending][0] : nullptr,
-                                  (timed && !packets) ? c->ev[c->ev_pending][1] : nullptr);
+    // event packets between two mixes
+    const char* name = launch_mix(sh.mix, m, sh.grid_z, ms, timed ? c->ev[c->ev_pending][0] : nullptr,
+                                  timed ? c->ev[c->ev_pending][1] : nullptr);
     if (!name) return fail(c, WBX_ERR_FAILED, "the render's mix instance is not compiled in");
     c->mix_kernel_name = name;
-    if (timed && packets) WBX_HIP(c, hipEventRecord(c->ev[c->ev_pending][1], ms));
     if (c->dist) WBX_HIP(c, dist_mix_issued(c, ms));
-    // (round 6) When the kernel carries the timer's stop event and its sum runs on another stream, THAT event is what the sum
-    // stream waits for, and mix_done — what later plans wait for — is recorded over there: no marker packet behind the mix on
-    // its own stream, where the next mix queues (every packet between two mixes is a round trip of the command processor to
-    // the queue in host memory, behind whatever the copy engine is posting).  WBX_MIX_MARKER=1: the marker, as until round 5.
-    by_kernel_event = timed && !packets && !c->knob_mix_marker && !c->dist && !c->mix_alternate && ms == c->stream && sum_beside;
+    by_kernel_event = timed && !c->dist && !c->ck.mix_alternate && ms == c->stream && sum_beside;
   }
   // the plan buffer is free as soon as the MIX has read it: releasing it before the sum lets the next plan run
   // beside sum_kernel (the GPU is nearly idle there) instead of competing with the next mix for CU slots — started
@@ -443,11 +431,10 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   float* const master_home = master_dst;
   size_t stage_bytes = 0;
   if (sum_beside && !c->dist && c->master_target && c->master_target_on_host && c->master_format != 5) {
-    static const bool direct = [] { const char* v = std::getenv("WBX_HOST_MASTER_DIRECT"); return v && v[0] == '1'; }();   // A/B aid
     // (from 4 MB: below, the copy's fixed cost on the sum stream outweighs the hold-up — a 256-track session rendering 256
     //  blocks at a time lost a quarter of its rate to it, and gains a quarter at 2048)
     const size_t bytes = (size_t)K * F * C * (c->master_format == 3 ? 2u : 4u);
-    if (!direct && bytes >= (4u << 20)) {
+    if (bytes >= (4u << 20)) {
       stage_bytes = bytes;
       WBX_HIP(c, c->d_stage[pp].ensure((stage_bytes + 3u) / 4u));
       master_dst = c->d_stage[pp].p;
@@ -475,11 +462,9 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   s.status_src = c->status_dst ? PB(c).counters : nullptr;
   s.status_dst = c->status_dst;
   s.zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
-  if (by_kernel_event && ss != ms) {
+  if (by_kernel_event) {   // (the mix on the main stream, its sum beside it: ss is the sum stream)
     WBX_HIP(c, hipStreamWaitEvent(ss, c->ev[c->ev_pending][1], 0));   // the kernel's own completion ...
     WBX_HIP(c, hipEventRecord(c->mix_done[pp], ss));                   // ... and, over here, "the mix has read its plan buffer"
-  } else if (by_kernel_event) {
-    WBX_HIP(c, hipEventRecord(c->mix_done[pp], ms));
   } else if (ss != ms) {
     WBX_HIP(c, hipStreamWaitEvent(ss, c->mix_done[pp], 0));   // (an earlier pending sum is ordered before this one by ss)
   }
@@ -502,20 +487,17 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
       c->cb_base = c->cb_base2 = 0;
     }
     unsigned long long* cb_dbg = nullptr;
-    {
-      static const bool dbg = std::getenv("WBX_CB_DBG") != nullptr;   // diagnostic: the phases of every workgroup (tools/cb_clocks.py)
-      if (dbg) {
-        c->dbg_wgs = ((size_t)6 * m.n_groups + 3) / 4;
-        WBX_HIP(c, c->d_dbg.ensure(4 * c->dbg_wgs));
-        cb_dbg = c->d_dbg.p;
-      }
+    if (c->ck.cb_dbg) {   // diagnostic: the phases of every workgroup (tools/cb_clocks.py)
+      c->dbg_wgs = ((size_t)6 * m.n_groups + 3) / 4;
+      WBX_HIP(c, c->d_dbg.ensure(4 * c->dbg_wgs));
+      cb_dbg = c->d_dbg.p;
     }
-    m.partial_through = c->knob_cb_fenced ? 0u : 1u;
+    m.partial_through = c->ck.cb_fenced ? 0u : 1u;
     // every workgroup adds a share of the master when the whole grid is resident at once (at most one workgroup per CU: two
     // fit) and the engine's pinned block has a completion word for each of them
-    const bool spread = !fused && !c->cb_no_spread && m.n_groups <= callback_spread_limit();
+    const bool spread = !fused && !c->cb_no_spread && m.n_groups <= callback_spread_limit(c->n_cus, c->ck.cu_mask);
     c->cb_flags = 1u;
-    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
+    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->ck.cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
     if (!name) return fail(c, WBX_ERR_FAILED, "the render's callback instance is not compiled in");
     c->mix_kernel_name = name;
     // (a one-group block takes no ticket; a grid larger than the device — "the last workgroup adds everything" — only the
@@ -608,14 +590,9 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
   // kernel's spread sum (by sum_kernel when the block shape takes the three-launch path).
   c->auto_group = c->cfg.group_size == 0;
   if (c->cfg.group_size == 0) c->cfg.group_size = c->cfg.max_blocks == 1 ? kStage / 2 : kStage;
-  c->knobs = ShapeKnobs::from_env();
-  if (const char* u = std::getenv("WBX_KERNEL_TIMER")) c->profiling = std::atoi(u) != 0;   // 0: no HIP-event kernel timer
-  // Events whose only waiters are other streams of this device (or a host that waits for "done" and reads nothing the device
-  // wrote): released to the DEVICE — a marker's default release is to the system.  (No measurable effect by itself; the A/Bs
-  // that seemed to show one were reading the copy engine's two speeds: EXPERIMENTS.md.)  Results leave through sum_done and the
-  // callback's own system-scope stores, which keep the system scope.  WBX_EVENT_SCOPE=system: as until round 5 (A/B aid).
-  const unsigned scope = [] { const char* es = std::getenv("WBX_EVENT_SCOPE"); return (es && es[0] == 's') ? 0u : (unsigned)hipEventReleaseToDevice; }();
-  c->dev_event_flags = hipEventDisableTiming | scope;
+  c->knobs = ShapeKnobs::from_env();   // every environment switch is read here (wbx_knobs.h), none on a render path
+  c->ck = CtxKnobs::from_env();
+  c->n_cus = (uint32_t)std::max(prop.multiProcessorCount, 0);
   if (cfg->stream) {
     c->stream = (hipStream_t)cfg->stream;
   } else {
@@ -627,8 +604,9 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
   }
   for (int i = 0; i < kEventRing; i++) {
     // (timing events: only their time stamps are read — no release to the system behind the kernel that carries them)
-    if (hipEventCreateWithFlags(&c->ev[i][0], scope) != hipSuccess || hipEventCreateWithFlags(&c->ev[i][1], scope) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev[i][2], scope) != hipSuccess) {
+    if (hipEventCreateWithFlags(&c->ev[i][0], hipEventReleaseToDevice) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev[i][1], hipEventReleaseToDevice) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev[i][2], hipEventReleaseToDevice) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_DEVICE;
     }
@@ -637,55 +615,30 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
     // The sequencer runs beside the mix of the previous render.  It is a few dozen latency-bound waves (one
     // lane per track): at low or equal priority they starve behind the 16 mix waves of their CU and the
     // plan becomes the critical path, so the plan stream gets the HIGHEST priority — the issue slots it
-    // takes from the bandwidth-bound mix are negligible.  WBX_OVERLAP=0 runs everything on the main stream;
-    // WBX_PLAN_PRIO=lo|hi picks the priority (tuning knobs).
+    // takes from the bandwidth-bound mix are negligible.  (WBX_OVERLAP=0 runs everything on the main stream.)
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    const char* ov = std::getenv("WBX_OVERLAP");
-    c->overlap = !(ov && ov[0] == '0');
-    const char* pp = std::getenv("WBX_PLAN_PRIO");
-    const int prio = (pp && pp[0] == 'l') ? lo : hi;
-    if (hipStreamCreateWithPriority(&c->plan_stream, hipStreamNonBlocking, prio) != hipSuccess) {
+    if (hipStreamCreateWithPriority(&c->plan_stream, hipStreamNonBlocking, hi) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_DEVICE;
     }
     // the sum stream: highest priority as well — its few hundred small workgroups start while the next mix floods
-    // the device.  WBX_SUM_OVERLAP=0 keeps the sum on the main stream.
-    const char* so = std::getenv("WBX_SUM_OVERLAP");
-    c->sum_overlap = !(so && so[0] == '0');
-    const char* sp = std::getenv("WBX_SUM_PRIO");
-    const unsigned dev_ev = c->dev_event_flags;
-    bool ok = hipStreamCreateWithPriority(&c->sum_stream, hipStreamNonBlocking, (sp && sp[0] == 'l') ? lo : hi) == hipSuccess;
+    // the device.  (WBX_SUM_OVERLAP=0 keeps the sum on the main stream.)
+    bool ok = hipStreamCreateWithPriority(&c->sum_stream, hipStreamNonBlocking, hi) == hipSuccess;
     for (int i = 0; i < kRing && ok; i++)
-      ok = hipEventCreateWithFlags(&c->mix_done[i], dev_ev) == hipSuccess &&
+      ok = hipEventCreateWithFlags(&c->mix_done[i], kDevEventFlags) == hipSuccess &&
            hipEventCreateWithFlags(&c->sum_done[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&c->partial_free[i], dev_ev) == hipSuccess;
+           hipEventCreateWithFlags(&c->partial_free[i], kDevEventFlags) == hipSuccess;
     if (ok) ok = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking) == hipSuccess;
-    if (ok) ok = hipStreamCreateWithFlags(&c->alt_stream, hipStreamNonBlocking) == hipSuccess;
     // measured (tools/ab_alt.sh): with consecutive mixes on alternating streams the two kernels share the device for
     // their whole length (each takes 1.05-1.2 ms instead of 0.74) and the step time does not move — off by default
-    if (const char* sb = std::getenv("WBX_CB_SPIN_BOUND")) c->cb_spin_bound = (uint32_t)std::atoi(sb);   // (tests: 0 forces the give-up path)
-    {   // the A/B switches the render path consults beside the shape's (wbx_ctx.h: read once, here)
-      auto is = [](const char* name, char what) { const char* v = std::getenv(name); return v && v[0] == what; };
-      c->knob_no_uniform = is("WBX_NO_UNIFORM", '1');
-      c->knob_cb_fenced = is("WBX_CB_FENCED", '1');
-      c->knob_partial_free_off = is("WBX_PARTIAL_FREE", '0');
-      c->knob_mix_marker = is("WBX_MIX_MARKER", '1');
-      c->knob_fast_partial_off = is("WBX_FAST_PARTIAL", '0');
-      c->knob_export_direct = is("WBX_EXPORT_DIRECT", '1');
-    }
+    if (ok) ok = hipStreamCreateWithFlags(&c->alt_stream, hipStreamNonBlocking) == hipSuccess;
     // the workgroup-id -> XCD layout the chained pieces and the segmented sequencer rest on, probed before anything relies on it
-    // (WBX_XCD_PROBE_FAIL=1: tests take the fallback path)
-    if (ok) {
-      const char* pf = std::getenv("WBX_XCD_PROBE_FAIL");
-      if (!probe_xcd_layout(c->stream, &c->n_xcds) || (pf && pf[0] == '1')) {
-        c->n_xcds = 0;
-        c->chain_broken = true;
-        c->seg_broken = true;
-      }
+    if (ok && (!probe_xcd_layout(c->stream, &c->n_xcds) || c->ck.xcd_probe_fail)) {
+      c->n_xcds = 0;
+      c->chain_broken = true;
+      c->seg_broken = true;
     }
-    const char* ma = std::getenv("WBX_MIX_ALT");
-    c->mix_alternate = ma && ma[0] == '1';
     if (!ok) {
       wbx_destroy(c);
       return WBX_ERR_DEVICE;
@@ -696,7 +649,7 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
   for (auto& B : c->pb) {
     B.pool_chunks = (uint32_t)chunks;
     if (B.pool.ensure(chunks * kChunk) != hipSuccess || hipMalloc((void**)&B.counters, 4 * sizeof(uint32_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&B.planned, c->dev_event_flags) != hipSuccess) {
+        hipEventCreateWithFlags(&B.planned, kDevEventFlags) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_OOM;
     }
@@ -810,15 +763,13 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
   s = ClipSlot{};
   const size_t stride = align_up((frames + kPad) * eb, 256);   // (varying the distance between a clip's channel rows: no effect)
   {
-    static const bool use_slabs = !(std::getenv("WBX_CLIP_ARENA") && std::getenv("WBX_CLIP_ARENA")[0] == '0');   // A/B aid
-    static const bool jitter = !(std::getenv("WBX_SLAB_JITTER") && std::getenv("WBX_SLAB_JITTER")[0] == '0');   // A/B aid (the gap: wbx_pool.h)
-    const PoolExtent ext = pool_extent(stride * channels, jitter ? c->slab_seq.fetch_add(1u, std::memory_order_relaxed) : 0u, jitter);
+    const PoolExtent ext = pool_extent(stride * channels, c->slab_seq.fetch_add(1u, std::memory_order_relaxed), true);   // (the gap: wbx_pool.h)
     const size_t need = ext.body + ext.gap;
     PoolTake where;
     {   // where the clip goes is wbx_pool.h's decision; hipMalloc is the slabs' source
       std::lock_guard<std::mutex> g(c->slab_mu);
       where = pool_take(c->slabs, need, stride * channels, c->pool_limit.load(std::memory_order_relaxed),
-                        c->own_alloc_bytes.load(std::memory_order_relaxed), use_slabs,
+                        c->own_alloc_bytes.load(std::memory_order_relaxed), true,
                         [](void*, size_t bytes) -> char* {
                           char* mem = nullptr;
                           if (hipMalloc((void**)&mem, bytes) == hipSuccess) return mem;
@@ -1265,8 +1216,8 @@ void wbx::export_release(wbx_ctx* c) {
 hipError_t wbx::side_prepare(wbx_ctx* c, SideStream& s) {
   if (s.stream) return hipSuccess;
   hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_main, c->dev_event_flags);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_upload, c->dev_event_flags);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_main, kDevEventFlags);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_upload, kDevEventFlags);
   if (e != hipSuccess) side_release(s);
   return e;
 }
@@ -1350,8 +1301,7 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
   const uint32_t C = src.channels;
   const size_t fb = out_format_bytes(out_format) * C;          // bytes of a frame in dst
   const uint64_t chunk = x.chunk, n_chunks = (n_frames + chunk - 1) / chunk;
-  const bool direct = c->knob_export_direct;
-  const bool to_dst = !direct && export_dst_is_pinned(dst, (size_t)n_frames * fb);   // the copy engine writes dst itself
+  const bool to_dst = export_dst_is_pinned(dst, (size_t)n_frames * fb);   // the copy engine writes dst itself
   wbx_export_stats acc{};
   auto issue = [&](uint64_t k) -> hipError_t {
     const int b = (int)(k % kExportSlots);
@@ -1362,7 +1312,7 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
     ExportArgs a{};
     for (uint32_t ch = 0; ch < C; ch++) a.src[ch] = clip_row(src, ch) + first_frame + at;
     if (C == 1) a.src[1] = a.src[0];
-    a.dst = direct ? x.h_slot[b] : x.d_slot[b];
+    a.dst = x.d_slot[b];
     a.stats = x.d_stats[b];
     a.n_frames = m;
     a.channels = C;
@@ -1370,7 +1320,7 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
     a.flags = flags;
     launch_export(a, on);
     e = hipGetLastError();
-    if (e == hipSuccess && !direct)
+    if (e == hipSuccess)
       e = hipMemcpyAsync(to_dst ? (void*)((char*)dst + (size_t)at * fb) : x.h_slot[b], x.d_slot[b], (size_t)m * fb,
                          hipMemcpyDeviceToHost, on);
     if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats + 8 * b, x.d_stats[b], 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, on);
@@ -1738,10 +1688,10 @@ extern "C" wbx_status wbx_pace(wbx_ctx* c, uint32_t max_ahead) {
   if (!c || max_ahead == 0 || max_ahead >= kPaceRing) return WBX_ERR_INVALID;
   (void)hipSetDevice(c->cfg.device);
   const uint32_t slot = (uint32_t)(c->pace_seq % kPaceRing);
-  if (!c->pace_ev[slot]) WBX_HIP(c, hipEventCreateWithFlags(&c->pace_ev[slot], c->dev_event_flags));   // (the host waits for "done", reads nothing)
-  // (behind the last render's sum when that runs on its own stream: no marker between two mixes; WBX_MIX_MARKER=1: on the mix stream)
+  if (!c->pace_ev[slot]) WBX_HIP(c, hipEventCreateWithFlags(&c->pace_ev[slot], kDevEventFlags));   // (the host waits for "done", reads nothing)
+  // (behind the last render's sum when that runs on its own stream: no marker between two mixes)
   hipStream_t where = c->cur_mix_stream ? c->cur_mix_stream : c->stream;
-  if (!c->knob_mix_marker && c->sum_pending >= 0 && c->sum_stream && !c->dist) where = c->sum_stream;
+  if (c->sum_pending >= 0 && c->sum_stream && !c->dist) where = c->sum_stream;
   WBX_HIP(c, hipEventRecord(c->pace_ev[slot], where));
   if (c->pace_seq >= max_ahead) WBX_HIP(c, hipEventSynchronize(c->pace_ev[(c->pace_seq - max_ahead) % kPaceRing]));
   c->pace_seq++;

@@ -7,59 +7,15 @@
 #pragma once
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 
 #include "wbx_dev.h"
+#include "wbx_knobs.h"
 
 namespace wbx {
 
 constexpr uint32_t kOverlapMinBlocks = 8;   // renders shorter than this run plan, mix and sum on the main stream
 
-// The A/B switches that enter the choice, read ONCE per context (wbx_create; a test sets the variable and creates a new
-// context): the audio callback never calls getenv, and what a context decides at plan time (masked rows, lane space)
-// cannot disagree with what it launches.
-struct ShapeKnobs {
-  bool ragged_off = false;        // WBX_RAGGED=0: blocks between the instances' shapes take the general instance
-  bool cb_any_off = false;        // WBX_CB_ANY=0: the one-launch callback only for blocks that are exactly one 256-lane workgroup
-  bool masked_rows_off = false;   // WBX_MASKED_ROWS=0: every clip boundary through the pre-render pass
-  bool chain_off = false;         // WBX_CHAIN=0: long renders walk whole member lists instead of chaining 128-track pieces
-  bool no_lean16 = false;         // WBX_NO_LEAN16: sessions of 16-bit PCM only through family 1
-  bool no_fam3 = false;           // WBX_NO_FAM3: resampled-integer sessions through family 1
-  bool no_cl2 = false;            // WBX_NO_CL2: never both channels of a frame in one lane
-  bool no_long_cl2 = false;       // WBX_NO_LONG_CL2=1: long chained renders of resampled fp32 sessions keep one channel per wave
-  bool no_long_24 = false;        // WBX_NO_LONG_24=1: long renders of large unity-speed fp32 sessions keep four rows per batch
-  bool callback_unfused = false;  // WBX_CALLBACK_FUSED=0: the one-block callback as three launches (results are identical)
-  bool force_cut = false;         // WBX_FORCE_CUT=1: an uncut session through the instances a session cut into clips takes
-  bool force_g = false;           // WBX_FORCE_G: always the everything family
-  int packed_x = -1;              // WBX_PACKED_X=0|1: the packed masked-row instances off / on for every shape (-1: the library's choice)
-  int mix_variant = 0;            // WBX_MIX_VARIANT=10*U+W (>= 1000: both channels per lane) forces a kernel variant (results
-                                  // are identical); 0 = chosen per render
-  int cb_u = 0;                   // WBX_CB_U=2|4|8: rows per pipeline batch of the lean callback instance
-  uint32_t exact_min_blocks = 1024;   // renders of at least this many workgroup columns walk whole member lists when the
-                                      // library picks the grouping (WBX_EXACT_MIN_BLOCKS; 0 = never)
-
-  static ShapeKnobs from_env() {
-    auto is = [](const char* name, char what) { const char* v = std::getenv(name); return v && v[0] == what; };
-    ShapeKnobs k;
-    k.ragged_off = is("WBX_RAGGED", '0');
-    k.cb_any_off = is("WBX_CB_ANY", '0');
-    k.masked_rows_off = is("WBX_MASKED_ROWS", '0');
-    k.chain_off = is("WBX_CHAIN", '0');
-    k.no_lean16 = std::getenv("WBX_NO_LEAN16") != nullptr;
-    k.no_fam3 = std::getenv("WBX_NO_FAM3") != nullptr;
-    k.no_cl2 = std::getenv("WBX_NO_CL2") != nullptr;
-    k.no_long_cl2 = is("WBX_NO_LONG_CL2", '1');
-    k.no_long_24 = is("WBX_NO_LONG_24", '1');
-    k.callback_unfused = is("WBX_CALLBACK_FUSED", '0');
-    k.force_cut = is("WBX_FORCE_CUT", '1');
-    if (const char* v = std::getenv("WBX_FORCE_G")) k.force_g = std::atoi(v) != 0;
-    if (const char* v = std::getenv("WBX_PACKED_X")) k.packed_x = std::atoi(v) != 0 ? 1 : 0;
-    if (const char* v = std::getenv("WBX_MIX_VARIANT")) k.mix_variant = std::atoi(v);
-    if (const char* v = std::getenv("WBX_CB_U")) k.cb_u = std::atoi(v);
-    if (const char* v = std::getenv("WBX_EXACT_MIN_BLOCKS")) k.exact_min_blocks = (uint32_t)std::atoi(v);
-    return k;
-  }
-};
+// (ShapeKnobs, the switches that enter the choice, read once per context at wbx_create: wbx_knobs.h)
 
 // What the session holds.  The defaults are layer 1's, whose host-sequenced plans say nothing about their clips:
 // "unknown, assume so".
@@ -149,8 +105,8 @@ struct RenderShape {
 // (config.cpp:146-149,217-222): 480 frames for WASAPI's 10 ms at 48 kHz, 416 at 44.1 kHz, 960 for 20 ms.  Such a block takes
 // the next shape above it; its surplus lanes clone the block's last four frames (wbx_mix.h).  WBX_RAGGED=0: the general
 // instance of earlier rounds instead (A/B aid).
-// (`ragged_off`: WBX_RAGGED=0 as the context read it when it was created — the audio callback never calls getenv, and the
-//  plan-time and launch-time choices of one context cannot disagree)
+// (`ragged_off`: WBX_RAGGED=0 as the context read it when it was created (wbx_knobs.h): the plan-time and launch-time choices
+//  of one context cannot disagree)
 inline uint32_t native_lane_span(uint32_t C, uint32_t S4, bool ragged_off) {
   const uint32_t lanes = C * S4;
   const bool exact = ((lanes % 256u == 0u) && (S4 % 64u == 0u)) || (C == 2u && S4 == 32u) ||
@@ -208,7 +164,7 @@ inline RenderShape choose_shape(const ShapeKnobs& k, const ShapeFacts& f) {
   // again, five alternating runs on one box (profiles/r05_ab_c3_instances.txt) read 0.711 of the roofline for it, 0.701 for
   // <2,true,3,..,2,128>, 0.694 for the one-channel-per-wave <2,true,4,..,1,256>; at 1024 and 256 blocks nothing to choose.
   auto long_chained_window_render = [&](bool chained) {
-    return !k.no_long_cl2 && C == 2u && F == 512u && chained && K >= 2048u && ses.window_clips && !f.integer_clips && !cut &&
+    return C == 2u && F == 512u && chained && K >= 2048u && ses.window_clips && !f.integer_clips && !cut &&
            !ses.stride_clips && !f.n_buses;
   };
 
@@ -246,7 +202,7 @@ inline RenderShape choose_shape(const ShapeKnobs& k, const ShapeFacts& f) {
     //  256-block renders; in renders of >= 2048 blocks of large sessions two rows at four waves, <2,true,4,..>, is ahead:
     //  c4 0.72-0.75 of the roofline against 0.67-0.69, u4096 0.755-0.777 against 0.746-0.763, one box, alternating
     //  (profiles/r05_ab_c3_instances.txt); 256-track sessions: nothing to choose)
-    const bool long_large = !k.no_long_24 && K >= 2048u && f.n_tracks >= 1024u;
+    const bool long_large = K >= 2048u && f.n_tracks >= 1024u;
     const int v = k.mix_variant                        ? k.mix_variant
                   : two_channels_per_lane(whole, chained) ? (long_chained_window_render(chained) ? 1013 : 1023)
                                                        : ((ses.window_clips || f.integer_clips || long_large) ? 24 : 43);
