@@ -294,6 +294,63 @@ wbx_status wbx_resample_table(uint32_t src_rate, uint32_t dst_rate, int quality,
 wbx_status wbx_clip_resample(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                              uint32_t dst_rate, int quality, wbx_clip_stats* stats_of_result);
 
+/* Splicing clips: a list of PARTS — each a wbx_clip_derive edit of some resident F32 clip, placed at an output frame —
+ * becomes ONE new F32 clip, without the samples leaving HBM: takes comped, a crossfade between two clips, a bounce joined
+ * to the take before it, a loop repeated, silence inserted, a region cut out.  wbx_clip_derive has one source; this is the
+ * call with several.  No reference counterpart: AudioClip::fade_start / fade_end (engine/clip.h:41-42) are read by nothing
+ * and Engine::reserve_track_region (engine.cpp:478-569) trims overlapping clips, it never blends them.  This text is the
+ * specification; tests/splice_model.py restates it in numpy and the device equals that BIT FOR BIT.
+ *   the result    dst_clip becomes a new F32 pool clip of `channels` (1 or 2) x n_frames frames (plus the pool's 16 zero
+ *                 frames of padding) at the sources' common sample rate; an existing dst_clip is replaced as
+ *                 wbx_clip_upload would replace it; dst_clip is no part's source
+ *   a part        part p has the value v_p[c][k], k in [0, n_p): exactly what wbx_clip_derive would STORE for frame k of the
+ *                 edit (first_frame, n_frames, flags, channel_mode, gain, fade_in, fade_out, shapes) of src_clip — the same
+ *                 operations in the same order with the same single roundings ("Editing clips" above)
+ *   a frame       output frame j of channel c walks, in LIST order, the parts that cover j (at_p <= j < at_p + n_p):
+ *                 the first one ASSIGNS acc = v_p[c][j - at_p]; every later one does acc = fl(acc + v_p[c][j - at_p]), one
+ *                 fp32 round-to-nearest addition.  A frame no part covers is +0.0f.  A NaN result is stored as 0x7FC00000
+ * Hence: a one-part splice with at = 0 and n_frames = n_p is bit-equal to wbx_clip_derive (-0.0 survives: it is assigned,
+ * not added to a zero); the order of the additions is the list's and nothing else's; a crossfade is two overlapping parts,
+ * one with a fade-out and one with a fade-in; concatenation, inserted silence, a removed region and a loop (one source in
+ * many parts) are part lists.
+ * stats_of_result (may be NULL): wbx_clip_measure of the whole result, a second pass over the output only.
+ * Stream and ordering are wbx_clip_derive's: the edits' stream, behind everything enqueued so far on the context's main
+ * and upload streams; one edit, conversion or splice runs at a time; the call returns when the result is complete.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: parts NULL or n_parts == 0,
+ * n_frames == 0 or >= 2^31 - 16, channels not 1 or 2, an unknown source clip, dst_clip equal to a part's source, a part
+ * with no frames, with a range past its clip or with at + n_p > n_frames, an unknown flag, mode or shape, a fade longer
+ * than its part, a mode that does not fit its source's channel count or does not yield `channels`, sources whose sample
+ * rates differ (convert first: wbx_clip_resample); WBX_ERR_UNSUPPORTED: a source whose storage format is not F32,
+ * n_parts > 65536, a tile table (below) of more than 2^24 entries.  WBX_ERR_OOM as for wbx_clip_derive.
+ * wbx_splice_plan is host-only and needs no device: the refusals above (all but dst_clip's) against a table of sources
+ * indexed by src_clip (an id >= n_sources, or an entry with channels == 0, is an unknown clip), and the table the kernel
+ * walks — the output cut into tiles of 512 frames, tile_off[t] .. tile_off[t + 1] indexing tile_parts[], the indices of the
+ * parts that touch tile t, ascending.  *n_tiles and *n_entries (each may be NULL) are always given on WBX_OK; the arrays are
+ * filled when both are non-NULL and cap_off >= n_tiles + 1 and cap_parts >= n_entries (WBX_ERR_INVALID when a capacity
+ * is too small; nothing written then). */
+typedef struct wbx_splice_part {   /* 64 bytes */
+  uint32_t src_clip;
+  uint32_t flags;                  /* WBX_EDIT_REVERSE */
+  uint64_t first_frame, n_frames;  /* the source range */
+  uint64_t at;                     /* output frame of the part's first frame */
+  int32_t channel_mode;            /* WBX_CH_* */
+  float gain;
+  uint64_t fade_in, fade_out;      /* frames, each <= n_frames */
+  int32_t fade_in_shape, fade_out_shape;   /* WBX_FADE_LINEAR / SQUARE / SMOOTH */
+} wbx_splice_part;
+typedef struct wbx_splice_source {   /* 24 bytes */
+  uint32_t channels;               /* 0: no such clip */
+  uint32_t sample_rate;
+  uint64_t frames;
+  int32_t format;                  /* WBX_FMT_* */
+  uint32_t _pad;
+} wbx_splice_source;
+wbx_status wbx_splice_plan(uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts, uint32_t n_parts,
+                           const wbx_splice_source* sources, uint32_t n_sources, uint64_t* n_tiles, uint64_t* n_entries,
+                           uint32_t* tile_off, size_t cap_off, uint32_t* tile_parts, size_t cap_parts);
+wbx_status wbx_clip_splice(wbx_ctx* ctx, uint32_t dst_clip, uint32_t channels, uint64_t n_frames,
+                           const wbx_splice_part* parts, uint32_t n_parts, wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -693,6 +750,15 @@ wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample, uint64_t 
  * through the unity row mode.  Arguments and refusals are wbx_clip_resample's. */
 wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                       uint32_t dst_rate, int quality, uint32_t* new_sample);
+/* wbx_clip_splice of engine samples (a part's src_clip is a sample id), under wbx_engine_derive_sample's rules to the
+ * letter: editing thread, the audio thread may keep calling wbx_engine_process*; the editor lock is held only to validate,
+ * to copy every source's storage description out, to pin, to order the stream, to publish and to unpin, never across a
+ * device wait; no transport state is touched and no edit is counted.  EVERY distinct source of the call is pinned for
+ * its life: wbx_engine_delete_sample refuses each of them meanwhile ("sample is being edited", asked before "still
+ * referenced by a clip").  *new_sample is a fresh sample id registered at the sources' common rate.  Arguments and
+ * refusals are wbx_clip_splice's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_splice_samples(wbx_engine* e, uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts,
+                                     uint32_t n_parts, uint32_t* new_sample);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

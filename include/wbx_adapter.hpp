@@ -336,6 +336,14 @@ struct Engine {
     check(wbx_engine_resample_sample(h, sample, first_frame, n_frames, dst_rate, quality, &id), "resample_sample");
     return id;
   }
+  // A NEW sample made of parts of other samples (wbx.h "Splicing clips"): takes comped, two samples crossfaded (two
+  // overlapping parts, one fading out, one fading in), samples joined, a loop repeated, silence inserted.  A part's src_clip
+  // is a sample id.  Editing thread, like derive_sample; every source is pinned for the call; the id goes where a bounce's go.
+  uint32_t splice_samples(uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts, uint32_t n_parts) {
+    uint32_t id = 0;
+    check(wbx_engine_splice_samples(h, channels, n_frames, parts, n_parts, &id), "splice_samples");
+    return id;
+  }
   // recording, engine.cpp:95-200: the takes are captured on the device from process()'s input buffer and become clips
   // on their tracks at stop_record (a take that lost blocks still does; stop_record then throws with WBX_ERR_OVERFLOW)
   void record() { check(wbx_engine_record(h), "record"); }

@@ -72,6 +72,17 @@ class ResampleInfo(C.Structure):       # wbx_resample_info, 24 bytes
                 ("table_floats", C.c_uint64)]
 
 
+class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
+    _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
+                ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
+                ("fade_out", C.c_uint64), ("fade_in_shape", C.c_int32), ("fade_out_shape", C.c_int32)]
+
+
+class SpliceSource(C.Structure):       # wbx_splice_source, 24 bytes
+    _fields_ = [("channels", C.c_uint32), ("sample_rate", C.c_uint32), ("frames", C.c_uint64), ("format", C.c_int32),
+                ("_pad", C.c_uint32)]
+
+
 class PlanRecord(C.Structure):
     _fields_ = [("block", C.c_uint32), ("track", C.c_uint32), ("buffer_offset", C.c_uint32),
                 ("num_samples", C.c_uint32), ("num_actual", C.c_uint32), ("sample", C.c_uint32),
@@ -120,6 +131,9 @@ SYMBOLS = {
     "wbx_resample_frames": (C.c_uint64, [_u32, _u32, C.c_uint64]),
     "wbx_resample_table": (C.c_int, [_u32, _u32, C.c_int, _vp, _sz]),
     "wbx_clip_resample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(ClipStats)]),
+    "wbx_splice_plan": (C.c_int, [_u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(SpliceSource), _u32,
+                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _sz, _vp, _sz]),
+    "wbx_clip_splice": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -212,6 +226,7 @@ SYMBOLS = {
     "wbx_engine_derive_sample": (C.c_int, [_vp, _u32, C.POINTER(ClipEditDesc), C.POINTER(_u32)]),
     "wbx_engine_normalize_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, C.POINTER(_u32), C.POINTER(_f)]),
     "wbx_engine_resample_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(_u32)]),
+    "wbx_engine_splice_samples": (C.c_int, [_vp, _u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(_u32)]),
     "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),
     "wbx_track_set_input": (C.c_int, [_vp, _u32, C.c_int, _u32, C.c_int]),

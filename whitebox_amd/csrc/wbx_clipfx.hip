@@ -30,23 +30,10 @@ namespace wbx {
 
 namespace {
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at a 4-byte aligned address
-typedef float f4v __attribute__((ext_vector_type(4)));               // a 16-B word of output
-
-constexpr uint32_t kCanonNaN = 0x7FC00000u;
-
 // bits of a non-NaN float -> an unsigned key with the floats' order (-inf < ... < -0.0 < +0.0 < ... < +inf)
 __device__ __forceinline__ uint32_t order_key(float v) {
   const uint32_t b = __float_as_uint(v);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ float fade_weight(uint32_t k, uint32_t len, uint32_t shape) {
-  const float t = __double2float_rn(__ddiv_rn((double)k, (double)len));
-  if (shape == (uint32_t)WBX_FADE_LINEAR) return t;
-  const float tt = __fmul_rn(t, t);
-  if (shape == (uint32_t)WBX_FADE_SQUARE) return tt;
-  return __fmul_rn(tt, __fsub_rn(3.0f, __fmul_rn(2.0f, t)));   // WBX_FADE_SMOOTH
 }
 
 template <class T, class Op>

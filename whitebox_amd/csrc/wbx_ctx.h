@@ -19,6 +19,7 @@
 #include "wbx_dev.h"
 #include "wbx_shape.h"
 #include "wbx_resample.h"
+#include "wbx_splice.h"
 #include "wbx_pool.h"
 
 namespace wbx {
@@ -100,6 +101,17 @@ struct ClipFxArgs {
   uint32_t reversed, src_channels, out_channels;   // src_channels: rows read (LEFT / RIGHT read one)
 };
 void launch_clipfx(const ClipFxArgs& a, hipStream_t s);
+// what clipfx_kernel and splice_kernel share: the vector words, the stored NaN and the fade weight of wbx.h "Editing clips"
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // four floats at a 4-byte aligned address
+typedef float f4v __attribute__((ext_vector_type(4)));               // a 16-B word of output
+constexpr uint32_t kCanonNaN = 0x7FC00000u;
+__device__ __forceinline__ float fade_weight(uint32_t k, uint32_t len, uint32_t shape) {
+  const float t = __double2float_rn(__ddiv_rn((double)k, (double)len));
+  if (shape == (uint32_t)WBX_FADE_LINEAR) return t;
+  const float tt = __fmul_rn(t, t);
+  if (shape == (uint32_t)WBX_FADE_SQUARE) return tt;
+  return __fmul_rn(tt, __fsub_rn(3.0f, __fmul_rn(2.0f, t)));   // WBX_FADE_SMOOTH
+}
 // converting a clip's sample rate (wbx_resample.hip): a frame range of a planar F32 clip -> a new planar F32 clip
 struct ResampleArgs {
   const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
@@ -111,6 +123,25 @@ struct ResampleArgs {
   uint32_t tile, span, n_tiles;   // filled by launch_resample: outputs per tile, floats staged per channel and tile, tiles
 };
 void launch_resample(ResampleArgs a, hipStream_t s);
+// splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
+struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
+  const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
+  uint32_t n, at;              // frames of the part / output frame of its first one
+  uint32_t fade_in, fade_out;  // frames (<= n)
+  float gain;
+  uint32_t bits;               // kSpliceShapeIn/Out: WBX_FADE_* in two bits each; kSpliceReversed; kSpliceMonoMix
+  uint32_t _pad[2];
+};
+constexpr uint32_t kSpliceShapeOutShift = 2, kSpliceReversed = 1u << 4, kSpliceMonoMix = 1u << 5;
+struct SpliceArgs {
+  const SplicePartDev* parts;  // device
+  const uint32_t* tile_off;    // device: [n_tiles + 1] (wbx_splice.h)
+  const uint32_t* tile_parts;  // device: [tile_off[n_tiles]]
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  uint32_t n_frames, n_tiles;  // n_frames < 2^31 - 16
+  uint32_t channels;           // of the result: 1 or 2
+};
+void launch_splice(const SpliceArgs& a, hipStream_t s);
 void launch_mip(const MipArgs& a, int format, int bits, hipStream_t s);
 }  // namespace wbx
 
@@ -213,6 +244,12 @@ struct ResampleTable {
   int quality = 0;
   float* d = nullptr;
   std::vector<float> host;     // the upload's source, until the stream has been waited for
+};
+
+// wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
+struct SpliceStage {
+  DevBuf<SplicePartDev> parts;
+  DevBuf<uint32_t> tile_off, tile_parts;
 };
 
 }  // namespace wbx
@@ -371,6 +408,7 @@ struct wbx_ctx {
   ClipFxStage fx;
   std::mutex fx_mu;
   std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.side.stream)
+  SpliceStage splice;                     // wbx_clip_splice (under fx_mu, on fx.side.stream)
 
   hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
   hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -492,6 +530,12 @@ wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_
 wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
 void resample_release(wbx_ctx* c);
+// splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
+// on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
+// the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)
+wbx_status splice_run(wbx_ctx* c, const ClipSrc* srcs, const wbx_splice_part* parts, uint32_t n_parts, const SplicePlan& plan,
+                      uint32_t channels, uint64_t n_frames, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
+void splice_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it

@@ -132,6 +132,8 @@ struct wbx_engine {
   // wbx_engine_measure_sample / derive_sample / normalize_sample: the source of the edit in flight (under the editor lock;
   // one edit at a time, wbx_ctx::fx_mu), refused by wbx_engine_delete_sample in the same way
   uint32_t edit_pin = kNoExport;
+  // wbx_engine_splice_samples: every distinct source of the splice in flight (same lock, same mutex, refused the same way)
+  std::vector<uint32_t> edit_pins;
 };
 
 namespace {
@@ -576,7 +578,8 @@ extern "C" wbx_status wbx_engine_delete_sample(wbx_engine* e, uint32_t sample) {
   e->hs.note_edit_locked();
   if (!e->hs.valid_sample(sample)) return efail(e, WBX_ERR_INVALID, "unknown sample");
   // the edit pin first: it passes by itself, and a caller told to delete the clips first would do so only to be refused again
-  if (e->edit_pin == sample) return efail(e, WBX_ERR_UNSUPPORTED, "sample is being edited (a measure, derive or normalize call is still reading it)");
+  if (e->edit_pin == sample || std::find(e->edit_pins.begin(), e->edit_pins.end(), sample) != e->edit_pins.end())
+    return efail(e, WBX_ERR_UNSUPPORTED, "sample is being edited (a measure, derive or normalize call is still reading it)");
   if (e->hs.sample_referenced(sample)) return efail(e, WBX_ERR_INVALID, "sample is still referenced by a clip (delete the clips first)");
   if (e->export_pin == sample) return efail(e, WBX_ERR_UNSUPPORTED, "sample is being exported (wbx_engine_export_sample is still reading it)");
   const wbx_status st = wbx_clip_free(e->ctx, sample);
@@ -608,22 +611,24 @@ wbx_status register_sample_locked(wbx_engine* e, ClipSlot& slot, uint32_t channe
 }
 
 // `mu` (export_mu or fx_mu) held for its life; begin_locked() validates, pin_locked() writes the pin word (export_pin or
-// edit_pin), the destructor clears it
+// edit_pin), the destructor clears it.  A splice pins a SET: pin_set_locked() fills edit_pins, the destructor empties it
 struct SamplePin {
   using Step = wbx_status(wbx_ctx*, std::string*);
   wbx_engine* e;
   std::lock_guard<std::mutex> one;
   uint32_t wbx_engine::* word;
-  bool pinned = false;
+  bool pinned = false, pinned_set = false;
   ClipSrc src;
   uint32_t rate = 0;
   SamplePin(wbx_engine* e_, std::mutex& mu, uint32_t wbx_engine::* word_) : e(e_), one(mu), word(word_) {
     (void)hipSetDevice(e->ctx->cfg.device);
   }
   ~SamplePin() {
-    if (!pinned) return;
+    if (!pinned && !pinned_set) return;
+    std::vector<uint32_t> gone;                            // (the set's storage is freed after the lock)
     LockGuard g(e->hs.editor_lock);
-    e->*word = wbx_engine::kNoExport;
+    if (pinned) e->*word = wbx_engine::kNoExport;
+    if (pinned_set) gone.swap(e->edit_pins);
   }
   // (editor lock held) the sample's storage
   wbx_status begin_locked(uint32_t sample, const char* what) {
@@ -636,6 +641,10 @@ struct SamplePin {
   void pin_locked(uint32_t sample) {
     e->*word = sample;
     pinned = true;
+  }
+  void pin_set_locked(std::vector<uint32_t>& distinct) {   // the distinct sources, listed by the caller before it took the lock
+    e->edit_pins.swap(distinct);
+    pinned_set = true;
   }
   wbx_status order(Step* prepare, Step* order_side, std::string* why) {   // the side stream: made without the lock, ordered under it
     const wbx_status st = prepare(e->ctx, why);
@@ -783,6 +792,55 @@ extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample,
   wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
   if (st == WBX_OK) st = resample_run(e->ctx, p.src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, &why);
   if (st == WBX_OK) st = p.publish(slot, p.src.channels, dst_rate, n_out, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// wbx_clip_splice of engine samples (wbx.h "Splicing clips"), under wbx_engine_derive_sample's rules: the editor lock covers
+// validating the part list against the samples, copying every source's storage description out, pinning every distinct
+// source, ordering the stream, registering the new sample — at the sources' common rate — and unpinning.  The tile table is
+// built, the descriptors are uploaded and the device is waited for without it.  No transport state is touched, no edit is
+// counted.
+extern "C" wbx_status wbx_engine_splice_samples(wbx_engine* e, uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts,
+                                                uint32_t n_parts, uint32_t* new_sample) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "splice_samples: new_sample is NULL");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SplicePlan plan;
+  const char* msg = "";
+  // what needs the heap is made before the lock: the distinct source ids (of a list not yet checked: nothing is pinned
+  // where the check refuses it) and room for the storage descriptions
+  std::vector<uint32_t> distinct;
+  std::vector<ClipSrc> srcs;
+  if (parts && n_parts && n_parts <= kSpliceMaxParts) {
+    distinct.reserve(n_parts);
+    for (uint32_t i = 0; i < n_parts; i++) distinct.push_back(parts[i].src_clip);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    srcs.resize(n_parts);
+  }
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_splice_source tmp{};
+    const auto source_of = [&](uint32_t id) -> const wbx_splice_source* {
+      const ClipSlot* s = e->hs.valid_sample(id) ? find_clip(e->ctx, id) : nullptr;
+      if (!s) return nullptr;
+      tmp = wbx_splice_source{s->d.channels, s->d.sample_rate, s->d.count, (int32_t)s->d.format, 0u};
+      return &tmp;
+    };
+    const wbx_status st = splice_check(channels, n_frames, parts, n_parts, source_of, &plan.rate, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "splice_samples: the pool's sample ids (2^24) would run out");
+    for (uint32_t i = 0; i < n_parts; i++) srcs[i] = clip_src(e->ctx->clips[parts[i].src_clip]);
+    p.pin_set_locked(distinct);
+  }
+  wbx_status st = splice_plan_table(n_frames, parts, n_parts, &plan, &msg);
+  if (st != WBX_OK) return efail(e, st, msg);
+  std::string why;
+  ClipSlot slot;
+  st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = splice_run(e->ctx, srcs.data(), parts, n_parts, plan, channels, n_frames, slot, nullptr, &why);
+  if (st == WBX_OK) st = p.publish(slot, channels, plan.rate, n_frames, new_sample, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }

@@ -28,9 +28,6 @@ namespace wbx {
 
 namespace {
 
-typedef float f4v __attribute__((ext_vector_type(4)));   // a 16-B word of output
-
-constexpr uint32_t kCanonNaN = 0x7FC00000u;
 constexpr uint32_t kTileMax = 1024, kSpanMax = 4096, kGridMax = 1u << 16;
 
 template <int CH>

@@ -671,6 +671,7 @@ extern "C" void wbx_destroy(wbx_ctx* c) {
   dist_destroy(c);
   export_release(c);
   resample_release(c);
+  splice_release(c);
   clipfx_release(c);
   if (c->plan_stream) (void)hipStreamSynchronize(c->plan_stream);
   if (c->sum_stream) (void)hipStreamSynchronize(c->sum_stream);

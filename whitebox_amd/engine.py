@@ -98,6 +98,40 @@ def edit_desc(first_frame: int, n_frames: int, reverse: bool = False, channel_mo
                              _ffi.FADE_SHAPE.get(fade_in_shape, fade_in_shape), _ffi.FADE_SHAPE.get(fade_out_shape, fade_out_shape))
 
 
+def splice_part(src_clip: int, first_frame: int, n_frames: int, at: int = 0, reverse: bool = False, channel_mode="keep",
+                gain: float = 1.0, fade_in: int = 0, fade_out: int = 0, fade_in_shape="linear", fade_out_shape="linear",
+                flags: Optional[int] = None):
+    """a wbx_splice_part: edit_desc's edit of clip (or sample) `src_clip`, its first frame placed at output frame `at`"""
+    return _ffi.SplicePart(src_clip, (_ffi.EDIT_REVERSE if reverse else 0) if flags is None else flags, first_frame, n_frames, at,
+                           _ffi.CH_MODE.get(channel_mode, channel_mode), gain, fade_in, fade_out,
+                           _ffi.FADE_SHAPE.get(fade_in_shape, fade_in_shape), _ffi.FADE_SHAPE.get(fade_out_shape, fade_out_shape))
+
+
+def _part_array(parts):
+    return (_ffi.SplicePart * len(parts))(*parts) if parts else None
+
+
+def splice_plan(channels: int, n_frames: int, parts, sources, tables: bool = True):
+    """wbx_splice_plan (host-only): the refusals of a part list against `sources` — {clip id: (channels, frames, rate, fmt)},
+    fmt a name of _ffi.FMT — and the tile table.  Returns (tile_off, tile_parts) as uint32 arrays, or (n_tiles, n_entries)
+    with tables=False; WbxError where the library refuses the list."""
+    L = _ffi.lib()
+    n_src = max(sources) + 1 if sources else 0
+    src = (_ffi.SpliceSource * max(n_src, 1))()
+    for k, (ch, frames, rate, fmt) in sources.items():
+        src[k] = _ffi.SpliceSource(ch, rate, frames, _ffi.FMT.get(fmt, fmt), 0)
+    arr = _part_array(parts)
+    nt, ne = C.c_uint64(), C.c_uint64()
+    _check(L.wbx_splice_plan(channels, n_frames, arr, len(parts), src, n_src, C.byref(nt), C.byref(ne), None, 0, None, 0),
+           "wbx_splice_plan")
+    if not tables:
+        return nt.value, ne.value
+    off, ent = np.zeros(nt.value + 1, dtype=np.uint32), np.zeros(max(ne.value, 1), dtype=np.uint32)
+    _check(L.wbx_splice_plan(channels, n_frames, arr, len(parts), src, n_src, None, None, off.ctypes.data, off.size,
+                             ent.ctypes.data, ent.size), "wbx_splice_plan")
+    return off, ent[:ne.value]
+
+
 def resample_plan(src_rate: int, dst_rate: int, quality="good") -> dict:
     """wbx_resample_plan (host-only): {"L", "M", "half_width", "taps", "table_floats"} of a conversion; WbxError where the
     library refuses it (status -4: a rate of 0, equal rates, unknown quality; -3: L > 1280 or more than 512 taps)"""
@@ -216,6 +250,14 @@ class MixContext:
                                         _ffi.SRC_QUALITY.get(quality, quality), C.byref(st) if stats_channels else None),
                "wbx_clip_resample", self.h)
         return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def clip_splice(self, dst_clip: int, channels: int, n_frames: int, parts, stats: bool = False):
+        """wbx_clip_splice: `dst_clip` becomes a new F32 clip of `channels` x `n_frames` frames, the parts
+        (splice_part(...)) assigned and added in list order; returns the result's statistics with `stats`, else None"""
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_clip_splice(self.h, dst_clip, channels, n_frames, _part_array(parts), len(parts),
+                                      C.byref(st) if stats else None), "wbx_clip_splice", self.h)
+        return _clip_stats(st, channels) if stats else None
 
     def set_export_chunk(self, frames: int):
         """frames per staging chunk of later exports (a multiple of 8; 0: the default) — tests reach chunk seams with it"""
@@ -762,6 +804,38 @@ class Engine:
         self._sample_shape[new.value] = (resample_frames(src_rate, dst_rate, n_frames) if src_rate else None, channels)
         self._sample_rate[new.value] = dst_rate
         return new.value
+
+    def splice_samples(self, channels: int, n_frames: int, parts) -> int:
+        """wbx_engine_splice_samples: a new sample of `channels` x `n_frames` frames made of the parts (splice_part(...),
+        src_clip = a sample id) — see MixContext.clip_splice.  Every source is pinned against delete_sample for the call's
+        life.  May be called while another thread runs process()."""
+        new = C.c_uint32()
+        _check(self.L.wbx_engine_splice_samples(self.h, channels, n_frames, _part_array(parts), len(parts), C.byref(new)),
+               "wbx_engine_splice_samples", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if parts[0].src_clip in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[parts[0].src_clip]
+        return new.value
+
+    def join_samples(self, samples, overlap: int = 0, shape="linear", frames=None, channels: Optional[int] = None) -> int:
+        """the samples one after the other as ONE new sample, each seam a crossfade of `overlap` frames: the earlier sample's
+        last `overlap` frames fade out (`shape`) while the later one's first `overlap` fade in.  Pure host: it builds the
+        part list of splice_samples.  `frames`: the samples' lengths where this object did not make them."""
+        assert len(samples) >= 1
+        lens = [self._shape_of(s, None if frames is None else frames[i], channels)[0] for i, s in enumerate(samples)]
+        assert all(n is not None for n in lens), "join_samples: give frames (the samples' lengths)"
+        assert all(overlap <= n for n in lens), "join_samples: the overlap is longer than a sample"
+        channels = self._shape_of(samples[0], None, channels)[1]
+        parts, at = [], 0
+        for i, (s, n) in enumerate(zip(samples, lens)):
+            parts.append(splice_part(s, 0, n, at, fade_in=overlap if i else 0, fade_out=overlap if i + 1 < len(samples) else 0,
+                                     fade_in_shape=shape, fade_out_shape=shape))
+            at += n - overlap
+        return self.splice_samples(channels, at + overlap, parts)
+
+    def crossfade_samples(self, a: int, b: int, overlap: int, shape="linear", frames=None, channels: Optional[int] = None) -> int:
+        """sample `a` crossfading into sample `b` over `overlap` frames as one new sample (join_samples of the two)"""
+        return self.join_samples([a, b], overlap, shape, frames, channels)
 
     def bounce_download(self, sample: int, frames: int) -> np.ndarray:
         """a bounced sample back on the host: [C][frames] fp32 (wbx_clip_download per channel)"""
