@@ -215,3 +215,47 @@ def test_knobs_and_shape_under_address_and_ub_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert out.stdout.startswith("host_knobs ok ")
+
+
+def _occurs(word):
+    """{file under whitebox_amd/csrc: the lines that hold `word`}"""
+    return {os.path.basename(p): [ln for ln in _text(p).splitlines() if word in ln] for p in _files(CSRC) if word in _text(p)}
+
+
+def test_one_header_frees_what_the_host_side_holds():
+    """under whitebox_amd/csrc, events, streams and pinned blocks are destroyed in wbx_res.h alone (named exceptions: the public
+    wbx_host_free of wbx_runtime.hip, and wbx_dist.hip); hipFree( occurs there, in wbx_dist.hip and in wbx_runtime.hip's clip
+    pool (clip slots, mip-maps, slabs) only; DevBuf is wbx_res.h's"""
+    for word in ("hipEventDestroy", "hipStreamDestroy"):
+        assert sorted(_occurs(word)) == ["wbx_dist.hip", "wbx_res.h"], word
+    pinned = _occurs("hipHostFree")
+    assert set(pinned) - {"wbx_dist.hip"} == {"wbx_res.h", "wbx_runtime.hip"}
+    assert pinned["wbx_runtime.hip"] == ["  return hipHostFree(p) == hipSuccess ? WBX_OK : WBX_ERR_DEVICE;"]
+    runtime = _text(os.path.join(CSRC, "wbx_runtime.hip"))
+    assert runtime.index('extern "C" wbx_status wbx_host_free(') < runtime.index("hipHostFree(p)") < runtime.index('extern "C"', runtime.index("hipHostFree(p)"))
+    frees = _occurs("hipFree(")
+    assert sorted(frees) == ["wbx_dist.hip", "wbx_res.h", "wbx_runtime.hip"]
+    import re
+    pool = re.compile(r"hipFree\((s\.alloc|s\.mip|sl->mem)\)")
+    assert all(len(pool.findall(ln)) == ln.count("hipFree(") for ln in frees["wbx_runtime.hip"]), frees["wbx_runtime.hip"]
+    assert "struct DevBuf" not in _text(os.path.join(CSRC, "wbx_ctx.h"))
+    assert "struct DevBuf" in _text(os.path.join(CSRC, "wbx_res.h"))
+    res = _text(os.path.join(CSRC, "wbx_res.h"))
+    assert "getenv" not in res and "wbx_ctx.h\"" not in res and "__global__" not in res
+    assert "wbx_res.h" in [w for ln in _text(os.path.join(CSRC, "Makefile")).splitlines() if ln.startswith("HDR") for w in ln.split()]
+
+
+def test_resource_holders_balance_under_address_and_ub_sanitizers(tmp_path):
+    """tests/cpp/res_main.cpp: the real wbx_res.h over a counting fake of the HIP calls it makes (no HIP library linked) — every
+    holder created, grown, moved, swapped, adopted and failed at each create in turn leaves the ledger at zero; the slot's verbs
+    make the calls they name.  Built with ASan and UBSan, run directly"""
+    import subprocess
+    exe = str(tmp_path / "res_main")
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-O1", "-g", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "cpp", "res_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-4000:]
+    lines = out.stdout.splitlines()
+    assert lines[-1] == "res_main ok" and len(lines) == 9 and "FAILED" not in out.stdout

@@ -249,11 +249,8 @@ wbx_status clipfx_check_derive(const ClipSrc& src, const wbx_clip_edit_desc* d, 
 }
 
 void clipfx_release(wbx_ctx* c) {
-  ClipFxStage& x = c->fx;
-  side_release(x.side);
-  if (x.d_stats) (void)hipFree(x.d_stats);
-  if (x.h_stats) (void)hipHostFree(x.h_stats);
-  x = ClipFxStage{};
+  side_release(c->fx.side);
+  c->fx = ClipFxStage{};
 }
 
 wbx_status clipfx_prepare(wbx_ctx* c, std::string* why) {
@@ -261,14 +258,14 @@ wbx_status clipfx_prepare(wbx_ctx* c, std::string* why) {
   if (x.side.stream) return WBX_OK;
   (void)hipSetDevice(c->cfg.device);
   hipError_t e = side_prepare(c, x.side);
-  if (e == hipSuccess) e = hipMalloc((void**)&x.d_stats, sizeof(ClipFxStats));
-  if (e == hipSuccess) e = hipHostMalloc((void**)&x.h_stats, 2 * sizeof(ClipFxStats), hipHostMallocDefault);
+  if (e == hipSuccess) e = x.d_stats.ensure(1);
+  if (e == hipSuccess) e = x.h_stats.ensure(2);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     clipfx_release(c);
     return stage_fail(why, WBX_ERR_DEVICE, "clip edit: stream, events and statistics block", e);
   }
-  ClipFxStats& init = x.h_stats[0];                          // what a launch starts from
+  ClipFxStats& init = x.h_stats.p[0];                         // what a launch starts from
   std::memset(&init, 0, sizeof(init));
   init.mn[0] = init.mn[1] = 0xFFFFFFFFu;
   return WBX_OK;
@@ -298,15 +295,15 @@ static float key_to_float(uint32_t key) {
 static hipError_t fx_launch(wbx_ctx* c, const ClipFxArgs& a, uint32_t channels, uint64_t n_frames, wbx_clip_stats* out) {
   ClipFxStage& x = c->fx;
   const hipStream_t on = x.side.stream;
-  hipError_t e = hipMemcpyAsync(x.d_stats, &x.h_stats[0], sizeof(ClipFxStats), hipMemcpyHostToDevice, on);
+  hipError_t e = hipMemcpyAsync(x.d_stats.p, &x.h_stats.p[0], sizeof(ClipFxStats), hipMemcpyHostToDevice, on);
   if (e != hipSuccess) return e;
   launch_clipfx(a, on);
   e = hipGetLastError();
-  if (e == hipSuccess && out) e = hipMemcpyAsync(&x.h_stats[1], x.d_stats, sizeof(ClipFxStats), hipMemcpyDeviceToHost, on);
+  if (e == hipSuccess && out) e = hipMemcpyAsync(&x.h_stats.p[1], x.d_stats.p, sizeof(ClipFxStats), hipMemcpyDeviceToHost, on);
   const hipError_t w = hipStreamSynchronize(on);             // (also after a failure: nothing may still write the new clip)
   if (e == hipSuccess) e = w;
   if (e != hipSuccess || !out) return e;
-  const ClipFxStats& r = x.h_stats[1];
+  const ClipFxStats& r = x.h_stats.p[1];
   wbx_clip_stats st{};
   for (uint32_t ch = 0; ch < channels; ch++) {
     const uint32_t bits = (uint32_t)(r.peak[ch] >> 32);
@@ -328,7 +325,7 @@ wbx_status clipfx_measure_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_fra
                               std::string* why) {
   ClipFxArgs a{};
   for (uint32_t ch = 0; ch < 2; ch++) a.src[ch] = clip_row(src, ch);
-  a.stats = c->fx.d_stats;
+  a.stats = c->fx.d_stats.p;
   a.first_frame = (uint32_t)first_frame;
   a.n_frames = (uint32_t)n_frames;
   a.src_channels = a.out_channels = src.channels;
@@ -355,7 +352,7 @@ wbx_status clipfx_derive_run(wbx_ctx* c, const ClipSrc& src, uint32_t sample_rat
   a.out_channels = out_channels;
   a.dst[0] = (float*)slot.d.ch[0];
   a.dst[1] = (float*)slot.d.ch[1];
-  a.stats = c->fx.d_stats;
+  a.stats = c->fx.d_stats.p;
   a.first_frame = (uint32_t)d.first_frame;
   a.n_frames = (uint32_t)d.n_frames;
   a.fade_in = (uint32_t)d.fade_in;

@@ -21,6 +21,7 @@
 #include "wbx_resample.h"
 #include "wbx_splice.h"
 #include "wbx_pool.h"
+#include "wbx_res.h"
 
 namespace wbx {
 void launch_plan(const PlanArgs& a, hipStream_t s);
@@ -177,25 +178,7 @@ struct ClipSlot {
   std::vector<uint64_t> mip_count;
 };
 
-template <class T>
-struct DevBuf {             // grow-only device array
-  T* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+// (DevBuf, PinnedBuf, Event, Stream, PinnedSlot — the holders every resource below lives in: wbx_res.h)
 
 struct DistState;   // wbx_dist.hip
 
@@ -203,8 +186,8 @@ struct DistState;   // wbx_dist.hip
 // call's own (no mix or sum stream) and the two events that order it behind what last wrote the pool: the main and the
 // upload stream.  Export and the clip edits each own one; side_prepare / side_order / side_release (wbx_runtime.hip).
 struct SideStream {
-  hipStream_t stream = nullptr;
-  hipEvent_t after_main = nullptr, after_upload = nullptr;
+  Stream stream;
+  Event after_main, after_upload;
 };
 
 // wbx_clip_export's staging: a side stream and kExportSlots chunks, each a device buffer the kernel writes, a pinned
@@ -215,11 +198,10 @@ constexpr uint32_t kExportChunkDefault = 1u << 20, kExportChunkMax = 1u << 24;
 struct ExportStage {
   SideStream side;
   uint32_t chunk = 0;                     // frames the slots were made for
-  void* d_slot[kExportSlots] = {};
-  void* h_slot[kExportSlots] = {};        // pinned
-  uint32_t* d_stats[kExportSlots] = {};   // 8 words each (6 used)
-  uint32_t* h_stats = nullptr;            // pinned: [kExportSlots][8]
-  hipEvent_t done[kExportSlots] = {};
+  DevBuf<uint8_t> d_slot[kExportSlots];
+  PinnedSlot<uint8_t> h_slot[kExportSlots];   // pinned; done: the chunk's copies out of the slot are over
+  DevBuf<uint32_t> d_stats[kExportSlots];     // 8 words each (6 used)
+  PinnedBuf<uint32_t> h_stats;                // pinned: [kExportSlots][8]
 };
 // a clip's storage as a side call needs it (layer 2 copies it out of the pool under the editor lock)
 struct ClipSrc {
@@ -233,8 +215,8 @@ struct ClipSrc {
 // starts from, [1] what it left) — made at first use, freed with the context
 struct ClipFxStage {
   SideStream side;
-  ClipFxStats* d_stats = nullptr;
-  ClipFxStats* h_stats = nullptr;
+  DevBuf<ClipFxStats> d_stats;
+  PinnedBuf<ClipFxStats> h_stats;
 };
 
 // wbx_clip_resample's coefficient tables on the device, one per (L, M, quality) a context has converted with — made at
@@ -242,7 +224,7 @@ struct ClipFxStage {
 struct ResampleTable {
   uint32_t L = 0, M = 0;
   int quality = 0;
-  float* d = nullptr;
+  DevBuf<float> d;
   std::vector<float> host;     // the upload's source, until the stream has been waited for
 };
 
@@ -258,8 +240,7 @@ using namespace wbx;   // (internal header: only the host-side translation units
 
 struct wbx_ctx {
   wbx_config cfg{};
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  Stream stream;                      // the main stream: made here, or wbx_config.stream adopted (never destroyed)
   std::string err;
 
   std::vector<ClipSlot> clips;
@@ -282,7 +263,7 @@ struct wbx_ctx {
   mutable bool chain_broken = false;  // a chained render reported a failed hand-over (plan_status_to_error)
   uint32_t chain_epoch = 0;
   DevBuf<uint32_t> d_chain;           // chained renders: the "running sum is out" words
-  uint32_t* d_sticky_status = nullptr;   // failure bits (32 | 64) of every chained render since the last report (render_status)
+  DevBuf<uint32_t> d_sticky_status;      // failure bits (32 | 64) of every chained render since the last report (render_status)
   DevBuf<uint32_t> d_order;
   DevBuf<DGroup> d_groups;
   bool routing_dirty = true;
@@ -297,19 +278,19 @@ struct wbx_ctx {
     DevBuf<DSeg> pool;
     uint32_t pool_chunks = 0;
     DevBuf<DBlockTime> times;         // [K] per-block transport records of a batch render (PlanArgs::times)
-    uint32_t* counters = nullptr;     // [0] pool chunks allocated, [1] status bits, [2] generic records queued,
+    DevBuf<uint32_t> counters;        // [0] pool chunks allocated, [1] status bits, [2] generic records queued,
                                       // [3] templates allocated
     bool counters_zero = true;        // cleared already (at creation, or by the sum kernel of a callback block)
     DevBuf<uint32_t> gen_list;        // pre-render queue of KIND_GENERIC records
     DevBuf<float> rows;               // [gen_cap][C][F+8] pre-rendered mixing buffers
     DevBuf<DTrackBlock> saved;        // original records of the queue (plan read-back)
     uint32_t gen_cap = 0;
-    hipEvent_t planned = nullptr;     // recorded on plan_stream when plan + pre-render are done
+    Event planned;                    // recorded on plan_stream when plan + pre-render are done
     hipEvent_t consumed = nullptr;    // (not owned) ctx->mix_done[] of the render whose mix read this buffer
     bool consumed_valid = false;
   } pb[kRing];
   int cur = 0;
-  hipStream_t plan_stream = nullptr;
+  Stream plan_stream;
   DevBuf<float> d_zero;               // zero page (F+8 floats)
   uint32_t* levels_target = nullptr;  // [N][C] running per-track maxima (VUMeter::level), or null
   DevBuf<float> d_partial2[kRing];    // group partials, one per render in flight (a sum may still read an older one)
@@ -320,17 +301,17 @@ struct wbx_ctx {
   // and `alt_stream`, so that nothing orders mix i+1 after mix i and the head of one can fill the CUs the tail of the
   // other leaves idle.  Everything else stays on the main stream, which joins the alternate one (join_alt) wherever it
   // joins the sum stream.  Measured: no gain in step time, each kernel's own interval grows by ~45 %.
-  hipStream_t alt_stream = nullptr;
+  Stream alt_stream;
   hipStream_t cur_mix_stream = nullptr;   // the stream of the mix about to be / last launched
   int alt_pending = -1;                   // partial-buffer index of a mix on alt_stream the main stream has not joined
   // The sum of render i runs on its own stream beside the mix of render i+1 (it is PCIe-bound when the master goes to
   // host memory and needs few CUs).  sum_pending: a sum has been issued that the main stream has not waited for yet.
-  hipStream_t sum_stream = nullptr;
-  hipEvent_t mix_done[kRing] = {}, sum_done[kRing] = {};
+  Stream sum_stream;
+  Event mix_done[kRing], sum_done[kRing];
   // recorded right behind the sum KERNEL, in front of the copy that takes a staged master to host memory: from here on the
   // partial buffer may be written again.  What the next user of the buffer waits for (round 6) — sum_done lies behind the
   // copy, 8 MB over PCIe per 2048-block render: a 256-track session's plans waited 0.3 ms for it and its mixes 0.07 ms for them
-  hipEvent_t partial_free[kRing] = {};
+  Event partial_free[kRing];
   bool sum_valid[kRing] = {};
   int sum_pending = -1;
   uint32_t render_seq = 0;
@@ -352,7 +333,7 @@ struct wbx_ctx {
   uint32_t* cb_gave_up = nullptr;     // pinned word: the launch's number when one of its workgroups gave up at the spread barrier
   uint32_t cb_seq = 0;
   bool cb_launched = false;
-  uint32_t* d_cb_done = nullptr;      // device: "workgroups done" ticket counter, never reset: launches count from cb_base
+  DevBuf<uint32_t> d_cb_done;         // device: "workgroups done" ticket counter, never reset: launches count from cb_base
   uint32_t cb_base = 0;               // ... the first counter (every multi-group launch arrives there)
   uint32_t cb_base2 = 0;              // ... the second one (only launches whose workgroups each add a share of the master)
   uint64_t cb_launches = 0, cb_spread_launches = 0;   // one-launch callbacks issued / ... with the spread sum
@@ -386,7 +367,7 @@ struct wbx_ctx {
   const float* master_init = nullptr; // wbx_set_master_init: the running sum the first group starts from, or null: zero
 
   // kernel timing (mix kernel)
-  hipEvent_t ev[kEventRing][3]{};       // before the mix, after the mix, after the sum
+  Event ev[kEventRing][3];              // before the mix, after the mix, after the sum
   int ev_pending = 0;
   double mix_ms_total = 0.0;
   double gap_ms_total = 0.0;           // end of one mix -> start of the next, consecutive launches of one drain (wbx_gap_time)
@@ -410,9 +391,9 @@ struct wbx_ctx {
   std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.side.stream)
   SpliceStage splice;                     // wbx_clip_splice (under fx_mu, on fx.side.stream)
 
-  hipStream_t upload_stream = nullptr; // clip uploads of layer 2 run here, outside the engine's editor lock
-  hipEvent_t ready_ev = nullptr;       // wbx_master_ready: results of an in-stream sum, for a foreign stream
-  hipEvent_t pace_ev[kPaceRing] = {};  // wbx_pace
+  Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
+  Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
+  Event pace_ev[kPaceRing];            // wbx_pace
   uint64_t pace_seq = 0;
   // layer 2 back pointer: asks whether a clip list still names a sample (wbx_clip_free), null for a bare ctx
   bool (*sample_in_use)(void* owner, uint32_t sample) = nullptr;
@@ -475,9 +456,9 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
                       const ClipFill& f, hipStream_t on);
 wbx_status clip_publish(wbx_ctx* c, uint32_t clip, ClipSlot& s);
 void clip_release(wbx_ctx* c, ClipSlot& s);
-// side streams: side_prepare makes the stream and its events (at once if they exist; after a failure the struct is zeroed
+// side streams: side_prepare makes the stream and its events (at once if they exist; after a failure the struct is empty
 // again), side_order puts the stream behind everything enqueued so far on the streams that write the pool's clips (enqueues
-// only; layer 2 calls it under the editor lock), side_release waits for the stream and destroys all three
+// only; layer 2 calls it under the editor lock), side_release waits for the stream and empties the struct
 hipError_t side_prepare(wbx_ctx* c, SideStream& s);
 hipError_t side_order(wbx_ctx* c, SideStream& s);
 void side_release(SideStream& s);
@@ -529,13 +510,11 @@ wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_
                           int quality, ResamplePlan* plan, uint64_t* n_out, const char** why);
 wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
-void resample_release(wbx_ctx* c);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)
 wbx_status splice_run(wbx_ctx* c, const ClipSrc* srcs, const wbx_splice_part* parts, uint32_t n_parts, const SplicePlan& plan,
                       uint32_t channels, uint64_t n_frames, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
-void splice_release(wbx_ctx* c);
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it

@@ -22,16 +22,11 @@ struct wbx_engine {
   // pinned host buffers the plan kernel reads in place (one 16-B / 8-B read per lane): state patches and per-track
   // gains reach the device without a copy and, above all, without a stream synchronisation that would drain the
   // renders the audio thread has run ahead by.  Rings of three; a buffer is refilled only after the plan kernel that
-  // last read it has finished.
-  DPatch* h_patch[kRing] = {};
-  uint32_t patch_cap[kRing] = {};
-  hipEvent_t patch_done[kRing] = {};
-  bool patch_valid[kRing] = {};
+  // last read it has finished (PinnedSlot, wbx_res.h: wait before the refill, mark behind the plan).
+  PinnedSlot<DPatch> patch[kRing];
   uint32_t patch_seq = 0;
-  float* h_gains[kRing] = {};           // [N][2] fl(volume * pan_coeffs[c])
-  uint32_t gains_cap = 0;
-  hipEvent_t gains_done[kRing] = {};
-  bool gains_valid[kRing] = {};
+  PinnedSlot<float> gains[kRing];       // [N][2] fl(volume * pan_coeffs[c])
+  uint32_t tables_cap = 0;              // tracks all six buffers hold (ensure_pinned_tables grows them together)
   int gains_slot = -1;                  // the buffer plans currently read
   std::vector<float> gains_tmp;
   // the one-block callback reads the gains from a device copy (refreshed, in stream order, only when a parameter changed):
@@ -43,15 +38,12 @@ struct wbx_engine {
   // pinned table (one lane of the GPU beside a running mix took 0.15-0.2 ms for 2048 blocks).  A ring of eight: the host
   // runs at most that many renders ahead of the sequencer before it waits for a table's copy.
   static constexpr int kTimesRing = 8;
-  DBlockTime* h_times[kTimesRing] = {};
-  uint32_t times_cap[kTimesRing] = {};
-  hipEvent_t times_done[kTimesRing] = {};
-  bool times_valid[kTimesRing] = {};
+  PinnedSlot<DBlockTime> times[kTimesRing];   // (each grown by the render that needs it larger)
   uint32_t times_seq = 0;
   // Engine::process (one block per call): pinned, device-mapped host staging the sum kernel writes the block into
   // and the plan status lands in — the callback path then needs no copy-engine transfer at all
-  float* h_block = nullptr;             // [C][F]
-  uint32_t* h_status = nullptr;         // plan counters [4]; from [8]: the one-launch callback's completion words (its sequence
+  PinnedBuf<float> h_block;             // [C][F]
+  PinnedBuf<uint32_t> h_status;         // plan counters [4]; from [8]: the one-launch callback's completion words (its sequence
                                         // number, one word or one per workgroup), kCbFlags of them
   static constexpr uint32_t kCbFlags = 256;
   uint32_t cb_seq = 0;                  // ... of the last launch
@@ -68,9 +60,9 @@ struct wbx_engine {
   DevBuf<uint32_t> d_seg_stats;         // [2] tracks with a seam that did not hold, segments planned again
   DevBuf<uint32_t> d_seg_ticket;        // [max_tracks] SegArgs::ticket (all zero between launches)
   hipStream_t seam_stream = nullptr;    // the stream that used d_seam last
-  hipEvent_t seam_done = nullptr;
+  Event seam_done;
   bool table_flags = false;             // the uploaded clip table holds a set internal_state_changed flag (segmented plans off)
-  uint32_t* h_flags_left = nullptr;     // pinned: how many of them are left — the sequencer counts down as it clears them
+  PinnedBuf<uint32_t> h_flags_left;     // pinned: how many of them are left — the sequencer counts down as it clears them
   uint64_t seg_renders = 0;             // renders planned by segments so far
   uint32_t seg_last_segs = 0;           // ... segments per track of the last one
   uint32_t state_tracks = 0;            // tracks that have device state
@@ -86,14 +78,14 @@ struct wbx_engine {
   DevBuf<float> d_levels;               // [max_tracks][2] running maxima, same invariant
   // wbx_engine_levels (UI thread): the take kernel runs on a stream of its own into this pinned block; the editor lock
   // is held only while the take is ENQUEUED behind the renders in flight, never across the wait for it
-  hipStream_t levels_stream = nullptr;
-  hipEvent_t levels_ev = nullptr;
+  Stream levels_stream;
+  Event levels_ev;
   // the sequencer of render n+1 continues from the per-track state render n's left: on one stream that is the stream's
   // order; when the stream changes (short renders plan on the main stream, batch renders on the plan stream) the new one
   // waits for this event, recorded at the old one's tail
   hipStream_t last_plan_stream = nullptr;
-  hipEvent_t plan_handover = nullptr;
-  uint32_t* h_levels = nullptr;         // [max_tracks][2]
+  Event plan_handover;
+  PinnedBuf<uint32_t> h_levels;         // [max_tracks][2]
 
   // ---- recording (wbx_engine_record ... ; semantics in wbx_host.h, HostSession::takes) ----
   // A take is a table of chunks of the clip pool (F32, rec_chunk frames, zeroed when taken) in HBM.  The audio thread copies
@@ -111,12 +103,11 @@ struct wbx_engine {
   std::unique_ptr<RecTake[]> rec_takes;
   uint32_t rec_n = 0, rec_table_cap = 0, rec_in_ch = 0, rec_F = 0;
   DevBuf<RecChunk> d_rec_table;                // [rec_n][rec_table_cap]
-  RecChunk* h_rec_table = nullptr;             // pinned source of the table writes, same shape
-  size_t h_rec_table_cap = 0;
-  uint32_t* h_rec_stage = nullptr;             // pinned [kRecSlots][rec_slot_words]: samples, then the take descriptors
-  size_t rec_slot_words = 0, h_rec_stage_cap = 0;
-  hipEvent_t rec_ev[kRecSlots] = {};           // the capture that read the slot last
-  bool rec_ev_valid[kRecSlots] = {};
+  PinnedBuf<RecChunk> h_rec_table;             // pinned source of the table writes, same shape
+  PinnedBuf<uint32_t> h_rec_stage;             // pinned [kRecSlots][rec_slot_words]: samples, then the take descriptors
+  size_t rec_slot_words = 0;
+  PinnedSlot<uint32_t> rec_stage[kRecSlots];   // slot i is h_rec_stage + i * rec_slot_words (one allocation: their own buffers
+                                               // stay empty); done: the capture that read the slot last
   uint32_t rec_slot = 0;
   std::thread rec_thread;
   std::atomic<bool> rec_run{false};
@@ -173,7 +164,7 @@ wbx_status cfail(wbx_engine* e, wbx_status s) {
 uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing) {
   if (e->knobs.plan_seg == 0) return 0u;   // (WBX_PLAN_SEG as wbx_engine_create read it)
   const uint32_t forced = e->knobs.plan_seg > 0 ? (uint32_t)e->knobs.plan_seg : 0u;
-  if (e->table_flags && e->h_flags_left && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left) == 0u)
+  if (e->table_flags && e->h_flags_left.p && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left.p) == 0u)
     e->table_flags = false;   // every flag of the table has been cleared by a plan that is over
   if (!playing || e->table_flags || e->in_process || N == 0u || e->ctx->seg_broken) return 0u;
   if (forced) return forced < K ? forced : 0u;
@@ -208,9 +199,8 @@ extern "C" wbx_status wbx_engine_create(const wbx_config* cfg, wbx_engine** out)
   e->hs.plan_lanes_knob = e->knobs.plan_lanes;
   c->owner = e;
   c->sample_in_use = sample_in_use_cb;
-  if (hipStreamCreateWithFlags(&e->levels_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&e->levels_ev, kDevEventFlags) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_levels, (size_t)cfg->max_tracks * 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+  if (e->levels_stream.create(hipStreamNonBlocking) != hipSuccess || e->levels_ev.ensure(kDevEventFlags) != hipSuccess ||
+      e->h_levels.ensure((size_t)cfg->max_tracks * 2) != hipSuccess) {
     wbx_engine_destroy(e);
     return WBX_ERR_OOM;
   }
@@ -223,50 +213,20 @@ void rec_release(wbx_engine* e);
 void rec_discard_takes_locked(wbx_engine* e);
 }
 
+// The waits, then the engine's own holders (they go with `delete e`), then the context's: the engine's pinned tables and
+// events are used by work on the context's streams, so they are dropped first and the streams last.
 extern "C" void wbx_engine_destroy(wbx_engine* e) {
   if (!e) return;
-  if (e->ctx) {
-    (void)hipSetDevice(e->ctx->cfg.device);
+  wbx_ctx* c = e->ctx;
+  if (c) {
+    (void)hipSetDevice(c->cfg.device);
     rec_release(e);   // a take still running is discarded
+    (void)hipStreamSynchronize(c->plan_stream);
+    (void)sync_main(c);
   }
-  for (int i = 0; i < wbx_engine::kRecSlots; i++)
-    if (e->rec_ev[i]) (void)hipEventDestroy(e->rec_ev[i]);
-  if (e->h_rec_stage) (void)hipHostFree(e->h_rec_stage);
-  if (e->h_rec_table) (void)hipHostFree(e->h_rec_table);
-  e->d_rec_table.release();
-  if (e->ctx) {
-    (void)hipSetDevice(e->ctx->cfg.device);
-    (void)hipStreamSynchronize(e->ctx->plan_stream);
-    (void)sync_main(e->ctx);
-  }
-  if (e->levels_stream) {
-    (void)hipStreamSynchronize(e->levels_stream);
-    (void)hipStreamDestroy(e->levels_stream);
-  }
-  if (e->levels_ev) (void)hipEventDestroy(e->levels_ev);
-  if (e->plan_handover) (void)hipEventDestroy(e->plan_handover);
-  if (e->h_levels) (void)hipHostFree(e->h_levels);
-  e->d_clips.release();
-  e->d_clip_first.release();
-  e->d_state.release();
-  e->d_levels.release();
-  e->d_gains_cb.release();
-  for (int i = 0; i < kRing; i++) {
-    if (e->h_patch[i]) (void)hipHostFree(e->h_patch[i]);
-    if (e->patch_done[i]) (void)hipEventDestroy(e->patch_done[i]);
-    if (e->h_gains[i]) (void)hipHostFree(e->h_gains[i]);
-    if (e->gains_done[i]) (void)hipEventDestroy(e->gains_done[i]);
-  }
-  if (e->seam_done) (void)hipEventDestroy(e->seam_done);
-  if (e->h_flags_left) (void)hipHostFree(e->h_flags_left);
-  for (int i = 0; i < wbx_engine::kTimesRing; i++) {
-    if (e->h_times[i]) (void)hipHostFree(e->h_times[i]);
-    if (e->times_done[i]) (void)hipEventDestroy(e->times_done[i]);
-  }
-  if (e->h_block) (void)hipHostFree(e->h_block);
-  if (e->h_status) (void)hipHostFree(e->h_status);
-  wbx_destroy(e->ctx);
+  if (e->levels_stream) (void)hipStreamSynchronize(e->levels_stream);
   delete e;
+  wbx_destroy(c);
 }
 
 // Engine::set_audio_channel_config (engine.cpp:43-57) on a live engine: new block size / channel count / device rate,
@@ -313,10 +273,7 @@ extern "C" wbx_status wbx_engine_set_audio_channel_config(wbx_engine* e, uint32_
   WBX_EHIP(e, c->d_zero.ensure(buffer_size + 8));
   WBX_EHIP(e, hipMemset(c->d_zero.p, 0, (buffer_size + 8) * sizeof(float)));
   c->last_K = 0;
-  if (e->h_block) {
-    WBX_EHIP(e, hipHostFree(e->h_block));
-    e->h_block = nullptr;
-  }
+  e->h_block.release();
   if (e->d_levels.p) WBX_EHIP(e, hipMemset(e->d_levels.p, 0, e->d_levels.cap * sizeof(float)));
   // the destination rate enters every clip's playback speed: which clips the hot loop streams directly is re-derived
   e->hs.set_dst_rate_locked(sample_rate);
@@ -995,24 +952,19 @@ namespace {
 // not happen in mid-run
 wbx_status ensure_pinned_tables(wbx_engine* e, uint32_t N) {
   wbx_ctx* c = e->ctx;
-  if (e->gains_cap >= N && e->patch_cap[0] >= N) return WBX_OK;
+  if (e->tables_cap >= N) return WBX_OK;
   WBX_EHIP(e, hipStreamSynchronize(c->plan_stream));
   WBX_EHIP(e, sync_main(c));
   const uint32_t cap = std::max<uint32_t>(N, c->cfg.max_tracks);
   for (int i = 0; i < kRing; i++) {
-    if (e->h_patch[i]) WBX_EHIP(e, hipHostFree(e->h_patch[i]));
-    if (e->h_gains[i]) WBX_EHIP(e, hipHostFree(e->h_gains[i]));
-    e->h_patch[i] = nullptr;
-    e->h_gains[i] = nullptr;
-    WBX_EHIP(e, hipHostMalloc((void**)&e->h_patch[i], (size_t)cap * sizeof(DPatch), hipHostMallocDefault));
-    WBX_EHIP(e, hipHostMalloc((void**)&e->h_gains[i], (size_t)cap * 2 * sizeof(float), hipHostMallocDefault));
-    e->patch_cap[i] = cap;
-    e->patch_valid[i] = false;
-    e->gains_valid[i] = false;
-    if (!e->patch_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->patch_done[i], kDevEventFlags));
-    if (!e->gains_done[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->gains_done[i], kDevEventFlags));
+    WBX_EHIP(e, e->patch[i].buf.ensure(cap));
+    WBX_EHIP(e, e->gains[i].buf.ensure((size_t)cap * 2));
+    e->patch[i].forget();
+    e->gains[i].forget();
+    WBX_EHIP(e, e->patch[i].done.ensure(kDevEventFlags));
+    WBX_EHIP(e, e->gains[i].done.ensure(kDevEventFlags));
   }
-  e->gains_cap = cap;
+  e->tables_cap = cap;
   e->gains_slot = -1;
   e->hs.gains_dirty = true;   // the buffers are new: fill one
   return WBX_OK;
@@ -1073,9 +1025,9 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   //    (track.cpp:618-643); the factor used per sample is fl(volume * pan_coeffs[c]) (track.cpp:728-731)
   if (hs.drain_params_locked()) {
     const int slot = (e->gains_slot + 1) % kRing;
-    if (e->gains_valid[slot]) WBX_EHIP(e, hipEventSynchronize(e->gains_done[slot]));   // its last reader, >= 2 changes ago
+    WBX_EHIP(e, e->gains[slot].wait());   // its last reader, >= 2 changes ago
     hs.build_gains_locked(e->gains_tmp);
-    std::memcpy(e->h_gains[slot], e->gains_tmp.data(), e->gains_tmp.size() * sizeof(float));
+    std::memcpy(e->gains[slot].buf.p, e->gains_tmp.data(), e->gains_tmp.size() * sizeof(float));
     e->gains_slot = slot;
     e->gains_gen++;
   }
@@ -1096,10 +1048,10 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     WBX_EHIP(e, e->d_clip_first.ensure(N + 1));
     e->d_clips_count = e->flat.size();
     e->clips_uploaded = true;
-    if (!e->h_flags_left) WBX_EHIP(e, hipHostMalloc((void**)&e->h_flags_left, 64, hipHostMallocDefault));
+    WBX_EHIP(e, e->h_flags_left.ensure(16));
     uint32_t set_flags = 0;   // (both streams were drained above: nothing counts down right now)
     for (const DClip& dc : e->flat) set_flags += dc.internal_state_changed != 0 ? 1u : 0u;
-    *e->h_flags_left = set_flags;
+    *e->h_flags_left.p = set_flags;
     e->table_flags = set_flags != 0u;
     if (!e->flat.empty()) WBX_EHIP(e, hipMemcpy(e->d_clips.p, e->flat.data(), e->flat.size() * sizeof(DClip), hipMemcpyHostToDevice));
     WBX_EHIP(e, hipMemcpy(e->d_clip_first.p, e->first.data(), e->first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1124,9 +1076,9 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   int patch_slot = -1;
   if (hs.patches_pending) {
     patch_slot = (int)(e->patch_seq++ % kRing);
-    if (e->patch_valid[patch_slot]) WBX_EHIP(e, hipEventSynchronize(e->patch_done[patch_slot]));
-    hs.take_patches_locked(e->h_patch[patch_slot]);
-    d_patch = e->h_patch[patch_slot];
+    WBX_EHIP(e, e->patch[patch_slot].wait());
+    hs.take_patches_locked(e->patch[patch_slot].buf.p);
+    d_patch = e->patch[patch_slot].buf.p;
   }
 
   // -- routing
@@ -1193,16 +1145,16 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   a.samples = c->d_samples.p;
   a.state = e->d_state.p;
   a.patch = d_patch;
-  a.gains = e->h_gains[e->gains_slot];
+  a.gains = e->gains[e->gains_slot].buf.p;
   a.rows = B.prows.p;
   a.tmpl = B.tmpl.p;
-  a.tmpl_count = B.counters + 3;
+  a.tmpl_count = B.counters.p + 3;
   a.tmpl_cap = B.tmpl_cap;
   a.pool = B.pool.p;
-  a.pool_count = B.counters;
-  a.status = B.counters + 1;
+  a.pool_count = B.counters.p;
+  a.status = B.counters.p + 1;
   a.gen_list = B.gen_list.p;
-  a.gen_count = B.counters + 2;
+  a.gen_count = B.counters.p + 2;
   a.gen_cap = B.gen_cap;
   a.pool_chunks = B.pool_chunks;
   a.n_tracks = N;
@@ -1212,7 +1164,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   a.sample_rate = sample_rate;
   a.playing = playing ? 1u : 0u;
   a.clips_changed = hs.clips_edited ? 1u : 0u;
-  a.flags_left = e->h_flags_left;
+  a.flags_left = e->h_flags_left.p;
   hs.clips_edited = false;
   // clip boundaries inside a block stay in the hot loop when the mix instance of this render can take them
   a.masked_rows = shape.masked_rows;
@@ -1233,28 +1185,21 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     // search the records all the time: theirs stay in LDS (device-memory latency tripled their plan) with the roomy instance.
     WBX_EHIP(e, B.times.ensure(K));
     a.times = B.times.p;
-    const int ts = (int)(e->times_seq++ % wbx_engine::kTimesRing);
-    if (e->times_valid[ts]) WBX_EHIP(e, hipEventSynchronize(e->times_done[ts]));   // its copy of 8 renders ago (long over)
-    if (e->times_cap[ts] < K) {
-      if (e->h_times[ts]) (void)hipHostFree(e->h_times[ts]);
-      e->h_times[ts] = nullptr;
-      e->times_cap[ts] = 0;
-      WBX_EHIP(e, hipHostMalloc((void**)&e->h_times[ts], (size_t)K * sizeof(DBlockTime), hipHostMallocDefault));
-      e->times_cap[ts] = K;
-    }
-    if (!e->times_done[ts]) WBX_EHIP(e, hipEventCreateWithFlags(&e->times_done[ts], kDevEventFlags));
-    block_times(a, e->h_times[ts]);   // wbx_seq.h: the source the device compiles
-    launch_times_copy(e->h_times[ts], B.times.p, K, need_zero ? B.counters : nullptr, ps);
+    auto& T = e->times[e->times_seq++ % wbx_engine::kTimesRing];
+    WBX_EHIP(e, T.wait());   // its copy of 8 renders ago (long over)
+    WBX_EHIP(e, T.buf.ensure(K));
+    WBX_EHIP(e, T.done.ensure(kDevEventFlags));
+    block_times(a, T.buf.p);   // wbx_seq.h: the source the device compiles
+    launch_times_copy(T.buf.p, B.times.p, K, need_zero ? B.counters.p : nullptr, ps);
     need_zero = false;
-    WBX_EHIP(e, hipEventRecord(e->times_done[ts], ps));
-    e->times_valid[ts] = true;
+    WBX_EHIP(e, T.mark(ps));
   }
-  if (need_zero) WBX_EHIP(e, hipMemsetAsync(B.counters, 0, 4 * sizeof(uint32_t), ps));
+  if (need_zero) WBX_EHIP(e, hipMemsetAsync(B.counters.p, 0, 4 * sizeof(uint32_t), ps));
   if (e->last_plan_stream && e->last_plan_stream != ps) {
     // (found by the random-pieces test once it left renders unfetched: a batch render's plan, on the idle plan stream,
     //  overtook the plan of a short render still queued on the main stream behind earlier mixes and read the state before
     //  that one had written it)
-    if (!e->plan_handover) WBX_EHIP(e, hipEventCreateWithFlags(&e->plan_handover, kDevEventFlags));
+    WBX_EHIP(e, e->plan_handover.ensure(kDevEventFlags));
     WBX_EHIP(e, hipEventRecord(e->plan_handover, e->last_plan_stream));
     WBX_EHIP(e, hipStreamWaitEvent(ps, e->plan_handover, 0));
   }
@@ -1273,7 +1218,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   if (one_launch) {
     if (e->d_gains_cb_gen != e->gains_gen || e->d_gains_cb.cap < (size_t)N * 2) {
       WBX_EHIP(e, e->d_gains_cb.ensure(std::max<size_t>((size_t)c->cfg.max_tracks, N) * 2));
-      WBX_EHIP(e, hipMemcpyAsync(e->d_gains_cb.p, e->h_gains[e->gains_slot], (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, ps));
+      WBX_EHIP(e, hipMemcpyAsync(e->d_gains_cb.p, e->gains[e->gains_slot].buf.p, (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, ps));
       e->d_gains_cb_gen = e->gains_gen;
     }
     a.gains = e->d_gains_cb.p;
@@ -1282,7 +1227,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     // one lane per (track, segment); the lane that completes a track checks its seams; the seam states live in one buffer
     const size_t per = (size_t)N * n_segs;
     if (e->seam_stream && e->seam_stream != ps) {   // (its last user ran on the other stream)
-      if (!e->seam_done) WBX_EHIP(e, hipEventCreateWithFlags(&e->seam_done, kDevEventFlags));
+      WBX_EHIP(e, e->seam_done.ensure(kDevEventFlags));
       WBX_EHIP(e, hipEventRecord(e->seam_done, e->seam_stream));
       WBX_EHIP(e, hipStreamWaitEvent(ps, e->seam_done, 0));
     }
@@ -1309,12 +1254,8 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     launch_plan(a, ps);
   }
   if (!e->in_process) {
-    if (patch_slot >= 0) {
-      WBX_EHIP(e, hipEventRecord(e->patch_done[patch_slot], ps));
-      e->patch_valid[patch_slot] = true;
-    }
-    WBX_EHIP(e, hipEventRecord(e->gains_done[e->gains_slot], ps));   // (re-recorded by every plan that reads the buffer)
-    e->gains_valid[e->gains_slot] = true;
+    if (patch_slot >= 0) WBX_EHIP(e, e->patch[patch_slot].mark(ps));
+    WBX_EHIP(e, e->gains[e->gains_slot].mark(ps));   // (re-recorded by every plan that reads the buffer)
   }
   if (!e->gen_skipped) {
     st = launch_pre_render(c, ps);
@@ -1328,8 +1269,8 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   const int mix_parity = (int)(c->render_seq % kRing);
   c->cb_plan = one_launch ? &a : nullptr;
   if (one_launch) {
-    c->cb_flag = e->h_status + 8;
-    c->cb_gave_up = e->h_status + 7;
+    c->cb_flag = e->h_status.p + 8;
+    c->cb_gave_up = e->h_status.p + 7;
     c->cb_flag_cap = wbx_engine::kCbFlags;
     if (++e->cb_seq == 0u) ++e->cb_seq;   // (0 is what the completion and election words hold before any launch)
     c->cb_seq = e->cb_seq;
@@ -1430,7 +1371,7 @@ struct BounceDev {
     a.channels = C;
     if (N) {   // (an empty session has no plan: its master is silence, it has no track to name)
       WBX_EHIP(e, d_gains.ensure(std::max<size_t>((size_t)N * 2, 2)));
-      WBX_EHIP(e, hipMemcpyAsync(d_gains.p, e->h_gains[e->gains_slot], (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+      WBX_EHIP(e, hipMemcpyAsync(d_gains.p, e->gains[e->gains_slot].buf.p, (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, s));
       a.rows = B.prows.p;
       a.tmpl = B.tmpl.p;
       a.tmpl_cap = B.tmpl_cap;
@@ -1448,7 +1389,7 @@ struct BounceDev {
     drain_events(c);
     if (N) {
       uint32_t pc[4] = {0, 0, 0, 0};
-      WBX_EHIP(e, hipMemcpy(pc, B.counters, sizeof(pc), hipMemcpyDeviceToHost));
+      WBX_EHIP(e, hipMemcpy(pc, B.counters.p, sizeof(pc), hipMemcpyDeviceToHost));
       st = plan_status_to_error(c, pc[1]);
       if (st == WBX_OK) st = render_status(c);
       if (st != WBX_OK) return cfail(e, st);
@@ -1515,9 +1456,9 @@ wbx_status rec_fill(wbx_engine* e, uint64_t written) {
       const wbx_status st = clip_build(c, s, WBX_FMT_F32, t.channels, c->cfg.sample_rate, e->rec_chunk, f, c->upload_stream);
       if (st != WBX_OK) return st;
       const size_t i = (size_t)k * e->rec_table_cap + t.chunks.size();
-      e->h_rec_table[i].ch[0] = (uint32_t*)s.d.ch[0];
-      e->h_rec_table[i].ch[1] = (uint32_t*)s.d.ch[1];
-      if (hipMemcpyAsync(e->d_rec_table.p + i, e->h_rec_table + i, sizeof(RecChunk), hipMemcpyHostToDevice, c->upload_stream) !=
+      e->h_rec_table.p[i].ch[0] = (uint32_t*)s.d.ch[0];
+      e->h_rec_table.p[i].ch[1] = (uint32_t*)s.d.ch[1];
+      if (hipMemcpyAsync(e->d_rec_table.p + i, e->h_rec_table.p + i, sizeof(RecChunk), hipMemcpyHostToDevice, c->upload_stream) !=
           hipSuccess) {
         clip_release(c, s);
         return WBX_ERR_DEVICE;
@@ -1587,8 +1528,8 @@ void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
   const bool silence = !in || n_in < e->rec_in_ch;
   const uint64_t start = hs.capture_block_locked(F, silence);
   const uint32_t slot = e->rec_slot;
-  const bool slot_free = !e->rec_ev_valid[slot] || hipEventQuery(e->rec_ev[slot]) == hipSuccess;
-  uint32_t* stage = e->h_rec_stage + slot * e->rec_slot_words;
+  const bool slot_free = e->rec_stage[slot].idle();
+  uint32_t* stage = e->h_rec_stage.p + slot * e->rec_slot_words;
   uint32_t* desc = stage + (size_t)e->rec_in_ch * F;
   const uint64_t last_chunk = (start + F - 1) / e->rec_chunk;
   bool any = false;
@@ -1621,10 +1562,9 @@ void rec_capture_locked(wbx_engine* e, const float* const* in, uint32_t n_in) {
     a.table_cap = e->rec_table_cap;
     a.chunk_frames = e->rec_chunk;
     launch_record_capture(a, c->upload_stream);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(e->rec_ev[slot], c->upload_stream) != hipSuccess) {
+    if (hipGetLastError() != hipSuccess || e->rec_stage[slot].mark(c->upload_stream) != hipSuccess) {
       for (uint32_t k = 0; k < e->rec_n; k++) hs.take_status_locked(k, REC_OVERFLOW);
     } else {
-      e->rec_ev_valid[slot] = true;
       e->rec_slot = (slot + 1) % wbx_engine::kRecSlots;
       e->rec_captures++;
     }
@@ -1737,23 +1677,12 @@ extern "C" wbx_status wbx_engine_record(wbx_engine* e) {
     e->rec_table_cap = (uint32_t)std::min<uint64_t>(65536u, (2147483631ull + e->rec_chunk - 1) / e->rec_chunk + 1);
     const size_t table = (size_t)n * e->rec_table_cap;
     WBX_EHIP(e, e->d_rec_table.ensure(table));
-    if (e->h_rec_table_cap < table) {
-      if (e->h_rec_table) WBX_EHIP(e, hipHostFree(e->h_rec_table));
-      e->h_rec_table = nullptr;
-      WBX_EHIP(e, hipHostMalloc((void**)&e->h_rec_table, table * sizeof(RecChunk), hipHostMallocDefault));
-      e->h_rec_table_cap = table;
-    }
+    WBX_EHIP(e, e->h_rec_table.ensure(table));
     e->rec_slot_words = align_up((size_t)in_ch * F + n, 64);
-    const size_t stage = e->rec_slot_words * wbx_engine::kRecSlots;
-    if (e->h_rec_stage_cap < stage) {
-      if (e->h_rec_stage) WBX_EHIP(e, hipHostFree(e->h_rec_stage));
-      e->h_rec_stage = nullptr;
-      WBX_EHIP(e, hipHostMalloc((void**)&e->h_rec_stage, stage * sizeof(uint32_t), hipHostMallocDefault));
-      e->h_rec_stage_cap = stage;
-    }
-    for (int i = 0; i < wbx_engine::kRecSlots; i++) {
-      if (!e->rec_ev[i]) WBX_EHIP(e, hipEventCreateWithFlags(&e->rec_ev[i], hipEventDisableTiming));
-      e->rec_ev_valid[i] = false;
+    WBX_EHIP(e, e->h_rec_stage.ensure(e->rec_slot_words * wbx_engine::kRecSlots));
+    for (auto& S : e->rec_stage) {
+      WBX_EHIP(e, S.done.ensure(hipEventDisableTiming));
+      S.forget();
     }
     e->rec_slot = 0;
     e->rec_takes.reset(new wbx_engine::RecTake[n]);
@@ -1919,13 +1848,13 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
     ~Restore() { c->master_format = f; }
   } restore{c, saved_format};
   const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
-  if (!e->h_block) WBX_EHIP(e, hipHostMalloc((void**)&e->h_block, (size_t)C * F * sizeof(float), hipHostMallocDefault));
-  if (!e->h_status) {
-    WBX_EHIP(e, hipHostMalloc((void**)&e->h_status, (8 + wbx_engine::kCbFlags) * sizeof(uint32_t), hipHostMallocDefault));
-    std::memset(e->h_status, 0, (8 + wbx_engine::kCbFlags) * sizeof(uint32_t));
+  WBX_EHIP(e, e->h_block.ensure((size_t)C * F));
+  if (!e->h_status.p) {
+    WBX_EHIP(e, e->h_status.ensure(8 + wbx_engine::kCbFlags));
+    std::memset(e->h_status.p, 0, (8 + wbx_engine::kCbFlags) * sizeof(uint32_t));
   }
-  c->master_target = e->h_block;          // sum_kernel's stores go over PCIe into the staging block,
-  c->status_dst = e->h_status;            // and it drops the plan status next to it
+  c->master_target = e->h_block.p;        // sum_kernel's stores go over PCIe into the staging block,
+  c->status_dst = e->h_status.p;          // and it drops the plan status next to it
   e->in_process = true;
   c->zero_status = true;
   c->cb_launched = false;
@@ -1941,7 +1870,7 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       // completion signal between the device and the return of the callback; a launch that never reports (a device fault)
       // falls through to the stream's own error after two seconds
       // (one word, or one per workgroup when every workgroup stores a share of the master: all of them)
-      volatile uint32_t* flag = e->h_status + 8;
+      volatile uint32_t* flag = e->h_status.p + 8;
       const uint32_t n_flags = c->cb_flags, seq = e->cb_seq;
       const auto t0 = std::chrono::steady_clock::now();
       uint32_t spins = 0, have = 0;
@@ -1957,7 +1886,7 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
           }
           if (have < n_flags) {   // the launch never reported: start the ticket count afresh
             st = efail(e, WBX_ERR_DEVICE, "the one-launch callback did not report its block");
-            if (c->d_cb_done) (void)hipMemset(c->d_cb_done, 0, kCbDoneWords * sizeof(uint32_t));
+            if (c->d_cb_done.p) (void)hipMemset(c->d_cb_done.p, 0, kCbDoneWords * sizeof(uint32_t));
             c->cb_base = c->cb_base2 = 0;
           }
           break;
@@ -1968,10 +1897,10 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       st = WBX_ERR_DEVICE;
     }
     if (st == WBX_OK) {
-      PB(c).counters_zero = e->h_status[2] == 0u;   // (sum_kernel cleared them unless something was queued)
+      PB(c).counters_zero = e->h_status.p[2] == 0u;   // (sum_kernel cleared them unless something was queued)
       e->plan_status_on_host = true;
     }
-    if (st == WBX_OK && one_launch && e->h_status[7] == e->cb_seq) {
+    if (st == WBX_OK && one_launch && e->h_status.p[7] == e->cb_seq) {
       // A workgroup of the spread sum gave up waiting for the rest of its grid (the grid was not resident at once: a CU mask
       // the attribute does not show, a device shared with another process): shares of the master were added from incomplete
       // group sums.  The launch itself is over (its flag is the LAST workgroup's) and the plan is intact — the counters were
@@ -1984,12 +1913,12 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       c->zero_status = false;
       c->status_dst = nullptr;
       st = launch_mix_sum(c, 1, e->hs.n_tracks());
-      c->status_dst = e->h_status;
+      c->status_dst = e->h_status.p;
       if (st == WBX_OK && sync_main(c) != hipSuccess) st = WBX_ERR_DEVICE;
       PB(c).counters_zero = false;
       if (st != WBX_OK) tls_err = c->err;
     }
-    if (st == WBX_OK && e->gen_skipped && e->h_status[2] != 0u) {
+    if (st == WBX_OK && e->gen_skipped && e->h_status.p[2] != 0u) {
       // the block did queue records for the pre-render pass: run it now and mix again (the plan is untouched; the
       // first pass counted those records as silence, so the running levels hold nothing wrong)
       c->zero_status = false;
@@ -2005,18 +1934,18 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
   c->status_dst = nullptr;
   if (st != WBX_OK) return st;
   if (!one_launch) WBX_EHIP(e, sync_main(c));
-  for (int i = 0; i < kRing; i++) e->patch_valid[i] = e->gains_valid[i] = false;   // every plan that read them is over
+  for (int i = 0; i < kRing; i++) e->patch[i].forget(), e->gains[i].forget();   // every plan that read them is over
   drain_events(c);
   if (out_format == 0) {
-    for (uint32_t ch = 0; ch < C; ch++) std::memcpy(out_planar[ch], e->h_block + (size_t)ch * F, F * sizeof(float));
+    for (uint32_t ch = 0; ch < C; ch++) std::memcpy(out_planar[ch], e->h_block.p + (size_t)ch * F, F * sizeof(float));
   } else if (out_format == WBX_OUT_I24) {   // (the reference's writer leaves the other 3*F*(C-1) bytes of the block untouched)
-    std::memcpy(out_il, e->h_block, (size_t)F * 3);
+    std::memcpy(out_il, e->h_block.p, (size_t)F * 3);
   } else {
-    std::memcpy(out_il, e->h_block, (size_t)F * C * (out_format == WBX_OUT_I16 ? 2 : 4));
+    std::memcpy(out_il, e->h_block.p, (size_t)F * C * (out_format == WBX_OUT_I16 ? 2 : 4));
   }
   c->last_master_on_host = true;   // set after launch_mix_sum cleared it: the master of this block is e->h_block
   if (e->hs.n_tracks() == 0) return WBX_OK;
-  return cfail(e, plan_status_to_error(c, e->h_status[1]));
+  return cfail(e, plan_status_to_error(c, e->h_status.p[1]));
 }
 
 }  // namespace
@@ -2049,12 +1978,12 @@ extern "C" wbx_status wbx_engine_levels(wbx_engine* e, float* levels, uint32_t n
       WBX_EHIP(e, join_alt(c));
       WBX_EHIP(e, hipEventRecord(e->levels_ev, c->stream));
       WBX_EHIP(e, hipStreamWaitEvent(e->levels_stream, e->levels_ev, 0));
-      launch_levels_take(reinterpret_cast<uint32_t*>(e->d_levels.p), e->h_levels, have * C, e->levels_stream);
+      launch_levels_take(reinterpret_cast<uint32_t*>(e->d_levels.p), e->h_levels.p, have * C, e->levels_stream);
     }
   }
   if (have) {
     WBX_EHIP(e, hipStreamSynchronize(e->levels_stream));
-    std::memcpy(levels, e->h_levels, (size_t)have * C * sizeof(float));
+    std::memcpy(levels, e->h_levels.p, (size_t)have * C * sizeof(float));
   }
   if (n_tracks > have) std::memset(levels + (size_t)have * C, 0, (size_t)(n_tracks - have) * C * sizeof(float));
   return WBX_OK;
@@ -2126,9 +2055,9 @@ extern "C" wbx_status wbx_engine_fetch_plan(wbx_engine* e, wbx_plan_record* out,
   uint32_t pc[4] = {0, 0, 0, 0};
   WBX_EHIP(e, sync_main(c));
   if (e->plan_status_on_host)
-    std::memcpy(pc, e->h_status, sizeof(pc));
+    std::memcpy(pc, e->h_status.p, sizeof(pc));
   else
-    WBX_EHIP(e, hipMemcpy(pc, PB(c).counters, sizeof(pc), hipMemcpyDeviceToHost));
+    WBX_EHIP(e, hipMemcpy(pc, PB(c).counters.p, sizeof(pc), hipMemcpyDeviceToHost));
   std::vector<DRow> rows((size_t)K * N);
   const uint32_t nt = std::min(PB(c).static_tmpl ? 2u * N : pc[3], PB(c).tmpl_cap);
   std::vector<DTrackBlock> tmpl(nt);

@@ -24,6 +24,7 @@
 #include "wbx_sum.h"
 #include "wbx_callback.h"
 #include "wbx_render.h"
+#include "wbx_res.h"
 
 namespace wbx {
 
@@ -569,13 +570,13 @@ __global__ __launch_bounds__(64) void xcc_probe_kernel(uint32_t* out) {
 }
 bool probe_xcd_layout(hipStream_t s, uint32_t* n_xcds) {
   constexpr uint32_t kProbe = 64;
-  uint32_t* d = nullptr;
+  DevBuf<uint32_t> d;
   uint32_t h[kProbe];
   *n_xcds = 0;
-  if (hipMalloc((void**)&d, sizeof(h)) != hipSuccess) return false;
-  hipLaunchKernelGGL(xcc_probe_kernel, dim3(kProbe), dim3(64), 0, s, d);
-  const bool ok = hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-  (void)hipFree(d);
+  if (d.ensure(kProbe) != hipSuccess) return false;
+  hipLaunchKernelGGL(xcc_probe_kernel, dim3(kProbe), dim3(64), 0, s, d.p);
+  const bool ok = hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  d.release();
   if (!ok) return false;
   for (uint32_t period : {1u, 2u, 4u, 8u}) {
     bool fits = true, distinct = true;

@@ -127,17 +127,11 @@ wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_
   return WBX_OK;
 }
 
-void resample_release(wbx_ctx* c) {
-  for (ResampleTable& t : c->rs_tables)
-    if (t.d) (void)hipFree(t.d);
-  c->rs_tables.clear();
-}
-
 // the device copy of the plan's table, phase-visit order [k][r]; made at first use (uploaded on the edit stream, which every
 // run waits for before it returns) and kept for the context: a session converts between a handful of rates
 static hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int quality, const float** out, bool* fresh) {
   for (const ResampleTable& t : c->rs_tables)
-    if (t.L == p.L && t.M == p.M && t.quality == quality) return *out = t.d, hipSuccess;
+    if (t.L == p.L && t.M == p.M && t.quality == quality) return *out = t.d.p, hipSuccess;
   const size_t n = (size_t)p.L * p.T;
   ResampleTable t;
   t.L = p.L, t.M = p.M, t.quality = quality;
@@ -148,14 +142,10 @@ static hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int q
     const float* h = &phase[(size_t)(((uint64_t)r * p.M) % p.L) * p.T];
     for (uint32_t k = 0; k < p.T; k++) t.host[(size_t)k * p.L + r] = h[k];
   }
-  hipError_t e = hipMalloc((void**)&t.d, n * sizeof(float));
+  hipError_t e = t.d.ensure(n);
+  if (e == hipSuccess) e = hipMemcpyAsync(t.d.p, t.host.data(), n * sizeof(float), hipMemcpyHostToDevice, c->fx.side.stream);
   if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(t.d, t.host.data(), n * sizeof(float), hipMemcpyHostToDevice, c->fx.side.stream);
-  if (e != hipSuccess) {
-    (void)hipFree(t.d);
-    return e;
-  }
-  *out = t.d;
+  *out = t.d.p;
   *fresh = true;
   c->rs_tables.push_back(std::move(t));                        // (the vector's buffer moves with it: the copy's source stays put)
   return hipSuccess;
@@ -187,10 +177,7 @@ wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, i
   if (e == hipSuccess) e = w;
   if (fresh) std::vector<float>().swap(c->rs_tables.back().host);   // uploaded (or never will be)
   if (e != hipSuccess) {
-    if (fresh) {                                               // its upload may not have happened
-      (void)hipFree(c->rs_tables.back().d);
-      c->rs_tables.pop_back();
-    }
+    if (fresh) c->rs_tables.pop_back();                        // its upload may not have happened
     clip_release(c, slot);
     return stage_fail(why, WBX_ERR_DEVICE, "clip resample", e);
   }

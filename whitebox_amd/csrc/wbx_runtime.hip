@@ -268,7 +268,7 @@ wbx_status launch_pre_render(wbx_ctx* c, hipStream_t on) {
   ga.tmpl = PB(c).tmpl.p;
   ga.pool = PB(c).pool.p;
   ga.gen_list = PB(c).gen_list.p;
-  ga.gen_count = PB(c).counters + 2;
+  ga.gen_count = PB(c).counters.p + 2;
   ga.rows = PB(c).rows.p;
   ga.saved = PB(c).saved.p;
   ga.gen_cap = PB(c).gen_cap;
@@ -362,7 +362,7 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   if (fused) {
     m.fused_master = master_dst;
     m.fused_clamp = c->clamp ? 1u : 0u;
-    m.fused_status_src = c->status_dst ? PB(c).counters : nullptr;
+    m.fused_status_src = c->status_dst ? PB(c).counters.p : nullptr;
     m.fused_status_dst = c->status_dst;
     m.fused_zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
   }
@@ -380,8 +380,8 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     }
     m.chain_epoch = c->chain_epoch;
     m.chain = c->d_chain.p;
-    m.chain_status = PB(c).counters + 1;
-    m.chain_sticky = c->d_sticky_status;
+    m.chain_status = PB(c).counters.p + 1;
+    m.chain_sticky = c->d_sticky_status.p;
   }
   m.dbg_clock = nullptr;
   if (c->ck.dbg_clock) {   // diagnostic: per-workgroup start / end times of the mix
@@ -459,7 +459,7 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   s.channels = C;
   s.clamp = c->clamp ? 1u : 0u;
   s.chain = chained ? 1u : 0u;
-  s.status_src = c->status_dst ? PB(c).counters : nullptr;
+  s.status_src = c->status_dst ? PB(c).counters.p : nullptr;
   s.status_dst = c->status_dst;
   s.zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
   if (by_kernel_event) {   // (the mix on the main stream, its sum beside it: ss is the sum stream)
@@ -481,9 +481,9 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
   if (ss == c->stream && ms != c->stream) c->alt_pending = -1;            // (the main stream has just joined that mix)
   if (one_launch) {
     // sequencer + mix + sum in one dispatch; the kernel itself tells the host when master and status are out (cb_flag)
-    if (!c->d_cb_done) {
-      WBX_HIP(c, hipMalloc((void**)&c->d_cb_done, kCbDoneWords * sizeof(uint32_t)));   // (two spread counters: wbx_callback.h)
-      WBX_HIP(c, hipMemsetAsync(c->d_cb_done, 0, kCbDoneWords * sizeof(uint32_t), ms));
+    if (!c->d_cb_done.p) {
+      WBX_HIP(c, c->d_cb_done.ensure(kCbDoneWords));   // (two spread counters: wbx_callback.h)
+      WBX_HIP(c, hipMemsetAsync(c->d_cb_done.p, 0, kCbDoneWords * sizeof(uint32_t), ms));
       c->cb_base = c->cb_base2 = 0;
     }
     unsigned long long* cb_dbg = nullptr;
@@ -497,7 +497,7 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     // fit) and the engine's pinned block has a completion word for each of them
     const bool spread = !fused && !c->cb_no_spread && m.n_groups <= callback_spread_limit(c->n_cus, c->ck.cu_mask);
     c->cb_flags = 1u;
-    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->ck.cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
+    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done.p, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->ck.cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
     if (!name) return fail(c, WBX_ERR_FAILED, "the render's callback instance is not compiled in");
     c->mix_kernel_name = name;
     // (a one-group block takes no ticket; a grid larger than the device — "the last workgroup adds everything" — only the
@@ -594,19 +594,15 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
   c->ck = CtxKnobs::from_env();
   c->n_cus = (uint32_t)std::max(prop.multiProcessorCount, 0);
   if (cfg->stream) {
-    c->stream = (hipStream_t)cfg->stream;
-  } else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete c;
-      return WBX_ERR_DEVICE;
-    }
-    c->own_stream = true;
+    c->stream.adopt((hipStream_t)cfg->stream);
+  } else if (c->stream.create(hipStreamNonBlocking) != hipSuccess) {
+    delete c;
+    return WBX_ERR_DEVICE;
   }
   for (int i = 0; i < kEventRing; i++) {
     // (timing events: only their time stamps are read — no release to the system behind the kernel that carries them)
-    if (hipEventCreateWithFlags(&c->ev[i][0], hipEventReleaseToDevice) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev[i][1], hipEventReleaseToDevice) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev[i][2], hipEventReleaseToDevice) != hipSuccess) {
+    if (c->ev[i][0].ensure(hipEventReleaseToDevice) != hipSuccess || c->ev[i][1].ensure(hipEventReleaseToDevice) != hipSuccess ||
+        c->ev[i][2].ensure(hipEventReleaseToDevice) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_DEVICE;
     }
@@ -618,21 +614,20 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
     // takes from the bandwidth-bound mix are negligible.  (WBX_OVERLAP=0 runs everything on the main stream.)
     int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (hipStreamCreateWithPriority(&c->plan_stream, hipStreamNonBlocking, hi) != hipSuccess) {
+    if (c->plan_stream.create_with_priority(hipStreamNonBlocking, hi) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_DEVICE;
     }
     // the sum stream: highest priority as well — its few hundred small workgroups start while the next mix floods
     // the device.  (WBX_SUM_OVERLAP=0 keeps the sum on the main stream.)
-    bool ok = hipStreamCreateWithPriority(&c->sum_stream, hipStreamNonBlocking, hi) == hipSuccess;
+    bool ok = c->sum_stream.create_with_priority(hipStreamNonBlocking, hi) == hipSuccess;
     for (int i = 0; i < kRing && ok; i++)
-      ok = hipEventCreateWithFlags(&c->mix_done[i], kDevEventFlags) == hipSuccess &&
-           hipEventCreateWithFlags(&c->sum_done[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&c->partial_free[i], kDevEventFlags) == hipSuccess;
-    if (ok) ok = hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking) == hipSuccess;
+      ok = c->mix_done[i].ensure(kDevEventFlags) == hipSuccess && c->sum_done[i].ensure(hipEventDisableTiming) == hipSuccess &&
+           c->partial_free[i].ensure(kDevEventFlags) == hipSuccess;
+    if (ok) ok = c->upload_stream.create(hipStreamNonBlocking) == hipSuccess;
     // measured (tools/ab_alt.sh): with consecutive mixes on alternating streams the two kernels share the device for
     // their whole length (each takes 1.05-1.2 ms instead of 0.74) and the step time does not move — off by default
-    if (ok) ok = hipStreamCreateWithFlags(&c->alt_stream, hipStreamNonBlocking) == hipSuccess;
+    if (ok) ok = c->alt_stream.create(hipStreamNonBlocking) == hipSuccess;
     // the workgroup-id -> XCD layout the chained pieces and the segmented sequencer rest on, probed before anything relies on it
     if (ok && (!probe_xcd_layout(c->stream, &c->n_xcds) || c->ck.xcd_probe_fail)) {
       c->n_xcds = 0;
@@ -648,30 +643,30 @@ extern "C" wbx_status wbx_create(const wbx_config* cfg, wbx_ctx** out) {
                                     : std::max<size_t>(1024, (size_t)cfg->max_blocks * cfg->max_tracks / 8);
   for (auto& B : c->pb) {
     B.pool_chunks = (uint32_t)chunks;
-    if (B.pool.ensure(chunks * kChunk) != hipSuccess || hipMalloc((void**)&B.counters, 4 * sizeof(uint32_t)) != hipSuccess ||
-        hipEventCreateWithFlags(&B.planned, kDevEventFlags) != hipSuccess) {
+    if (B.pool.ensure(chunks * kChunk) != hipSuccess || B.counters.ensure(4) != hipSuccess ||
+        B.planned.ensure(kDevEventFlags) != hipSuccess) {
       wbx_destroy(c);
       return WBX_ERR_OOM;
     }
-    (void)hipMemset(B.counters, 0, 4 * sizeof(uint32_t));
+    (void)hipMemset(B.counters.p, 0, 4 * sizeof(uint32_t));
   }
-  if (c->d_zero.ensure(cfg->block_frames + 8) != hipSuccess || hipMalloc((void**)&c->d_sticky_status, sizeof(uint32_t)) != hipSuccess) {
+  if (c->d_zero.ensure(cfg->block_frames + 8) != hipSuccess || c->d_sticky_status.ensure(1) != hipSuccess) {
     wbx_destroy(c);
     return WBX_ERR_OOM;
   }
-  (void)hipMemset(c->d_sticky_status, 0, sizeof(uint32_t));
+  (void)hipMemset(c->d_sticky_status.p, 0, sizeof(uint32_t));
   (void)hipMemset(c->d_zero.p, 0, (cfg->block_frames + 8) * sizeof(float));
   *out = c;
   return WBX_OK;
 }
 
+// What is not ownership: the device, the waits, and the clip pool (whose storage the pool policy owns).  Everything else is
+// a holder of wbx_res.h and goes with the context; nothing runs any more when it does.
 extern "C" void wbx_destroy(wbx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->cfg.device);
   dist_destroy(c);
   export_release(c);
-  resample_release(c);
-  splice_release(c);
   clipfx_release(c);
   if (c->plan_stream) (void)hipStreamSynchronize(c->plan_stream);
   if (c->sum_stream) (void)hipStreamSynchronize(c->sum_stream);
@@ -683,50 +678,6 @@ extern "C" void wbx_destroy(wbx_ctx* c) {
   }
   for (auto& sl : c->slabs)
     if (sl->mem) (void)hipFree(sl->mem);
-  c->d_samples.release();
-  c->d_order.release();
-  c->d_groups.release();
-  for (auto& B : c->pb) {
-    B.prows.release();
-    B.tmpl.release();
-    B.pool.release();
-    B.times.release();
-    B.gen_list.release();
-    B.rows.release();
-    B.saved.release();
-    if (B.counters) (void)hipFree(B.counters);
-    if (B.planned) (void)hipEventDestroy(B.planned);
-  }
-  if (c->plan_stream) (void)hipStreamDestroy(c->plan_stream);
-  if (c->sum_stream) (void)hipStreamDestroy(c->sum_stream);
-  if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
-  if (c->alt_stream) (void)hipStreamDestroy(c->alt_stream);
-  if (c->ready_ev) (void)hipEventDestroy(c->ready_ev);
-  for (auto& ev : c->pace_ev)
-    if (ev) (void)hipEventDestroy(ev);
-  for (int i = 0; i < kRing; i++) {
-    if (c->mix_done[i]) (void)hipEventDestroy(c->mix_done[i]);
-    if (c->sum_done[i]) (void)hipEventDestroy(c->sum_done[i]);
-    if (c->partial_free[i]) (void)hipEventDestroy(c->partial_free[i]);
-  }
-  for (auto& P : c->d_partial2) P.release();
-  c->d_master.release();
-  for (auto& st : c->d_stage) st.release();
-  c->d_buses.release();
-  for (auto& P : c->d_peaks) P.release();
-  c->d_gains.release();
-  c->d_conv.release();
-  c->d_chain.release();
-  if (c->d_sticky_status) (void)hipFree(c->d_sticky_status);
-  if (c->d_cb_done) (void)hipFree(c->d_cb_done);
-  c->d_dbg.release();
-  c->d_zero.release();
-  for (int i = 0; i < kEventRing; i++) {
-    if (c->ev[i][0]) (void)hipEventDestroy(c->ev[i][0]);
-    if (c->ev[i][1]) (void)hipEventDestroy(c->ev[i][1]);
-    if (c->ev[i][2]) (void)hipEventDestroy(c->ev[i][2]);
-  }
-  if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -807,8 +758,8 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
   s.used = true;
   s.stride = stride;
   hipError_t err = hipSuccess;
-  void* stage[2] = {nullptr, nullptr};
-  hipEvent_t freed[2] = {nullptr, nullptr};
+  DevBuf<uint8_t> stage[2];
+  Event freed[2];
   auto pad_tails = [&]() {   // the padding frames (and the alignment slack) read as zero
     for (uint32_t ch = 0; ch < channels && err == hipSuccess; ch++)
       err = hipMemsetAsync((char*)s.base + stride * ch + frames * eb, 0, stride - frames * eb, on);
@@ -848,8 +799,8 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
       const size_t chunk_bytes = (size_t)chunk_frames * channels * eb;
       const int nstage = frames > chunk_frames ? 2 : 1;
       for (int i = 0; i < nstage && err == hipSuccess; i++) {
-        err = hipMalloc(&stage[i], std::min<size_t>(chunk_bytes, std::max<size_t>(16, (size_t)frames * channels * eb)));
-        if (err == hipSuccess) err = hipEventCreateWithFlags(&freed[i], hipEventDisableTiming);
+        err = stage[i].ensure(std::min<size_t>(chunk_bytes, std::max<size_t>(16, (size_t)frames * channels * eb)));
+        if (err == hipSuccess) err = freed[i].ensure(hipEventDisableTiming);
       }
       uint64_t done = 0;
       for (int i = 0; done < frames && err == hipSuccess; i++) {
@@ -857,21 +808,17 @@ wbx_status clip_build(wbx_ctx* c, ClipSlot& s, int format, uint32_t channels, ui
         const int b = i % nstage;
         if (i >= nstage) err = hipEventSynchronize(freed[b]);
         if (err == hipSuccess)
-          err = hipMemcpyAsync(stage[b], (const char*)f.interleaved + (size_t)done * channels * eb, (size_t)n * channels * eb,
+          err = hipMemcpyAsync(stage[b].p, (const char*)f.interleaved + (size_t)done * channels * eb, (size_t)n * channels * eb,
                                hipMemcpyHostToDevice, on);
         if (err == hipSuccess) {
-          launch_deinterleave(stage[b], (char*)s.base + (size_t)done * eb,
+          launch_deinterleave(stage[b].p, (char*)s.base + (size_t)done * eb,
                               (char*)s.base + (channels > 1 ? stride : 0) + (size_t)done * eb, n, channels, (uint32_t)eb, on);
           err = hipEventRecord(freed[b], on);
         }
         done += n;
       }
       if (err == hipSuccess) err = hipStreamSynchronize(on);
-      else (void)hipStreamSynchronize(on);   // nothing may still read the staging buffers freed below
-      for (int i = 0; i < 2; i++) {
-        if (stage[i]) (void)hipFree(stage[i]);
-        if (freed[i]) (void)hipEventDestroy(freed[i]);
-      }
+      else (void)hipStreamSynchronize(on);   // nothing may still read the staging buffers, freed at the function's end
       break;
     }
   }
@@ -1193,32 +1140,25 @@ static void export_free_slots(wbx_ctx* c) {
   ExportStage& x = c->exp;
   if (x.side.stream) (void)hipStreamSynchronize(x.side.stream);
   for (int i = 0; i < kExportSlots; i++) {
-    if (x.d_slot[i]) (void)hipFree(x.d_slot[i]);
-    if (x.h_slot[i]) (void)hipHostFree(x.h_slot[i]);
-    if (x.d_stats[i]) (void)hipFree(x.d_stats[i]);
-    x.d_slot[i] = x.h_slot[i] = nullptr;
-    x.d_stats[i] = nullptr;
+    x.d_slot[i].release();
+    x.h_slot[i].buf.release();
+    x.d_stats[i].release();
   }
-  if (x.h_stats) (void)hipHostFree(x.h_stats);
-  x.h_stats = nullptr;
+  x.h_stats.release();
   x.chunk = 0;
 }
 
 void wbx::export_release(wbx_ctx* c) {
-  ExportStage& x = c->exp;
-  export_free_slots(c);
-  for (auto& ev : x.done)
-    if (ev) (void)hipEventDestroy(ev);
-  side_release(x.side);
-  x = ExportStage{};
+  side_release(c->exp.side);
+  c->exp = ExportStage{};
 }
 
 // ---- side streams (wbx_ctx.h SideStream) ------------------------------------------------------------------------------
 hipError_t wbx::side_prepare(wbx_ctx* c, SideStream& s) {
   if (s.stream) return hipSuccess;
-  hipError_t e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_main, kDevEventFlags);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&s.after_upload, kDevEventFlags);
+  hipError_t e = s.stream.create(hipStreamNonBlocking);
+  if (e == hipSuccess) e = s.after_main.ensure(kDevEventFlags);
+  if (e == hipSuccess) e = s.after_upload.ensure(kDevEventFlags);
   if (e != hipSuccess) side_release(s);
   return e;
 }
@@ -1238,12 +1178,7 @@ hipError_t wbx::side_order(wbx_ctx* c, SideStream& s) {
 }
 
 void wbx::side_release(SideStream& s) {
-  if (s.stream) {
-    (void)hipStreamSynchronize(s.stream);
-    (void)hipStreamDestroy(s.stream);
-  }
-  if (s.after_main) (void)hipEventDestroy(s.after_main);
-  if (s.after_upload) (void)hipEventDestroy(s.after_upload);
+  if (s.stream) (void)hipStreamSynchronize(s.stream);
   s = SideStream{};
 }
 
@@ -1252,7 +1187,7 @@ wbx_status wbx::export_prepare(wbx_ctx* c, std::string* why) {
   (void)hipSetDevice(c->cfg.device);
   hipError_t e = side_prepare(c, x.side);
   for (int i = 0; i < kExportSlots && e == hipSuccess; i++)
-    if (!x.done[i]) e = hipEventCreateWithFlags(&x.done[i], hipEventDisableTiming);
+    e = x.h_slot[i].done.ensure(hipEventDisableTiming);
   if (e != hipSuccess) {
     export_release(c);
     return stage_fail(why, WBX_ERR_DEVICE, "export: stream and events", e);
@@ -1263,11 +1198,11 @@ wbx_status wbx::export_prepare(wbx_ctx* c, std::string* why) {
     export_free_slots(c);
     const size_t bytes = (size_t)want * 8u;   // two channels of 32 bits: the widest frame
     for (int i = 0; i < kExportSlots && e == hipSuccess; i++) {
-      e = hipMalloc(&x.d_slot[i], bytes);
-      if (e == hipSuccess) e = hipHostMalloc(&x.h_slot[i], bytes, hipHostMallocDefault);
-      if (e == hipSuccess) e = hipMalloc((void**)&x.d_stats[i], 8 * sizeof(uint32_t));
+      e = x.d_slot[i].ensure(bytes);
+      if (e == hipSuccess) e = x.h_slot[i].buf.ensure(bytes);
+      if (e == hipSuccess) e = x.d_stats[i].ensure(8);
     }
-    if (e == hipSuccess) e = hipHostMalloc((void**)&x.h_stats, kExportSlots * 8 * sizeof(uint32_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = x.h_stats.ensure(kExportSlots * 8);
     if (e != hipSuccess) {
       (void)hipGetLastError();
       export_free_slots(c);
@@ -1308,13 +1243,13 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
     const int b = (int)(k % kExportSlots);
     const uint64_t at = k * chunk;
     const uint32_t m = (uint32_t)std::min<uint64_t>(chunk, n_frames - at);
-    hipError_t e = hipMemsetAsync(x.d_stats[b], 0, 8 * sizeof(uint32_t), on);
+    hipError_t e = hipMemsetAsync(x.d_stats[b].p, 0, 8 * sizeof(uint32_t), on);
     if (e != hipSuccess) return e;
     ExportArgs a{};
     for (uint32_t ch = 0; ch < C; ch++) a.src[ch] = clip_row(src, ch) + first_frame + at;
     if (C == 1) a.src[1] = a.src[0];
-    a.dst = x.d_slot[b];
-    a.stats = x.d_stats[b];
+    a.dst = x.d_slot[b].p;
+    a.stats = x.d_stats[b].p;
     a.n_frames = m;
     a.channels = C;
     a.format = (uint32_t)out_format;
@@ -1322,19 +1257,19 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
     launch_export(a, on);
     e = hipGetLastError();
     if (e == hipSuccess)
-      e = hipMemcpyAsync(to_dst ? (void*)((char*)dst + (size_t)at * fb) : x.h_slot[b], x.d_slot[b], (size_t)m * fb,
+      e = hipMemcpyAsync(to_dst ? (void*)((char*)dst + (size_t)at * fb) : x.h_slot[b].buf.p, x.d_slot[b].p, (size_t)m * fb,
                          hipMemcpyDeviceToHost, on);
-    if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats + 8 * b, x.d_stats[b], 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, on);
-    if (e == hipSuccess) e = hipEventRecord(x.done[b], on);
+    if (e == hipSuccess) e = hipMemcpyAsync(x.h_stats.p + 8 * b, x.d_stats[b].p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, on);
+    if (e == hipSuccess) e = x.h_slot[b].mark(on);
     return e;
   };
   hipError_t e = hipSuccess;
   for (uint64_t k = 0; k < std::min<uint64_t>(kExportSlots - 1, n_chunks) && e == hipSuccess; k++) e = issue(k);
   for (uint64_t k = 0; k < n_chunks && e == hipSuccess; k++) {
     const int b = (int)(k % kExportSlots);
-    e = hipEventSynchronize(x.done[b]);
+    e = x.h_slot[b].wait();
     if (e != hipSuccess) break;
-    const uint32_t* hs = x.h_stats + 8 * b;
+    const uint32_t* hs = x.h_stats.p + 8 * b;
     for (uint32_t ch = 0; ch < C; ch++) {
       float pk;
       std::memcpy(&pk, hs + ch, sizeof(float));
@@ -1345,7 +1280,7 @@ wbx_status wbx::export_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame,
     if (k + kExportSlots - 1 < n_chunks) e = issue(k + kExportSlots - 1);   // (its slot was emptied one iteration ago)
     if (!to_dst) {
       const uint64_t at = k * chunk;
-      std::memcpy((char*)dst + (size_t)at * fb, x.h_slot[b], (size_t)std::min<uint64_t>(chunk, n_frames - at) * fb);
+      std::memcpy((char*)dst + (size_t)at * fb, x.h_slot[b].buf.p, (size_t)std::min<uint64_t>(chunk, n_frames - at) * fb);
     }
   }
   if (e != hipSuccess) {
@@ -1480,7 +1415,7 @@ extern "C" wbx_status wbx_submit(wbx_ctx* c, uint32_t K, uint32_t N, const wbx_s
   if (st != WBX_OK) return st;
   {
     uint32_t counters[4] = {0u, 0u, (uint32_t)gen_idx.size(), (uint32_t)((size_t)K * N)};
-    WBX_HIP(c, hipMemcpyAsync(PB(c).counters, counters, sizeof(counters), hipMemcpyHostToDevice, c->stream));
+    WBX_HIP(c, hipMemcpyAsync(PB(c).counters.p, counters, sizeof(counters), hipMemcpyHostToDevice, c->stream));
     if (!gen_idx.empty())
       WBX_HIP(c, hipMemcpyAsync(PB(c).gen_list.p, gen_idx.data(), gen_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     WBX_HIP(c, sync_main(c));   // counters / gen_idx are stack / local storage
@@ -1520,7 +1455,7 @@ extern "C" wbx_status wbx_master_ready(wbx_ctx* c, void* stream) {
   if (c->sum_pending >= 0) {   // the sum runs on its own stream: its event orders any stream
     WBX_HIP(c, hipStreamWaitEvent(on, c->sum_done[c->sum_pending], 0));
   } else {                     // everything is on the main stream: mark where it stands now
-    if (!c->ready_ev) WBX_HIP(c, hipEventCreateWithFlags(&c->ready_ev, hipEventDisableTiming));
+    WBX_HIP(c, c->ready_ev.ensure(hipEventDisableTiming));
     WBX_HIP(c, hipEventRecord(c->ready_ev, c->stream));
     WBX_HIP(c, hipStreamWaitEvent(on, c->ready_ev, 0));
   }
@@ -1555,11 +1490,11 @@ wbx_status wbx::plan_status_to_error(wbx_ctx* c, uint32_t bits) {
 // Chained renders report a failed hand-over through a word of the context that outlives their plan buffers: read it (the
 // streams are idle), clear it, turn it into the error — and into whole-list walks from then on.
 wbx_status wbx::render_status(wbx_ctx* c) {
-  if (!c->d_sticky_status || c->chain_epoch == 0u) return WBX_OK;   // (no chained render so far)
+  if (!c->d_sticky_status.p || c->chain_epoch == 0u) return WBX_OK;   // (no chained render so far)
   uint32_t bits = 0;
-  WBX_HIP(c, hipMemcpy(&bits, c->d_sticky_status, sizeof(bits), hipMemcpyDeviceToHost));
+  WBX_HIP(c, hipMemcpy(&bits, c->d_sticky_status.p, sizeof(bits), hipMemcpyDeviceToHost));
   if (!bits) return WBX_OK;
-  WBX_HIP(c, hipMemset(c->d_sticky_status, 0, sizeof(uint32_t)));
+  WBX_HIP(c, hipMemset(c->d_sticky_status.p, 0, sizeof(uint32_t)));
   return plan_status_to_error(c, bits & 96u);
 }
 
@@ -1598,7 +1533,7 @@ extern "C" wbx_status wbx_fetch(wbx_ctx* c, float* const* master_planar, float* 
   WBX_HIP(c, sync_main(c));
   drain_events(c);
   uint32_t pc[4] = {0, 0, 0, 0};
-  WBX_HIP(c, hipMemcpy(pc, PB(c).counters, sizeof(pc), hipMemcpyDeviceToHost));
+  WBX_HIP(c, hipMemcpy(pc, PB(c).counters.p, sizeof(pc), hipMemcpyDeviceToHost));
   const wbx_status rs = render_status(c);   // (an earlier, unfetched render's failure counts too)
   const wbx_status ps = plan_status_to_error(c, pc[1]);
   return ps != WBX_OK ? ps : rs;
@@ -1689,7 +1624,7 @@ extern "C" wbx_status wbx_pace(wbx_ctx* c, uint32_t max_ahead) {
   if (!c || max_ahead == 0 || max_ahead >= kPaceRing) return WBX_ERR_INVALID;
   (void)hipSetDevice(c->cfg.device);
   const uint32_t slot = (uint32_t)(c->pace_seq % kPaceRing);
-  if (!c->pace_ev[slot]) WBX_HIP(c, hipEventCreateWithFlags(&c->pace_ev[slot], kDevEventFlags));   // (the host waits for "done", reads nothing)
+  WBX_HIP(c, c->pace_ev[slot].ensure(kDevEventFlags));   // (the host waits for "done", reads nothing)
   // (behind the last render's sum when that runs on its own stream: no marker between two mixes)
   hipStream_t where = c->cur_mix_stream ? c->cur_mix_stream : c->stream;
   if (c->sum_pending >= 0 && c->sum_stream && !c->dist) where = c->sum_stream;

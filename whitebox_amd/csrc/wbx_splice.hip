@@ -157,12 +157,6 @@ void launch_splice(const SpliceArgs& a, hipStream_t s) {
 
 // ---- layer 1: the descriptors, the run ----------------------------------------------------------------------------------------
 
-void splice_release(wbx_ctx* c) {
-  c->splice.parts.release();
-  c->splice.tile_off.release();
-  c->splice.tile_parts.release();
-}
-
 // a part as the kernel reads it: the rows its output channels read, moved to the part's first source frame in 64 bits
 static SplicePartDev splice_part_dev(const ClipSrc& src, const wbx_splice_part& p) {
   const float* row[2] = {clip_row(src, 0) + p.first_frame, clip_row(src, 1) + p.first_frame};
