@@ -351,6 +351,83 @@ wbx_status wbx_splice_plan(uint32_t channels, uint64_t n_frames, const wbx_splic
 wbx_status wbx_clip_splice(wbx_ctx* ctx, uint32_t dst_clip, uint32_t channels, uint64_t n_frames,
                            const wbx_splice_part* parts, uint32_t n_parts, wbx_clip_stats* stats_of_result);
 
+/* Measuring a clip's loudness: ITU-R BS.1770-4 / EBU R 128 figures of frames [first_frame, first_frame + n) of a resident
+ * F32 clip of 1 or 2 channels at `rate` — integrated loudness, momentary and short-term maxima, loudness range (EBU Tech
+ * 3342) and true peak — without the samples leaving HBM: a bounce is delivered to a loudness target (-14, -16, -23 LUFS)
+ * under a true-peak ceiling, and wbx_clip_measure knows only the sample peak and a sum of squares.  No reference
+ * counterpart (dsp/dsp_ops.h stops at find_abs_maximum).  This text is the specification; tests/loudness_model.py restates
+ * it in numpy, and the coefficients, the hop energies, the powers, the counts and the true peak equal that BIT FOR BIT.
+ *   range     8000 <= rate <= 384000.  hop = (rate + 5) / 10 in integers (100 ms); hops = n / hop: only complete hops
+ *             count, trailing frames are ignored.  x is ZERO outside the range, whatever the clip holds there, and a frame
+ *             outside the range is never read.  A NaN sample enters the filter as 0.0
+ *   K filter  two biquads, coefficients in fp64 on the host:
+ *               stage 1 (shelf)      f0 = 1681.974450955533, Q = 0.7071752369554196, Vh = 1.5848647011308556,
+ *                                    Vb = 1.2587209302325617 (decimal literals, no pow);  K = tan(pi*f0/rate), KQ = K/Q, KK = K*K,
+ *                                    a0 = (1 + KQ) + KK;  b0 = ((Vh + Vb*KQ) + KK)/a0, b1 = (2*(KK - Vh))/a0,
+ *                                    b2 = ((Vh - Vb*KQ) + KK)/a0;  a1 = (2*(KK - 1))/a0, a2 = ((1 - KQ) + KK)/a0
+ *               stage 2 (high-pass)  f0 = 38.13547087602444, Q = 0.5003270373238773;  b = [1, -2, 1], a1 and a2 as above
+ *             tan is built from + - * / alone in a fixed number of steps (libm's last place differs between platforms):
+ *               y = (pi*f0) / (double)rate (pi = 3.141592653589793); y2 = y*y; s = c = 1;
+ *               for n = 13 .. 1: s = 1 - (s*y2) / ((2n)(2n+1)), c = 1 - (c*y2) / ((2n-1)(2n));  K = (y*s) / c
+ *             At 48000 Hz this is the standard's published table to its 14 decimals
+ *   energies  per channel c and hop h both stages run in fp64 from rest (all state 0), starting at frame (h - 2)*hop of
+ *             the range (frames below 0 are zero) through frame (h + 1)*hop - 1, direct form I, per stage
+ *               y = ((((b0*x + b1*x1) + b2*x2) - a1*y1) - a2*y2)
+ *             every * + - a single IEEE fp64 operation, nothing fused.  E[c][h] = the sum over the hop's own `hop` frames,
+ *             ascending, of e = e + v*v, v being stage 2's output.  The first three hops ARE one sequential pass; later
+ *             hops equal it to about 1e-14 relative (the filter's memory of what lies two hops back is below fp64's
+ *             resolution).  The segmented definition is the specification, not an approximation of one: hops are
+ *             independent of each other, which is what lets a lane own a hop
+ *   gate      on the host in fp64, on powers; log10 is called only on the final figures.  blocks = hops >= 4 ? hops - 3 : 0;
+ *             block j: s_c = ((E[c][j] + E[c][j+1]) + E[c][j+2]) + E[c][j+3], z_j = (s_0 [+ s_1]) / (double)(4*hop), both
+ *             channels at weight 1.0.  Absolute gate: z_j > 1.1724653045822981e-07 (= 10^((-70 + 0.691)/10)); m = the
+ *             ascending sum of the passing z_j divided by their count; relative gate: z_j > m * 0.1.  gated_power = the
+ *             ascending sum of the z_j that pass both, divided by their count (blocks_gated);
+ *             integrated = -0.691 + 10*log10(gated_power), -infinity when no block passes
+ *   momentary_max   the same formula over the largest z_j, ungated; -infinity without a block
+ *   short_term_max  windows of 30 hops starting at every hop: per channel s = 0, s = s + E[c][j+k] for k = 0 .. 29,
+ *                   w_c = s / (double)(30*hop); w_j = w_0 [+ w_1]; the formula over the largest w_j
+ *   range_lu        over the windows w_j at j = 0, 10, 20, ...: keep those above the absolute gate; then those above
+ *                   0.01 x (their ascending sum / their count); sort the n survivors ascending;
+ *                   lo = s[(size_t)((n-1)*0.10 + 0.5)], hi = s[(size_t)((n-1)*0.95 + 0.5)]; 10*log10(hi/lo); 0 when n < 2
+ *   true_peak       with WBX_LOUD_TRUE_PEAK, per channel.  factor = 4 below 96000 Hz, 2 below 192000, else 1 (`oversampling`).
+ *                   factor > 1: the largest |value| among the range's own samples and every output frame of
+ *                   "Converting a clip's sample rate" from rate to factor*rate at WBX_SRC_GOOD (L = factor, M = 1, T = 48,
+ *                   the same table, fp64 accumulation in ascending tap order, one rounding to fp32); nothing is stored.
+ *                   factor 1: the sample peak.  The maximum is taken by `a > peak` from 0 (wbx_clip_measure's rule: a NaN
+ *                   never raises it) and is independent of the order of reduction, hence exact.  A range cut hard out of a
+ *                   louder signal overshoots at its ends, legitimately; 0 when not asked for
+ * A range shorter than 4 hops is no error: blocks = 0 and integrated = -infinity.
+ * wbx_loudness_hop_frames (0 outside the supported rates), wbx_loudness_hops, wbx_loudness_coefficients (out[0..4] stage
+ * 1's b0 b1 b2 a1 a2, out[5..9] stage 2's; WBX_ERR_UNSUPPORTED outside the supported rates) and wbx_loudness_gate (E is
+ * [channels][hops]; fills every field but true_peak and oversampling, which become 0; WBX_ERR_INVALID: channels not 1 or 2,
+ * hop_frames == 0, NULL out, NULL E with hops > 0) are host-only and need no device.
+ * wbx_clip_loudness runs on the edits' stream behind wbx_clip_derive's ordering, one edit or measurement at a time, and
+ * returns when *out is complete.  hop_energy (may be NULL): E as the device wrote it, [channels][hops].
+ * Refused before any device call — WBX_ERR_INVALID: unknown clip, NULL out, n_frames == 0, a range past the clip, an unknown
+ * flag, cap_doubles below channels*hops when hop_energy is given; WBX_ERR_UNSUPPORTED: a source whose storage format is not
+ * F32, more than 2 channels, a rate outside 8000 .. 384000, with true peak factor*n_frames >= 2^31 - 16. */
+enum { WBX_LOUD_TRUE_PEAK = 1 };
+typedef struct wbx_loudness {   /* 80 bytes */
+  double integrated;         /*  0: LUFS */
+  double gated_power;        /*  8 */
+  double momentary_max;      /* 16: LUFS */
+  double short_term_max;     /* 24: LUFS */
+  double range_lu;           /* 32: LU */
+  float true_peak[2];        /* 40: linear */
+  uint64_t hops;             /* 48 */
+  uint64_t blocks;           /* 56 */
+  uint64_t blocks_gated;     /* 64 */
+  uint32_t hop_frames;       /* 72 */
+  uint32_t oversampling;     /* 76: the true peak's factor; 0 when not asked for */
+} wbx_loudness;
+uint32_t wbx_loudness_hop_frames(uint32_t rate);
+uint64_t wbx_loudness_hops(uint32_t rate, uint64_t n_frames);
+wbx_status wbx_loudness_coefficients(uint32_t rate, double out[10]);
+wbx_status wbx_loudness_gate(uint32_t channels, uint64_t hops, uint32_t hop_frames, const double* hop_energy, wbx_loudness* out);
+wbx_status wbx_clip_loudness(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t flags,
+                             wbx_loudness* out, double* hop_energy, size_t cap_doubles);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -759,6 +836,21 @@ wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample, uint64_t f
  * refusals are wbx_clip_splice's (there is no dst_clip to collide with). */
 wbx_status wbx_engine_splice_samples(wbx_engine* e, uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts,
                                      uint32_t n_parts, uint32_t* new_sample);
+/* wbx_clip_loudness of an engine sample, under wbx_engine_measure_sample's rules to the letter: editing thread, the audio
+ * thread may keep calling wbx_engine_process*; the editor lock is held only to validate, pin, order the stream and unpin,
+ * never across a device wait; wbx_engine_delete_sample refuses the source meanwhile ("sample is being edited"); no
+ * transport state is touched and no edit is counted.  Arguments, results and refusals are wbx_clip_loudness's.
+ *   normalize  measures the range (with true peak when true_peak_ceiling, linear, is not 0), takes
+ *              g = (float)pow(10.0, (target_lufs - integrated) / 20.0) and, with a ceiling,
+ *              g = min(g, ceiling / max(true_peak[0], true_peak[1])) as ONE IEEE fp32 division on the host (*gain_used, may be
+ *              NULL), and derives that range with it (WBX_CH_KEEP, no fade) as wbx_engine_normalize_sample does: *new_sample is
+ *              a fresh sample id.  WBX_ERR_INVALID, and no sample, when `integrated` is not finite (a silent range, one
+ *              shorter than 4 hops), when the gain is not finite and positive, or for a negative or NaN ceiling */
+wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t flags,
+                                      wbx_loudness* out, double* hop_energy, size_t cap_doubles);
+wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                double target_lufs, float true_peak_ceiling, uint32_t* new_sample,
+                                                float* gain_used);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

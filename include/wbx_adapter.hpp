@@ -336,6 +336,22 @@ struct Engine {
     check(wbx_engine_resample_sample(h, sample, first_frame, n_frames, dst_rate, quality, &id), "resample_sample");
     return id;
   }
+  // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
+  // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
+  // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like
+  // measure_sample and normalize_sample.
+  wbx_loudness loudness_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t flags = 0) {
+    wbx_loudness out{};
+    check(wbx_engine_loudness_sample(h, sample, first_frame, n_frames, flags, &out, nullptr, 0), "loudness_sample");
+    return out;
+  }
+  uint32_t normalize_loudness_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, double target_lufs,
+                                     float true_peak_ceiling = 0.0f, float* gain_used = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_normalize_loudness_sample(h, sample, first_frame, n_frames, target_lufs, true_peak_ceiling, &id, gain_used),
+          "normalize_loudness_sample");
+    return id;
+  }
   // A NEW sample made of parts of other samples (wbx.h "Splicing clips"): takes comped, two samples crossfaded (two
   // overlapping parts, one fading out, one fading in), samples joined, a loop repeated, silence inserted.  A part's src_clip
   // is a sample id.  Editing thread, like derive_sample; every source is pinned for the call; the id goes where a bounce's go.

@@ -72,6 +72,12 @@ class ResampleInfo(C.Structure):       # wbx_resample_info, 24 bytes
                 ("table_floats", C.c_uint64)]
 
 
+class Loudness(C.Structure):           # wbx_loudness, 80 bytes
+    _fields_ = [("integrated", C.c_double), ("gated_power", C.c_double), ("momentary_max", C.c_double),
+                ("short_term_max", C.c_double), ("range_lu", C.c_double), ("true_peak", C.c_float * 2), ("hops", C.c_uint64),
+                ("blocks", C.c_uint64), ("blocks_gated", C.c_uint64), ("hop_frames", C.c_uint32), ("oversampling", C.c_uint32)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -103,6 +109,7 @@ CH_MODE = {"keep": 0, "swap": 1, "left": 2, "right": 3, "mono_mix": 4, "dual_mon
 CH_MODE_OUT = {"swap": 2, "left": 1, "right": 1, "mono_mix": 1, "dual_mono": 2}          # channels of the result ("keep": the source's)
 FADE_SHAPE = {"linear": 0, "square": 1, "smooth": 2}    # WBX_FADE_*
 SRC_QUALITY = {"fast": 0, "good": 1, "best": 2}         # WBX_SRC_*
+LOUD_TRUE_PEAK = 1                                      # WBX_LOUD_TRUE_PEAK
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
 _vp, _u32, _i32, _f, _d, _sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_double, C.c_size_t
@@ -134,6 +141,11 @@ SYMBOLS = {
     "wbx_splice_plan": (C.c_int, [_u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(SpliceSource), _u32,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _sz, _vp, _sz]),
     "wbx_clip_splice": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(ClipStats)]),
+    "wbx_loudness_hop_frames": (_u32, [_u32]),
+    "wbx_loudness_hops": (C.c_uint64, [_u32, C.c_uint64]),
+    "wbx_loudness_coefficients": (C.c_int, [_u32, _vp]),
+    "wbx_loudness_gate": (C.c_int, [_u32, C.c_uint64, _u32, _vp, C.POINTER(Loudness)]),
+    "wbx_clip_loudness": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -226,6 +238,9 @@ SYMBOLS = {
     "wbx_engine_derive_sample": (C.c_int, [_vp, _u32, C.POINTER(ClipEditDesc), C.POINTER(_u32)]),
     "wbx_engine_normalize_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, C.POINTER(_u32), C.POINTER(_f)]),
     "wbx_engine_resample_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(_u32)]),
+    "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
+    "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
+                                                       C.POINTER(_f)]),
     "wbx_engine_splice_samples": (C.c_int, [_vp, _u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(_u32)]),
     "wbx_clip_pool_limit": (C.c_int, [_vp, C.c_uint64]),
     "wbx_engine_set_input_channels": (C.c_int, [_vp, _u32]),

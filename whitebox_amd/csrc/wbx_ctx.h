@@ -18,6 +18,7 @@
 #include "../../include/wbx.h"
 #include "wbx_dev.h"
 #include "wbx_shape.h"
+#include "wbx_loudness.h"
 #include "wbx_resample.h"
 #include "wbx_splice.h"
 #include "wbx_pool.h"
@@ -124,6 +125,24 @@ struct ResampleArgs {
   uint32_t tile, span, n_tiles;   // filled by launch_resample: outputs per tile, floats staged per channel and tile, tiles
 };
 void launch_resample(ResampleArgs a, hipStream_t s);
+// measuring a clip's loudness (wbx_loudness.hip): hop energies behind the K filter, and the oversampled peak
+struct LoudnessArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  double* energy;              // device: [channels][hops]
+  double coef[10];             // wbx_loudness.h: stage 1's b0 b1 b2 a1 a2, stage 2's
+  uint32_t hop, hops;          // frames per hop (800 .. 38400) / complete hops of the range (>= 1; hops * hop < 2^31)
+  uint32_t channels;           // 1 or 2
+};
+void launch_loudness(const LoudnessArgs& a, hipStream_t s);
+struct TruePeakArgs {
+  const float* src[2];         // as above
+  const float* table;          // device: resample_kernel's table for rate -> factor * rate, [T][L]
+  uint32_t* peak;              // device: bits of the largest |value| per channel — zero before the launch
+  uint32_t n_in;               // frames of the range; n_in * L < 2^31 - 16
+  uint32_t L, H, T;            // the plan: factor (4 or 2), 24, 48
+  uint32_t channels;
+};
+void launch_true_peak(const TruePeakArgs& a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -226,6 +245,14 @@ struct ResampleTable {
   int quality = 0;
   DevBuf<float> d;
   std::vector<float> host;     // the upload's source, until the stream has been waited for
+};
+
+// wbx_clip_loudness's results on the device and in pinned memory — grown on demand, freed with the context
+struct LoudnessStage {
+  DevBuf<double> d_energy;
+  PinnedBuf<double> h_energy;
+  DevBuf<uint32_t> d_peak;     // 2 words
+  PinnedBuf<uint32_t> h_peak;
 };
 
 // wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
@@ -390,6 +417,7 @@ struct wbx_ctx {
   std::mutex fx_mu;
   std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.side.stream)
   SpliceStage splice;                     // wbx_clip_splice (under fx_mu, on fx.side.stream)
+  LoudnessStage loud;                     // wbx_clip_loudness (under fx_mu, on fx.side.stream)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -510,6 +538,19 @@ wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_
                           int quality, ResamplePlan* plan, uint64_t* n_out, const char** why);
 wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
+// the device copy of a plan's table in resample_kernel's order, made on the edit stream at first use and kept (*fresh: this
+// call uploaded it, from rs_tables.back().host, which must outlive the stream's next wait)
+hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int quality, const float** out, bool* fresh);
+// measuring a clip's loudness (wbx_loudness.hip), cut the same way: the checks make no device call; the run works under
+// fx_mu on the edit stream behind clipfx_prepare / clipfx_order and waits for the device
+struct LoudnessPlan {
+  uint32_t rate = 0, hop = 0, factor = 0;   // factor: 0 without true peak
+  uint64_t hops = 0;
+};
+wbx_status loudness_check(const ClipSrc& src, uint32_t rate, uint64_t first_frame, uint64_t n_frames, uint32_t flags,
+                          const wbx_loudness* out, const double* hop_energy, size_t cap_doubles, LoudnessPlan* plan, const char** why);
+wbx_status loudness_run(wbx_ctx* c, const ClipSrc& src, const LoudnessPlan& p, uint64_t first_frame, uint64_t n_frames,
+                        wbx_loudness* out, double* hop_energy, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -620,6 +620,12 @@ struct SamplePin {
     if (st == WBX_OK) st = clipfx_measure_run(e->ctx, src, first_frame, n_frames, out, why);
     return st;
   }
+  wbx_status loudness(const LoudnessPlan& plan, uint64_t first_frame, uint64_t n_frames, wbx_loudness* out, double* hop_energy,
+                      std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = loudness_run(e->ctx, src, plan, first_frame, n_frames, out, hop_energy, why);
+    return st;
+  }
   wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
     wbx_status st = order(clipfx_prepare, clipfx_order, why);
     ClipSlot slot;
@@ -751,6 +757,74 @@ extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample,
   if (st == WBX_OK) st = p.publish(slot, p.src.channels, dst_rate, n_out, new_sample, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
+}
+
+// wbx_clip_loudness of an engine sample (wbx.h "Measuring a clip's loudness"), beside wbx_engine_measure_sample and under its
+// rules: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
+extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                 uint32_t flags, wbx_loudness* out, double* hop_energy, size_t cap_doubles) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  LoudnessPlan plan;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "loudness_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = loudness_check(p.src, p.rate, first_frame, n_frames, flags, out, hop_energy, cap_doubles, &plan, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.loudness(plan, first_frame, n_frames, out, hop_energy, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// ... and the range derived at the gain that brings its integrated loudness to target_lufs, under a true-peak ceiling:
+// wbx_engine_normalize_sample with another measurement in front
+extern "C" wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                           double target_lufs, float true_peak_ceiling, uint32_t* new_sample,
+                                                           float* gain_used) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: new_sample is NULL");
+  if (!(true_peak_ceiling >= 0.0f)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: a negative ceiling, or a NaN");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  wbx_clip_edit_desc d{};
+  d.first_frame = first_frame;
+  d.n_frames = n_frames;
+  d.channel_mode = WBX_CH_KEEP;
+  uint32_t out_channels = 0;
+  LoudnessPlan plan;
+  wbx_loudness m{};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "normalize_loudness_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = loudness_check(p.src, p.rate, first_frame, n_frames, true_peak_ceiling > 0.0f ? (uint32_t)WBX_LOUD_TRUE_PEAK : 0u, &m, nullptr,
+                        0, &plan, &msg);
+    if (st == WBX_OK) st = clipfx_check_derive(p.src, &d, &out_channels, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "normalize_loudness_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  wbx_status st = p.loudness(plan, first_frame, n_frames, &m, nullptr, &why);
+  if (st != WBX_OK) return tls_err = why, st;
+  if (!std::isfinite(m.integrated)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: the range has no integrated loudness (silent, or shorter than 4 hops)");
+  float g = (float)std::pow(10.0, (target_lufs - m.integrated) / 20.0);
+  if (true_peak_ceiling > 0.0f) {
+    const float peak = out_channels > 1 && m.true_peak[1] > m.true_peak[0] ? m.true_peak[1] : m.true_peak[0];
+    const float top = true_peak_ceiling / peak;   // one IEEE fp32 division (no fast-math in this build)
+    if (top < g) g = top;
+  }
+  if (!(g > 0.0f) || !std::isfinite(g)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: the gain is not finite and positive");
+  d.gain = g;
+  st = p.derive(d, out_channels, new_sample, &why);
+  if (st != WBX_OK) return tls_err = why, st;
+  if (gain_used) *gain_used = g;
+  return WBX_OK;
 }
 
 // wbx_clip_splice of engine samples (wbx.h "Splicing clips"), under wbx_engine_derive_sample's rules: the editor lock covers

@@ -129,7 +129,7 @@ wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_
 
 // the device copy of the plan's table, phase-visit order [k][r]; made at first use (uploaded on the edit stream, which every
 // run waits for before it returns) and kept for the context: a session converts between a handful of rates
-static hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int quality, const float** out, bool* fresh) {
+hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int quality, const float** out, bool* fresh) {
   for (const ResampleTable& t : c->rs_tables)
     if (t.L == p.L && t.M == p.M && t.quality == quality) return *out = t.d.p, hipSuccess;
   const size_t n = (size_t)p.L * p.T;

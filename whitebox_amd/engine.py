@@ -154,6 +154,49 @@ def resample_table(src_rate: int, dst_rate: int, quality="good") -> np.ndarray:
     return out
 
 
+def loudness_hops(rate: int, n_frames: int) -> int:
+    """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
+    the supported rates 8000 .. 384000"""
+    return int(_ffi.lib().wbx_loudness_hops(rate, n_frames))
+
+
+def loudness_coefficients(rate: int) -> np.ndarray:
+    """wbx_loudness_coefficients (host-only): the K filter's [10] fp64 coefficients at `rate` — stage 1's b0 b1 b2 a1 a2, then
+    stage 2's"""
+    out = np.zeros(10, dtype=np.float64)
+    _check(_ffi.lib().wbx_loudness_coefficients(rate, out.ctypes.data), "wbx_loudness_coefficients")
+    return out
+
+
+def _loudness(st, channels: int) -> dict:
+    """wbx_loudness -> a dict of its fields; "true_peak" one float32 per channel"""
+    out = {k: getattr(st, k) for k, _ in _ffi.Loudness._fields_ if k != "true_peak"}
+    out["true_peak"] = [np.float32(st.true_peak[c]) for c in range(channels)]
+    return out
+
+
+def loudness_gate(hop_energy: np.ndarray, hop_frames: int) -> dict:
+    """wbx_loudness_gate (host-only): the BS.1770 gate over hop energies [channels][hops] (fp64) — every field of
+    wbx_loudness but the true peak"""
+    E = np.ascontiguousarray(hop_energy, dtype=np.float64)
+    assert E.ndim == 2
+    st = _ffi.Loudness()
+    _check(_ffi.lib().wbx_loudness_gate(E.shape[0], E.shape[1], hop_frames, E.ctypes.data if E.size else None, C.byref(st)),
+           "wbx_loudness_gate")
+    out = _loudness(st, 0)
+    del out["true_peak"], out["oversampling"]
+    return out
+
+
+def _run_loudness(fn, what, h, engine, ident, channels, rate, first_frame, n_frames, true_peak, energies):
+    st = _ffi.Loudness()
+    E = np.zeros((channels, loudness_hops(rate, n_frames)), dtype=np.float64) if energies else None
+    _check(fn(h, ident, first_frame, n_frames, _ffi.LOUD_TRUE_PEAK if true_peak else 0, C.byref(st),
+              E.ctypes.data if energies else None, E.size if energies else 0), what, h, engine)
+    out = _loudness(st, channels)
+    return (out, E) if energies else out
+
+
 def _clip_stats(st, channels: int) -> dict:
     """wbx_clip_stats -> {"peak", "peak_frame", "min", "max", "over", "nans", "sum", "sum_sq"}, one entry per channel"""
     f32 = ("peak", "min", "max")
@@ -250,6 +293,15 @@ class MixContext:
                                         _ffi.SRC_QUALITY.get(quality, quality), C.byref(st) if stats_channels else None),
                "wbx_clip_resample", self.h)
         return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
+                      energies: bool = False):
+        """wbx_clip_loudness: ITU-R BS.1770-4 / EBU R 128 figures of frames [first_frame, first_frame + n_frames) of a
+        resident F32 clip uploaded at `rate`, measured on the device: {"integrated", "gated_power", "momentary_max",
+        "short_term_max", "range_lu", "true_peak", "hops", "blocks", "blocks_gated", "hop_frames", "oversampling"}; the true
+        peak only with `true_peak`.  With `energies` returns (dict, the hop energies [channels][hops] as the device wrote them)"""
+        return _run_loudness(self.L.wbx_clip_loudness, "wbx_clip_loudness", self.h, False, clip, channels, rate, first_frame,
+                             n_frames, true_peak, energies)
 
     def clip_splice(self, dst_clip: int, channels: int, n_frames: int, parts, stats: bool = False):
         """wbx_clip_splice: `dst_clip` becomes a new F32 clip of `channels` x `n_frames` frames, the parts
@@ -781,6 +833,39 @@ class Engine:
         new, gain = C.c_uint32(), C.c_float()
         _check(self.L.wbx_engine_normalize_sample(self.h, sample, first_frame, n_frames, target_peak, C.byref(new), C.byref(gain)),
                "wbx_engine_normalize_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return new.value, float(gain.value)
+
+    def loudness_sample(self, sample: int, first_frame: int = 0, n_frames: Optional[int] = None, true_peak=False,
+                        energies: bool = False, channels: Optional[int] = None, frames: Optional[int] = None,
+                        rate: Optional[int] = None):
+        """wbx_engine_loudness_sample — see MixContext.clip_loudness; `frames` / `channels` as in export_sample, `rate` the
+        sample's rate where this object did not make it (needed with `energies` only).  May be called while another thread
+        runs process(); delete_sample of the sample is refused meanwhile."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "loudness_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        return _run_loudness(self.L.wbx_engine_loudness_sample, "wbx_engine_loudness_sample", self.h, True, sample, channels,
+                             rate, first_frame, n_frames, true_peak, energies)
+
+    def normalize_loudness_sample(self, sample: int, target_lufs: float, true_peak_ceiling: float = 0.0, first_frame: int = 0,
+                                  n_frames: Optional[int] = None, channels: Optional[int] = None,
+                                  frames: Optional[int] = None) -> tuple:
+        """wbx_engine_normalize_loudness_sample: a new sample = the range brought to `target_lufs` integrated loudness, the
+        gain capped so that its true peak stays at or below `true_peak_ceiling` (linear; 0: no ceiling); returns (new sample
+        id, the gain used).  A range without an integrated loudness (silent, shorter than 400 ms) raises WbxError (-4)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "normalize_loudness_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        new, gain = C.c_uint32(), C.c_float()
+        _check(self.L.wbx_engine_normalize_loudness_sample(self.h, sample, first_frame, n_frames, target_lufs, true_peak_ceiling,
+                                                           C.byref(new), C.byref(gain)),
+               "wbx_engine_normalize_loudness_sample", self.h, True)
         self._sample_shape[new.value] = (n_frames, channels)
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
