@@ -343,7 +343,7 @@ struct HsimShape {
   char mix[64], callback[64];   // the instances' names as nm -C spells them
   uint32_t family, masked_rows, walks_lists, chained, blocks_per_workgroup, mix_sb, cb_one_launch, cb_lane_span;
 };
-int hsim_render_shape(HostSim* s, uint32_t K, uint32_t group_size, uint32_t n_buses, uint32_t longest_list, int in_process, HsimShape* out) {
+int hsim_render_shape(HostSim* s, uint32_t K, uint32_t group_size, uint32_t n_buses, uint32_t longest_list, int process_block, HsimShape* out) {
   if (K == 0 || K > s->max_blocks) return WBX_ERR_INVALID;
   LockGuard g(s->hs.editor_lock);
   ShapeFacts f;
@@ -360,7 +360,7 @@ int hsim_render_shape(HostSim* s, uint32_t K, uint32_t group_size, uint32_t n_bu
   f.longest_list = longest_list;
   f.n_blocks = K;
   f.n_tracks = s->hs.n_tracks();
-  f.callback = in_process != 0 && !s->hs.any_slow_clip;
+  f.callback = process_block != 0 && !s->hs.any_slow_clip;
   const RenderShape r = choose_shape(ShapeKnobs::from_env(), f);
   r.mix.name(out->mix, sizeof(out->mix));
   r.cb.name(out->callback, sizeof(out->callback));
@@ -384,6 +384,45 @@ void hsim_shape_knobs(HsimKnobs* out) {
   const ShapeKnobs k = ShapeKnobs::from_env();
   *out = HsimKnobs{k.ragged_off, k.cb_any_off, k.masked_rows_off, k.chain_off, k.no_lean16, k.no_fam3, k.no_cl2, k.callback_unfused,
                    k.force_cut, k.force_g, k.packed_x, k.mix_variant, k.cb_u, (int32_t)k.exact_min_blocks};
+}
+
+// How a render is issued (wbx_shape.h: choose_issue).  The numbers are passed as they are; the boolean facts and the five
+// CtxKnobs that enter (and `overlap`, which must not) as one word — bit 0 chained, 1 cb_one_launch, 2 callback_plan, 3 dist,
+// 4 init, 5 target_set, 6 target_on_host, 7 mix_on_main, 8 cb_no_spread, 9 sum_overlap, 10 profiling, 11 mix_alternate,
+// 12 cu_mask, 13 overlap (kIssueBits of them).
+constexpr uint32_t kIssueBits = 14;
+struct HsimIssue {
+  uint32_t sum_beside, fused, timed, one_launch, by_kernel_event, spread;
+  uint64_t stage_bytes;
+};
+static RenderIssue issue_of(uint32_t K, uint32_t n_groups, uint32_t n_buses, uint32_t tiles, uint32_t F, uint32_t C, int format, uint32_t n_cus,
+                            uint32_t bits) {
+  IssueFacts f;
+  f.K = K, f.n_groups = n_groups, f.n_buses = n_buses, f.tiles = tiles, f.block_frames = F, f.channels = C;
+  f.master_format = format;
+  f.n_cus = n_cus;
+  f.chained = bits >> 0 & 1u, f.cb_one_launch = bits >> 1 & 1u, f.callback_plan = bits >> 2 & 1u, f.dist = bits >> 3 & 1u;
+  f.init = bits >> 4 & 1u, f.target_set = bits >> 5 & 1u, f.target_on_host = bits >> 6 & 1u, f.mix_on_main = bits >> 7 & 1u;
+  f.cb_no_spread = bits >> 8 & 1u;
+  CtxKnobs k;
+  k.sum_overlap = bits >> 9 & 1u, k.profiling = bits >> 10 & 1u, k.mix_alternate = bits >> 11 & 1u, k.cu_mask = bits >> 12 & 1u;
+  k.overlap = bits >> 13 & 1u;
+  return choose_issue(k, f);
+}
+void hsim_render_issue(uint32_t K, uint32_t n_groups, uint32_t n_buses, uint32_t tiles, uint32_t F, uint32_t C, int format, uint32_t n_cus,
+                       uint32_t bits, HsimIssue* out) {
+  const RenderIssue r = issue_of(K, n_groups, n_buses, tiles, F, C, format, n_cus, bits);
+  *out = HsimIssue{r.sum_beside, r.fused, r.timed, r.one_launch, r.by_kernel_event, r.spread, r.stage_bytes};
+}
+// ... for every value of the word at once: flags[bits] = sum_beside | fused << 1 | timed << 2 | one_launch << 3 |
+// by_kernel_event << 4 | spread << 5, stage[bits] = stage_bytes (1 << kIssueBits entries each)
+void hsim_render_issue_all(uint32_t K, uint32_t n_groups, uint32_t n_buses, uint32_t tiles, uint32_t F, uint32_t C, int format, uint32_t n_cus,
+                           uint8_t* flags, uint64_t* stage) {
+  for (uint32_t bits = 0; bits < (1u << kIssueBits); bits++) {
+    const RenderIssue r = issue_of(K, n_groups, n_buses, tiles, F, C, format, n_cus, bits);
+    flags[bits] = (uint8_t)(r.sum_beside | r.fused << 1 | r.timed << 2 | r.one_launch << 3 | r.by_kernel_event << 4 | r.spread << 5);
+    stage[bits] = r.stage_bytes;
+  }
 }
 
 // plan status bits of the last render (PlanArgs::status) and the number of templates / pre-render rows it used
@@ -535,7 +574,7 @@ int main() {
   };
   const HsimKnobs d = flat();
   ok = ok && std::memcmp(&d, std::array<int32_t, 14>{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, -1, 0, 0, 1024}.data(), sizeof d) == 0;
-  uint64_t shapes = 0;
+  uint64_t shapes = 0, issues = 0;
   auto sweep = [&] {   // choose_shape over sessions x block shapes x render lengths, the knobs as the environment sets them
     const ShapeKnobs k = ShapeKnobs::from_env();
     for (uint32_t bits = 0; bits < 64u; bits++)
@@ -565,9 +604,26 @@ int main() {
             r.mix.name(name, sizeof name);
             r.cb.name(name, sizeof name);
             shapes += r.mix.key() != 0u;
+            // ... and how that render is issued (choose_issue): no group, one, more than the spread limit, over a thinned fact word
+            for (uint32_t n_groups : {0u, 1u, 257u})
+              for (uint32_t bits = 0; bits < (1u << kIssueBits); bits += 331u) {
+                const RenderIssue is = issue_of(K, n_groups, f.n_buses, r.tiles, F, C, (bits & 1u) ? WBX_OUT_I16 : 0, K == 8u ? 64u : 304u,
+                                                bits ^ (r.chained ? 1u : 0u));
+                issues += is.stage_bytes != 0u || is.sum_beside || !is.spread;
+              }
           }
   };
   sweep();
+  // choose_issue over every value of the fact word, at both sides of the 4 MiB staging edge (blocks of 512 x 2 in 16 bits:
+  // 2048 of them are 4 MiB, 2047 are not) and of the spread limit
+  for (uint32_t K : {1u, 7u, 8u, 2047u, 2048u})
+    for (uint32_t n_groups : {0u, 1u, 256u, 257u})
+      for (int format : {0, (int)WBX_OUT_I16, (int)WBX_OUT_I24})
+        for (uint32_t bits = 0; bits < (1u << kIssueBits); bits++) {
+          const RenderIssue is = issue_of(K, n_groups, bits & 2u, 1u + (bits & 1u), 512u, 2u, format, 256u, bits);
+          issues += is.stage_bytes != 0u || is.sum_beside || !is.spread;
+          if (is.stage_bytes != 0u && (K < 2047u || format == (int)WBX_OUT_I24 || (K == 2047u && format == (int)WBX_OUT_I16))) ok = false;
+        }
   for (size_t i = 0; i < std::size(kShape); i++) {   // each switch flips its own field and no other
     setenv(kShape[i][0], kShape[i][1], 1);
     const HsimKnobs h = flat();
@@ -591,7 +647,8 @@ int main() {
   ok = ok && e1.plan_seg == 0 && e1.plan_lanes == 16u && dist_init_timeout_s() == 2.5;   // (WBX_PLAN_SEG: max(0, atoi))
   setenv("WBX_PLAN_LANES", "3", 1);
   ok = ok && EngineKnobs::from_env().plan_lanes == 0u;   // (not a power of two up to 64: ignored)
-  std::printf(ok ? "host_knobs ok %llu\n" : "host_knobs FAILED %llu\n", (unsigned long long)shapes);
+  ok = ok && issues != 0u;
+  std::printf(ok ? "host_knobs ok %llu %llu\n" : "host_knobs FAILED %llu %llu\n", (unsigned long long)shapes, (unsigned long long)issues);
   return ok ? 0 : 1;
 }
 #endif

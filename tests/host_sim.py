@@ -69,6 +69,37 @@ def build_knobs_main(out: str) -> str:
     return out
 
 
+class RenderIssue(C.Structure):
+    """hsim_render_issue's result (tests/cpp/host_sim.cpp HsimIssue): RenderIssue of wbx_shape.h"""
+    _fields_ = [(n, C.c_uint32) for n in ("sum_beside", "fused", "timed", "one_launch", "by_kernel_event", "spread")] + [
+        ("stage_bytes", C.c_uint64)]
+
+
+# the boolean facts and knobs of choose_issue in the order of hsim_render_issue's `bits` word, and its results in the order of
+# hsim_render_issue_all's flag byte
+ISSUE_BITS = ("chained", "cb_one_launch", "callback_plan", "dist", "init", "target_set", "target_on_host", "mix_on_main",
+              "cb_no_spread", "sum_overlap", "profiling", "mix_alternate", "cu_mask", "overlap")
+ISSUE_FLAGS = ("sum_beside", "fused", "timed", "one_launch", "by_kernel_event", "spread")
+
+
+def render_issue(k, n_groups, n_buses, tiles, frames, channels, fmt, n_cus, **bools) -> RenderIssue:
+    """choose_issue (wbx_shape.h) for one set of facts; bools: the names of ISSUE_BITS that are true"""
+    assert set(bools) <= set(ISSUE_BITS)
+    bits = sum(1 << i for i, n in enumerate(ISSUE_BITS) if bools.get(n))
+    out = RenderIssue()
+    lib().hsim_render_issue(k, n_groups, n_buses, tiles, frames, channels, fmt, n_cus, bits, C.byref(out))
+    return out
+
+
+def render_issue_all(k, n_groups, n_buses, tiles, frames, channels, fmt, n_cus):
+    """... for every value of the `bits` word: (flag bytes [1 << len(ISSUE_BITS)], stage_bytes [same])"""
+    n = 1 << len(ISSUE_BITS)
+    flags, stage = np.empty(n, np.uint8), np.empty(n, np.uint64)
+    lib().hsim_render_issue_all(k, n_groups, n_buses, tiles, frames, channels, fmt, n_cus,
+                                flags.ctypes.data_as(C.POINTER(C.c_uint8)), stage.ctypes.data_as(C.POINTER(C.c_uint64)))
+    return flags, stage
+
+
 def shape_knobs() -> dict:
     """ShapeKnobs::from_env() as this process's environment stands now"""
     k = ShapeKnobs()
@@ -93,6 +124,11 @@ def lib() -> C.CDLL:
         L.hsim_segment_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.hsim_shape_knobs.restype = None
         L.hsim_shape_knobs.argtypes = [C.POINTER(ShapeKnobs)]
+        issue_facts = [C.c_uint32] * 6 + [C.c_int, C.c_uint32]
+        L.hsim_render_issue.restype = None
+        L.hsim_render_issue.argtypes = issue_facts + [C.c_uint32, C.POINTER(RenderIssue)]
+        L.hsim_render_issue_all.restype = None
+        L.hsim_render_issue_all.argtypes = issue_facts + [C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
         sig = {
             "hsim_set_bpm": [C.c_double], "hsim_set_playhead_position": [C.c_double],
             "hsim_add_track": [C.POINTER(C.c_uint32)],

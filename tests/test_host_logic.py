@@ -259,3 +259,83 @@ def test_resource_holders_balance_under_address_and_ub_sanitizers(tmp_path):
     assert out.returncode == 0, out.stdout[-4000:] + out.stderr[-4000:]
     lines = out.stdout.splitlines()
     assert lines[-1] == "res_main ok" and len(lines) == 9 and "FAILED" not in out.stdout
+
+
+# ---- how a render is issued: choose_issue (wbx_shape.h) against its rules written out again --------------------------------------
+OUT_I16, OUT_I24 = 3, 5          # WBX_OUT_* (include/wbx.h)
+OVERLAP_MIN_BLOCKS = 8           # kOverlapMinBlocks: renders shorter than this stay on the main stream
+
+
+def _issue_rules(K, n_groups, n_buses, tiles, F, Ch, fmt, n_cus, b):
+    """the seven rules, over arrays of the boolean facts and knobs `b` (name -> bool array); -> (name -> bool array, stage_bytes)"""
+    sum_beside = b["sum_overlap"] & (K >= OVERLAP_MIN_BLOCKS)
+    fused = ~b["dist"] & ~b["init"] & ~b["chained"] & (K < OVERLAP_MIN_BLOCKS and n_groups == 1 and n_buses == 0 and tiles == 1 and fmt == 0)
+    timed = b["profiling"] & (K > 1)
+    one_launch = b["callback_plan"] & b["cb_one_launch"] & (n_groups != 0)
+    by_kernel_event = ~one_launch & timed & ~b["dist"] & ~b["mix_alternate"] & b["mix_on_main"] & sum_beside & (n_groups != 0)
+    nbytes = K * F * Ch * (2 if fmt == OUT_I16 else 4)
+    staged = sum_beside & ~b["dist"] & b["target_set"] & b["target_on_host"] & (fmt != OUT_I24 and nbytes >= 4 << 20)
+    limit = np.where(b["cu_mask"], 0, min(n_cus, 256))
+    spread = one_launch & ~fused & ~b["cb_no_spread"] & (n_groups <= limit)
+    return dict(sum_beside=sum_beside, fused=fused, timed=timed, one_launch=one_launch, by_kernel_event=by_kernel_event,
+                spread=spread), np.where(staged, nbytes, 0).astype(np.uint64)
+
+
+def test_render_issue_matches_its_rules_over_the_full_cross_product():
+    """choose_issue == the rules for K x n_groups x n_buses x tiles x format x (F, C) x n_cus x every boolean fact and knob both
+    ways (`overlap` included: it must not enter); the 4 MiB staging edge is hit from both sides"""
+    import itertools
+    import host_sim as HS
+    word = np.arange(1 << len(HS.ISSUE_BITS), dtype=np.uint32)
+    b = {n: (word >> i & 1).astype(bool) for i, n in enumerate(HS.ISSUE_BITS)}
+    cases = 0
+    for K, n_groups, n_buses, tiles, fmt, (F, Ch), n_cus in itertools.product(
+            (1, 7, 8, 2047, 2048), (0, 1, 2, 256, 257), (0, 2), (1, 2), (0, 3, 5, 7), ((512, 2), (128, 1)), (64, 256, 304)):
+        flags, stage = HS.render_issue_all(K, n_groups, n_buses, tiles, F, Ch, fmt, n_cus)
+        want, want_stage = _issue_rules(K, n_groups, n_buses, tiles, F, Ch, fmt, n_cus, b)
+        for i, name in enumerate(HS.ISSUE_FLAGS):
+            got = (flags >> i & 1).astype(bool)
+            assert np.array_equal(got, want[name]), (name, K, n_groups, n_buses, tiles, fmt, F, Ch, n_cus, int(word[got != want[name]][0]))
+        assert np.array_equal(stage, want_stage), (K, n_groups, n_buses, tiles, fmt, F, Ch, n_cus)
+        assert not (flags >> len(HS.ISSUE_FLAGS)).any()
+        cases += len(word)
+    assert cases == 5 * 5 * 2 * 2 * 4 * 2 * 3 * 2 ** 14
+    # the staging edge, by name: 2048 blocks of 512 x 2 in fp32 (8 MiB) and in 16 bits (4 MiB exactly) are staged, 2047 are not
+    host = dict(sum_overlap=True, target_set=True, target_on_host=True, mix_on_main=True, profiling=True)
+    assert HS.render_issue(2048, 32, 0, 1, 512, 2, 0, 256, **host).stage_bytes == 8 << 20
+    assert HS.render_issue(2048, 32, 0, 1, 512, 2, OUT_I16, 256, **host).stage_bytes == 4 << 20
+    assert HS.render_issue(2047, 32, 0, 1, 512, 2, OUT_I16, 256, **host).stage_bytes == 0
+    assert HS.render_issue(2047, 32, 0, 1, 512, 2, 0, 256, **host).stage_bytes == 2047 * 512 * 2 * 4
+    assert HS.render_issue(2048, 32, 0, 1, 512, 2, OUT_I24, 256, **host).stage_bytes == 0
+    # ... and the one-block callback of a 64-group session: one launch, spread, nothing beside the main stream
+    cb = HS.render_issue(1, 64, 0, 1, 512, 2, 0, 256, callback_plan=True, cb_one_launch=True, sum_overlap=True, profiling=True, mix_on_main=True)
+    assert (cb.one_launch, cb.spread, cb.fused, cb.sum_beside, cb.timed, cb.by_kernel_event, cb.stage_bytes) == (1, 1, 0, 0, 0, 0, 0)
+
+
+# the per-call inputs and results launch_mix_sum once took from / left in wbx_ctx, wbx_engine's flag that said "inside
+# wbx_engine_process", and the spare completion words: deleted (RenderCall, wbx_ctx.h)
+DELETED_CTX_FIELDS = ("partial_wait_done", "cb_plan", "cb_flag", "cb_gave_up", "cb_seq", "cb_flag_cap", "cb_flags", "cb_launched",
+                      "status_dst", "zero_status")
+DELETED_ENGINE_NAMES = ("in_process", "kCbFlags")
+# names that live on elsewhere, as other structs' members: SumArgs::status_dst / zero_status (wbx_dev.h, what the kernels read)
+# and wbx_engine::cb_seq (the number of the last one-launch callback) — for these the test is "no member of wbx_ctx, and
+# reached through no context pointer"
+SURVIVING_ELSEWHERE = ("cb_seq", "status_dst", "zero_status")
+
+
+def test_deleted_context_fields_are_named_nowhere():
+    """none of the ten deleted wbx_ctx fields, nor wbx_engine's in_process / kCbFlags, under whitebox_amd/csrc, include or
+    tests/cpp: as a word anywhere, or — the three names other structs keep — in wbx_ctx's body or behind `c->` / `ctx->`"""
+    import re
+    paths = [p for top in (CSRC, os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp")) for p in _files(top)]
+    assert len(paths) > 30 and len(DELETED_CTX_FIELDS) == 10
+    gone = [n for n in DELETED_CTX_FIELDS + DELETED_ENGINE_NAMES if n not in SURVIVING_ELSEWHERE]
+    anywhere = re.compile(r"\b(?:%s)\b" % "|".join(gone))
+    through_ctx = re.compile(r"\b(?:c|ctx)\s*(?:->|\.)\s*(?:%s)\b" % "|".join(SURVIVING_ELSEWHERE))
+    hits = [(os.path.relpath(p, ROOT), m.group(0)) for p in paths for t in [_text(p)] for rx in (anywhere, through_ctx) for m in rx.finditer(t)]
+    assert not hits, hits
+    ctx_h = _text(os.path.join(CSRC, "wbx_ctx.h"))
+    body = ctx_h[ctx_h.index("struct wbx_ctx {"):ctx_h.index("inline wbx_ctx::PlanBuf& PB(")]
+    assert len(body) > 5000
+    assert not re.findall(r"\b(?:%s)\b" % "|".join(DELETED_CTX_FIELDS), body)
+    assert "struct RenderCall" in ctx_h and "choose_issue" in _text(os.path.join(CSRC, "wbx_shape.h"))

@@ -35,7 +35,6 @@ void launch_sum(const SumArgs& a, uint32_t n_blocks, hipStream_t s);
 // the one-block callback as one launch (wbx_callback.h): sequencer + mix + sum + completion flag -> the instance's name
 const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s, uint32_t* done, uint32_t done_base, uint32_t done_base2,
                             bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st);
-uint32_t callback_spread_limit(uint32_t n_cus, bool cu_mask);   // grids of at most this many workgroups are resident at once
 void launch_clamp(float* buf, size_t n, hipStream_t s);
 void launch_clamp_into(const float* src, float* dst, size_t n, int clamp, hipStream_t s);
 void launch_convert(const float* master, void* dst, uint32_t n_blocks, uint32_t F, uint32_t C, int fmt, hipStream_t s);
@@ -329,7 +328,7 @@ struct wbx_ctx {
   // other leaves idle.  Everything else stays on the main stream, which joins the alternate one (join_alt) wherever it
   // joins the sum stream.  Measured: no gain in step time, each kernel's own interval grows by ~45 %.
   Stream alt_stream;
-  hipStream_t cur_mix_stream = nullptr;   // the stream of the mix about to be / last launched
+  hipStream_t cur_mix_stream = nullptr;   // the stream of the last mix (launch_mix_sum): what wbx_pace marks and the alternation reads
   int alt_pending = -1;                   // partial-buffer index of a mix on alt_stream the main stream has not joined
   // The sum of render i runs on its own stream beside the mix of render i+1 (it is PCIe-bound when the master goes to
   // host memory and needs few CUs).  sum_pending: a sum has been issued that the main stream has not waited for yet.
@@ -342,7 +341,6 @@ struct wbx_ctx {
   bool sum_valid[kRing] = {};
   int sum_pending = -1;
   uint32_t render_seq = 0;
-  bool partial_wait_done = false;     // the caller already ordered this render after the sum of two renders ago
   DevBuf<uint8_t> d_conv;
   DevBuf<unsigned long long> d_dbg;   // diagnostic (WBX_DBG_CLOCK=1): per-workgroup start / end times of the last mix
   size_t dbg_wgs = 0;
@@ -351,15 +349,7 @@ struct wbx_ctx {
   std::vector<DSeg> h_pool;
 
   uint32_t last_K = 0, last_N = 0;
-  uint32_t* status_dst = nullptr;     // set by wbx_engine_process around its render: where sum_kernel drops the plan status
-  // the one-launch callback (wbx_callback.h): set by wbx_engine_process around its render — the sequencer's arguments (the
-  // launch then runs plan + mix + sum as one kernel), the pinned word the kernel writes `cb_seq` into when master and status
-  // are out, and whether launch_mix_sum took that path
-  const PlanArgs* cb_plan = nullptr;
-  uint32_t* cb_flag = nullptr;
-  uint32_t* cb_gave_up = nullptr;     // pinned word: the launch's number when one of its workgroups gave up at the spread barrier
-  uint32_t cb_seq = 0;
-  bool cb_launched = false;
+  // the one-launch callback (wbx_callback.h; what one launch needs from its caller: RenderCall)
   DevBuf<uint32_t> d_cb_done;         // device: "workgroups done" ticket counter, never reset: launches count from cb_base
   uint32_t cb_base = 0;               // ... the first counter (every multi-group launch arrives there)
   uint32_t cb_base2 = 0;              // ... the second one (only launches whose workgroups each add a share of the master)
@@ -374,12 +364,9 @@ struct wbx_ctx {
   RenderShape shape;
   uint32_t n_xcds = 0;                // the XCD layout probe of wbx_create: 8 / 4 / 2 / 1, or 0 — not round-robin: no chained pieces
                                       // (chain_broken), no segmented sequencer (seg_broken) from the start
-  uint32_t n_cus = 0;                 // the device's CU count (wbx_create), what callback_spread_limit starts from
+  uint32_t n_cus = 0;                 // the device's CU count (wbx_create), what callback_spread_limit (wbx_shape.h) starts from
   bool cb_no_spread = false;          // a spread launch gave up waiting for the whole grid (not resident at once: a CU mask, a
                                       // device shared with another process): the context keeps to "the last workgroup adds"
-  uint32_t cb_flags = 1;              // completion words the launch writes (one, or one per workgroup: cb_flag[0 .. cb_flags))
-  uint32_t cb_flag_cap = 1;           // ... and how many the engine's pinned block holds
-  bool zero_status = false;           // ... and whether it clears the counters for the buffer's next plan
   bool buses_alias_partials = false;  // see build_routing
   const float* last_buses = nullptr;  // where the last render's bus sums are: d_buses or the partial buffer
   bool buses_clean = false;           // d_buses zeroed since the last routing change / reallocation
@@ -388,7 +375,7 @@ struct wbx_ctx {
   bool clamp = true;
   float* master_target = nullptr;     // caller-owned device buffer, or null: d_master
   bool master_target_on_host = false; // ... it is pinned host memory: batch renders stage the master in d_stage and copy it out
-  DevBuf<float> d_stage[kRing];       // (see launch_mix_sum: a sum that stores 8 MB over PCIe itself holds up the next mix)
+  DevBuf<float> d_stage[kRing];       // (see choose_issue, wbx_shape.h: a sum that stores 8 MB over PCIe itself holds up the next mix)
   int master_format = 0;              // wbx_set_master_format: 0 planar fp32, else WBX_OUT_* interleaved (sum kernel epilogue)
   int last_master_format = 0;         // ... of the last render
   const float* master_init = nullptr; // wbx_set_master_init: the running sum the first group starts from, or null: zero
@@ -432,6 +419,28 @@ struct wbx_ctx {
 namespace wbx {
 
 inline wbx_ctx::PlanBuf& PB(wbx_ctx* c) { return c->pb[c->cur]; }
+
+// What ONE call of launch_mix_sum needs from its caller.  wbx_ctx holds state — what outlives a render —; the inputs of a
+// single render are arguments: built by value where the call is made (wbx_submit, render_locked, each repeat path of
+// wbx_engine_process), read only by the callee, gone when it returns.
+struct RenderCall {
+  hipStream_t mix_stream = nullptr;   // where the mix runs: the main stream or the alternate one (pick_mix_stream)
+  bool plan_waits_partial = false;    // the plan stream — which the mix follows — already waits for partial_free[] of this
+                                      // render's partial buffer: no second wait on the mix stream
+  uint32_t* status = nullptr;         // pinned: where the sum (or the one launch) drops the plan's four counters, or null
+  bool clear_counters = false;        // ... and the kernel then clears the device's copy for the buffer's next plan
+  // the one-launch callback (wbx_callback.h): the sequencer's arguments — the block may then run plan + mix + sum as one
+  // kernel —, the pinned word that kernel writes `seq` into when master and status are out, and the pinned word it writes
+  // `seq` into when one of its workgroups gave up at the spread barrier
+  const PlanArgs* plan = nullptr;
+  uint32_t* done_word = nullptr;
+  uint32_t* gave_up_word = nullptr;
+  uint32_t seq = 0;
+  // wbx_engine_process: the block's master goes here (pinned host memory) in this format, whatever the setters say;
+  // null: the context's own master_target / master_format
+  float* master = nullptr;
+  int format = 0;
+};
 
 // a failure's text, `what[: the HIP error]`, into *why (the side calls' messages) ...
 inline wbx_status stage_fail(std::string* why, wbx_status st, const char* what, hipError_t e = hipSuccess) {
@@ -559,7 +568,7 @@ wbx_status splice_run(wbx_ctx* c, const ClipSrc* srcs, const wbx_splice_part* pa
 hipError_t join_sum(wbx_ctx* c);
 hipError_t join_alt(wbx_ctx* c);
 hipError_t sync_main(wbx_ctx* c);          // the host waits for the main stream and every mix / sum beside it
-hipStream_t pick_mix_stream(wbx_ctx* c, uint32_t K, bool alternate);
+hipStream_t pick_mix_stream(const wbx_ctx* c, uint32_t K, bool alternate);   // (a choice, stored nowhere: RenderCall::mix_stream)
 void drain_events(wbx_ctx* c, int upto = 0);
 wbx_status upload_tables(wbx_ctx* c, uint32_t n_tracks);
 wbx_status ensure_result_buffers(wbx_ctx* c, uint32_t K, uint32_t N);
@@ -567,10 +576,11 @@ wbx_status ensure_template_capacity(wbx_ctx* c, size_t n);
 wbx_status ensure_gen_capacity(wbx_ctx* c, size_t rows);
 wbx_status ensure_pool_slack(wbx_ctx* c);   // twice the default overflow pool (renders planned by segments; not when the host fixed max_segments)
 wbx_status launch_pre_render(wbx_ctx* c, hipStream_t on);
-wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N);
+// mix + sum over the current plan buffer as `call` says; *one_launch (if asked for): the block ran as the one-launch callback
+wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N, const RenderCall& call, bool* one_launch = nullptr);
 wbx_status plan_status_to_error(wbx_ctx* c, uint32_t bits);
 wbx_status render_status(wbx_ctx* c);      // the latched hand-over failures of chained renders (the streams must be idle)
-float* begin_master(wbx_ctx* c, hipStream_t writer, hipError_t* err);
+float* begin_master(wbx_ctx* c, float* target, hipStream_t writer, hipError_t* err);   // target: the caller's buffer, or null
 RenderShape render_shape(const wbx_ctx* c, uint32_t K, uint32_t N, bool callback);   // choose_shape over the context's facts
 
 // wbx_dist.hip

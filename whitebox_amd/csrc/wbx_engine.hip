@@ -43,14 +43,12 @@ struct wbx_engine {
   // Engine::process (one block per call): pinned, device-mapped host staging the sum kernel writes the block into
   // and the plan status lands in — the callback path then needs no copy-engine transfer at all
   PinnedBuf<float> h_block;             // [C][F]
-  PinnedBuf<uint32_t> h_status;         // plan counters [4]; from [8]: the one-launch callback's completion words (its sequence
-                                        // number, one word or one per workgroup), kCbFlags of them
-  static constexpr uint32_t kCbFlags = 256;
+  PinnedBuf<uint32_t> h_status;         // kStatusWords: plan counters [0..4); the one-launch callback's give-up word [7] and
+                                        // completion word [8], each holding the sequence number of the launch that wrote it
+  static constexpr uint32_t kStatusWords = 9;
   uint32_t cb_seq = 0;                  // ... of the last launch
   uint32_t cb_give_ups = 0;             // one-launch callbacks mixed again because a workgroup gave up at the spread barrier
-  bool in_process = false;              // render_locked runs inside wbx_engine_process, which waits for the block: the
-                                        // pinned tables need no completion events
-  bool gen_skipped = false;             // ... and left the pre-render launch out (expecting an empty queue)
+  bool gen_skipped = false;             // the process block's render left the pre-render launch out (expecting an empty queue)
   bool plan_status_on_host = false;     // the counters of the last plan are in h_status (the device copy was cleared)
   size_t d_clips_count = 0;
   bool clips_uploaded = false;          // the device holds a clip table (its internal_state_changed flags are live)
@@ -161,12 +159,12 @@ wbx_status cfail(wbx_engine* e, wbx_status s) {
 // About 16 k lanes: segments of K * N / 24576 blocks rounded up to a power of two, at least 32 (measured, profiles/
 // r04_ab_seglen.txt: 256 tracks best at 32-64 blocks — 16 and 128 are 9-15 % slower —, 4096 tracks x 2048 short blocks at 512).
 // WBX_PLAN_SEG=0: off; =<n>: segments of n blocks (A/B aid, tests).
-uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing) {
+uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing, bool in_callback) {
   if (e->knobs.plan_seg == 0) return 0u;   // (WBX_PLAN_SEG as wbx_engine_create read it)
   const uint32_t forced = e->knobs.plan_seg > 0 ? (uint32_t)e->knobs.plan_seg : 0u;
   if (e->table_flags && e->h_flags_left.p && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left.p) == 0u)
     e->table_flags = false;   // every flag of the table has been cleared by a plan that is over
-  if (!playing || e->table_flags || e->in_process || N == 0u || e->ctx->seg_broken) return 0u;
+  if (!playing || e->table_flags || in_callback || N == 0u || e->ctx->seg_broken) return 0u;
   if (forced) return forced < K ? forced : 0u;
   if (!e->hs.cut_tracks || K < 128u) return 0u;
   // (also where the one-lane walk would hide behind the previous mix — c3 / 16-bit sessions cut into 5.3- or 20-block clips at
@@ -1044,9 +1042,13 @@ wbx_status ensure_pinned_tables(wbx_engine* e, uint32_t N) {
   return WBX_OK;
 }
 
-// the audio thread's render, editor lock held by the caller
-wbx_status render_locked(wbx_engine* e, uint32_t K) {
+// the audio thread's render, editor lock held by the caller.  `process`: the one block of wbx_engine_process, which waits
+// for it before it returns (the pinned tables need no completion events) — where its master and its plan status go; null:
+// a batch render, a bounce pass.  *as_one_launch (if asked for): the block ran as the one-launch callback
+wbx_status render_locked(wbx_engine* e, uint32_t K, const RenderCall* process = nullptr, bool* as_one_launch = nullptr) {
   wbx_ctx* c = e->ctx;
+  float* const master_target = process ? process->master : c->master_target;
+  const int master_format = process ? process->format : c->master_format;
   HostSession& hs = e->hs;
   tls_err.clear();
   if (K > c->cfg.max_blocks) return efail(e, WBX_ERR_INVALID, "n_blocks above wbx_config.max_blocks");
@@ -1067,10 +1069,10 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
     WBX_EHIP(e, join_sum(c));
     WBX_EHIP(e, c->d_master.ensure((size_t)K * C * F));
     const bool continues = c->master_init || dist_receives_running_sum(c);
-    if (c->master_format && (c->dist || continues))
+    if (master_format && (c->dist || continues))
       return efail(e, WBX_ERR_UNSUPPORTED, "an empty session continues a running master / feeds a multi-GPU exchange in planar fp32 only");
     hipError_t me = hipSuccess;
-    float* master = begin_master(c, s, &me);
+    float* master = begin_master(c, master_target, s, &me);
     WBX_EHIP(e, me);
     if (continues) {
       wbx_status ist = WBX_OK;
@@ -1080,11 +1082,11 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
       if (c->dist) WBX_EHIP(e, dist_mix_issued(c, s));
       WBX_EHIP(e, hipGetLastError());
     } else {   // (all-zero bytes are silence in every output format; packed 24-bit counts its 3 bytes per sample)
-      const size_t eb = c->master_format == WBX_OUT_I16 ? 2 : c->master_format == WBX_OUT_I24 ? 3 : 4;
+      const size_t eb = master_format == WBX_OUT_I16 ? 2 : master_format == WBX_OUT_I24 ? 3 : 4;
       WBX_EHIP(e, hipMemsetAsync(master, 0, (size_t)K * C * F * eb, s));
     }
     c->last_master = master;
-    c->last_master_format = c->master_format;
+    c->last_master_format = master_format;
     c->last_master_on_host = false;
     c->last_K = K;
     c->last_N = 0;
@@ -1171,12 +1173,12 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   // -- the mix instance of this render and what follows from it (wbx_shape.h): decided here, once, behind upload_tables (which
   //    reads the clip table's formats) and in front of everything that plans or launches for this render
   c->session = hs.shape_facts();
-  c->shape = render_shape(c, K, N, e->in_process && !hs.any_slow_clip);
+  c->shape = render_shape(c, K, N, process && !hs.any_slow_clip);
   const RenderShape& shape = c->shape;
 
   // -- rows for the track-blocks the hot loop cannot stream directly, and the plan's templates
   // the sequencer of this render: one lane per track, or — long renders of sessions cut into clips — per (track, segment)
-  const uint32_t seg_len = plan_segment_length(e, K, N, playing);
+  const uint32_t seg_len = plan_segment_length(e, K, N, playing, process != nullptr);
   const uint32_t n_segs = seg_len ? (K + seg_len - 1u) / seg_len : 1u;
   // (segments: a track whose seam missed is planned again from there, and what its replaced segments queued / took from the
   //  pool / reserved stays allocated and unused — room for both versions of every row, so that a miss on a session that leans
@@ -1196,14 +1198,15 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   wbx_ctx::PlanBuf& B = PB(c);
   const bool plan_beside = c->ck.overlap && K >= kOverlapMinBlocks;
   hipStream_t ps = plan_beside ? c->plan_stream : s;
-  hipStream_t ms = pick_mix_stream(c, K, true);   // main stream, or the alternate one for every other batch render
+  RenderCall call = process ? *process : RenderCall{};
+  hipStream_t ms = call.mix_stream = pick_mix_stream(c, K, true);   // main stream, or the alternate one for every other batch render
   const bool plan_event = ps != ms;               // the mix runs on another stream than its plan
   if (B.consumed_valid) WBX_EHIP(e, hipStreamWaitEvent(ps, B.consumed, 0));   // the mix that read this buffer two renders ago
   {
     const int pp = (int)(c->render_seq % kRing);
     if (plan_beside && c->sum_valid[pp]) {   // ... and the sum that read the partial buffer this render's mix will write
       WBX_EHIP(e, hipStreamWaitEvent(ps, c->partial_free[pp], 0));   // (the sum KERNEL: not the copy-out of its master behind it)
-      c->partial_wait_done = true;
+      call.plan_waits_partial = true;
     }
   }
   // the plan's four counters start from zero: cleared by the kernel that brings the transport table in front of the plan when
@@ -1283,7 +1286,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   // looks at the queue counter afterwards and repeats pre-render + mix for the (rare) block that needed it.
   // (sessions whose boundary blocks do go through the pre-render pass take the same bet when the block can be one launch:
   //  a steady block — nearly all — wins two launches, a boundary block pays the repeat)
-  e->gen_skipped = e->in_process && !hs.any_slow_clip && (shape.masked_rows || shape.cb_one_launch);
+  e->gen_skipped = process && !hs.any_slow_clip && (shape.masked_rows || shape.cb_one_launch);
   // ... and then sequencer, mix and sum are ONE launch (wbx_callback.h): every mix workgroup plans its own tracks first, the
   // last one to finish sums the block and tells the host
   const bool one_launch = shape.cb_one_launch;
@@ -1327,7 +1330,7 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   } else if (!one_launch) {
     launch_plan(a, ps);
   }
-  if (!e->in_process) {
+  if (!process) {
     if (patch_slot >= 0) WBX_EHIP(e, e->patch[patch_slot].mark(ps));
     WBX_EHIP(e, e->gains[e->gains_slot].mark(ps));   // (re-recorded by every plan that reads the buffer)
   }
@@ -1341,19 +1344,19 @@ wbx_status render_locked(wbx_engine* e, uint32_t K) {
   if (plan_event) WBX_EHIP(e, hipStreamWaitEvent(ms, B.planned, 0));
   c->levels_target = reinterpret_cast<uint32_t*>(e->d_levels.p);
   const int mix_parity = (int)(c->render_seq % kRing);
-  c->cb_plan = one_launch ? &a : nullptr;
-  if (one_launch) {
-    c->cb_flag = e->h_status.p + 8;
-    c->cb_gave_up = e->h_status.p + 7;
-    c->cb_flag_cap = wbx_engine::kCbFlags;
+  if (one_launch) {   // (only a process block's shape says so: h_status is there)
+    call.plan = &a;
+    call.done_word = e->h_status.p + 8;
+    call.gave_up_word = e->h_status.p + 7;
     if (++e->cb_seq == 0u) ++e->cb_seq;   // (0 is what the completion and election words hold before any launch)
-    c->cb_seq = e->cb_seq;
+    call.seq = e->cb_seq;
   }
-  st = launch_mix_sum(c, K, N);
-  c->cb_plan = nullptr;
+  bool launched_as_one = false;
+  st = launch_mix_sum(c, K, N, call, &launched_as_one);
   if (st != WBX_OK) return cfail(e, st);
+  if (as_one_launch) *as_one_launch = launched_as_one;
   B.consumed = c->mix_done[mix_parity];   // recorded right after the mix: the plan buffer is free before the sum runs
-  B.consumed_valid = !c->cb_launched;   // (the one-launch callback records no event: wbx_engine_process waits for the launch itself)
+  B.consumed_valid = !launched_as_one;   // (the one-launch callback records no event: wbx_engine_process waits for the launch itself)
 
   // -- transport: the host repeats the arithmetic of Engine::process (engine.cpp:1578-1585, :1619-1623) that
   //    the plan kernel performs for its K blocks, so both sides hold the same playhead / sample_position bits
@@ -1914,51 +1917,38 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
     rec_capture_locked(e, in, n_in);
     return cfail(e, wbx_fetch(c, out_planar, nullptr, nullptr));
   }
-  const int saved_format = c->master_format;
-  c->master_format = out_format;
-  struct Restore {
-    wbx_ctx* c;
-    int f;
-    ~Restore() { c->master_format = f; }
-  } restore{c, saved_format};
   const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
   WBX_EHIP(e, e->h_block.ensure((size_t)C * F));
   if (!e->h_status.p) {
-    WBX_EHIP(e, e->h_status.ensure(8 + wbx_engine::kCbFlags));
-    std::memset(e->h_status.p, 0, (8 + wbx_engine::kCbFlags) * sizeof(uint32_t));
+    WBX_EHIP(e, e->h_status.ensure(wbx_engine::kStatusWords));
+    std::memset(e->h_status.p, 0, wbx_engine::kStatusWords * sizeof(uint32_t));
   }
-  c->master_target = e->h_block.p;        // sum_kernel's stores go over PCIe into the staging block,
-  c->status_dst = e->h_status.p;          // and it drops the plan status next to it
-  e->in_process = true;
-  c->zero_status = true;
-  c->cb_launched = false;
-  wbx_status st = render_locked(e, 1);
-  e->in_process = false;
+  RenderCall block;                       // what every pass over this block shares:
+  block.master = e->h_block.p;            // sum_kernel's stores go over PCIe into the staging block, in the caller's format,
+  block.format = out_format;
+  block.status = e->h_status.p;           // and it drops the plan status next to it ...
+  RenderCall first = block;
+  first.clear_counters = true;            // ... the first pass clearing the counters for the buffer's next plan
+  bool launched_as_one = false;
+  wbx_status st = render_locked(e, 1, &first, &launched_as_one);
   // the recorder tap, once per played block whichever path the block takes below (one launch, mixed again after a
   // give-up, three launches): launched on the upload stream beside the block's kernels, not waited for
   if (st == WBX_OK) rec_capture_locked(e, in, n_in);
-  const bool one_launch = st == WBX_OK && c->cb_launched;
+  const bool one_launch = st == WBX_OK && launched_as_one;
   if (st == WBX_OK && e->hs.n_tracks() != 0) {
     if (one_launch) {
       // the kernel's own word: master and status are in host memory when it reads this launch's number.  Polled — no
       // completion signal between the device and the return of the callback; a launch that never reports (a device fault)
       // falls through to the stream's own error after two seconds
-      // (one word, or one per workgroup when every workgroup stores a share of the master: all of them)
       volatile uint32_t* flag = e->h_status.p + 8;
-      const uint32_t n_flags = c->cb_flags, seq = e->cb_seq;
+      const uint32_t seq = e->cb_seq;
       const auto t0 = std::chrono::steady_clock::now();
-      uint32_t spins = 0, have = 0;
-      while (have < n_flags) {
-        if (flag[have] == seq) {
-          have++;
-          continue;
-        }
+      uint32_t spins = 0;
+      while (*flag != seq) {
         __builtin_ia32_pause();
         if ((++spins & 0xFFFFu) == 0u && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
           (void)sync_main(c);
-          for (have = 0; have < n_flags && flag[have] == seq; have++) {
-          }
-          if (have < n_flags) {   // the launch never reported: start the ticket count afresh
+          if (*flag != seq) {   // the launch never reported: start the ticket count afresh
             st = efail(e, WBX_ERR_DEVICE, "the one-launch callback did not report its block");
             if (c->d_cb_done.p) (void)hipMemset(c->d_cb_done.p, 0, kCbDoneWords * sizeof(uint32_t));
             c->cb_base = c->cb_base2 = 0;
@@ -1984,28 +1974,24 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       // not drop the device's copy over them (workgroup 0 may have cleared it: an overflow bit of this block would be lost).
       c->cb_no_spread = true;
       e->cb_give_ups++;
-      c->zero_status = false;
-      c->status_dst = nullptr;
-      st = launch_mix_sum(c, 1, e->hs.n_tracks());
-      c->status_dst = e->h_status.p;
+      RenderCall again = block;
+      again.status = nullptr;   // (no status destination)
+      st = launch_mix_sum(c, 1, e->hs.n_tracks(), again);
       if (st == WBX_OK && sync_main(c) != hipSuccess) st = WBX_ERR_DEVICE;
       PB(c).counters_zero = false;
       if (st != WBX_OK) tls_err = c->err;
     }
     if (st == WBX_OK && e->gen_skipped && e->h_status.p[2] != 0u) {
       // the block did queue records for the pre-render pass: run it now and mix again (the plan is untouched; the
-      // first pass counted those records as silence, so the running levels hold nothing wrong)
-      c->zero_status = false;
+      // first pass counted those records as silence, so the running levels hold nothing wrong; the status is dropped
+      // again, the counters stay: `block` as it is)
       st = launch_pre_render(c, c->stream);
-      if (st == WBX_OK) st = launch_mix_sum(c, 1, e->hs.n_tracks());
+      if (st == WBX_OK) st = launch_mix_sum(c, 1, e->hs.n_tracks(), block);
       if (st == WBX_OK && sync_main(c) != hipSuccess) st = WBX_ERR_DEVICE;
       PB(c).counters_zero = false;
       if (st != WBX_OK) tls_err = c->err;
     }
   }
-  c->zero_status = false;
-  c->master_target = nullptr;
-  c->status_dst = nullptr;
   if (st != WBX_OK) return st;
   if (!one_launch) WBX_EHIP(e, sync_main(c));
   for (int i = 0; i < kRing; i++) e->patch[i].forget(), e->gains[i].forget();   // every plan that read them is over

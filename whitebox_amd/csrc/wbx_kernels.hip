@@ -494,13 +494,6 @@ const char* launch_mix(const MixInstance& inst, const MixArgs& a, uint32_t grid_
   return nullptr;
 }
 
-// The spread sum's ticket barrier needs every workgroup of the grid resident at once: at most one per CU the process may use.
-// A CU mask (HSA_CU_MASK / ROC_GLOBAL_CU_MASK) takes CUs away without the attribute saying so: no spreading then.  (A device
-// shared with another process can still hold workgroups back; the barrier's wait is bounded, a give-up is reported and the
-// block is mixed again through three launches — wbx_engine_process — and the context stops spreading.)
-// `n_cus`, `cu_mask`: the device's CU count and CtxKnobs::cu_mask, as wbx_create found them.
-uint32_t callback_spread_limit(uint32_t n_cus, bool cu_mask) { return cu_mask ? 0u : (n_cus < 256u ? n_cus : 256u); }
-
 const char* launch_callback(const MixInstance& inst, const MixArgs& m, const PlanArgs& p, const SumArgs& s0, uint32_t* done, uint32_t done_base, uint32_t done_base2,
                             bool spread, uint32_t* gave_up, uint32_t spin_bound, uint32_t* flag, uint32_t seq, unsigned long long* dbg, hipStream_t st) {
   SumArgs s = s0;

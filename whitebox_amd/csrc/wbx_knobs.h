@@ -75,7 +75,7 @@ struct CtxKnobs {
   bool dbg_clock = false;         // WBX_DBG_CLOCK: per-workgroup start / end times of the mix (tools/wg_clocks.py)
   bool cb_dbg = false;            // WBX_CB_DBG: the phases of every workgroup of the one-launch callback (tools/cb_clocks.py)
   bool cu_mask = false;           // HSA_CU_MASK / ROC_GLOBAL_CU_MASK is set: CUs are taken away without the device's attribute
-                                  // saying so — the callback's spread sum is off (wbx_kernels.hip: callback_spread_limit)
+                                  // saying so — the callback's spread sum is off (wbx_shape.h: callback_spread_limit)
 
   static CtxKnobs from_env() {
     CtxKnobs k;

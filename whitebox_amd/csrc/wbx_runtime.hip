@@ -35,10 +35,9 @@ hipError_t sync_main(wbx_ctx* c) {
 }
 
 // which stream the next mix runs on: batch renders of layer 2 alternate (see wbx_ctx::alt_stream)
-hipStream_t pick_mix_stream(wbx_ctx* c, uint32_t K, bool alternate) {
+hipStream_t pick_mix_stream(const wbx_ctx* c, uint32_t K, bool alternate) {
   const bool alt = alternate && c->ck.mix_alternate && c->alt_stream && K >= kOverlapMinBlocks && c->cur_mix_stream == c->stream;
-  c->cur_mix_stream = alt ? c->alt_stream : c->stream;
-  return c->cur_mix_stream;
+  return alt ? c->alt_stream : c->stream;
 }
 
 // the kernel timer's pending launches -> the totals; `upto` > 0: only the oldest `upto` of them (a full ring: the newer half
@@ -280,97 +279,153 @@ wbx_status launch_pre_render(wbx_ctx* c, hipStream_t on) {
 }
 
 // where the master of the render about to be issued goes; `writer` is the stream its last writer runs on
-float* begin_master(wbx_ctx* c, hipStream_t writer, hipError_t* err) {
+float* begin_master(wbx_ctx* c, float* target, hipStream_t writer, hipError_t* err) {
   *err = hipSuccess;
   if (c->dist) return dist_begin_render(c, writer, err);
-  return c->master_target ? c->master_target : c->d_master.p;
+  return target ? target : c->d_master.p;
 }
 
-// mix + sum over the current plan buffer, on the main stream
-wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
-  const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
+namespace {
+
+// the group set of a render: workgroup-sized pieces, or the whole member lists (the reference's summation order)
+struct GroupSet {
+  const DGroup* d_groups;
+  uint32_t n_groups;
+  bool buses_alias;
+};
+GroupSet render_groups(const wbx_ctx* c) {
+  const bool whole = c->shape.walks_lists && !c->shape.chained;
+  return {c->d_groups.p + (whole ? c->groups.size() : 0), (uint32_t)(whole ? c->groups_exact.size() : c->groups.size()),
+          whole ? c->buses_alias_exact : c->buses_alias_partials};
+}
+
+// the facts choose_issue decides from (wbx_shape.h): the render's shape, the call, the context's state
+IssueFacts issue_facts(const wbx_ctx* c, uint32_t K, uint32_t n_groups, const RenderCall& call, hipStream_t ms) {
+  const RenderShape& sh = c->shape;
+  IssueFacts f;
+  f.K = K;
+  f.n_groups = n_groups;
+  f.n_buses = c->n_buses;
+  f.tiles = sh.tiles;
+  f.block_frames = c->cfg.block_frames;
+  f.channels = c->cfg.channels;
+  f.chained = sh.chained;
+  f.cb_one_launch = sh.cb_one_launch;
+  f.callback_plan = call.plan != nullptr;
+  f.master_format = call.master ? call.format : c->master_format;
+  f.mix_on_main = ms == c->stream;
+  f.dist = c->dist != nullptr;
+  f.init = c->master_init != nullptr || dist_receives_running_sum(c);   // (what dist_mix_init will hand the mix: non-null)
+  f.target_set = call.master != nullptr || c->master_target != nullptr;
+  f.target_on_host = c->master_target_on_host;   // (the setter's finding; wbx_engine_process's one block is never staged)
+  f.cb_no_spread = c->cb_no_spread;
+  f.n_cus = c->n_cus;
+  return f;
+}
+
+// step 1: the mix's arguments (what goes with the choice of streams and launches is filled in by the caller)
+MixArgs mix_args(wbx_ctx* c, uint32_t K, uint32_t N, const GroupSet& g, const RenderIssue& is, const RenderCall& call, int pp,
+                 float* peaks, const float* init, float* master_dst) {
+  const RenderShape& sh = c->shape;
   MixArgs m{};
   m.rows = PB(c).prows.p;
   m.tmpl = PB(c).tmpl.p;
   m.zero_page = c->d_zero.p;
   m.pool = PB(c).pool.p;
   m.order = c->d_order.p;
-  // the group set of this render: workgroup-sized pieces, or the whole member lists (the reference's summation order)
-  const RenderShape& sh = c->shape;
-  const bool chained = sh.chained;
-  const bool whole = sh.walks_lists && !chained;
-  const DGroup* d_groups = c->d_groups.p + (whole ? c->groups.size() : 0);
-  const uint32_t n_groups = (uint32_t)(whole ? c->groups_exact.size() : c->groups.size());
-  const bool buses_alias = whole ? c->buses_alias_exact : c->buses_alias_partials;
-  m.groups = d_groups;
-  const int pp = (int)(c->render_seq % kRing);
-  // this partial buffer was last read by the sum of kRing renders ago; the engine path has already made the PLAN
-  // stream wait for that sum (the mix waits for the plan), which keeps the barrier off the main stream
-  if (!c->cur_mix_stream) c->cur_mix_stream = c->stream;
-  hipStream_t ms = c->cur_mix_stream;             // the main stream, or the alternate one (pick_mix_stream)
-  const int pk = ms == c->stream ? 0 : 1;         // its peaks buffer
-  if (c->sum_valid[pp] && !c->partial_wait_done) WBX_HIP(c, hipStreamWaitEvent(ms, c->partial_free[pp], 0));
-  c->partial_wait_done = false;
+  m.groups = g.d_groups;
   m.partial = c->d_partial2[pp].p;
-  m.peaks = c->d_peaks[pk].p;
-  c->last_peaks = m.peaks;
+  m.peaks = peaks;
   m.levels = c->levels_target;
-  // short renders (the one-block callback path above all) keep everything on the main stream: the cross-stream
-  // hand-overs cost more than the few microseconds of overlap they could buy
-  const bool sum_beside = c->ck.sum_overlap && K >= kOverlapMinBlocks;
-  hipStream_t ss = sum_beside ? c->sum_stream : c->stream;
-  // (argument checks first: once dist_mix_init has posted this render's receive, a failure would leave it unmatched)
-  if (c->master_format && c->dist) return fail(c, WBX_ERR_UNSUPPORTED, "wbx_set_master_format: a multi-GPU partial master stays planar fp32");
-  if (c->n_buses && (c->master_init || dist_receives_running_sum(c)))
-    return fail(c, WBX_ERR_UNSUPPORTED, "a running master (wbx_set_master_init / WBX_DIST_CHAIN) cannot be continued through sub-buses");
-  // where this render's master goes (the ctx's own buffer, the caller's target, or the multi-GPU ring slot) and what its
-  // sum starts from (zero; wbx_set_master_init's running sum; chain mode: the previous rank's, received for this render)
-  float* master_dst = nullptr;
-  {
-    hipError_t me = hipSuccess;
-    master_dst = begin_master(c, ss, &me);
-    WBX_HIP(c, me);
-    wbx_status ist = WBX_OK;
-    m.init = c->dist ? dist_mix_init(c, K, ms, &ist) : c->master_init;
-    if (ist != WBX_OK) return ist;
-  }
+  m.init = init;
   m.n_tracks = N;
-  m.n_groups = n_groups;
-  m.block_frames = F;
-  m.channels = C;
+  m.n_groups = g.n_groups;
+  m.block_frames = c->cfg.block_frames;
+  m.channels = c->cfg.channels;
   m.lane_span = sh.lane_span;
   m.fast_partial = c->ck.fast_partial_off ? 0u : 1u;
   m.tiles = sh.tiles;
   m.n_blocks = K;
   m.masked_rows = sh.masked_rows ? 1u : 0u;
-  {   // one resampling ratio for every window row of this render (layer 2's word; MODE_WNU / WINU: the products fl(j * speed)
-      // hoisted out of the track loop).  WBX_NO_UNIFORM=1 withholds it.  [Round 3's split of this function lost this line: the
-      // modes were carried but never taken until round 5 — SQ_INSTS_VALU_MUL_F64 of the r03-r05 PMC passes shows it.]
-    m.uniform_speed = c->ck.no_uniform ? 0.0 : sh.uniform_speed;
-    c->last_uniform_speed = m.uniform_speed;
+  // one resampling ratio for every window row of this render (layer 2's word; MODE_WNU / WINU: the products fl(j * speed)
+  // hoisted out of the track loop).  WBX_NO_UNIFORM=1 withholds it.  [Round 3's split of this function lost this line: the
+  // modes were carried but never taken until round 5 — SQ_INSTS_VALU_MUL_F64 of the r03-r05 PMC passes shows it.]
+  m.uniform_speed = c->ck.no_uniform ? 0.0 : sh.uniform_speed;
+  if (is.fused) {   // (the mix workgroup clamps and stores the master itself, and drops the plan status like the sum would)
+    m.fused_master = master_dst;
+    m.fused_clamp = c->clamp ? 1u : 0u;
+    m.fused_status_src = call.status ? PB(c).counters.p : nullptr;
+    m.fused_status_dst = call.status;
+    m.fused_zero_status = (call.status && call.clear_counters) ? 1u : 0u;
   }
-  // A short render of a session that is one group (the callback configuration up to 64 tracks; no sub-buses, planar fp32
-  // master, nothing to continue): the mix workgroup clamps and stores the master itself — the sum kernel is not launched
+  return m;
+}
+
+// step 2: the sum's arguments
+SumArgs sum_args(wbx_ctx* c, const GroupSet& g, const RenderCall& call, int pp, float* master_dst, int format) {
+  SumArgs s{};
+  s.partial = c->d_partial2[pp].p;
+  s.groups = g.d_groups;
+  s.master = master_dst;
+  if (format) {   // the device format is the sum's epilogue: interleaved samples instead of planar fp32
+    s.out_il = master_dst;
+    s.out_format = (uint32_t)format;
+  }
+  s.buses = (c->n_buses && !g.buses_alias) ? c->d_buses.p : nullptr;
+  s.n_groups = g.n_groups;
+  s.n_buses = c->n_buses;
+  s.block_frames = c->cfg.block_frames;
+  s.channels = c->cfg.channels;
+  s.clamp = c->clamp ? 1u : 0u;
+  s.chain = c->shape.chained ? 1u : 0u;
+  s.status_src = call.status ? PB(c).counters.p : nullptr;
+  s.status_dst = call.status;
+  s.zero_status = (call.status && call.clear_counters) ? 1u : 0u;
+  return s;
+}
+
+}  // namespace
+
+// mix + sum over the current plan buffer: what is launched, on which streams and with which waits between them is decided
+// once (choose_issue, wbx_shape.h); then the mix's arguments, the sum's arguments, and the issue
+wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N, const RenderCall& call, bool* one_launch) {
+  if (one_launch) *one_launch = false;
+  const uint32_t C = c->cfg.channels;
+  const RenderShape& sh = c->shape;
+  const GroupSet g = render_groups(c);
+  hipStream_t ms = call.mix_stream ? call.mix_stream : c->stream;   // the main stream, or the alternate one (pick_mix_stream)
+  c->cur_mix_stream = ms;
+  float* const target = call.master ? call.master : c->master_target;
+  const int format = call.master ? call.format : c->master_format;
+  const RenderIssue is = choose_issue(c->ck, issue_facts(c, K, g.n_groups, call, ms));
+  hipStream_t ss = is.sum_beside ? c->sum_stream : c->stream;
+  const int pp = (int)(c->render_seq % kRing);
+  const int pk = ms == c->stream ? 0 : 1;         // the mix stream's peaks buffer
+  // this partial buffer was last read by the sum of kRing renders ago; the engine path has already made the PLAN
+  // stream wait for that sum (the mix waits for the plan), which keeps the barrier off the main stream
+  if (c->sum_valid[pp] && !call.plan_waits_partial) WBX_HIP(c, hipStreamWaitEvent(ms, c->partial_free[pp], 0));
+  c->last_peaks = c->d_peaks[pk].p;
+  // (argument checks first: once dist_mix_init has posted this render's receive, a failure would leave it unmatched)
+  if (format && c->dist) return fail(c, WBX_ERR_UNSUPPORTED, "wbx_set_master_format: a multi-GPU partial master stays planar fp32");
+  if (c->n_buses && (c->master_init || dist_receives_running_sum(c)))
+    return fail(c, WBX_ERR_UNSUPPORTED, "a running master (wbx_set_master_init / WBX_DIST_CHAIN) cannot be continued through sub-buses");
+  // where this render's master goes (the ctx's own buffer, the caller's target, or the multi-GPU ring slot) and what its
+  // sum starts from (zero; wbx_set_master_init's running sum; chain mode: the previous rank's, received for this render)
+  hipError_t me = hipSuccess;
+  float* const master_home = begin_master(c, target, ss, &me);
+  WBX_HIP(c, me);
+  wbx_status ist = WBX_OK;
+  const float* init = c->dist ? dist_mix_init(c, K, ms, &ist) : c->master_init;
+  if (ist != WBX_OK) return ist;
   // A short render's sum runs on the main stream (and a one-group session's mix stores the master itself): neither may
   // overtake the sum of a batch render that is still pending on the sum stream — they write the same master (and bus)
   // buffers, and the late one would overwrite the head of the short render's blocks.  (Found by the edit scripts once they
   // stopped fetching every render: nobody had made the main stream wait, because a fetch in between always had.)
   if (ss == c->stream) WBX_HIP(c, join_sum(c));
-  const bool fused = K < kOverlapMinBlocks && n_groups == 1u && c->n_buses == 0u && m.tiles == 1u && !c->master_format && !c->dist &&
-                     !m.init && !chained;
-  m.fused_master = nullptr;
-  if (fused) {
-    m.fused_master = master_dst;
-    m.fused_clamp = c->clamp ? 1u : 0u;
-    m.fused_status_src = c->status_dst ? PB(c).counters.p : nullptr;
-    m.fused_status_dst = c->status_dst;
-    m.fused_zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
-  }
-  m.chain = nullptr;
-  m.chain_status = nullptr;
-  m.chain_sticky = nullptr;
-  if (chained) {   // one "sum is out" word per (workgroup column, group), tagged with this render's epoch: no clearing
-    const size_t words = (size_t)K * m.tiles * n_groups;   // between renders (a memset here waits out the previous sum)
+  MixArgs m = mix_args(c, K, N, g, is, call, pp, c->d_peaks[pk].p, init, master_home);
+  c->last_uniform_speed = m.uniform_speed;
+  if (sh.chained) {   // one "sum is out" word per (workgroup column, group), tagged with this render's epoch: no clearing
+    const size_t words = (size_t)K * m.tiles * g.n_groups;   // between renders (a memset here waits out the previous sum)
     const size_t had = c->d_chain.cap;
     WBX_HIP(c, c->d_chain.ensure(words));
     c->chain_epoch = (c->chain_epoch + 1u) & 0x0FFFFFFFu;
@@ -383,93 +438,52 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     m.chain_status = PB(c).counters.p + 1;
     m.chain_sticky = c->d_sticky_status.p;
   }
-  m.dbg_clock = nullptr;
   if (c->ck.dbg_clock) {   // diagnostic: per-workgroup start / end times of the mix
-    c->dbg_wgs = (size_t)K * n_groups * m.tiles;
+    c->dbg_wgs = (size_t)K * g.n_groups * m.tiles;
     WBX_HIP(c, c->d_dbg.ensure(4 * c->dbg_wgs));
     m.dbg_clock = c->d_dbg.p;
   }
   if (m.tiles > 1) WBX_HIP(c, hipMemsetAsync(m.peaks, 0, (size_t)K * N * C * sizeof(float), ms));
-  // the kernel timer is for batch renders; the one-block callback path skips its three event records
-  const bool timed = c->ck.profiling && K > 1;
-  const bool one_launch = c->cb_plan != nullptr && m.n_groups != 0u && sh.cb_one_launch;
-  if (one_launch) {   // (the callback instance's own lane space: one 256-lane workgroup per block)
+  if (is.one_launch) {   // (the callback instance's own lane space: one 256-lane workgroup per block)
     m.lane_span = sh.cb_lane_span;
     m.tiles = 1u;
   }
-  c->cb_launched = false;
-  // (round 6) When the kernel carries the timer's stop event and its sum runs on the sum stream, THAT event is what the sum
-  // stream waits for, and mix_done — what later plans wait for — is recorded over there: no marker packet behind the mix on
-  // its own stream, where the next mix queues (every packet between two mixes is a round trip of the command processor to
-  // the queue in host memory, behind whatever the copy engine is posting; what the marker cost: EXPERIMENTS.md, round 6).
-  bool by_kernel_event = false;
-  if (m.n_groups && !one_launch) {
-    if (timed && c->ev_pending == kEventRing) {   // the older half: 32 launches behind the newest, over long ago
+  if (g.n_groups && !is.one_launch) {
+    if (is.timed && c->ev_pending == kEventRing) {   // the older half: 32 launches behind the newest, over long ago
       WBX_HIP(c, hipEventSynchronize(c->ev[kEventRing / 2 - 1][2]));
       drain_events(c, kEventRing / 2);
     }
     // the timer's two events ride on the kernel's own dispatch packet (start / end time stamps of the kernel itself): no
     // event packets between two mixes
-    const char* name = launch_mix(sh.mix, m, sh.grid_z, ms, timed ? c->ev[c->ev_pending][0] : nullptr,
-                                  timed ? c->ev[c->ev_pending][1] : nullptr);
+    const char* name = launch_mix(sh.mix, m, sh.grid_z, ms, is.timed ? c->ev[c->ev_pending][0] : nullptr,
+                                  is.timed ? c->ev[c->ev_pending][1] : nullptr);
     if (!name) return fail(c, WBX_ERR_FAILED, "the render's mix instance is not compiled in");
     c->mix_kernel_name = name;
     if (c->dist) WBX_HIP(c, dist_mix_issued(c, ms));
-    by_kernel_event = timed && !c->dist && !c->ck.mix_alternate && ms == c->stream && sum_beside;
   }
   // the plan buffer is free as soon as the MIX has read it: releasing it before the sum lets the next plan run
   // beside sum_kernel (the GPU is nearly idle there) instead of competing with the next mix for CU slots — started
   // together with a mix, the one-wave-per-track plan kernel is starved until that mix drains
-  if (!one_launch && !by_kernel_event) WBX_HIP(c, hipEventRecord(c->mix_done[pp], ms));   // (one launch: recorded behind it, below)
+  if (!is.one_launch && !is.by_kernel_event) WBX_HIP(c, hipEventRecord(c->mix_done[pp], ms));   // (one launch: no event at all, below)
   if (ms != c->stream) c->alt_pending = pp;
-  // A master bound for pinned host memory leaves a batch render through a device staging buffer and the copy engine.  Stored
-  // by the sum kernel itself, its megabytes of posted writes fill the GPU's upstream queue in a few microseconds and drain at
-  // the PCIe rate; the command processor's own reads of host memory (the next dispatch packet, its signals) wait behind
-  // them, and the next mix started only when the sum had ended — 0.15 ms per 2048-block render.  (One-block callbacks keep
-  // the direct stores: 4 KB, and no second operation in the latency path.  Packed 24-bit too: its writer leaves part of
-  // the target untouched, which a whole-buffer copy would not.)
-  float* const master_home = master_dst;
-  size_t stage_bytes = 0;
-  if (sum_beside && !c->dist && c->master_target && c->master_target_on_host && c->master_format != 5) {
-    // (from 4 MB: below, the copy's fixed cost on the sum stream outweighs the hold-up — a 256-track session rendering 256
-    //  blocks at a time lost a quarter of its rate to it, and gains a quarter at 2048)
-    const size_t bytes = (size_t)K * F * C * (c->master_format == 3 ? 2u : 4u);
-    if (bytes >= (4u << 20)) {
-      stage_bytes = bytes;
-      WBX_HIP(c, c->d_stage[pp].ensure((stage_bytes + 3u) / 4u));
-      master_dst = c->d_stage[pp].p;
-    }
+  // (a master bound for pinned host memory leaves a batch render through a staging buffer and the copy engine: choose_issue)
+  float* master_dst = master_home;
+  if (is.stage_bytes) {
+    WBX_HIP(c, c->d_stage[pp].ensure((size_t)(is.stage_bytes + 3u) / 4u));
+    master_dst = c->d_stage[pp].p;
   }
-  SumArgs s{};
-  s.partial = c->d_partial2[pp].p;
-  s.groups = d_groups;
-  s.master = master_dst;
-  if (c->master_format) {   // the device format is the sum's epilogue: interleaved samples instead of planar fp32
-    s.out_il = master_dst;
-    s.out_format = (uint32_t)c->master_format;
-  }
-  c->last_master_format = c->master_format;
+  const SumArgs s = sum_args(c, g, call, pp, master_dst, format);
+  c->last_master_format = format;
   c->last_master = master_home;
   c->last_master_on_host = false;
-  s.buses = (c->n_buses && !buses_alias) ? c->d_buses.p : nullptr;
-  c->last_buses = c->n_buses ? (buses_alias ? c->d_partial2[pp].p : c->d_buses.p) : nullptr;
-  s.n_groups = m.n_groups;
-  s.n_buses = c->n_buses;
-  s.block_frames = F;
-  s.channels = C;
-  s.clamp = c->clamp ? 1u : 0u;
-  s.chain = chained ? 1u : 0u;
-  s.status_src = c->status_dst ? PB(c).counters.p : nullptr;
-  s.status_dst = c->status_dst;
-  s.zero_status = (c->status_dst && c->zero_status) ? 1u : 0u;
-  if (by_kernel_event) {   // (the mix on the main stream, its sum beside it: ss is the sum stream)
+  c->last_buses = c->n_buses ? (g.buses_alias ? c->d_partial2[pp].p : c->d_buses.p) : nullptr;
+  if (is.by_kernel_event) {   // (the mix on the main stream, its sum beside it: ss is the sum stream)
     WBX_HIP(c, hipStreamWaitEvent(ss, c->ev[c->ev_pending][1], 0));   // the kernel's own completion ...
     WBX_HIP(c, hipEventRecord(c->mix_done[pp], ss));                   // ... and, over here, "the mix has read its plan buffer"
   } else if (ss != ms) {
     WBX_HIP(c, hipStreamWaitEvent(ss, c->mix_done[pp], 0));   // (an earlier pending sum is ordered before this one by ss)
   }
-
-  if (c->n_buses && !buses_alias && !c->buses_clean) {
+  if (c->n_buses && !g.buses_alias && !c->buses_clean) {
     // buses without member groups must read as zero; every bus that has members is rewritten by each render, so the
     // buffer only needs clearing when the routing or the allocation changed (64 MB per render saved on config 4).
     // On the SUM's stream, in front of the sum: cleared on the mix stream behind the mix, it raced with a sum that runs
@@ -479,8 +493,8 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
     c->buses_clean = true;
   }
   if (ss == c->stream && ms != c->stream) c->alt_pending = -1;            // (the main stream has just joined that mix)
-  if (one_launch) {
-    // sequencer + mix + sum in one dispatch; the kernel itself tells the host when master and status are out (cb_flag)
+  if (is.one_launch) {
+    // sequencer + mix + sum in one dispatch; the kernel itself tells the host when master and status are out (call.done_word)
     if (!c->d_cb_done.p) {
       WBX_HIP(c, c->d_cb_done.ensure(kCbDoneWords));   // (two spread counters: wbx_callback.h)
       WBX_HIP(c, hipMemsetAsync(c->d_cb_done.p, 0, kCbDoneWords * sizeof(uint32_t), ms));
@@ -493,32 +507,29 @@ wbx_status launch_mix_sum(wbx_ctx* c, uint32_t K, uint32_t N) {
       cb_dbg = c->d_dbg.p;
     }
     m.partial_through = c->ck.cb_fenced ? 0u : 1u;
-    // every workgroup adds a share of the master when the whole grid is resident at once (at most one workgroup per CU: two
-    // fit) and the engine's pinned block has a completion word for each of them
-    const bool spread = !fused && !c->cb_no_spread && m.n_groups <= callback_spread_limit(c->n_cus, c->ck.cu_mask);
-    c->cb_flags = 1u;
-    const char* name = launch_callback(sh.cb, m, *c->cb_plan, s, c->d_cb_done.p, c->cb_base, c->cb_base2, spread, c->cb_gave_up, c->ck.cb_spin_bound, c->cb_flag, c->cb_seq, cb_dbg, ms);
+    const char* name = launch_callback(sh.cb, m, *call.plan, s, c->d_cb_done.p, c->cb_base, c->cb_base2, is.spread, call.gave_up_word,
+                                       c->ck.cb_spin_bound, call.done_word, call.seq, cb_dbg, ms);
     if (!name) return fail(c, WBX_ERR_FAILED, "the render's callback instance is not compiled in");
     c->mix_kernel_name = name;
     // (a one-group block takes no ticket; a grid larger than the device — "the last workgroup adds everything" — only the
     //  first one: the second counter has a base of its own, or the first spread launch after such a block would wait for a
     //  count that wrapped)
-    if (!fused) c->cb_base += m.n_groups;
-    if (spread) c->cb_base2 += m.n_groups;
+    if (!is.fused) c->cb_base += m.n_groups;
+    if (is.spread) c->cb_base2 += m.n_groups;
     c->cb_launches++;
-    if (spread) c->cb_spread_launches++;
-    c->cb_launched = true;
+    if (is.spread) c->cb_spread_launches++;
+    if (one_launch) *one_launch = true;
     // (no event behind it: wbx_engine_process waits for the launch's own word before it returns, nothing can overlap it)
-  } else if (!fused) {
+  } else if (!is.fused) {
     launch_sum(s, K, ss);
   }
-  if (sum_beside) WBX_HIP(c, hipEventRecord(c->partial_free[pp], ss));   // (in front of the staged master's copy: wbx_ctx.h)
-  if (stage_bytes) WBX_HIP(c, hipMemcpyAsync(master_home, master_dst, stage_bytes, hipMemcpyDeviceToHost, ss));
-  if (m.n_groups && timed) {
+  if (is.sum_beside) WBX_HIP(c, hipEventRecord(c->partial_free[pp], ss));   // (in front of the staged master's copy: wbx_ctx.h)
+  if (is.stage_bytes) WBX_HIP(c, hipMemcpyAsync(master_home, master_dst, (size_t)is.stage_bytes, hipMemcpyDeviceToHost, ss));
+  if (m.n_groups && is.timed) {
     WBX_HIP(c, hipEventRecord(c->ev[c->ev_pending][2], ss));
     c->ev_pending++;
   }
-  if (sum_beside) {
+  if (is.sum_beside) {
     WBX_HIP(c, hipEventRecord(c->sum_done[pp], ss));
     c->sum_valid[pp] = true;
     c->sum_pending = pp;
@@ -1428,14 +1439,15 @@ extern "C" wbx_status wbx_submit(wbx_ctx* c, uint32_t K, uint32_t N, const wbx_s
   WBX_HIP(c, hipMemcpyAsync(PB(c).prows.p, c->h_rows.data(), c->h_rows.size() * sizeof(DRow), hipMemcpyHostToDevice, c->stream));
   if (!c->h_pool.empty())
     WBX_HIP(c, hipMemcpyAsync(PB(c).pool.p, c->h_pool.data(), c->h_pool.size() * sizeof(DSeg), hipMemcpyHostToDevice, c->stream));
-  (void)pick_mix_stream(c, K, false);   // host-sequenced plans are uploaded on the main stream: their mix follows there
+  RenderCall call;
+  call.mix_stream = pick_mix_stream(c, K, false);   // host-sequenced plans are uploaded on the main stream: their mix follows there
   // host-sequenced plans say nothing about their clips, send every partial row through the pre-render pass and make no
   // promise about their playback speeds
   c->session = SessionFacts{};
   c->shape = render_shape(c, K, N, false);
   st = launch_pre_render(c, c->stream);
   if (st != WBX_OK) return st;
-  return launch_mix_sum(c, K, N);
+  return launch_mix_sum(c, K, N, call);
 }
 
 extern "C" wbx_status wbx_sync(wbx_ctx* c) {

@@ -4,10 +4,14 @@
 //
 // The conditions here are the only copy.  The launchers (wbx_kernels.hip, wbx_mix_fam<N>.hip) look the chosen instance up
 // by its template arguments and launch it; they decide nothing.
+//
+// Beside it, in the same way: choose_issue — how a render's launches are issued (streams, fusing, the one-launch callback,
+// the staged master) — from (knobs, facts) to a RenderIssue, called once per launch_mix_sum.
 #pragma once
 #include <cstdint>
 #include <cstdio>
 
+#include "../../include/wbx.h"
 #include "wbx_dev.h"
 #include "wbx_knobs.h"
 
@@ -328,6 +332,79 @@ inline RenderShape choose_shape(const ShapeKnobs& k, const ShapeFacts& f) {
   //  is bound by instruction issue — U = 2: 11.3 us, 4: 11.6, 8: 13.4.  Family 3 = 1 without the per-frame taps: one instance
   //  serves both)
   r.cb = fam == 0 ? MixInstance::callback(k.cb_u == 8 ? 8 : k.cb_u == 4 ? 4 : 2, 0) : MixInstance::callback(2, fam == 2 ? 2 : 1);
+  return r;
+}
+
+// ---- how a render is issued -------------------------------------------------------------------------------------------
+// Which streams the mix and the sum of a render take, which launches it is made of and what is recorded between them: one
+// pure function from (knobs, facts) to a RenderIssue, called once at the top of launch_mix_sum (wbx_runtime.hip), which
+// then only fills arguments and issues.  tests/test_host_logic.py holds it against the rules written out again.
+
+struct IssueFacts {
+  // the render and its RenderShape (tiles: the shape's value, before the callback instance overrides it)
+  uint32_t K = 1, n_groups = 0, n_buses = 0, tiles = 1, block_frames = 512, channels = 2;
+  bool chained = false, cb_one_launch = false;
+  // the call (RenderCall, wbx_ctx.h)
+  bool callback_plan = false;   // the caller handed the sequencer's arguments in: the block may run as one launch
+  int master_format = 0;        // 0 planar fp32, else WBX_OUT_*
+  bool mix_on_main = true;      // the mix runs on the main stream (not the alternate one)
+  // the context's state
+  bool dist = false;            // a multi-GPU exchange is attached
+  bool init = false;            // the sum continues a running master (wbx_set_master_init, chain mode's received sum)
+  bool target_set = false, target_on_host = false;   // the master goes to a caller's buffer / ... which is pinned host memory
+  bool cb_no_spread = false;    // a spread launch gave up before: "the last workgroup adds" from then on
+  uint32_t n_cus = 0;
+};
+
+struct RenderIssue {
+  bool sum_beside = false;      // the sum runs on the sum stream, beside the next mix
+  bool fused = false;           // the mix workgroup clamps and stores the master itself: no sum launch
+  bool timed = false;           // the kernel timer's events ride on this render
+  bool one_launch = false;      // sequencer + mix + sum as ONE launch (wbx_callback.h)
+  bool by_kernel_event = false; // the sum stream waits for the mix kernel's own stop event, mix_done is recorded over there
+  bool spread = false;          // every workgroup of the one launch adds a share of the master
+  uint64_t stage_bytes = 0;     // > 0: the master leaves through a device staging buffer and one copy of this many bytes
+};
+
+// The spread sum's ticket barrier needs every workgroup of the grid resident at once: at most one per CU the process may use.
+// A CU mask (HSA_CU_MASK / ROC_GLOBAL_CU_MASK) takes CUs away without the attribute saying so: no spreading then.  (A device
+// shared with another process can still hold workgroups back; the barrier's wait is bounded, a give-up is reported and the
+// block is mixed again through three launches — wbx_engine_process — and the context stops spreading.)
+// `n_cus`, `cu_mask`: the device's CU count and CtxKnobs::cu_mask, as wbx_create found them.
+inline uint32_t callback_spread_limit(uint32_t n_cus, bool cu_mask) { return cu_mask ? 0u : (n_cus < 256u ? n_cus : 256u); }
+
+inline RenderIssue choose_issue(const CtxKnobs& k, const IssueFacts& f) {
+  RenderIssue r;
+  // short renders (the one-block callback path above all) keep everything on the main stream: the cross-stream
+  // hand-overs cost more than the few microseconds of overlap they could buy
+  r.sum_beside = k.sum_overlap && f.K >= kOverlapMinBlocks;
+  // A short render of a session that is one group (the callback configuration up to 64 tracks; no sub-buses, planar fp32
+  // master, nothing to continue): the mix workgroup clamps and stores the master itself — the sum kernel is not launched
+  r.fused = f.K < kOverlapMinBlocks && f.n_groups == 1u && f.n_buses == 0u && f.tiles == 1u && !f.master_format && !f.dist && !f.init &&
+            !f.chained;
+  // the kernel timer is for batch renders; the one-block callback path skips its three event records
+  r.timed = k.profiling && f.K > 1u;
+  r.one_launch = f.callback_plan && f.n_groups != 0u && f.cb_one_launch;
+  // (round 6) When the kernel carries the timer's stop event and its sum runs on the sum stream, THAT event is what the sum
+  // stream waits for, and mix_done — what later plans wait for — is recorded over there: no marker packet behind the mix on
+  // its own stream, where the next mix queues (every packet between two mixes is a round trip of the command processor to
+  // the queue in host memory, behind whatever the copy engine is posting; what the marker cost: EXPERIMENTS.md, round 6).
+  r.by_kernel_event = f.n_groups != 0u && !r.one_launch && r.timed && !f.dist && !k.mix_alternate && f.mix_on_main && r.sum_beside;
+  // A master bound for pinned host memory leaves a batch render through a device staging buffer and the copy engine.  Stored
+  // by the sum kernel itself, its megabytes of posted writes fill the GPU's upstream queue in a few microseconds and drain at
+  // the PCIe rate; the command processor's own reads of host memory (the next dispatch packet, its signals) wait behind
+  // them, and the next mix started only when the sum had ended — 0.15 ms per 2048-block render.  (One-block callbacks keep
+  // the direct stores: 4 KB, and no second operation in the latency path.  Packed 24-bit too: its writer leaves part of
+  // the target untouched, which a whole-buffer copy would not.)
+  if (r.sum_beside && !f.dist && f.target_set && f.target_on_host && f.master_format != WBX_OUT_I24) {
+    // (from 4 MB: below, the copy's fixed cost on the sum stream outweighs the hold-up — a 256-track session rendering 256
+    //  blocks at a time lost a quarter of its rate to it, and gains a quarter at 2048)
+    const uint64_t bytes = (uint64_t)f.K * f.block_frames * f.channels * (f.master_format == WBX_OUT_I16 ? 2u : 4u);
+    if (bytes >= (4u << 20)) r.stage_bytes = bytes;
+  }
+  // every workgroup adds a share of the master when the whole grid is resident at once (at most one workgroup per CU: two
+  // fit)
+  r.spread = r.one_launch && !r.fused && !f.cb_no_spread && f.n_groups <= callback_spread_limit(f.n_cus, k.cu_mask);
   return r;
 }
 
