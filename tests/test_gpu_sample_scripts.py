@@ -1,24 +1,38 @@
-"""Sample life scripts on the device (tests/sample_scripts.py): uploads, derived, normalized and resampled samples, recorder
-takes, bounces and deletes chained at random in ONE clip pool, with placements, playback, measure, export and mip-maps in
-between.  Every feature's own test checks its own result; this one checks THE OTHERS: after every op every live sample is
-downloaded and compared bit for bit (uint32 views) with the model — an extent handed to two clips corrupts whoever was
-written first, which is never the clip a feature test looks at — and the padding behind every producer's result shows when a
-clip of another rate plays to its end against the oracle engine, whose copy of the sample is the model's planes + 16 zeros.
-The pool's three figures are checked after every op and are the starting ones at the end.
+"""Sample life scripts on the device (tests/sample_scripts.py): uploads, derived, normalized, resampled, spliced and
+loudness-normalized samples, recorder takes, bounces and deletes chained at random in ONE clip pool, with placements,
+playback, measure, loudness, export and mip-maps in between.  Every feature's own test checks its own result; this one
+checks THE OTHERS: after every op every live sample is downloaded and compared bit for bit (uint32 views) with the model —
+an extent handed to two clips, or a store past a row, corrupts whoever lies beside the clip a feature test looks at — and
+the padding behind every producer's result shows when a clip of another rate plays to its end against the oracle engine,
+whose copy of the sample is the model's planes + 16 zeros.  The pool's three figures are checked after every op and are
+the starting ones at the end.
 
-Measured on an MI355X: 0.07 - 0.45 s per case, 2.2 - 2.5 s for the module's twelve cases (MEASUREMENTS.md "Sample life scripts");
+A splice's sources are takes, bounces, earlier splices and everything else of one rate; a loudness normalization's gain is
+the model's within one spacing (pow's last place) and the fp32 quotient where the ceiling binds, its planes the model's
+derive at the gain the product used; a loudness measurement is compared as tests/test_gpu_loudness.py compares one (hop
+energies and the true peak bit for bit) and, being a consumer, must leave every sample and the pool alone.  A refused
+splice (an i16 source: -3, two rates: -4) or normalization (fewer than 4 hops: -4) returns its status, makes no sample id
+and changes nothing; the script often deletes one of its sources next, which a pin left behind would refuse.
+
+Measured on an MI355X: 0.84 - 1.7 s per case, 15.3 s for the module's twelve cases (0.07 - 0.45 s and 2.2 - 2.5 s before
+splice and loudness joined: the time is numpy's twin of the loudness filter; MEASUREMENTS.md "Sample life scripts");
 no time is asserted."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import bounce_util as BU
 import clipfx_model as FX
+import loudness_model as LM
 import oracle_ffi as O
 import record_model as RM
 import sample_scripts as SS
+import splice_model as SP
 import whitebox_amd as W
-from whitebox_amd import synth
+from whitebox_amd import _ffi, synth
 from test_gpu_clipfx import check_stats
+from test_gpu_loudness import assert_result, bits64
 from test_gpu_export import expected_bytes, expected_stats, same_stats
 from test_gpu_record import Rig, input_blocks
 
@@ -133,6 +147,40 @@ class LifeRig(Rig):
                 sid = eng.resample_sample(self.sid[src], dst, q, first, n, channels=len(c.s[src][2]), frames=len(c.s[src][2][0]),
                                           src_rate=c.s[src][1])
                 self.new_sample(key, sid, len(c.s[key][2][0]), len(c.s[src][2]), dst)
+            elif k == "splice":
+                _, key, channels, n_frames, parts, status = op
+                ffi = [SP.to_ffi(W, SP.Part(*p)._replace(src=self.sid[p[0]])) for p in parts]
+                if status:                                   # refused: the status, and no sample id
+                    return self.refused(eng.L.wbx_engine_splice_samples, channels, n_frames, (_ffi.SplicePart * len(ffi))(*ffi), len(ffi))
+                c.apply(op)
+                sid = eng.splice_samples(channels, n_frames, ffi)
+                self.new_sample(key, sid, n_frames, channels, c.s[parts[0][0]][1])
+            elif k == "loudnorm":
+                _, key, src, target, ceiling, first, n, status = op
+                if status:
+                    return self.refused(eng.L.wbx_engine_normalize_loudness_sample, self.sid[src], first, n, target, ceiling)
+                model, free, top = c.loudnorm_gains(op)
+                planes = c.s[src][2]
+                sid, gain = eng.normalize_loudness_sample(self.sid[src], target, ceiling, first, n, channels=len(planes), frames=len(planes[0]))
+                assert abs(np.float32(gain) - model) <= np.spacing(model), ("gain", gain, model, free, top)   # pow's last place
+                if top < free - np.spacing(free):            # the ceiling binds whatever pow's last place: the fp32 quotient
+                    assert np.float32(gain).tobytes() == np.float32(top).tobytes(), ("gain under the ceiling", gain, top)
+                c.apply_loudnorm(op, np.float32(gain))
+                self.new_sample(key, sid, n, len(planes), c.s[src][1])
+            elif k == "loudness":
+                _, src, true_peak, first, n = op
+                _, rate, planes = c.s[src]
+                got, E = eng.loudness_sample(self.sid[src], first, n, true_peak=true_peak, energies=True, channels=len(planes),
+                                             frames=len(planes[0]), rate=rate)
+                want_E = LM.hop_energies(planes, first, n, rate)
+                assert E.shape == want_E.shape == (len(planes), n // LM.hop_frames(rate))
+                bad = np.flatnonzero(bits64(E).ravel() != bits64(want_E).ravel())
+                assert bad.size == 0, ("hop energies", src, bad[:8].tolist(), bad.size)
+                assert_result(got, LM.gate(want_E, LM.hop_frames(rate)), ("loudness", src))
+                want_peak = LM.true_peak(planes, first, n, rate) if true_peak else [np.float32(0.0)] * len(planes)
+                assert got["oversampling"] == (LM.oversampling(rate) if true_peak else 0)
+                assert BU.bits(np.array(got["true_peak"], dtype=np.float32)).tolist() == BU.bits(np.array(want_peak, dtype=np.float32)).tolist(), \
+                    ("true peak", src, got["true_peak"], want_peak)
             elif k == "take":
                 _, key, track, kind, index, b0, n, beat = op
                 made = len(self.made)
@@ -205,6 +253,14 @@ class LifeRig(Rig):
             return ex.status
         return 0
 
+    def refused(self, fn, *args):
+        """a producer the product must refuse -> its status; no sample id and no gain came back"""
+        new, gain = C.c_uint32(0xFEED), C.c_float(7.0)
+        tail = (C.byref(new), C.byref(gain)) if fn is self.eng.L.wbx_engine_normalize_loudness_sample else (C.byref(new),)
+        status = fn(self.eng.h, *args, *tail)
+        assert status != 0 and new.value == 0xFEED and gain.value == 7.0, ("a refused producer made a sample", status, new.value)
+        return status
+
     def close(self):
         Rig.close(self)
         self.tw.close()
@@ -220,7 +276,7 @@ def test_every_sample_outlives_its_neighbours(seed):
         for i, op in enumerate(ops):
             try:
                 status = rig.life_op(op)
-                assert status == (op[2] if op[0] == "delete" else 0), ("status", status)
+                assert status == (op[2] if op[0] == "delete" else op[-1] if op[0] in ("splice", "loudnorm") else 0), ("status", status)
                 rig.check_bystanders()
             except AssertionError as ex:
                 raise AssertionError((seed, i, op[:3], ex.args)) from ex
