@@ -268,7 +268,7 @@ int hsim_render(HostSim* s, uint32_t K) {
   }
   hs.routing_dirty = false;
   s->rows.assign((size_t)K * N, DRow{});
-  // (the conditions of wbx_engine.hip plan_segment_length with a forced segment length)
+  // (the conditions of choose_plan, wbx_shape.h, with a forced segment length)
   if (s->table_flags && s->flags_left == 0u) s->table_flags = false;
   const uint32_t L = (s->seg_len && s->seg_len < K && playing && !s->table_flags) ? s->seg_len : 0u;
   const uint32_t S = L ? (K + L - 1u) / L : 1u;
@@ -305,7 +305,7 @@ int hsim_render(HostSim* s, uint32_t K) {
   a.flags_left = &s->flags_left;
   hs.clips_edited = false;
   a.masked_rows = s->masked_rows;
-  a.tmpl_reserve = HostSession::template_reserve(K);
+  a.tmpl_reserve = template_reserve(K);
   a.playhead = hs.playhead;
   a.sample_position = hs.sample_position;
   a.beat_duration = beat_duration;
@@ -313,7 +313,7 @@ int hsim_render(HostSim* s, uint32_t K) {
   block_times(a, times.data());
   if (L) {
     // every lane of plan_seg_kernel, in an order no lane may rely on (segments backwards, tracks forwards), then the seam pass
-    a.tmpl_reserve = 8u;
+    a.tmpl_reserve = kSegmentTemplateReserve;
     std::vector<DTrackState> guess((size_t)N * S), ends((size_t)N * S);
     const DBlockTime* tv = times.data();
     for (uint32_t sg = S; sg-- > 0u;)
@@ -423,6 +423,41 @@ void hsim_render_issue_all(uint32_t K, uint32_t n_groups, uint32_t n_buses, uint
     flags[bits] = (uint8_t)(r.sum_beside | r.fused << 1 | r.timed << 2 | r.one_launch << 3 | r.by_kernel_event << 4 | r.spread << 5);
     stage[bits] = r.stage_bytes;
   }
+}
+
+// How a render is planned (wbx_shape.h: choose_plan).  K, N, EngineKnobs::plan_seg and the shape's masked_rows are passed as
+// they are; the boolean facts and knobs as one word — bit 0 playing, 1 callback, 2 any_slow_clip, 3 cut, 4 table_flags,
+// 5 seg_broken, 6 cb_one_launch, 7 counters_zero, 8 overlap, 9 force_cut (kPlanBits of them).
+constexpr uint32_t kPlanBits = 10;
+struct HsimPlan {
+  uint32_t seg_len, n_segs, tmpl_reserve, flags;   // flags: plan_flags below
+};
+static RenderPlan plan_of(uint32_t K, uint32_t N, int plan_seg, uint32_t masked_rows, uint32_t bits) {
+  PlanFacts f;
+  f.K = K, f.N = N, f.masked_rows = masked_rows;
+  f.playing = bits >> 0 & 1u, f.callback = bits >> 1 & 1u, f.any_slow_clip = bits >> 2 & 1u, f.cut = bits >> 3 & 1u;
+  f.table_flags = bits >> 4 & 1u, f.seg_broken = bits >> 5 & 1u, f.cb_one_launch = bits >> 6 & 1u, f.counters_zero = bits >> 7 & 1u;
+  EngineKnobs ek;
+  ek.plan_seg = plan_seg;
+  CtxKnobs ck;
+  ck.overlap = bits >> 8 & 1u;
+  ShapeKnobs sk;
+  sk.force_cut = bits >> 9 & 1u;
+  return choose_plan(ek, ck, sk, f);
+}
+// beside | device_times << 1 | skip_pre_render << 2 | static_tmpl << 3 | double_rows << 4 | pool_slack << 5 | sequencer << 6
+// (0 plain, 1 segments, 2 none) | zeroing << 8 (0 nobody, 1 the times-copy kernel, 2 a memset)
+static uint32_t plan_flags(const RenderPlan& r) {
+  return (uint32_t)r.beside | (uint32_t)r.device_times << 1 | (uint32_t)r.skip_pre_render << 2 | (uint32_t)r.static_tmpl << 3 |
+         (uint32_t)r.double_rows << 4 | (uint32_t)r.pool_slack << 5 | (uint32_t)r.sequencer << 6 | (uint32_t)r.zeroing << 8;
+}
+void hsim_render_plan(uint32_t K, uint32_t N, int plan_seg, uint32_t masked_rows, uint32_t bits, HsimPlan* out) {
+  const RenderPlan r = plan_of(K, N, plan_seg, masked_rows, bits);
+  *out = HsimPlan{r.seg_len, r.n_segs, r.tmpl_reserve, plan_flags(r)};
+}
+// ... for every value of the word at once (1 << kPlanBits entries)
+void hsim_render_plan_all(uint32_t K, uint32_t N, int plan_seg, uint32_t masked_rows, HsimPlan* out) {
+  for (uint32_t bits = 0; bits < (1u << kPlanBits); bits++) hsim_render_plan(K, N, plan_seg, masked_rows, bits, out + bits);
 }
 
 // plan status bits of the last render (PlanArgs::status) and the number of templates / pre-render rows it used
@@ -551,7 +586,8 @@ int main() {
 
 #ifdef HOST_SIM_KNOBS_MAIN
 // wbx_knobs.h and wbx_shape.h stand-alone, for a build with -fsanitize=address,undefined: every reader with the environment
-// empty and with each switch set, and choose_shape over a sweep of sessions and render lengths under each setting.
+// empty and with each switch set, choose_shape and choose_issue over a sweep of sessions and render lengths under each
+// setting, and choose_plan over every value of its fact word.
 #include <array>
 #include <cstdlib>
 #include <iterator>
@@ -624,6 +660,20 @@ int main() {
           issues += is.stage_bytes != 0u || is.sum_beside || !is.spread;
           if (is.stage_bytes != 0u && (K < 2047u || format == (int)WBX_OUT_I24 || (K == 2047u && format == (int)WBX_OUT_I16))) ok = false;
         }
+  // choose_plan over every value of its fact word: segments never in a callback and always shorter than the render, the
+  // counters zeroed by somebody exactly when they are not zero yet
+  uint64_t plans = 0;
+  for (uint32_t K : {1u, 7u, 8u, 127u, 128u, 2048u, 1u << 20})
+    for (uint32_t N : {0u, 1u, 256u, 4096u, 1u << 20})
+      for (int plan_seg : {-1, 0, 16, 128, 0x7FFFFFFF})
+        for (uint32_t masked_rows : {0u, 4u})
+          for (uint32_t bits = 0; bits < (1u << kPlanBits); bits++) {
+            const RenderPlan p = plan_of(K, N, plan_seg, masked_rows, bits);
+            plans += p.seg_len != 0u;
+            if (p.seg_len >= K || (p.seg_len != 0u && (bits & 2u)) || (uint64_t)p.n_segs * (p.seg_len ? p.seg_len : K) < K) ok = false;
+            if ((p.zeroing == RenderPlan::NOBODY) != ((bits >> 7 & 1u) != 0u) || plan_flags(p) >> 10) ok = false;
+          }
+  ok = ok && plans != 0u;
   for (size_t i = 0; i < std::size(kShape); i++) {   // each switch flips its own field and no other
     setenv(kShape[i][0], kShape[i][1], 1);
     const HsimKnobs h = flat();

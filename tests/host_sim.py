@@ -100,6 +100,40 @@ def render_issue_all(k, n_groups, n_buses, tiles, frames, channels, fmt, n_cus):
     return flags, stage
 
 
+class RenderPlan(C.Structure):
+    """hsim_render_plan's result (tests/cpp/host_sim.cpp HsimPlan): RenderPlan of wbx_shape.h, its booleans and enums in `flags`"""
+    _fields_ = [(n, C.c_uint32) for n in ("seg_len", "n_segs", "tmpl_reserve", "flags")]
+
+
+# the boolean facts and knobs of choose_plan in the order of hsim_render_plan's `bits` word; its boolean results in the order of
+# the low bits of HsimPlan::flags, then two bits each of `sequencer` and `zeroing`
+PLAN_BITS = ("playing", "callback", "any_slow_clip", "cut", "table_flags", "seg_broken", "cb_one_launch", "counters_zero", "overlap",
+             "force_cut")
+PLAN_FLAGS = ("beside", "device_times", "skip_pre_render", "static_tmpl", "double_rows", "pool_slack")
+PLAN_SEQUENCER = ("plain", "segments", "none")             # flags >> 6 & 3
+PLAN_ZEROING = ("nobody", "times_copy", "memset")          # flags >> 8 & 3
+PLAN_FLAG_BITS = len(PLAN_FLAGS) + 4
+
+
+def render_plan(k, n, plan_seg=-1, masked_rows=0, **bools) -> dict:
+    """choose_plan (wbx_shape.h) for one set of facts; bools: the names of PLAN_BITS that are true"""
+    assert set(bools) <= set(PLAN_BITS)
+    bits = sum(1 << i for i, name in enumerate(PLAN_BITS) if bools.get(name))
+    out = RenderPlan()
+    lib().hsim_render_plan(k, n, plan_seg, masked_rows, bits, C.byref(out))
+    r = dict(seg_len=out.seg_len, n_segs=out.n_segs, tmpl_reserve=out.tmpl_reserve,
+             sequencer=PLAN_SEQUENCER[out.flags >> 6 & 3], zeroing=PLAN_ZEROING[out.flags >> 8 & 3])
+    r.update({name: bool(out.flags >> i & 1) for i, name in enumerate(PLAN_FLAGS)})
+    return r
+
+
+def render_plan_all(k, n, plan_seg, masked_rows):
+    """... for every value of the `bits` word: uint32 [1 << len(PLAN_BITS), 4] — seg_len, n_segs, tmpl_reserve, flags"""
+    out = np.empty((1 << len(PLAN_BITS), 4), np.uint32)
+    lib().hsim_render_plan_all(k, n, plan_seg, masked_rows, out.ctypes.data_as(C.POINTER(RenderPlan)))
+    return out
+
+
 def shape_knobs() -> dict:
     """ShapeKnobs::from_env() as this process's environment stands now"""
     k = ShapeKnobs()
@@ -129,6 +163,11 @@ def lib() -> C.CDLL:
         L.hsim_render_issue.argtypes = issue_facts + [C.c_uint32, C.POINTER(RenderIssue)]
         L.hsim_render_issue_all.restype = None
         L.hsim_render_issue_all.argtypes = issue_facts + [C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
+        plan_facts = [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
+        L.hsim_render_plan.restype = None
+        L.hsim_render_plan.argtypes = plan_facts + [C.c_uint32, C.POINTER(RenderPlan)]
+        L.hsim_render_plan_all.restype = None
+        L.hsim_render_plan_all.argtypes = plan_facts + [C.POINTER(RenderPlan)]
         sig = {
             "hsim_set_bpm": [C.c_double], "hsim_set_playhead_position": [C.c_double],
             "hsim_add_track": [C.POINTER(C.c_uint32)],

@@ -339,3 +339,113 @@ def test_deleted_context_fields_are_named_nowhere():
     assert len(body) > 5000
     assert not re.findall(r"\b(?:%s)\b" % "|".join(DELETED_CTX_FIELDS), body)
     assert "struct RenderCall" in ctx_h and "choose_issue" in _text(os.path.join(CSRC, "wbx_shape.h"))
+
+
+# ---- how a render is planned: choose_plan (wbx_shape.h) against its rules written out again ---------------------------------------
+def _template_reserve(K, segmented):
+    return 8 if segmented else 32 if K >= 64 else 8 if K >= 8 else 1
+
+
+def _plan_rules(K, N, plan_seg, masked_rows, b):
+    """the rules, over arrays of the boolean facts and knobs `b` (name -> bool array); -> name -> array"""
+    may = b["playing"] & ~b["table_flags"] & ~b["callback"] & ~b["seg_broken"] & (plan_seg != 0 and N != 0)
+    if plan_seg > 0:                       # a forced length
+        seg = np.where(may, plan_seg if plan_seg < K else 0, 0)
+    else:                                  # about 16 k lanes, from 32 blocks up, sessions cut into clips only
+        length = 32
+        while (K // length) * N > 24576 and length < K:
+            length *= 2
+        seg = np.where(may & b["cut"] & (K >= 128), length if length < K else 0, 0)
+    segmented = seg != 0
+    beside = b["overlap"] & (K >= OVERLAP_MIN_BLOCKS)
+    device_times = segmented | (beside & ~(b["cut"] | b["force_cut"]))
+    one = b["cb_one_launch"]
+    return dict(
+        seg_len=seg, n_segs=np.where(segmented, (K + seg - 1) // np.maximum(seg, 1), 1), beside=beside, device_times=device_times,
+        zeroing=np.where(b["counters_zero"], 0, np.where(device_times, 1, 2)),
+        skip_pre_render=b["callback"] & ~b["any_slow_clip"] & (one | (masked_rows != 0)),
+        sequencer=np.where(segmented, 1, np.where(one, 2, 0)),
+        tmpl_reserve=np.where(one, 0, np.where(segmented, _template_reserve(K, True), _template_reserve(K, False))),
+        static_tmpl=one, double_rows=segmented, pool_slack=segmented)
+
+
+def test_render_plan_matches_its_rules_over_the_full_cross_product():
+    """choose_plan == the rules for K x N x WBX_PLAN_SEG x masked_rows x every boolean fact and knob both ways, every result field;
+    the segment lengths its comments promise, by name; segments never in a callback, no sequencer launch only for the one-launch
+    callback, the counters zeroed by exactly one party when they are not zero and by none when they are; template_hint's
+    stranded templates of a segmented render are those of choose_plan's reserve"""
+    import itertools
+    import host_sim as HS
+    word = np.arange(1 << len(HS.PLAN_BITS), dtype=np.uint32)
+    b = {n: (word >> i & 1).astype(bool) for i, n in enumerate(HS.PLAN_BITS)}
+    cases = 0
+    for K, N, plan_seg, masked_rows in itertools.product(
+            (1, 7, 8, 16, 17, 127, 128, 129, 2048), (0, 1, 64, 256, 4096), (-1, 0, 16, 128, 4096), (0, 1, 2)):
+        got = HS.render_plan_all(K, N, plan_seg, masked_rows)
+        flags = got[:, 3]
+        have = dict(seg_len=got[:, 0], n_segs=got[:, 1], tmpl_reserve=got[:, 2], sequencer=flags >> 6 & 3, zeroing=flags >> 8 & 3)
+        have.update({name: (flags >> i & 1).astype(bool) for i, name in enumerate(HS.PLAN_FLAGS)})
+        want = _plan_rules(K, N, plan_seg, masked_rows, b)
+        assert sorted(have) == sorted(want)
+        for name in want:
+            bad = have[name] != want[name]
+            assert not bad.any(), (name, K, N, plan_seg, masked_rows, int(word[bad][0]))
+        # no undefined result bit, no undefined enum value
+        assert not (flags >> HS.PLAN_FLAG_BITS).any() and (have["sequencer"] < 3).all() and (have["zeroing"] < 3).all()
+        # the three properties
+        assert not (have["seg_len"] != 0)[b["callback"]].any()
+        assert b["cb_one_launch"][have["sequencer"] == 2].all()
+        assert np.array_equal(have["zeroing"] == 0, b["counters_zero"])
+        cases += len(word)
+    assert cases == 9 * 5 * 5 * 3 * 2 ** 10
+    # the lengths the comments promise
+    cut = dict(cut=True, playing=True)
+    assert HS.render_plan(2048, 256, **cut)["seg_len"] == 32
+    assert HS.render_plan(2048, 4096, **cut)["seg_len"] == 512
+    assert HS.render_plan(128, 4096, **cut)["seg_len"] == 32
+    for N in (1, 64, 256, 4096, 1 << 20):
+        assert HS.render_plan(127, N, **cut)["seg_len"] == 0
+    assert HS.render_plan(16, 64, plan_seg=16, playing=True)["seg_len"] == 0
+    assert HS.render_plan(17, 64, plan_seg=16, playing=True)["seg_len"] == 16
+    assert HS.render_plan(2048, 64, plan_seg=128, playing=True)["seg_len"] == 128
+    assert HS.render_plan(2048, 64, plan_seg=128, playing=True, table_flags=True)["seg_len"] == 0
+    # HostSession::template_hint and choose_plan take the segmented reservation from one place: a session of 4 empty tracks
+    # rendering 64 blocks in segments of 16 — hint = min(2 K N, 2 boundary blocks + 3 N + 64) + (reserve + 3) N lanes
+    K, N, seg = 64, 4, 16
+    plan = HS.render_plan(K, N, plan_seg=seg, playing=True)
+    assert (plan["seg_len"], plan["n_segs"], plan["sequencer"]) == (seg, 4, "segments")
+    eng = HS.HostSimEngine(N, max_blocks=K)
+    try:
+        eng.set_segments(seg)
+        for _ in range(N):
+            eng.add_track()
+        eng.play()
+        eng.render(K)
+        assert eng.segment_stats()[0] == 1
+        boundary = min(K * N, 2 * N + 64)
+        stranded = eng.template_capacity() - 64 - min(2 * K * N, 2 * boundary + 3 * N + 64)
+        assert stranded == (plan["tmpl_reserve"] + 3) * N * plan["n_segs"] == (8 + 3) * 4 * 4
+    finally:
+        eng.close()
+
+
+def test_render_plan_leftovers_are_named_nowhere():
+    """plan_segment_length occurs nowhere under whitebox_amd/csrc, include or tests/cpp; wbx_engine has no gen_skipped member and
+    nothing reaches one through an engine pointer; choose_plan is wbx_shape.h's; template_reserve is defined in one file;
+    wbx_engine.hip spells no output format's size out: it names WBX_OUT_I16 nowhere and compares with WBX_OUT_I24 once, for the
+    packed-24 copy"""
+    import re
+    paths = [p for top in (CSRC, os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp")) for p in _files(top)]
+    assert len(paths) > 30
+    hits = [(os.path.relpath(p, ROOT), m.group(0)) for p in paths
+            for m in re.finditer(r"\bplan_segment_length\b|\b(?:e|eng|engine)\s*(?:->|\.)\s*gen_skipped\b", _text(p))]
+    assert not hits, hits
+    engine = _text(os.path.join(CSRC, "wbx_engine.hip"))
+    body = engine[engine.index("struct wbx_engine {"):engine.index("namespace {")]
+    assert len(body) > 5000 and not re.search(r"\bgen_skipped\b", body)
+    assert "inline RenderPlan choose_plan(" in _text(os.path.join(CSRC, "wbx_shape.h"))
+    defined = [os.path.relpath(p, ROOT) for p in paths if re.search(r"\btemplate_reserve\s*\(\s*uint32_t\b", _text(p))]
+    assert defined == [os.path.join("whitebox_amd", "csrc", "wbx_shape.h")]
+    assert "WBX_OUT_I16" not in engine
+    assert len(re.findall(r"[=!]=\s*WBX_OUT_I24\b", engine)) == 1 and "(size_t)F * 3)" in engine
+    assert engine.count("out_format_bytes(") >= 4 and "size_t out_format_bytes(int fmt);" in _text(os.path.join(CSRC, "wbx_ctx.h"))

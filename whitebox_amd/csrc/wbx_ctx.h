@@ -474,6 +474,8 @@ inline size_t fmt_bytes(int fmt) {
   }
 }
 
+size_t out_format_bytes(int fmt);   // bytes of a sample in a WBX_OUT_* device format, 0: no such format (wbx_runtime.hip)
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 enum : int { CLIP_SRC_PLANAR = 0, CLIP_SRC_INTERLEAVED_HOST = 1, CLIP_SRC_INTERLEAVED_DEVICE = 2, CLIP_SRC_SYNTH = 3,

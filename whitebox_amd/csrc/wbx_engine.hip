@@ -48,7 +48,6 @@ struct wbx_engine {
   static constexpr uint32_t kStatusWords = 9;
   uint32_t cb_seq = 0;                  // ... of the last launch
   uint32_t cb_give_ups = 0;             // one-launch callbacks mixed again because a workgroup gave up at the spread barrier
-  bool gen_skipped = false;             // the process block's render left the pre-render launch out (expecting an empty queue)
   bool plan_status_on_host = false;     // the counters of the last plan are in h_status (the device copy was cleared)
   size_t d_clips_count = 0;
   bool clips_uploaded = false;          // the device holds a clip table (its internal_state_changed flags are live)
@@ -151,29 +150,12 @@ wbx_status cfail(wbx_engine* e, wbx_status s) {
     }                                                               \
   } while (0)
 
-// Blocks per segment when the sequencer of this render is cut along the time axis (wbx_seq.h: plan_segment), 0 = one lane
-// per track walks all K blocks.  Taken by batch renders of sessions with tracks cut into clips — a chain of dependent look-ups
-// per clip boundary and lane: c3 cut into 5.3-block clips planned 2048 blocks in 5.4 ms (4.4 ms for 128-frame blocks, in front
-// of a 2.6 ms mix) — while the transport runs and no clip carries a set internal_state_changed flag (the sequencer clears
-// those in passing, track.cpp:373,392,418: the run-up of one lane and the real walk of another would race for them).
-// About 16 k lanes: segments of K * N / 24576 blocks rounded up to a power of two, at least 32 (measured, profiles/
-// r04_ab_seglen.txt: 256 tracks best at 32-64 blocks — 16 and 128 are 9-15 % slower —, 4096 tracks x 2048 short blocks at 512).
-// WBX_PLAN_SEG=0: off; =<n>: segments of n blocks (A/B aid, tests).
-uint32_t plan_segment_length(wbx_engine* e, uint32_t K, uint32_t N, bool playing, bool in_callback) {
-  if (e->knobs.plan_seg == 0) return 0u;   // (WBX_PLAN_SEG as wbx_engine_create read it)
-  const uint32_t forced = e->knobs.plan_seg > 0 ? (uint32_t)e->knobs.plan_seg : 0u;
-  if (e->table_flags && e->h_flags_left.p && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left.p) == 0u)
-    e->table_flags = false;   // every flag of the table has been cleared by a plan that is over
-  if (!playing || e->table_flags || in_callback || N == 0u || e->ctx->seg_broken) return 0u;
-  if (forced) return forced < K ? forced : 0u;
-  if (!e->hs.cut_tracks || K < 128u) return 0u;
-  // (also where the one-lane walk would hide behind the previous mix — c3 / 16-bit sessions cut into 5.3- or 20-block clips at
-  //  512 frames: the segment lanes are done early, the next mix starts 0.06 instead of 0.15 ms behind its predecessor, steps
-  //  0-3 % shorter, never longer: profiles/r04_ab_planseg.txt)
-  uint32_t len = 32u;
-  while ((uint64_t)(K / len) * N > 24576u && len < K) len *= 2u;
-  return len < K ? len : 0u;
-}
+// a step that has left its own message behind
+#define WBX_STEP(call)                  \
+  do {                                  \
+    const wbx_status _s = (call);       \
+    if (_s != WBX_OK) return _s;        \
+  } while (0)
 
 bool sample_in_use_cb(void* owner, uint32_t sample) { return static_cast<wbx_engine*>(owner)->hs.sample_referenced(sample); }
 
@@ -1020,13 +1002,18 @@ extern "C" wbx_status wbx_engine_stop(wbx_engine* e) {   // engine.cpp:82-93, Tr
 
 namespace {
 
+// the host waits for both streams a render uses: what a step does before it replaces a buffer that work in flight may read
+hipError_t sync_plan_and_main(wbx_ctx* c) {
+  const hipError_t he = hipStreamSynchronize(c->plan_stream);
+  return he != hipSuccess ? he : sync_main(c);
+}
+
 // (re)allocate the three pinned patch and gain buffers at once — pinning memory synchronises the device, so it must
 // not happen in mid-run
 wbx_status ensure_pinned_tables(wbx_engine* e, uint32_t N) {
   wbx_ctx* c = e->ctx;
   if (e->tables_cap >= N) return WBX_OK;
-  WBX_EHIP(e, hipStreamSynchronize(c->plan_stream));
-  WBX_EHIP(e, sync_main(c));
+  WBX_EHIP(e, sync_plan_and_main(c));
   const uint32_t cap = std::max<uint32_t>(N, c->cfg.max_tracks);
   for (int i = 0; i < kRing; i++) {
     WBX_EHIP(e, e->patch[i].buf.ensure(cap));
@@ -1042,186 +1029,164 @@ wbx_status ensure_pinned_tables(wbx_engine* e, uint32_t N) {
   return WBX_OK;
 }
 
-// the audio thread's render, editor lock held by the caller.  `process`: the one block of wbx_engine_process, which waits
-// for it before it returns (the pinned tables need no completion events) — where its master and its plan status go; null:
-// a batch render, a bounce pass.  *as_one_launch (if asked for): the block ran as the one-launch callback
-wbx_status render_locked(wbx_engine* e, uint32_t K, const RenderCall* process = nullptr, bool* as_one_launch = nullptr) {
+// ---- the steps of render_locked (below), in the order it takes them --------------------------------------------------
+
+// Engine::process with an empty track list: output_buffer.clear() and the transport advance (engine.cpp:1598, :1619-1623) —
+// silence — or, with a running master to continue (wbx_set_master_init; WBX_DIST_CHAIN on a rank whose shard is empty: more
+// ranks than tracks, or all of its tracks deleted), that sum handed on unchanged: the receive must be posted like any other
+// render's, or the previous rank's send is never matched and the sum of all earlier ranks is lost
+wbx_status render_empty_session(wbx_engine* e, uint32_t K, float* master_target, int master_format, double beat_duration) {
   wbx_ctx* c = e->ctx;
-  float* const master_target = process ? process->master : c->master_target;
-  const int master_format = process ? process->format : c->master_format;
-  HostSession& hs = e->hs;
-  tls_err.clear();
-  if (K > c->cfg.max_blocks) return efail(e, WBX_ERR_INVALID, "n_blocks above wbx_config.max_blocks");
-  const uint32_t N = hs.n_tracks();
-  (void)hipSetDevice(c->cfg.device);
   const uint32_t C = c->cfg.channels, F = c->cfg.block_frames;
   hipStream_t s = c->stream;
-  hs.render_edit_seq = hs.edit_seq;
-  // engine.cpp:1579,1585: the tempo and the play state are read once per block
-  const double beat_duration = hs.beat_duration.load(std::memory_order_relaxed);
-  const bool playing = hs.playing.load(std::memory_order_relaxed);
-  if (N == 0) {
-    // Engine::process with an empty track list: output_buffer.clear() and the transport advance (engine.cpp:1598,
-    // :1619-1623) — silence
-    // — or, with a running master to continue (wbx_set_master_init; WBX_DIST_CHAIN on a rank whose shard is empty: more ranks
-    // than tracks, or all of its tracks deleted), that sum handed on unchanged: the receive must be posted like any other
-    // render's, or the previous rank's send is never matched and the sum of all earlier ranks is lost
-    WBX_EHIP(e, join_sum(c));
-    WBX_EHIP(e, c->d_master.ensure((size_t)K * C * F));
-    const bool continues = c->master_init || dist_receives_running_sum(c);
-    if (master_format && (c->dist || continues))
-      return efail(e, WBX_ERR_UNSUPPORTED, "an empty session continues a running master / feeds a multi-GPU exchange in planar fp32 only");
-    hipError_t me = hipSuccess;
-    float* master = begin_master(c, master_target, s, &me);
-    WBX_EHIP(e, me);
-    if (continues) {
-      wbx_status ist = WBX_OK;
-      const float* init = c->dist ? dist_mix_init(c, K, s, &ist) : c->master_init;
-      if (ist != WBX_OK) return cfail(e, ist);
-      launch_clamp_into(init, master, (size_t)K * C * F, c->clamp ? 1 : 0, s);   // (the clamp follows the last addition: none here)
-      if (c->dist) WBX_EHIP(e, dist_mix_issued(c, s));
-      WBX_EHIP(e, hipGetLastError());
-    } else {   // (all-zero bytes are silence in every output format; packed 24-bit counts its 3 bytes per sample)
-      const size_t eb = master_format == WBX_OUT_I16 ? 2 : master_format == WBX_OUT_I24 ? 3 : 4;
-      WBX_EHIP(e, hipMemsetAsync(master, 0, (size_t)K * C * F * eb, s));
-    }
-    c->last_master = master;
-    c->last_master_format = master_format;
-    c->last_master_on_host = false;
-    c->last_K = K;
-    c->last_N = 0;
-    hs.advance_transport_locked(K, F, beat_duration);
-    return WBX_OK;
+  WBX_EHIP(e, join_sum(c));
+  WBX_EHIP(e, c->d_master.ensure((size_t)K * C * F));
+  const bool continues = c->master_init || dist_receives_running_sum(c);
+  if (master_format && (c->dist || continues))
+    return efail(e, WBX_ERR_UNSUPPORTED, "an empty session continues a running master / feeds a multi-GPU exchange in planar fp32 only");
+  hipError_t me = hipSuccess;
+  float* master = begin_master(c, master_target, s, &me);
+  WBX_EHIP(e, me);
+  if (continues) {
+    wbx_status ist = WBX_OK;
+    const float* init = c->dist ? dist_mix_init(c, K, s, &ist) : c->master_init;
+    if (ist != WBX_OK) return cfail(e, ist);
+    launch_clamp_into(init, master, (size_t)K * C * F, c->clamp ? 1 : 0, s);   // (the clamp follows the last addition: none here)
+    if (c->dist) WBX_EHIP(e, dist_mix_issued(c, s));
+    WBX_EHIP(e, hipGetLastError());
+  } else {   // (all-zero bytes are silence in every output format; packed 24-bit counts its 3 bytes per sample)
+    const size_t eb = master_format ? out_format_bytes(master_format) : sizeof(float);
+    WBX_EHIP(e, hipMemsetAsync(master, 0, (size_t)K * C * F * eb, s));
   }
+  c->last_master = master;
+  c->last_master_format = master_format;
+  c->last_master_on_host = false;
+  c->last_K = K;
+  c->last_N = 0;
+  e->hs.advance_transport_locked(K, F, beat_duration);
+  return WBX_OK;
+}
 
-  wbx_status st = ensure_pinned_tables(e, N);
-  if (st != WBX_OK) return st;
+// parameters: drain the message rings (process_track_messages track.cpp:773-779) and apply them (track.cpp:618-643); the
+// factor used per sample is fl(volume * pan_coeffs[c]) (track.cpp:728-731)
+wbx_status refresh_gains(wbx_engine* e) {
+  if (!e->hs.drain_params_locked()) return WBX_OK;
+  const int slot = (e->gains_slot + 1) % kRing;
+  WBX_EHIP(e, e->gains[slot].wait());   // its last reader, >= 2 changes ago
+  e->hs.build_gains_locked(e->gains_tmp);
+  std::memcpy(e->gains[slot].buf.p, e->gains_tmp.data(), e->gains_tmp.size() * sizeof(float));
+  e->gains_slot = slot;
+  e->gains_gen++;
+  return WBX_OK;
+}
 
-  // -- parameters: drain the message rings (process_track_messages track.cpp:773-779) and apply them
-  //    (track.cpp:618-643); the factor used per sample is fl(volume * pan_coeffs[c]) (track.cpp:728-731)
-  if (hs.drain_params_locked()) {
-    const int slot = (e->gains_slot + 1) % kRing;
-    WBX_EHIP(e, e->gains[slot].wait());   // its last reader, >= 2 changes ago
-    hs.build_gains_locked(e->gains_tmp);
-    std::memcpy(e->gains[slot].buf.p, e->gains_tmp.data(), e->gains_tmp.size() * sizeof(float));
-    e->gains_slot = slot;
-    e->gains_gen++;
+// clip lists: the table is replaced whole when an edit touched it
+wbx_status upload_clip_table(wbx_engine* e, uint32_t N) {
+  HostSession& hs = e->hs;
+  if (!hs.clips_dirty) return WBX_OK;
+  WBX_EHIP(e, sync_plan_and_main(e->ctx));
+  // Clip::internal_state_changed is cleared by the sequencer on the device (track.cpp:373,392,418): before
+  // the table is replaced, take the live flags back for every clip no edit has touched since the last upload
+  if (e->clips_uploaded && e->d_clips_count) {
+    std::vector<DClip> live(e->d_clips_count);
+    WBX_EHIP(e, hipMemcpy(live.data(), e->d_clips.p, live.size() * sizeof(DClip), hipMemcpyDeviceToHost));
+    hs.merge_live_flags_locked(live.data(), live.size());
   }
+  hs.flatten_clips_locked(e->flat, e->first);
+  WBX_EHIP(e, e->d_clips.ensure(std::max<size_t>(1, e->flat.size())));
+  WBX_EHIP(e, e->d_clip_first.ensure(N + 1));
+  e->d_clips_count = e->flat.size();
+  e->clips_uploaded = true;
+  WBX_EHIP(e, e->h_flags_left.ensure(16));
+  uint32_t set_flags = 0;   // (both streams were drained above: nothing counts down right now)
+  for (const DClip& dc : e->flat) set_flags += dc.internal_state_changed != 0 ? 1u : 0u;
+  *e->h_flags_left.p = set_flags;
+  e->table_flags = set_flags != 0u;
+  if (!e->flat.empty()) WBX_EHIP(e, hipMemcpy(e->d_clips.p, e->flat.data(), e->flat.size() * sizeof(DClip), hipMemcpyHostToDevice));
+  WBX_EHIP(e, hipMemcpy(e->d_clip_first.p, e->first.data(), e->first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return WBX_OK;
+}
 
-  // -- clip lists
-  if (hs.clips_dirty) {
-    WBX_EHIP(e, hipStreamSynchronize(c->plan_stream));
-    WBX_EHIP(e, sync_main(c));
-    // Clip::internal_state_changed is cleared by the sequencer on the device (track.cpp:373,392,418): before
-    // the table is replaced, take the live flags back for every clip no edit has touched since the last upload
-    if (e->clips_uploaded && e->d_clips_count) {
-      std::vector<DClip> live(e->d_clips_count);
-      WBX_EHIP(e, hipMemcpy(live.data(), e->d_clips.p, live.size() * sizeof(DClip), hipMemcpyDeviceToHost));
-      hs.merge_live_flags_locked(live.data(), live.size());
-    }
-    hs.flatten_clips_locked(e->flat, e->first);
-    WBX_EHIP(e, e->d_clips.ensure(std::max<size_t>(1, e->flat.size())));
-    WBX_EHIP(e, e->d_clip_first.ensure(N + 1));
-    e->d_clips_count = e->flat.size();
-    e->clips_uploaded = true;
-    WBX_EHIP(e, e->h_flags_left.ensure(16));
-    uint32_t set_flags = 0;   // (both streams were drained above: nothing counts down right now)
-    for (const DClip& dc : e->flat) set_flags += dc.internal_state_changed != 0 ? 1u : 0u;
-    *e->h_flags_left.p = set_flags;
-    e->table_flags = set_flags != 0u;
-    if (!e->flat.empty()) WBX_EHIP(e, hipMemcpy(e->d_clips.p, e->flat.data(), e->flat.size() * sizeof(DClip), hipMemcpyHostToDevice));
-    WBX_EHIP(e, hipMemcpy(e->d_clip_first.p, e->first.data(), e->first.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+// per-track device state: allocated once at max_tracks capacity; tracks added since the last render find their slots cleared
+// already (wbx_engine::d_state)
+wbx_status ensure_track_state(wbx_engine* e, uint32_t N) {
+  wbx_ctx* c = e->ctx;
+  if (e->state_tracks >= N) return WBX_OK;
+  if (e->d_state.cap < N) {
+    WBX_EHIP(e, sync_plan_and_main(c));
+    WBX_EHIP(e, e->d_state.ensure(std::max<size_t>(N, c->cfg.max_tracks)));
+    WBX_EHIP(e, e->d_levels.ensure((size_t)c->cfg.max_tracks * 2));
+    WBX_EHIP(e, hipMemset(e->d_state.p, 0, e->d_state.cap * sizeof(DTrackState)));
+    WBX_EHIP(e, hipMemset(e->d_levels.p, 0, e->d_levels.cap * sizeof(float)));
   }
+  e->state_tracks = N;
+  return WBX_OK;
+}
 
-  // -- per-track device state: allocated once at max_tracks capacity; tracks added since the last render find their
-  //    slots cleared already (wbx_engine::d_state)
-  if (e->state_tracks < N) {
-    if (e->d_state.cap < N) {
-      WBX_EHIP(e, hipStreamSynchronize(c->plan_stream));
-      WBX_EHIP(e, sync_main(c));
-      WBX_EHIP(e, e->d_state.ensure(std::max<size_t>(N, c->cfg.max_tracks)));
-      WBX_EHIP(e, e->d_levels.ensure((size_t)c->cfg.max_tracks * 2));
-      WBX_EHIP(e, hipMemset(e->d_state.p, 0, e->d_state.cap * sizeof(DTrackState)));
-      WBX_EHIP(e, hipMemset(e->d_levels.p, 0, e->d_levels.cap * sizeof(float)));
-    }
-    e->state_tracks = N;
-  }
+// pending state edits (play / stop / clip-list changes) into the next pinned patch buffer; *slot: which, -1 = none pending
+wbx_status take_patches(wbx_engine* e, int* slot) {
+  *slot = -1;
+  if (!e->hs.patches_pending) return WBX_OK;
+  *slot = (int)(e->patch_seq++ % kRing);
+  WBX_EHIP(e, e->patch[*slot].wait());
+  e->hs.take_patches_locked(e->patch[*slot].buf.p);
+  return WBX_OK;
+}
 
-  // -- pending state edits (play / stop / clip-list changes)
-  const DPatch* d_patch = nullptr;
-  int patch_slot = -1;
-  if (hs.patches_pending) {
-    patch_slot = (int)(e->patch_seq++ % kRing);
-    WBX_EHIP(e, e->patch[patch_slot].wait());
-    hs.take_patches_locked(e->patch[patch_slot].buf.p);
-    d_patch = e->patch[patch_slot].buf.p;
-  }
-
-  // -- routing
+// routing, layer 1's tables and its result buffers
+wbx_status upload_routing_and_tables(wbx_engine* e, uint32_t K, uint32_t N) {
+  wbx_ctx* c = e->ctx;
+  HostSession& hs = e->hs;
   if (hs.routing_dirty || c->routing_tracks != N) {
     std::vector<int32_t> tb(N);
     for (uint32_t t = 0; t < N; t++) tb[t] = hs.tracks[t]->bus;
-    st = wbx_set_routing(c, N, hs.n_buses ? tb.data() : nullptr, hs.n_buses);
-    if (st != WBX_OK) return cfail(e, st);
+    WBX_STEP(cfail(e, wbx_set_routing(c, N, hs.n_buses ? tb.data() : nullptr, hs.n_buses)));
     hs.routing_dirty = false;
   }
-  st = upload_tables(c, N);
-  if (st != WBX_OK) return cfail(e, st);
-  st = ensure_result_buffers(c, K, N);
-  if (st != WBX_OK) return cfail(e, st);
+  WBX_STEP(cfail(e, upload_tables(c, N)));
+  return cfail(e, ensure_result_buffers(c, K, N));
+}
 
-  // -- the mix instance of this render and what follows from it (wbx_shape.h): decided here, once, behind upload_tables (which
-  //    reads the clip table's formats) and in front of everything that plans or launches for this render
-  c->session = hs.shape_facts();
-  c->shape = render_shape(c, K, N, process && !hs.any_slow_clip);
-  const RenderShape& shape = c->shape;
+// A device observation, not a decision: the sequencer counts h_flags_left down as it clears the table's flags
+void refresh_table_flags(wbx_engine* e) {
+  if (e->table_flags && e->h_flags_left.p && *reinterpret_cast<volatile uint32_t*>(e->h_flags_left.p) == 0u)
+    e->table_flags = false;   // every flag of the table has been cleared by a plan that is over
+}
 
-  // -- rows for the track-blocks the hot loop cannot stream directly, and the plan's templates
-  // the sequencer of this render: one lane per track, or — long renders of sessions cut into clips — per (track, segment)
-  const uint32_t seg_len = plan_segment_length(e, K, N, playing, process != nullptr);
-  const uint32_t n_segs = seg_len ? (K + seg_len - 1u) / seg_len : 1u;
-  // (segments: a track whose seam missed is planned again from there, and what its replaced segments queued / took from the
-  //  pool / reserved stays allocated and unused — room for both versions of every row, so that a miss on a session that leans
-  //  on the pre-render pass cannot turn into a capacity error)
-  st = ensure_gen_capacity(c, hs.gen_rows_hint(K, shape.masked_rows, ((double)F / (double)c->cfg.sample_rate) / beat_duration) * (seg_len ? 2u : 1u));
-  if (st != WBX_OK) return cfail(e, st);
-  if (seg_len) {
-    st = ensure_pool_slack(c);
-    if (st != WBX_OK) return cfail(e, st);
-  }
-  st = ensure_template_capacity(c, std::max(hs.template_hint(K, n_segs), (size_t)2 * N));   // (2 N: the one-launch callback's static pairs)
-  if (st != WBX_OK) return cfail(e, st);
+// rows for the track-blocks the hot loop cannot stream directly, pool chunks, and the plan's templates
+wbx_status ensure_plan_capacity(wbx_engine* e, uint32_t K, uint32_t N, const RenderPlan& plan, double beat_duration) {
+  wbx_ctx* c = e->ctx;
+  HostSession& hs = e->hs;
+  const double block_beats = ((double)c->cfg.block_frames / (double)c->cfg.sample_rate) / beat_duration;
+  WBX_STEP(cfail(e, ensure_gen_capacity(c, hs.gen_rows_hint(K, c->shape.masked_rows, block_beats) * (plan.double_rows ? 2u : 1u))));
+  if (plan.pool_slack) WBX_STEP(cfail(e, ensure_pool_slack(c)));
+  return cfail(e, ensure_template_capacity(c, std::max(hs.template_hint(K, plan.n_segs), (size_t)2 * N)));   // (2 N: the one-launch callback's static pairs)
+}
 
-  // -- plan (sequencer on the device) + pre-render on the plan stream, into the other plan buffer; it may run
-  //    while the mix of the previous render is still busy on the main stream
-  c->cur = (c->cur + 1) % kRing;
+// the plan stream `ps` behind the last readers of what this render's plan and mix will write
+wbx_status order_plan_stream(wbx_engine* e, const RenderPlan& plan, hipStream_t ps, RenderCall* call) {
+  wbx_ctx* c = e->ctx;
   wbx_ctx::PlanBuf& B = PB(c);
-  const bool plan_beside = c->ck.overlap && K >= kOverlapMinBlocks;
-  hipStream_t ps = plan_beside ? c->plan_stream : s;
-  RenderCall call = process ? *process : RenderCall{};
-  hipStream_t ms = call.mix_stream = pick_mix_stream(c, K, true);   // main stream, or the alternate one for every other batch render
-  const bool plan_event = ps != ms;               // the mix runs on another stream than its plan
   if (B.consumed_valid) WBX_EHIP(e, hipStreamWaitEvent(ps, B.consumed, 0));   // the mix that read this buffer two renders ago
-  {
-    const int pp = (int)(c->render_seq % kRing);
-    if (plan_beside && c->sum_valid[pp]) {   // ... and the sum that read the partial buffer this render's mix will write
-      WBX_EHIP(e, hipStreamWaitEvent(ps, c->partial_free[pp], 0));   // (the sum KERNEL: not the copy-out of its master behind it)
-      call.plan_waits_partial = true;
-    }
+  const int pp = (int)(c->render_seq % kRing);
+  if (plan.beside && c->sum_valid[pp]) {   // ... and the sum that read the partial buffer this render's mix will write
+    WBX_EHIP(e, hipStreamWaitEvent(ps, c->partial_free[pp], 0));   // (the sum KERNEL: not the copy-out of its master behind it)
+    call->plan_waits_partial = true;
   }
-  // the plan's four counters start from zero: cleared by the kernel that brings the transport table in front of the plan when
-  // there is one (below), else by a memset — a 16-byte fill is a launch of its own, ~50 us beside a running mix, at the head of
-  // the chain fill -> table -> plan -> pre-render that a short render's mix waits for
-  bool need_zero = !B.counters_zero;
-  B.counters_zero = false;
-  e->plan_status_on_host = false;
-  const double sample_rate = (double)c->cfg.sample_rate;
+  return WBX_OK;
+}
+
+// the sequencer's arguments over the current plan buffer (times: set by stage_transport_table; reads only)
+PlanArgs plan_args(const wbx_engine* e, uint32_t K, uint32_t N, const RenderPlan& plan, int patch_slot, bool playing, double beat_duration) {
+  wbx_ctx* c = e->ctx;
+  const HostSession& hs = e->hs;
+  const wbx_ctx::PlanBuf& B = PB(c);
   PlanArgs a{};
   a.clips = e->d_clips.p;
   a.clip_first = e->d_clip_first.p;
   a.samples = c->d_samples.p;
   a.state = e->d_state.p;
-  a.patch = d_patch;
+  a.patch = patch_slot >= 0 ? e->patch[patch_slot].buf.p : nullptr;
   a.gains = e->gains[e->gains_slot].buf.p;
   a.rows = B.prows.p;
   a.tmpl = B.tmpl.p;
@@ -1236,131 +1201,214 @@ wbx_status render_locked(wbx_engine* e, uint32_t K, const RenderCall* process = 
   a.pool_chunks = B.pool_chunks;
   a.n_tracks = N;
   a.n_blocks = K;
-  a.block_frames = F;
-  a.channels = C;
-  a.sample_rate = sample_rate;
+  a.block_frames = c->cfg.block_frames;
+  a.channels = c->cfg.channels;
+  a.sample_rate = (double)c->cfg.sample_rate;
   a.playing = playing ? 1u : 0u;
   a.clips_changed = hs.clips_edited ? 1u : 0u;
   a.flags_left = e->h_flags_left.p;
-  hs.clips_edited = false;
   // clip boundaries inside a block stay in the hot loop when the mix instance of this render can take them
-  a.masked_rows = shape.masked_rows;
-  a.tmpl_reserve = HostSession::template_reserve(K);
+  a.masked_rows = c->shape.masked_rows;
+  a.tmpl_reserve = plan.tmpl_reserve;
   a.lanes = hs.plan_lanes(K);
   a.playhead = hs.playhead;
   a.sample_position = hs.sample_position;
   a.beat_duration = beat_duration;
   a.times = nullptr;
-  // (cut sessions keep the LDS table.  Measured again in round 4, with the run end estimated instead of searched: plan of c3
-  //  cut into 5.3-block clips 5.4 ms from LDS, 10.9 ms from device memory, 4 / 2 / 1 tracks per wave 12-25 ms: every record
-  //  look-up at a clip boundary is a memory round trip for its lane)
-  if (seg_len) a.tmpl_reserve = 8u;   // (a lane plans seg_len blocks, not K: a smaller reservation strands less)
-  if (seg_len || (plan_beside && !(hs.cut_tracks != 0 || c->knobs.force_cut))) {
-    // Batch render of a session whose tracks are single clips (a steady run per track, a handful of look-ups): the transport
-    // records live in device memory and the sequencer takes the register-capped instance — nothing in LDS, a wave no larger
-    // than a mix wave, so it runs BESIDE the previous mix instead of in the drain at its end.  Sessions cut into clips
-    // search the records all the time: theirs stay in LDS (device-memory latency tripled their plan) with the roomy instance.
+  return a;
+}
+
+// the plan's four counters to zero, and — where the plan reads it from device memory — the transport table in front of it
+wbx_status stage_transport_table(wbx_engine* e, uint32_t K, const RenderPlan& plan, PlanArgs* a, hipStream_t ps) {
+  wbx_ctx::PlanBuf& B = PB(e->ctx);
+  B.counters_zero = false;
+  e->plan_status_on_host = false;
+  if (plan.device_times) {
     WBX_EHIP(e, B.times.ensure(K));
-    a.times = B.times.p;
+    a->times = B.times.p;
     auto& T = e->times[e->times_seq++ % wbx_engine::kTimesRing];
     WBX_EHIP(e, T.wait());   // its copy of 8 renders ago (long over)
     WBX_EHIP(e, T.buf.ensure(K));
     WBX_EHIP(e, T.done.ensure(kDevEventFlags));
-    block_times(a, T.buf.p);   // wbx_seq.h: the source the device compiles
-    launch_times_copy(T.buf.p, B.times.p, K, need_zero ? B.counters.p : nullptr, ps);
-    need_zero = false;
+    block_times(*a, T.buf.p);   // wbx_seq.h: the source the device compiles
+    launch_times_copy(T.buf.p, B.times.p, K, plan.zeroing == RenderPlan::TIMES_COPY ? B.counters.p : nullptr, ps);
     WBX_EHIP(e, T.mark(ps));
   }
-  if (need_zero) WBX_EHIP(e, hipMemsetAsync(B.counters.p, 0, 4 * sizeof(uint32_t), ps));
+  if (plan.zeroing == RenderPlan::MEMSET) WBX_EHIP(e, hipMemsetAsync(B.counters.p, 0, 4 * sizeof(uint32_t), ps));
+  return WBX_OK;
+}
+
+// the sequencer of render n+1 continues from the per-track state render n's left: `ps` behind the stream that planned last
+// (found by the random-pieces test once it left renders unfetched: a batch render's plan, on the idle plan stream, overtook
+//  the plan of a short render still queued on the main stream behind earlier mixes and read the state before that one had
+//  written it)
+wbx_status hand_plan_stream_over(wbx_engine* e, hipStream_t ps) {
   if (e->last_plan_stream && e->last_plan_stream != ps) {
-    // (found by the random-pieces test once it left renders unfetched: a batch render's plan, on the idle plan stream,
-    //  overtook the plan of a short render still queued on the main stream behind earlier mixes and read the state before
-    //  that one had written it)
     WBX_EHIP(e, e->plan_handover.ensure(kDevEventFlags));
     WBX_EHIP(e, hipEventRecord(e->plan_handover, e->last_plan_stream));
     WBX_EHIP(e, hipStreamWaitEvent(ps, e->plan_handover, 0));
   }
   e->last_plan_stream = ps;
-  // The one-block callback of a session whose clip boundaries stay in the hot loop: the pre-render queue is empty
-  // unless a block holds three or more stream calls or overlapping ones.  Leave the launch out; wbx_engine_process
-  // looks at the queue counter afterwards and repeats pre-render + mix for the (rare) block that needed it.
-  // (sessions whose boundary blocks do go through the pre-render pass take the same bet when the block can be one launch:
-  //  a steady block — nearly all — wins two launches, a boundary block pays the repeat)
-  e->gen_skipped = process && !hs.any_slow_clip && (shape.masked_rows || shape.cb_one_launch);
-  // ... and then sequencer, mix and sum are ONE launch (wbx_callback.h): every mix workgroup plans its own tracks first, the
-  // last one to finish sums the block and tells the host
-  const bool one_launch = shape.cb_one_launch;
-  B.static_tmpl = one_launch;
-  if (one_launch) a.tmpl_reserve = 0u;   // track t owns templates 2t, 2t + 1: no allocation round trip in the latency chain
-  if (one_launch) {
+  return WBX_OK;
+}
+
+// the seam states of a plan by segments: one buffer, behind its last user
+wbx_status ensure_seam_buffers(wbx_engine* e, uint32_t N, size_t per, hipStream_t ps) {
+  wbx_ctx* c = e->ctx;
+  if (e->seam_stream && e->seam_stream != ps) {   // (its last user ran on the other stream)
+    WBX_EHIP(e, e->seam_done.ensure(kDevEventFlags));
+    WBX_EHIP(e, hipEventRecord(e->seam_done, e->seam_stream));
+    WBX_EHIP(e, hipStreamWaitEvent(ps, e->seam_done, 0));
+  }
+  if (e->d_seam.cap < 2 * per) {
+    if (e->seam_stream) WBX_EHIP(e, hipStreamSynchronize(e->seam_stream));
+    WBX_EHIP(e, e->d_seam.ensure(2 * per));
+  }
+  if (!e->d_seg_stats.p) {
+    WBX_EHIP(e, e->d_seg_stats.ensure(2));
+    WBX_EHIP(e, hipMemsetAsync(e->d_seg_stats.p, 0, 2 * sizeof(uint32_t), ps));
+  }
+  if (e->d_seg_ticket.cap < N) {
+    if (e->seam_stream) WBX_EHIP(e, hipStreamSynchronize(e->seam_stream));
+    const size_t cap = std::max<size_t>(N, c->cfg.max_tracks);
+    WBX_EHIP(e, e->d_seg_ticket.ensure(cap));
+    WBX_EHIP(e, hipMemsetAsync(e->d_seg_ticket.p, 0, e->d_seg_ticket.cap * sizeof(uint32_t), ps));
+  }
+  e->seam_stream = ps;
+  return WBX_OK;
+}
+
+// the sequencer of this render: one lane per track, or — long renders of sessions cut into clips — per (track, segment); the
+// one-launch callback has none (its mix launch plans for itself) and reads the gains from the device copy
+wbx_status launch_sequencer(wbx_engine* e, uint32_t N, const RenderPlan& plan, PlanArgs* a, hipStream_t ps) {
+  wbx_ctx* c = e->ctx;
+  PB(c).static_tmpl = plan.static_tmpl;
+  if (plan.static_tmpl) {
     if (e->d_gains_cb_gen != e->gains_gen || e->d_gains_cb.cap < (size_t)N * 2) {
       WBX_EHIP(e, e->d_gains_cb.ensure(std::max<size_t>((size_t)c->cfg.max_tracks, N) * 2));
       WBX_EHIP(e, hipMemcpyAsync(e->d_gains_cb.p, e->gains[e->gains_slot].buf.p, (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, ps));
       e->d_gains_cb_gen = e->gains_gen;
     }
-    a.gains = e->d_gains_cb.p;
+    a->gains = e->d_gains_cb.p;
   }
-  if (seg_len) {
+  if (plan.sequencer == RenderPlan::SEGMENTS) {
     // one lane per (track, segment); the lane that completes a track checks its seams; the seam states live in one buffer
-    const size_t per = (size_t)N * n_segs;
-    if (e->seam_stream && e->seam_stream != ps) {   // (its last user ran on the other stream)
-      WBX_EHIP(e, e->seam_done.ensure(kDevEventFlags));
-      WBX_EHIP(e, hipEventRecord(e->seam_done, e->seam_stream));
-      WBX_EHIP(e, hipStreamWaitEvent(ps, e->seam_done, 0));
-    }
-    if (e->d_seam.cap < 2 * per) {
-      if (e->seam_stream) WBX_EHIP(e, hipStreamSynchronize(e->seam_stream));
-      WBX_EHIP(e, e->d_seam.ensure(2 * per));
-    }
-    if (!e->d_seg_stats.p) {
-      WBX_EHIP(e, e->d_seg_stats.ensure(2));
-      WBX_EHIP(e, hipMemsetAsync(e->d_seg_stats.p, 0, 2 * sizeof(uint32_t), ps));
-    }
-    if (e->d_seg_ticket.cap < N) {
-      if (e->seam_stream) WBX_EHIP(e, hipStreamSynchronize(e->seam_stream));
-      const size_t cap = std::max<size_t>(N, c->cfg.max_tracks);
-      WBX_EHIP(e, e->d_seg_ticket.ensure(cap));
-      WBX_EHIP(e, hipMemsetAsync(e->d_seg_ticket.p, 0, e->d_seg_ticket.cap * sizeof(uint32_t), ps));
-    }
-    e->seam_stream = ps;
-    SegArgs g{e->d_seam.p, e->d_seam.p + per, e->d_seg_stats.p, e->d_seg_ticket.p, seg_len, n_segs};
-    launch_plan_segments(a, g, plan_beside, ps);
+    const size_t per = (size_t)N * plan.n_segs;
+    WBX_STEP(ensure_seam_buffers(e, N, per, ps));
+    SegArgs g{e->d_seam.p, e->d_seam.p + per, e->d_seg_stats.p, e->d_seg_ticket.p, plan.seg_len, plan.n_segs};
+    launch_plan_segments(*a, g, plan.beside, ps);
     e->seg_renders++;
-    e->seg_last_segs = n_segs;
-  } else if (!one_launch) {
-    launch_plan(a, ps);
+    e->seg_last_segs = plan.n_segs;
+  } else if (plan.sequencer == RenderPlan::PLAIN) {
+    launch_plan(*a, ps);
   }
-  if (!process) {
+  return WBX_OK;
+}
+
+// behind the sequencer on `ps`: the marks of the pinned buffers it read (a process block waits for its render: none), the
+// pre-render pass, and the event a mix on another stream waits for
+wbx_status finish_plan(wbx_engine* e, const RenderPlan& plan, int patch_slot, bool callback, hipStream_t ps, bool plan_event) {
+  wbx_ctx* c = e->ctx;
+  if (!callback) {
     if (patch_slot >= 0) WBX_EHIP(e, e->patch[patch_slot].mark(ps));
     WBX_EHIP(e, e->gains[e->gains_slot].mark(ps));   // (re-recorded by every plan that reads the buffer)
   }
-  if (!e->gen_skipped) {
-    st = launch_pre_render(c, ps);
-    if (st != WBX_OK) return cfail(e, st);
-  }
-  if (plan_event) WBX_EHIP(e, hipEventRecord(B.planned, ps));   // (plan and mix on one stream: the mix simply follows)
+  if (!plan.skip_pre_render) WBX_STEP(cfail(e, launch_pre_render(c, ps)));
+  if (plan_event) WBX_EHIP(e, hipEventRecord(PB(c).planned, ps));   // (plan and mix on one stream: the mix simply follows)
+  return WBX_OK;
+}
 
-  // -- mix (main stream, or the alternate one for every other batch render) + sum, after the plan
-  if (plan_event) WBX_EHIP(e, hipStreamWaitEvent(ms, B.planned, 0));
+// mix (main stream, or the alternate one for every other batch render) + sum, after the plan
+wbx_status launch_mix(wbx_engine* e, uint32_t K, uint32_t N, RenderCall* call, const PlanArgs& a, bool plan_event, bool* launched_as_one) {
+  wbx_ctx* c = e->ctx;
+  wbx_ctx::PlanBuf& B = PB(c);
+  if (plan_event) WBX_EHIP(e, hipStreamWaitEvent(call->mix_stream, B.planned, 0));
   c->levels_target = reinterpret_cast<uint32_t*>(e->d_levels.p);
   const int mix_parity = (int)(c->render_seq % kRing);
-  if (one_launch) {   // (only a process block's shape says so: h_status is there)
-    call.plan = &a;
-    call.done_word = e->h_status.p + 8;
-    call.gave_up_word = e->h_status.p + 7;
+  if (c->shape.cb_one_launch) {   // (only a process block's shape says so: h_status is there)
+    call->plan = &a;
+    call->done_word = e->h_status.p + 8;
+    call->gave_up_word = e->h_status.p + 7;
     if (++e->cb_seq == 0u) ++e->cb_seq;   // (0 is what the completion and election words hold before any launch)
-    call.seq = e->cb_seq;
+    call->seq = e->cb_seq;
   }
-  bool launched_as_one = false;
-  st = launch_mix_sum(c, K, N, call, &launched_as_one);
-  if (st != WBX_OK) return cfail(e, st);
-  if (as_one_launch) *as_one_launch = launched_as_one;
+  WBX_STEP(cfail(e, launch_mix_sum(c, K, N, *call, launched_as_one)));
   B.consumed = c->mix_done[mix_parity];   // recorded right after the mix: the plan buffer is free before the sum runs
-  B.consumed_valid = !launched_as_one;   // (the one-launch callback records no event: wbx_engine_process waits for the launch itself)
+  B.consumed_valid = !*launched_as_one;   // (the one-launch callback records no event: wbx_engine_process waits for the launch itself)
+  return WBX_OK;
+}
+
+// What one render_locked call reports beside its status
+struct RenderResult {
+  bool one_launch = false;          // the block ran as the one-launch callback
+  bool pre_render_skipped = false;  // the render left the pre-render launch out (expecting an empty queue)
+};
+
+// the audio thread's render, editor lock held by the caller.  `process`: the one block of wbx_engine_process, which waits
+// for it before it returns (the pinned tables need no completion events) — where its master and its plan status go; null:
+// a batch render, a bounce pass.  *result (if asked for): RenderResult
+wbx_status render_locked(wbx_engine* e, uint32_t K, const RenderCall* process = nullptr, RenderResult* result = nullptr) {
+  wbx_ctx* c = e->ctx;
+  HostSession& hs = e->hs;
+  tls_err.clear();
+  if (K > c->cfg.max_blocks) return efail(e, WBX_ERR_INVALID, "n_blocks above wbx_config.max_blocks");
+  const uint32_t N = hs.n_tracks();
+  (void)hipSetDevice(c->cfg.device);
+  hs.render_edit_seq = hs.edit_seq;
+  // engine.cpp:1579,1585: the tempo and the play state are read once per block
+  const double beat_duration = hs.beat_duration.load(std::memory_order_relaxed);
+  const bool playing = hs.playing.load(std::memory_order_relaxed);
+  if (N == 0)
+    return render_empty_session(e, K, process ? process->master : c->master_target, process ? process->format : c->master_format, beat_duration);
+
+  // -- what the sequencer and the mix read: pinned tables, gains, clip lists, per-track state, patches, routing
+  int patch_slot = -1;
+  WBX_STEP(ensure_pinned_tables(e, N));
+  WBX_STEP(refresh_gains(e));
+  WBX_STEP(upload_clip_table(e, N));
+  WBX_STEP(ensure_track_state(e, N));
+  WBX_STEP(take_patches(e, &patch_slot));
+  WBX_STEP(upload_routing_and_tables(e, K, N));
+
+  // -- the mix instance of this render and what follows from it (wbx_shape.h): decided here, once, behind upload_tables (which
+  //    reads the clip table's formats) and in front of everything that plans or launches for this render
+  c->session = hs.shape_facts();
+  c->shape = render_shape(c, K, N, process && !hs.any_slow_clip);
+
+  // -- ... and how it is planned (wbx_shape.h: choose_plan), in front of everything that is sized, ordered or launched for the plan
+  refresh_table_flags(e);
+  PlanFacts pf;
+  pf.K = K, pf.N = N;
+  pf.playing = playing, pf.callback = process != nullptr, pf.any_slow_clip = hs.any_slow_clip, pf.cut = hs.cut_tracks != 0;
+  pf.table_flags = e->table_flags, pf.seg_broken = c->seg_broken;
+  pf.masked_rows = c->shape.masked_rows, pf.cb_one_launch = c->shape.cb_one_launch;
+  pf.counters_zero = c->pb[(c->cur + 1) % kRing].counters_zero;   // (the buffer this render plans into)
+  const RenderPlan plan = choose_plan(e->knobs, c->ck, c->knobs, pf);
+  WBX_STEP(ensure_plan_capacity(e, K, N, plan, beat_duration));
+
+  // -- plan (sequencer on the device) + pre-render on the plan stream, into the other plan buffer; it may run
+  //    while the mix of the previous render is still busy on the main stream
+  c->cur = (c->cur + 1) % kRing;
+  hipStream_t ps = plan.beside ? c->plan_stream : c->stream;
+  RenderCall call = process ? *process : RenderCall{};
+  call.mix_stream = pick_mix_stream(c, K, true);   // main stream, or the alternate one for every other batch render
+  const bool plan_event = ps != call.mix_stream;   // the mix runs on another stream than its plan
+  WBX_STEP(order_plan_stream(e, plan, ps, &call));
+  PlanArgs a = plan_args(e, K, N, plan, patch_slot, playing, beat_duration);
+  hs.clips_edited = false;   // (PlanArgs::clips_changed has taken it)
+  WBX_STEP(stage_transport_table(e, K, plan, &a, ps));
+  WBX_STEP(hand_plan_stream_over(e, ps));
+  WBX_STEP(launch_sequencer(e, N, plan, &a, ps));
+  WBX_STEP(finish_plan(e, plan, patch_slot, process != nullptr, ps, plan_event));
+
+  RenderResult r;
+  r.pre_render_skipped = plan.skip_pre_render;
+  WBX_STEP(launch_mix(e, K, N, &call, a, plan_event, &r.one_launch));
+  if (result) *result = r;
 
   // -- transport: the host repeats the arithmetic of Engine::process (engine.cpp:1578-1585, :1619-1623) that
   //    the plan kernel performs for its K blocks, so both sides hold the same playhead / sample_position bits
-  hs.advance_transport_locked(K, F, beat_duration);
+  hs.advance_transport_locked(K, c->cfg.block_frames, beat_duration);
   return WBX_OK;
 }
 
@@ -1876,9 +1924,7 @@ extern "C" wbx_status wbx_engine_process_in(wbx_engine* e, const float* const* i
 // launch.  dst: F * C samples of the format (packed 24-bit: the reference's bytes, see WBX_OUT_I24).
 extern "C" wbx_status wbx_engine_process_interleaved(wbx_engine* e, int out_format, void* dst) {
   if (!e || !dst) return WBX_ERR_INVALID;
-  if (out_format != WBX_OUT_I16 && out_format != WBX_OUT_I24 && out_format != WBX_OUT_I24_X8 && out_format != WBX_OUT_I32 &&
-      out_format != WBX_OUT_F32)
-    return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
+  if (!out_format_bytes(out_format)) return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
   return process_block(e, nullptr, out_format, dst, nullptr, 0);
 }
 
@@ -1886,9 +1932,7 @@ extern "C" wbx_status wbx_engine_process_interleaved(wbx_engine* e, int out_form
 extern "C" wbx_status wbx_engine_process_interleaved_in(wbx_engine* e, const float* const* in_planar, uint32_t n_in_channels,
                                                         int out_format, void* dst) {
   if (!e || !in_planar || !dst) return WBX_ERR_INVALID;
-  if (out_format != WBX_OUT_I16 && out_format != WBX_OUT_I24 && out_format != WBX_OUT_I24_X8 && out_format != WBX_OUT_I32 &&
-      out_format != WBX_OUT_F32)
-    return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
+  if (!out_format_bytes(out_format)) return efail(e, WBX_ERR_UNSUPPORTED, "interleaved output format");
   return process_block(e, nullptr, out_format, dst, in_planar, n_in_channels);
 }
 
@@ -1929,12 +1973,12 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
   block.status = e->h_status.p;           // and it drops the plan status next to it ...
   RenderCall first = block;
   first.clear_counters = true;            // ... the first pass clearing the counters for the buffer's next plan
-  bool launched_as_one = false;
-  wbx_status st = render_locked(e, 1, &first, &launched_as_one);
+  RenderResult rendered;
+  wbx_status st = render_locked(e, 1, &first, &rendered);
   // the recorder tap, once per played block whichever path the block takes below (one launch, mixed again after a
   // give-up, three launches): launched on the upload stream beside the block's kernels, not waited for
   if (st == WBX_OK) rec_capture_locked(e, in, n_in);
-  const bool one_launch = st == WBX_OK && launched_as_one;
+  const bool one_launch = st == WBX_OK && rendered.one_launch;
   if (st == WBX_OK && e->hs.n_tracks() != 0) {
     if (one_launch) {
       // the kernel's own word: master and status are in host memory when it reads this launch's number.  Polled — no
@@ -1981,7 +2025,7 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
       PB(c).counters_zero = false;
       if (st != WBX_OK) tls_err = c->err;
     }
-    if (st == WBX_OK && e->gen_skipped && e->h_status.p[2] != 0u) {
+    if (st == WBX_OK && rendered.pre_render_skipped && e->h_status.p[2] != 0u) {
       // the block did queue records for the pre-render pass: run it now and mix again (the plan is untouched; the
       // first pass counted those records as silence, so the running levels hold nothing wrong; the status is dropped
       // again, the counters stay: `block` as it is)
@@ -2001,7 +2045,7 @@ wbx_status process_block_locked(wbx_engine* e, float* const* out_planar, int out
   } else if (out_format == WBX_OUT_I24) {   // (the reference's writer leaves the other 3*F*(C-1) bytes of the block untouched)
     std::memcpy(out_il, e->h_block.p, (size_t)F * 3);
   } else {
-    std::memcpy(out_il, e->h_block.p, (size_t)F * C * (out_format == WBX_OUT_I16 ? 2 : 4));
+    std::memcpy(out_il, e->h_block.p, (size_t)F * C * out_format_bytes(out_format));
   }
   c->last_master_on_host = true;   // set after launch_mix_sum cleared it: the master of this block is e->h_block
   if (e->hs.n_tracks() == 0) return WBX_OK;

@@ -759,12 +759,13 @@ struct HostSession {
     (void)K;
     return plan_lanes_knob ? plan_lanes_knob : 64u;
   }
-  static uint32_t template_reserve(uint32_t K) { return K >= 64u ? 32u : K >= 8u ? 8u : 1u; }
+  // (the session's name for wbx_shape.h's function, which holds the figures: code written against the session keeps compiling)
+  static constexpr auto& template_reserve = wbx::template_reserve;
   // (lanes: lanes per track of the sequencer — more than one when it is cut along the time axis; every lane may strand a
-  //  reservation and splits a steady run at its seam)
+  //  reservation (wbx_shape.h: template_reserve, kSegmentTemplateReserve) and splits a steady run at its seam)
   size_t template_hint(uint32_t K, uint32_t lanes = 1u) const {
     const size_t all = (size_t)K * n_tracks();
-    const size_t stranded = (size_t)((lanes > 1u ? 8u : template_reserve(K)) + (lanes > 1u ? 3u : 1u)) * n_tracks() * lanes;
+    const size_t stranded = (size_t)((lanes > 1u ? kSegmentTemplateReserve : wbx::template_reserve(K)) + (lanes > 1u ? 3u : 1u)) * n_tracks() * lanes;
     if (any_crawl_clip) return 2 * all + stranded;
     return std::min(2 * all, 2 * boundary_blocks_hint(K) + 3 * (size_t)n_tracks() + 64) + stranded;
   }

@@ -1100,7 +1100,7 @@ extern "C" wbx_status wbx_set_clamp(wbx_ctx* c, int on) {
   return WBX_OK;
 }
 
-static size_t out_format_bytes(int fmt) {
+size_t wbx::out_format_bytes(int fmt) {
   switch (fmt) {
     case WBX_OUT_I16: return 2;
     case WBX_OUT_I24: return 3;
@@ -1555,15 +1555,8 @@ extern "C" wbx_status wbx_fetch_interleaved(wbx_ctx* c, int out_format, void* ds
   if (!c || !dst) return WBX_ERR_INVALID;
   if (c->last_K == 0) return fail(c, WBX_ERR_FAILED, "nothing submitted");
   WBX_HIP(c, join_sum(c));
-  size_t eb;
-  switch (out_format) {
-    case WBX_OUT_I16: eb = 2; break;
-    case WBX_OUT_I24: eb = 3; break;
-    case WBX_OUT_I24_X8:
-    case WBX_OUT_I32:
-    case WBX_OUT_F32: eb = 4; break;
-    default: return fail(c, WBX_ERR_UNSUPPORTED, "interleaved output format");
-  }
+  const size_t eb = out_format_bytes(out_format);
+  if (!eb) return fail(c, WBX_ERR_UNSUPPORTED, "interleaved output format");
   const uint32_t K = c->last_K, C = c->cfg.channels, F = c->cfg.block_frames;
   if (c->last_master_format) {   // the sum kernel already wrote this format (wbx_set_master_format): a copy
     if (c->last_master_format != out_format) return fail(c, WBX_ERR_INVALID, "the last render's master is in another device format");

@@ -6,7 +6,9 @@
 // by its template arguments and launch it; they decide nothing.
 //
 // Beside it, in the same way: choose_issue — how a render's launches are issued (streams, fusing, the one-launch callback,
-// the staged master) — from (knobs, facts) to a RenderIssue, called once per launch_mix_sum.
+// the staged master) — from (knobs, facts) to a RenderIssue, called once per launch_mix_sum; and choose_plan — how a render is
+// planned (the sequencer's launch and stream, its transport table, counters and reservations) — to a RenderPlan, called once
+// per render_locked.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -405,6 +407,104 @@ inline RenderIssue choose_issue(const CtxKnobs& k, const IssueFacts& f) {
   // every workgroup adds a share of the master when the whole grid is resident at once (at most one workgroup per CU: two
   // fit)
   r.spread = r.one_launch && !r.fused && !f.cb_no_spread && f.n_groups <= callback_spread_limit(f.n_cus, k.cu_mask);
+  return r;
+}
+
+// ---- how a render is planned ------------------------------------------------------------------------------------------
+// Which sequencer launch a render takes, where it runs, where its transport table lives, who zeroes its counters, how much it
+// reserves and whether the pre-render launch is left out: one pure function from (knobs, facts) to a RenderPlan, called once by
+// render_locked (wbx_engine.hip) behind render_shape and in front of everything that is sized, ordered or launched for the
+// plan.  tests/test_host_logic.py holds it against the rules written out again.
+
+// Templates a sequencer lane reserves at a time (PlanArgs::tmpl_reserve; every track may strand part of a reservation) when it
+// walks all K blocks of its track, and when the sequencer is cut along the time axis (a lane plans seg_len blocks, not K: a
+// smaller reservation strands less)
+inline uint32_t template_reserve(uint32_t K) { return K >= 64u ? 32u : K >= 8u ? 8u : 1u; }
+constexpr uint32_t kSegmentTemplateReserve = 8u;
+
+struct PlanFacts {
+  uint32_t K = 1, N = 0;        // blocks and tracks of the render
+  bool playing = false;         // the transport runs
+  bool callback = false;        // a process block (the one block of wbx_engine_process)
+  bool any_slow_clip = false;   // HostSession::any_slow_clip
+  bool cut = false;             // some track holds more than one clip (HostSession::cut_tracks)
+  bool table_flags = false;     // the uploaded clip table still holds a set internal_state_changed flag
+  bool seg_broken = false;      // a segmented plan failed before (wbx_ctx::seg_broken)
+  uint32_t masked_rows = 0;     // the render's RenderShape: masked_rows ...
+  bool cb_one_launch = false;   // ... and cb_one_launch
+  bool counters_zero = false;   // the plan buffer's four counters are zero already
+};
+
+struct RenderPlan {
+  enum Sequencer : uint8_t { PLAIN, SEGMENTS, NONE };   // plan_kernel; plan_seg_kernel; none: the one launch plans for itself
+  enum Zeroing : uint8_t { NOBODY, TIMES_COPY, MEMSET };
+  uint32_t seg_len = 0;         // blocks per segment when the sequencer is cut along the time axis, 0: one lane per track
+  uint32_t n_segs = 1;          // segments per track
+  bool beside = false;          // the plan runs on the plan stream, beside the previous mix
+  bool device_times = false;    // the transport table goes to device memory (PlanArgs::times), copied in front of the plan
+  Zeroing zeroing = NOBODY;     // who clears the plan's four counters
+  bool skip_pre_render = false; // the pre-render launch is left out (expecting an empty queue)
+  Sequencer sequencer = PLAIN;
+  uint32_t tmpl_reserve = 1;    // PlanArgs::tmpl_reserve
+  bool static_tmpl = false;     // track t owns templates 2t, 2t + 1 (PlanBuf::static_tmpl)
+  bool double_rows = false;     // room for both versions of every pre-render row
+  bool pool_slack = false;      // ... and of every pool chunk (ensure_pool_slack)
+};
+
+// seg_len — blocks per segment when the sequencer of this render is cut along the time axis (wbx_seq.h: plan_segment), 0 = one
+// lane per track walks all K blocks.  Taken by batch renders of sessions with tracks cut into clips — a chain of dependent
+// look-ups per clip boundary and lane: c3 cut into 5.3-block clips planned 2048 blocks in 5.4 ms (4.4 ms for 128-frame blocks,
+// in front of a 2.6 ms mix) — while the transport runs and no clip carries a set internal_state_changed flag (the sequencer
+// clears those in passing, track.cpp:373,392,418: the run-up of one lane and the real walk of another would race for them).
+// About 16 k lanes: segments of K * N / 24576 blocks rounded up to a power of two, at least 32 (measured, profiles/
+// r04_ab_seglen.txt: 256 tracks best at 32-64 blocks — 16 and 128 are 9-15 % slower —, 4096 tracks x 2048 short blocks at 512).
+// WBX_PLAN_SEG=0: off; =<n>: segments of n blocks (A/B aid, tests).
+inline RenderPlan choose_plan(const EngineKnobs& ek, const CtxKnobs& ck, const ShapeKnobs& sk, const PlanFacts& f) {
+  RenderPlan r;
+  const uint32_t K = f.K;
+  if (ek.plan_seg != 0 && f.playing && !f.table_flags && !f.callback && f.N != 0u && !f.seg_broken) {
+    if (ek.plan_seg > 0) {
+      r.seg_len = (uint32_t)ek.plan_seg;
+    } else if (f.cut && K >= 128u) {
+      // (also where the one-lane walk would hide behind the previous mix — c3 / 16-bit sessions cut into 5.3- or 20-block clips
+      //  at 512 frames: the segment lanes are done early, the next mix starts 0.06 instead of 0.15 ms behind its predecessor,
+      //  steps 0-3 % shorter, never longer: profiles/r04_ab_planseg.txt)
+      r.seg_len = 32u;
+      while ((uint64_t)(K / r.seg_len) * f.N > 24576u && r.seg_len < K) r.seg_len *= 2u;
+    }
+    if (r.seg_len >= K) r.seg_len = 0u;
+  }
+  const bool segmented = r.seg_len != 0u;
+  r.n_segs = segmented ? (K + r.seg_len - 1u) / r.seg_len : 1u;
+  r.beside = ck.overlap && K >= kOverlapMinBlocks;
+  // Batch render of a session whose tracks are single clips (a steady run per track, a handful of look-ups): the transport
+  // records live in device memory and the sequencer takes the register-capped instance — nothing in LDS, a wave no larger
+  // than a mix wave, so it runs BESIDE the previous mix instead of in the drain at its end.  Sessions cut into clips
+  // search the records all the time: theirs stay in LDS (device-memory latency tripled their plan) with the roomy instance.
+  // (cut sessions keep the LDS table.  Measured again in round 4, with the run end estimated instead of searched: plan of c3
+  //  cut into 5.3-block clips 5.4 ms from LDS, 10.9 ms from device memory, 4 / 2 / 1 tracks per wave 12-25 ms: every record
+  //  look-up at a clip boundary is a memory round trip for its lane)
+  r.device_times = segmented || (r.beside && !(f.cut || sk.force_cut));
+  // the plan's four counters start from zero: cleared by the kernel that brings the transport table in front of the plan when
+  // there is one, else by a memset — a 16-byte fill is a launch of its own, ~50 us beside a running mix, at the head of the
+  // chain fill -> table -> plan -> pre-render that a short render's mix waits for
+  r.zeroing = f.counters_zero ? RenderPlan::NOBODY : r.device_times ? RenderPlan::TIMES_COPY : RenderPlan::MEMSET;
+  // The one-block callback of a session whose clip boundaries stay in the hot loop: the pre-render queue is empty
+  // unless a block holds three or more stream calls or overlapping ones.  Leave the launch out; wbx_engine_process
+  // looks at the queue counter afterwards and repeats pre-render + mix for the (rare) block that needed it.
+  // (sessions whose boundary blocks do go through the pre-render pass take the same bet when the block can be one launch:
+  //  a steady block — nearly all — wins two launches, a boundary block pays the repeat)
+  r.skip_pre_render = f.callback && !f.any_slow_clip && (f.masked_rows != 0u || f.cb_one_launch);
+  // ... and then sequencer, mix and sum are ONE launch (wbx_callback.h): every mix workgroup plans its own tracks first, the
+  // last one to finish sums the block and tells the host
+  r.sequencer = segmented ? RenderPlan::SEGMENTS : f.cb_one_launch ? RenderPlan::NONE : RenderPlan::PLAIN;
+  // (one launch: track t owns templates 2t, 2t + 1 — no allocation round trip in the latency chain)
+  r.static_tmpl = f.cb_one_launch;
+  r.tmpl_reserve = f.cb_one_launch ? 0u : segmented ? kSegmentTemplateReserve : template_reserve(K);
+  // (segments: a track whose seam missed is planned again from there, and what its replaced segments queued / took from the
+  //  pool / reserved stays allocated and unused — room for both versions of every row, so that a miss on a session that leans
+  //  on the pre-render pass cannot turn into a capacity error)
+  r.double_rows = r.pool_slack = segmented;
   return r;
 }
 
