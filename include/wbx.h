@@ -428,6 +428,81 @@ wbx_status wbx_loudness_gate(uint32_t channels, uint64_t hops, uint32_t hop_fram
 wbx_status wbx_clip_loudness(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t flags,
                              wbx_loudness* out, double* hop_energy, size_t cap_doubles);
 
+/* Filtering a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels run through a
+ * cascade of 1 .. 8 biquads into a NEW F32 clip of n_frames + tail_frames frames (the tail is the ring-out over zero
+ * input), without the samples leaving HBM: rumble or DC removed from a take, a bounce low-passed or notched, a corrective
+ * EQ baked into a frozen stem.  No reference counterpart (its filters live in plug-ins).  This text is the specification;
+ * tests/filter_model.py restates it in numpy, and the coefficients, the carry matrix and every output frame equal that
+ * BIT FOR BIT.
+ *   design    wbx_filter_design: out = b0 b1 b2 a1 a2 (a0 divided out) of one Audio-EQ-Cookbook biquad in fp64, every
+ *             operator below one IEEE operation in the order written.  gain is a LINEAR amplitude ratio (no pow) and is
+ *             ignored (but checked) by the kinds without one.  sinpi is "Converting a clip's sample rate"'s:
+ *               t = (2*f)/rate, h = f/rate;  sn = sinpi(t), cs = sinpi(t + 0.5);  hm = sinpi(h)*sinpi(h),
+ *               hp = sinpi(h + 0.5)*sinpi(h + 0.5);  omc = 2*hm (1 - cos, without the cancellation), opc = 2*hp (1 + cos);
+ *               alpha = sn/(2*q);  m2cs = 0 - 2*cs
+ *               LOWPASS    a0 = 1 + alpha;  b = [hm, omc, hm];                  a1 = m2cs, a2 = 1 - alpha
+ *               HIGHPASS   a0 = 1 + alpha;  b = [hp, 0 - opc, hp];              a1 = m2cs, a2 = 1 - alpha
+ *               BANDPASS   a0 = 1 + alpha;  b = [alpha, 0, 0 - alpha];          a1 = m2cs, a2 = 1 - alpha   (0 dB peak)
+ *               NOTCH      a0 = 1 + alpha;  b = [1, m2cs, 1];                   a1 = m2cs, a2 = 1 - alpha
+ *               ALLPASS    a0 = 1 + alpha;  b = [1 - alpha, m2cs, 1 + alpha];   a1 = m2cs, a2 = 1 - alpha
+ *               PEAK       A = sqrt(gain), aA = alpha*A, aoA = alpha/A;  a0 = 1 + aoA;  b = [1 + aA, m2cs, 1 - aA];
+ *                          a1 = m2cs, a2 = 1 - aoA
+ *               shelves    A = sqrt(gain), beta = (2*sqrt(A))*alpha, P = A*omc + opc, Q = A*opc + omc
+ *               LOWSHELF   a0 = Q + beta;  b = [A*(P + beta), (2*A)*(A*omc - opc), A*(P - beta)];
+ *                          a1 = 0 - 2*(A*opc - omc), a2 = Q - beta
+ *               HIGHSHELF  a0 = P + beta;  b = [A*(Q + beta), 0 - (2*A)*(A*opc - omc), A*(Q - beta)];
+ *                          a1 = 2*(A*omc - opc), a2 = P - beta
+ *             and out = [b0/a0, b1/a0, b2/a0, a1/a0, a2/a0].  WBX_ERR_INVALID: NULL out, an unknown kind, rate == 0,
+ *             freq_hz not inside (0, rate/2), q or gain not finite and > 0
+ *   check     wbx_filter_check: WBX_OK when every value is finite, 1 <= n_stages <= 8 and every stage lies strictly inside
+ *             the stability triangle (|a2| < 1 and |a1| < 1 + a2), else WBX_ERR_INVALID.  Any such cascade may be used, not
+ *             only designed ones; coef is [n_stages][5]
+ *   input     per channel x[i], i in [0, n_frames + tail_frames): (double) of the fp32 sample for i < n_frames, a sample that
+ *             is not finite (NaN, +-inf) entering as 0.0; ZERO from n_frames on.  Whatever the clip holds beside the range
+ *             does not count and is never read
+ *   a stage   direct form I, y = ((((b0*x + b1*x1) + b2*x2) - a1*y1) - a2*y2), every * + - a single IEEE fp64 operation,
+ *             nothing fused; then x2 = x1, x1 = x, y2 = y1, y1 = y
+ *   cascade   stage s's input is stage s-1's output, so stage s's x1, x2 ARE stage s-1's y1, y2 and a channel's state is
+ *             v = [x1, x2, y1_1, y2_1, ..., y1_S, y2_S], D = 2S + 2 doubles.  The output frame is (float) of the last
+ *             stage's y, rounded once; a NaN is stored as 0x7FC00000 (wbx_clip_derive's rule)
+ *   chunks    the frames are cut into chunks of C = 512 (wbx_filter_chunk_frames).  For every chunk j but the last, z_j is the
+ *             state after running chunk j's frames from REST (v = 0).  The carry matrix M (wbx_filter_transition, D x D,
+ *             row-major M[i][k]) has as column k the state after C frames of zero input from the unit state e_k, run by the
+ *             same step in fp64 on the host.  t_0 = 0 and t_{j+1}[i] = z_j[i] + acc_i, where acc_i starts at 0.0 and does
+ *             acc_i = acc_i + M[i][k]*t_j[k] for k = 0 .. D-1 ascending, single operations.  The STORED output of chunk j is
+ *             the run of its frames from state t_j
+ * Hence chunk 0 — and any result of at most 512 frames — IS the one sequential pass; later chunks equal it up to the
+ * rounding of the carry: direct form I with poles near z = 1 is ill-conditioned, M*t cancels against z, and M's own rounding
+ * acts as a small systematic coefficient error.  Measured against a wider sequential pass the deviation
+ * stays below one fp32 ulp of the output's peak up to 384 kHz — it is no 1e-15.  The chunked definition is the
+ * specification, not an approximation of one: chunks are independent but for D doubles, which is what lets a lane own one.
+ * wbx_filter_design / _check / _transition / _chunk_frames are host-only and need no device (wbx_filter_transition:
+ * WBX_ERR_INVALID for NULL M, cap_doubles below D*D, or a cascade wbx_filter_check refuses; M untouched then).
+ * wbx_clip_filter: dst_clip becomes a new F32 pool clip of n_frames + tail_frames frames (plus the pool's 16 zero frames
+ * of padding) at the source's rate and channel count, replaced or allocated as wbx_clip_derive does it, on the same stream
+ * and behind the same ordering; one edit, conversion or filter runs at a time.  stats_of_result (may be NULL):
+ * wbx_clip_measure of the whole result, a second pass over the output only.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: unknown source clip,
+ * n_frames == 0, a range past the clip, dst_clip == src_clip, NULL coef, a cascade wbx_filter_check refuses,
+ * n_frames + tail_frames >= 2^31 - 16; WBX_ERR_UNSUPPORTED: a source whose storage format is not F32 or with more than 2
+ * channels.  WBX_ERR_OOM as for wbx_clip_derive.
+ * wbx_filter_phase_ms: device milliseconds of the three launches of the context's last completed filter (layer 1's or layer
+ * 2's), between events on the edits' stream — out[0] the zero-state runs, out[1] the carry, out[2] the runs from the carried
+ * states; the first two are 0 for a result of one chunk.  WBX_ERR_INVALID for NULL arguments or when no filter has
+ * completed.  For tools/bench_filter.py; nothing else reads it.
+ * Not offered: zero-phase filtering (filter, derive reversed, filter, derive reversed does it), filters at render time,
+ * FIR / convolution, more than 8 stages or 2 channels, in-place edits. */
+enum { WBX_FILT_LOWPASS = 0, WBX_FILT_HIGHPASS = 1, WBX_FILT_BANDPASS = 2, WBX_FILT_NOTCH = 3, WBX_FILT_ALLPASS = 4,
+       WBX_FILT_PEAK = 5, WBX_FILT_LOWSHELF = 6, WBX_FILT_HIGHSHELF = 7 };
+wbx_status wbx_filter_design(uint32_t rate, int kind, double freq_hz, double q, double gain, double out[5]);
+wbx_status wbx_filter_check(const double* coef, uint32_t n_stages);
+wbx_status wbx_filter_transition(const double* coef, uint32_t n_stages, double* M, size_t cap_doubles);
+uint32_t wbx_filter_chunk_frames(void);
+wbx_status wbx_filter_phase_ms(wbx_ctx* ctx, double out[3]);
+wbx_status wbx_clip_filter(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                           uint64_t tail_frames, const double* coef /* [n_stages][5] */, uint32_t n_stages,
+                           wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -851,6 +926,13 @@ wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t f
 wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                 double target_lufs, float true_peak_ceiling, uint32_t* new_sample,
                                                 float* gain_used);
+/* wbx_clip_filter of an engine sample, under wbx_engine_derive_sample's rules to the letter: editing thread, the audio
+ * thread may keep calling wbx_engine_process*; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin, never across a device wait; wbx_engine_delete_sample refuses the source meanwhile ("sample is being edited");
+ * no transport state is touched and no edit is counted.  *new_sample is a fresh sample id registered at the source's rate
+ * with n_frames + tail_frames frames.  Arguments and refusals are wbx_clip_filter's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_filter_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                    uint64_t tail_frames, const double* coef, uint32_t n_stages, uint32_t* new_sample);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -336,6 +336,15 @@ struct Engine {
     check(wbx_engine_resample_sample(h, sample, first_frame, n_frames, dst_rate, quality, &id), "resample_sample");
     return id;
   }
+  // A NEW sample holding the range run through a cascade of 1 .. 8 biquads (wbx.h "Filtering a clip"; coef is
+  // [n_stages][b0 b1 b2 a1 a2], designed by wbx_filter_design or the caller's own), tail_frames of ring-out appended: a
+  // high-pass against rumble, a notch, a corrective EQ baked into a stem.  Editing thread, like derive_sample.
+  uint32_t filter_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t tail_frames, const double* coef,
+                         uint32_t n_stages) {
+    uint32_t id = 0;
+    check(wbx_engine_filter_sample(h, sample, first_frame, n_frames, tail_frames, coef, n_stages, &id), "filter_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

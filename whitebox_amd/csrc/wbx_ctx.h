@@ -18,6 +18,7 @@
 #include "../../include/wbx.h"
 #include "wbx_dev.h"
 #include "wbx_shape.h"
+#include "wbx_filter.h"
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
 #include "wbx_splice.h"
@@ -142,6 +143,20 @@ struct TruePeakArgs {
   uint32_t channels;
 };
 void launch_true_peak(const TruePeakArgs& a, hipStream_t s);
+// filtering a clip (wbx_filter.hip): zero-state runs per chunk, the serial carry over them, the runs from the carried states
+struct FilterArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  double* state;               // device: [n_chunks - 1][channels][D] — z_j, which the carry overwrites with t_{j+1}
+  const double* M;             // device: the carry matrix, [D][D] (wbx_filter.h)
+  double coef[5 * kFilterMaxStages];   // [stages][b0 b1 b2 a1 a2]
+  uint32_t n_in, n_out;        // frames of the range / of the result (n_in + tail), n_out < 2^31 - 16
+  uint32_t n_chunks;           // ceil(n_out / 512)
+  uint32_t channels, stages;   // 1 or 2 / 1 .. 8
+};
+void launch_filter_state(const FilterArgs& a, hipStream_t s);   // (n_chunks > 1)
+void launch_filter_carry(const FilterArgs& a, hipStream_t s);   // (n_chunks > 1)
+void launch_filter_apply(const FilterArgs& a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -252,6 +267,15 @@ struct LoudnessStage {
   PinnedBuf<double> h_energy;
   DevBuf<uint32_t> d_peak;     // 2 words
   PinnedBuf<uint32_t> h_peak;
+};
+
+// wbx_clip_filter's chunk states and carry matrix on the device, the matrix's upload source in pinned memory — grown on
+// demand, freed with the context
+struct FilterStage {
+  DevBuf<double> d_state, d_M;
+  PinnedBuf<double> h_M;
+  Event mark[4];               // (timing events) around the three launches of the last run: wbx_filter_phase_ms
+  bool timed = false, carried = false;   // the last run completed / had more than one chunk
 };
 
 // wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
@@ -405,6 +429,7 @@ struct wbx_ctx {
   std::vector<ResampleTable> rs_tables;   // wbx_clip_resample (under fx_mu, on fx.side.stream)
   SpliceStage splice;                     // wbx_clip_splice (under fx_mu, on fx.side.stream)
   LoudnessStage loud;                     // wbx_clip_loudness (under fx_mu, on fx.side.stream)
+  FilterStage filt;                       // wbx_clip_filter (under fx_mu, on fx.side.stream)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -562,6 +587,12 @@ wbx_status loudness_check(const ClipSrc& src, uint32_t rate, uint64_t first_fram
                           const wbx_loudness* out, const double* hop_energy, size_t cap_doubles, LoudnessPlan* plan, const char** why);
 wbx_status loudness_run(wbx_ctx* c, const ClipSrc& src, const LoudnessPlan& p, uint64_t first_frame, uint64_t n_frames,
                         wbx_loudness* out, double* hop_energy, std::string* why);
+// filtering a clip (wbx_filter.hip), cut the same way: the checks make no device call; the run works under fx_mu on the edit
+// stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run
+wbx_status filter_check_call(const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, uint64_t tail_frames, const double* coef,
+                             uint32_t n_stages, const char** why);
+wbx_status filter_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, uint64_t first_frame, uint64_t n_frames, uint64_t tail_frames,
+                      const double* coef, uint32_t n_stages, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

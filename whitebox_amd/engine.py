@@ -154,6 +154,32 @@ def resample_table(src_rate: int, dst_rate: int, quality="good") -> np.ndarray:
     return out
 
 
+def filter_design(rate: int, kind, freq: float, q: float = 0.7071067811865476, gain_db: float = 0.0) -> np.ndarray:
+    """wbx_filter_design (host-only): b0 b1 b2 a1 a2 (a0 = 1) of one Audio-EQ-Cookbook biquad at `rate` — kind "lowpass" /
+    "highpass" / "bandpass" / "notch" / "allpass" / "peak" / "lowshelf" / "highshelf" (or WBX_FILT_*); `gain_db` becomes the
+    library's LINEAR amplitude ratio here, 10 ** (gain_db / 20).  WbxError (-4) where the library refuses the design"""
+    out = np.zeros(5, dtype=np.float64)
+    _check(_ffi.lib().wbx_filter_design(rate, _ffi.FILTER_KIND.get(kind, kind), float(freq), float(q),
+                                        10.0 ** (float(gain_db) / 20.0), out.ctypes.data), "wbx_filter_design")
+    return out
+
+
+def _cascade(coef) -> np.ndarray:
+    """[stages][5] fp64, contiguous (one stage may be given flat)"""
+    k = np.ascontiguousarray(coef, dtype=np.float64)
+    return k.reshape(-1, 5)
+
+
+def filter_transition(coef) -> np.ndarray:
+    """wbx_filter_transition (host-only): the carry matrix [D][D], D = 2 * stages + 2, of a cascade [stages][5] over one chunk
+    of wbx_filter_chunk_frames() = 512 frames; WbxError (-4) for a cascade wbx_filter_check refuses"""
+    k = _cascade(coef)
+    D = 2 * len(k) + 2
+    M = np.zeros((D, D), dtype=np.float64)
+    _check(_ffi.lib().wbx_filter_transition(k.ctypes.data, len(k), M.ctypes.data, M.size), "wbx_filter_transition")
+    return M
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -293,6 +319,23 @@ class MixContext:
                                         _ffi.SRC_QUALITY.get(quality, quality), C.byref(st) if stats_channels else None),
                "wbx_clip_resample", self.h)
         return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def clip_filter(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, coef, tail_frames: int = 0,
+                    stats_channels: int = 0):
+        """wbx_clip_filter: `dst_clip` becomes a new F32 clip holding frames [first_frame, first_frame + n_frames) of
+        `src_clip` run through the cascade `coef` ([stages][b0 b1 b2 a1 a2], filter_design(...) rows) and `tail_frames` of
+        ring-out; returns the result's statistics when `stats_channels` (its channel count) is given, else None"""
+        st = _ffi.ClipStats()
+        k = _cascade(coef)
+        _check(self.L.wbx_clip_filter(self.h, src_clip, dst_clip, first_frame, n_frames, tail_frames, k.ctypes.data, len(k),
+                                      C.byref(st) if stats_channels else None), "wbx_clip_filter", self.h)
+        return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def filter_phase_ms(self) -> tuple:
+        """wbx_filter_phase_ms: device milliseconds (zero-state runs, carry, runs from the carried states) of the last filter"""
+        out = np.zeros(3, dtype=np.float64)
+        _check(self.L.wbx_filter_phase_ms(self.h, out.ctypes.data), "wbx_filter_phase_ms", self.h)
+        return tuple(float(v) for v in out)
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
                       energies: bool = False):
@@ -888,6 +931,24 @@ class Engine:
         src_rate = self._sample_rate.get(sample) if src_rate is None else src_rate
         self._sample_shape[new.value] = (resample_frames(src_rate, dst_rate, n_frames) if src_rate else None, channels)
         self._sample_rate[new.value] = dst_rate
+        return new.value
+
+    def filter_sample(self, sample: int, coef, tail_frames: int = 0, first_frame: int = 0, n_frames: Optional[int] = None,
+                      channels: Optional[int] = None, frames: Optional[int] = None) -> int:
+        """wbx_engine_filter_sample: a new sample = the range run through the cascade `coef` plus `tail_frames` of ring-out,
+        registered at the source's rate — see MixContext.clip_filter; `frames` / `channels` as in export_sample.  May be
+        called while another thread runs process(); delete_sample of the source is refused meanwhile."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "filter_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        new = C.c_uint32()
+        k = _cascade(coef)
+        _check(self.L.wbx_engine_filter_sample(self.h, sample, first_frame, n_frames, tail_frames, k.ctypes.data, len(k),
+                                               C.byref(new)), "wbx_engine_filter_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames + tail_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
         return new.value
 
     def splice_samples(self, channels: int, n_frames: int, parts) -> int:
