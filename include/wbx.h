@@ -491,7 +491,7 @@ wbx_status wbx_clip_loudness(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, 
  * states; the first two are 0 for a result of one chunk.  WBX_ERR_INVALID for NULL arguments or when no filter has
  * completed.  For tools/bench_filter.py; nothing else reads it.
  * Not offered: zero-phase filtering (filter, derive reversed, filter, derive reversed does it), filters at render time,
- * FIR / convolution, more than 8 stages or 2 channels, in-place edits. */
+ * FIR by FFT (direct convolution: "Convolving a clip" below), more than 8 stages or 2 channels, in-place edits. */
 enum { WBX_FILT_LOWPASS = 0, WBX_FILT_HIGHPASS = 1, WBX_FILT_BANDPASS = 2, WBX_FILT_NOTCH = 3, WBX_FILT_ALLPASS = 4,
        WBX_FILT_PEAK = 5, WBX_FILT_LOWSHELF = 6, WBX_FILT_HIGHSHELF = 7 };
 wbx_status wbx_filter_design(uint32_t rate, int kind, double freq_hz, double q, double gain, double out[5]);
@@ -502,6 +502,79 @@ wbx_status wbx_filter_phase_ms(wbx_ctx* ctx, double out[3]);
 wbx_status wbx_clip_filter(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                            uint64_t tail_frames, const double* coef /* [n_stages][5] */, uint32_t n_stages,
                            wbx_clip_stats* stats_of_result);
+
+/* Convolving a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels convolved with
+ * frames [ir_first, ir_first + ir_frames) of another resident F32 clip, the impulse response of L = ir_frames taps, into a
+ * NEW F32 clip, without the samples leaving HBM: a recorded room, plate or cabinet put on a frozen stem, a linear-phase
+ * low-pass or band-stop baked into a bounce, a measured response used as a match EQ.  Direct convolution in fp64; no
+ * reference counterpart.  This text is the specification; tests/convolve_model.py restates it in numpy, and the designed
+ * taps and every output frame equal that BIT FOR BIT.
+ *   input     x[c][i], i in [0, n_frames): (double) of the source range's fp32 sample; h[c][k], k in [0, L): (double) of the
+ *             response range's fp32 sample.  A value that is not finite (NaN, +-inf) enters as 0.0 — the filter's rule,
+ *             applied to both.  x is ZERO outside [0, n_frames), whatever the clip holds beside the range.  Nothing beside
+ *             either range counts or is ever read: the response may be longer than the pool's 16 padding frames, and a range
+ *             may start at frame 0 of a slab
+ *   output    the full result has n_frames + L - 1 frames (wbx_convolve_frames); stored frame j, j in [0, out_frames), is
+ *             full-result frame m = out_first + j:
+ *               acc = 0.0;  for k = 0 .. L-1 ascending: acc = acc + h[k] * x[m - k]     (fp64, one IEEE operation each)
+ *               y = (float)(gain * acc)                       (one multiplication, one rounding)
+ *             a NaN is stored as 0x7FC00000 (wbx_clip_derive's rule); it can arise only from gain = 0 times an overflow,
+ *             which no input can cause (|acc| <= 2^20 * 2^128 * 2^128).  The product of two fp32 values is exact in fp64,
+ *             so fma(h, x, acc) IS acc + h * x and only the order of the additions is fixed.  A tap whose x[m - k] lies
+ *             outside the range may be skipped or computed with a zero: acc starts at +0.0 and can never become -0.0
+ *             (a sum of +0.0 and +-0.0 is +0.0, an exact cancellation rounds to +0.0), and adding h * 0 = +-0 to it never
+ *             changes it.  The same holds for a tap that entered as 0.0
+ *   window    out_first lets a linear-phase FIR's delay (L - 1) / 2 be dropped; out_first = 0 with out_frames = n_frames
+ *             gives a result as long as the range; out_frames = n_frames + L - 1 gives the whole ring-out
+ *   channels  the result has max(source channels, response channels) channels and the source's rate.  A mono response goes
+ *             to every source channel, a stereo response on a stereo source works channel by channel, a stereo response on a
+ *             mono source gives a stereo result (source * left, source * right)
+ * The response may be the source itself (an autocorrelation's cousin).  dst_clip becomes a new F32 pool clip of out_frames
+ * frames (plus the pool's 16 zero frames of padding), replaced or allocated as wbx_clip_derive does it, on the same stream
+ * and behind the same ordering; one edit, conversion, filter or convolution runs at a time.  The work is issued as several
+ * bounded launches.  stats_of_result (may be NULL): wbx_clip_measure of the whole result, a second pass over
+ * the output only.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: an unknown source or response
+ * clip, n_frames, ir_frames or out_frames of 0, a range past its clip, out_first + out_frames > n_frames + ir_frames - 1,
+ * dst_clip equal to the source or the response, a gain that is not finite, out_frames >= 2^31 - 16, sample rates that
+ * differ (convert first: wbx_clip_resample); WBX_ERR_UNSUPPORTED: either clip not F32 or with more than 2 channels,
+ * ir_frames > 2^20 (21.8 s at 48 kHz), out_frames * ir_frames * channels > 2^46 multiply-adds (channels: the result's).
+ * The sizes are judged before the clips are looked at.  WBX_ERR_OOM as for wbx_clip_derive.
+ * The work cap is a stated limit of the interface — one hour of stereo at 48 kHz with a 4 s response, 6.6e13, lies under it;
+ * DESIGN.md 7i says how long a call at the cap takes.  The way past it: convolve ranges of the source (each with its
+ * ring-out) and overlap-add them with wbx_clip_splice, whose parts are added in list order — a sum of rounded fp32 parts,
+ * NOT bit-equal to one call.
+ * Host-only, no device: wbx_convolve_frames — the full result's length n_frames + ir_frames - 1, or 0 for a pair no window
+ * of which is accepted (either 0, ir_frames > 2^20, a sum past 64 bits); wbx_convolve_tile_frames (2048, the output frames
+ * one workgroup owns) and wbx_convolve_segment_taps (2048, the taps walked per staging) — the kernel's two shape constants.
+ * wbx_fir_design (host-only; wbx_convolve.h, which a C++ compiler takes alone): n_taps of a Kaiser-windowed sinc, linear
+ * phase, in fp64 through "Converting a clip's sample rate"'s sinpi, sinc and I0 — no libm; every operator below is one
+ * IEEE operation in the order written.  n_taps odd, 3 .. 65535;  c = (n_taps - 1) / 2;  for k = 0 .. n_taps - 1:
+ *               d = (double)(k - c);  u = d / c;  a = max(0, 1 - u*u);  w[k] = I0(beta * sqrt(a)) / I0(beta)
+ *               lp_f[k] = ((t * sinc(t * d)) * w[k]) / S_f   with t = (2*f) / rate and S_f = the sum over k ascending of
+ *                         (t * sinc(t * d)) * w[k], started at 0.0
+ *               LOWPASS = lp_f1;  HIGHPASS = delta - lp_f1;  BANDPASS = lp_f2 - lp_f1;  BANDSTOP = delta - (lp_f2 - lp_f1)
+ *             delta is 1.0 at tap c and 0.0 elsewhere; out[k] is the value rounded once to fp32.  f2_hz is not looked at
+ *             by LOWPASS and HIGHPASS.  The taps are symmetric, out[k] == out[n_taps - 1 - k]; played with
+ *             out_first = c the result carries no delay.  WBX_ERR_INVALID: NULL out, cap_floats below n_taps, an unknown
+ *             kind, rate == 0, n_taps even or out of range, an edge not inside (0, rate / 2), f2 <= f1 for the band kinds,
+ *             a beta that is not finite or outside [0, 14].  The taps become a response through wbx_clip_upload (one
+ *             channel, F32): there is no other upload path.
+ * wbx_convolve_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed convolution (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_convolve.py; nothing else reads it.
+ * Not offered: FFT or partitioned convolution (not reproducible bit for bit), convolution at render time, more than 2
+ * channels, "true stereo" matrices of four responses, responses longer than 2^20 frames. */
+enum { WBX_FIR_LOWPASS = 0, WBX_FIR_HIGHPASS = 1, WBX_FIR_BANDPASS = 2, WBX_FIR_BANDSTOP = 3 };
+wbx_status wbx_fir_design(uint32_t rate, int kind, double f1_hz, double f2_hz, uint32_t n_taps, double beta, float* out,
+                          size_t cap_floats);
+uint64_t wbx_convolve_frames(uint64_t n_frames, uint64_t ir_frames);
+uint32_t wbx_convolve_tile_frames(void);
+uint32_t wbx_convolve_segment_taps(void);
+wbx_status wbx_convolve_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_convolve(wbx_ctx* ctx, uint32_t src_clip, uint32_t ir_clip, uint32_t dst_clip, uint64_t first_frame,
+                             uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
+                             uint64_t out_frames, double gain, wbx_clip_stats* stats_of_result);
 
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
@@ -933,6 +1006,15 @@ wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32_t sample, 
  * with n_frames + tail_frames frames.  Arguments and refusals are wbx_clip_filter's (there is no dst_clip to collide with). */
 wbx_status wbx_engine_filter_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                     uint64_t tail_frames, const double* coef, uint32_t n_stages, uint32_t* new_sample);
+/* wbx_clip_convolve of two engine samples, under wbx_engine_filter_sample's rules: BOTH the source and the response are
+ * pinned for the call, so wbx_engine_delete_sample refuses either meanwhile ("sample is being edited"); the editor lock is
+ * held only to validate, pin, order the stream, publish and unpin.  *new_sample is a fresh sample id registered at the
+ * source's rate with out_frames frames and max(source, response) channels.  Arguments and refusals are wbx_clip_convolve's
+ * (there is no dst_clip to collide with). */
+wbx_status wbx_engine_convolve_sample(wbx_engine* e, uint32_t sample, uint32_t ir_sample, uint64_t first_frame,
+                                      uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
+                                      uint64_t out_frames, double gain, uint32_t* new_sample,
+                                      wbx_clip_stats* stats_of_result);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

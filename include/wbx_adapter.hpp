@@ -345,6 +345,18 @@ struct Engine {
     check(wbx_engine_filter_sample(h, sample, first_frame, n_frames, tail_frames, coef, n_stages, &id), "filter_sample");
     return id;
   }
+  // A NEW sample holding frames [out_first, out_first + out_frames) of the range convolved with the range of ir_sample,
+  // the impulse response, times gain (wbx.h "Convolving a clip"): a room or cabinet on a stem, a linear-phase FIR from
+  // wbx_fir_design uploaded as a mono sample (out_first = (taps - 1) / 2 drops its delay).  Both samples are pinned for
+  // the call.  Editing thread, like derive_sample.
+  uint32_t convolve_sample(uint32_t sample, uint32_t ir_sample, uint64_t first_frame, uint64_t n_frames, uint64_t ir_first,
+                           uint64_t ir_frames, uint64_t out_first, uint64_t out_frames, double gain = 1.0,
+                           wbx_clip_stats* stats_of_result = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_convolve_sample(h, sample, ir_sample, first_frame, n_frames, ir_first, ir_frames, out_first, out_frames,
+                                     gain, &id, stats_of_result), "convolve_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

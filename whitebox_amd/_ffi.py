@@ -112,6 +112,7 @@ SRC_QUALITY = {"fast": 0, "good": 1, "best": 2}         # WBX_SRC_*
 LOUD_TRUE_PEAK = 1                                      # WBX_LOUD_TRUE_PEAK
 FILTER_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass": 4, "peak": 5, "lowshelf": 6,
                "highshelf": 7}                          # WBX_FILT_*
+FIR_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # WBX_FIR_*
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
 _vp, _u32, _i32, _f, _d, _sz = C.c_void_p, C.c_uint32, C.c_int32, C.c_float, C.c_double, C.c_size_t
@@ -154,6 +155,13 @@ SYMBOLS = {
     "wbx_filter_chunk_frames": (_u32, []),
     "wbx_filter_phase_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_filter": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, C.POINTER(ClipStats)]),
+    "wbx_fir_design": (C.c_int, [_u32, C.c_int, _d, _d, _u32, _d, _vp, _sz]),
+    "wbx_convolve_frames": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "wbx_convolve_tile_frames": (_u32, []),
+    "wbx_convolve_segment_taps": (_u32, []),
+    "wbx_convolve_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_convolve": (C.c_int, [_vp, _u32, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                    _d, C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -247,6 +255,8 @@ SYMBOLS = {
     "wbx_engine_normalize_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, C.POINTER(_u32), C.POINTER(_f)]),
     "wbx_engine_resample_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(_u32)]),
     "wbx_engine_filter_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, C.POINTER(_u32)]),
+    "wbx_engine_convolve_sample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, _d, C.POINTER(_u32), C.POINTER(ClipStats)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

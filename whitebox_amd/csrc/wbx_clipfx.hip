@@ -283,6 +283,14 @@ wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, co
   return WBX_OK;
 }
 
+wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t src2_clip, uint32_t dst_clip, const char* unknown_src,
+                            const char* unknown_src2, const char* same) {
+  if (!find_clip(c, src_clip)) return fail(c, WBX_ERR_INVALID, unknown_src);
+  if (!find_clip(c, src2_clip)) return fail(c, WBX_ERR_INVALID, unknown_src2);
+  if (dst_clip == src2_clip) return fail(c, WBX_ERR_INVALID, same);
+  return clipfx_check_ids(c, src_clip, dst_clip, unknown_src, same);
+}
+
 static float key_to_float(uint32_t key) {
   const uint32_t b = (key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key;
   float f;

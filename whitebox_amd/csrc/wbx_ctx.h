@@ -18,6 +18,7 @@
 #include "../../include/wbx.h"
 #include "wbx_dev.h"
 #include "wbx_shape.h"
+#include "wbx_convolve.h"
 #include "wbx_filter.h"
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
@@ -157,6 +158,21 @@ struct FilterArgs {
 void launch_filter_state(const FilterArgs& a, hipStream_t s);   // (n_chunks > 1)
 void launch_filter_carry(const FilterArgs& a, hipStream_t s);   // (n_chunks > 1)
 void launch_filter_apply(const FilterArgs& a, hipStream_t s);
+// convolving a clip (wbx_convolve.hip): the response sanitised into doubles once, then bands of tiles of the result
+struct ConvolveArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  const float* ir[2];          // the response's channel rows at ITS range's first frame (mono: ir[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  double* taps;                // device: [ir_channels][l_pad] — the response as doubles, what is not finite as 0.0, zero-padded (and 8 more behind)
+  double gain;
+  uint64_t out_first;          // full-result frame of stored frame 0 (< 2^32 + 2^20)
+  uint32_t n_in, n_ir, n_out;  // frames of the source range / of the response range / of the result (< 2^31 - 16)
+  uint32_t l_pad;              // n_ir rounded up to a multiple of 16
+  uint32_t tile0;              // this launch's first tile (the grid is its band of tiles)
+  uint32_t src_channels, ir_channels;   // 1 or 2 each
+};
+void launch_convolve_taps(const ConvolveArgs& a, hipStream_t s);
+void launch_convolve(const ConvolveArgs& a, uint32_t n_tiles, hipStream_t s);   // tiles [tile0, tile0 + n_tiles)
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -276,6 +292,13 @@ struct FilterStage {
   PinnedBuf<double> h_M;
   Event mark[4];               // (timing events) around the three launches of the last run: wbx_filter_phase_ms
   bool timed = false, carried = false;   // the last run completed / had more than one chunk
+};
+
+// wbx_clip_convolve's response as doubles on the device (at most 2 x 2^20 x 8 bytes) — grown on demand, freed with the context
+struct ConvolveStage {
+  DevBuf<double> d_taps;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_convolve_ms
+  bool timed = false;          // the last run completed
 };
 
 // wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
@@ -430,6 +453,7 @@ struct wbx_ctx {
   SpliceStage splice;                     // wbx_clip_splice (under fx_mu, on fx.side.stream)
   LoudnessStage loud;                     // wbx_clip_loudness (under fx_mu, on fx.side.stream)
   FilterStage filt;                       // wbx_clip_filter (under fx_mu, on fx.side.stream)
+  ConvolveStage conv;                     // wbx_clip_convolve (under fx_mu, on fx.side.stream)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -557,6 +581,9 @@ void clipfx_release(wbx_ctx* c);
 // layer 1's calls that make clip dst_clip out of clip src_clip on the edit stream (wbx_clip_derive, wbx_clip_resample): the
 // test of the two ids with the caller's messages, and "prepare, order, run(slot, why), publish" under fx_mu
 wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, const char* unknown_src, const char* same);
+// ... out of TWO clips (wbx_clip_convolve: the second may be the first, the result may be neither)
+wbx_status clipfx_check_ids(wbx_ctx* c, uint32_t src_clip, uint32_t src2_clip, uint32_t dst_clip, const char* unknown_src,
+                            const char* unknown_src2, const char* same);
 template <class Run>
 wbx_status clipfx_into_clip(wbx_ctx* c, uint32_t dst_clip, Run run) {
   std::lock_guard<std::mutex> g(c->fx_mu);
@@ -593,6 +620,19 @@ wbx_status filter_check_call(const ClipSrc& src, uint64_t first_frame, uint64_t 
                              uint32_t n_stages, const char** why);
 wbx_status filter_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, uint64_t first_frame, uint64_t n_frames, uint64_t tail_frames,
                       const double* coef, uint32_t n_stages, ClipSlot& slot, wbx_clip_stats* stats, std::string* why);
+// convolving a clip (wbx_convolve.hip), cut the same way: the check makes no device call (and looks at the arithmetic of the
+// call before it looks at the clips); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order and
+// measures its result through clipfx_measure_run
+struct ConvolveCall {
+  uint64_t first_frame, n_frames;   // range of the source
+  uint64_t ir_first, ir_frames;     // range of the response
+  uint64_t out_first, out_frames;   // window of the full result
+  double gain;
+};
+wbx_status convolve_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc& ir, uint32_t ir_rate, const ConvolveCall& k,
+                          uint32_t* out_channels, const char** why);
+wbx_status convolve_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& ir, uint32_t rate, const ConvolveCall& k, ClipSlot& slot,
+                        wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -766,6 +766,44 @@ extern "C" wbx_status wbx_engine_filter_sample(wbx_engine* e, uint32_t sample, u
   return st;
 }
 
+// wbx_clip_convolve of two engine samples (wbx.h "Convolving a clip"), under wbx_engine_filter_sample's rules with
+// wbx_engine_splice_samples' pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the
+// source and the response (one id where they are the same sample), ordering the stream, registering the new sample — at
+// the source's rate — and unpinning; it is never held across the device wait.  No transport state is touched, no edit is
+// counted.
+extern "C" wbx_status wbx_engine_convolve_sample(wbx_engine* e, uint32_t sample, uint32_t ir_sample, uint64_t first_frame,
+                                                 uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
+                                                 uint64_t out_frames, double gain, uint32_t* new_sample, wbx_clip_stats* stats_of_result) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "convolve_sample: new_sample is NULL");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const ConvolveCall k{first_frame, n_frames, ir_first, ir_frames, out_first, out_frames, gain};
+  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
+  if (ir_sample != sample) distinct.push_back(ir_sample);
+  ClipSrc ir;
+  uint32_t ch = 0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "convolve_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const ClipSlot* r = e->hs.valid_sample(ir_sample) ? find_clip(e->ctx, ir_sample) : nullptr;
+    if (!r) return efail(e, WBX_ERR_INVALID, "convolve_sample: unknown response sample");
+    ir = clip_src(*r);
+    const char* msg = "";
+    st = convolve_check(p.src, p.rate, ir, r->d.sample_rate, k, &ch, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "convolve_sample: the pool's sample ids (2^24) would run out");
+    p.pin_set_locked(distinct);
+  }
+  std::string why;
+  ClipSlot slot;
+  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = convolve_run(e->ctx, p.src, ir, p.rate, k, slot, stats_of_result, &why);
+  if (st == WBX_OK) st = p.publish(slot, ch, p.rate, out_frames, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
 // wbx_clip_loudness of an engine sample (wbx.h "Measuring a clip's loudness"), beside wbx_engine_measure_sample and under its
 // rules: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,

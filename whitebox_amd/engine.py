@@ -180,6 +180,22 @@ def filter_transition(coef) -> np.ndarray:
     return M
 
 
+def fir_design(rate: int, kind, f1: float, f2: float = 0.0, n_taps: int = 255, beta: float = 8.6) -> np.ndarray:
+    """wbx_fir_design (host-only): `n_taps` (odd, 3 .. 65535) fp32 taps of a linear-phase Kaiser-windowed sinc at `rate` —
+    kind "lowpass" / "highpass" (edge f1) / "bandpass" / "bandstop" (edges f1 < f2), or WBX_FIR_*; beta 8.6 is about 90 dB
+    of stop band.  The delay is (n_taps - 1) // 2 frames: convolve with out_first = that to drop it.  WbxError (-4) where
+    the library refuses the design"""
+    out = np.zeros(max(int(n_taps), 1), dtype=np.float32)
+    _check(_ffi.lib().wbx_fir_design(rate, _ffi.FIR_KIND.get(kind, kind), float(f1), float(f2), n_taps, float(beta),
+                                     out.ctypes.data, out.size), "wbx_fir_design")
+    return out
+
+
+def convolve_frames(n_frames: int, ir_frames: int) -> int:
+    """wbx_convolve_frames (host-only): the full result's length n_frames + ir_frames - 1; 0 where every window is refused"""
+    return int(_ffi.lib().wbx_convolve_frames(n_frames, ir_frames))
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -336,6 +352,26 @@ class MixContext:
         out = np.zeros(3, dtype=np.float64)
         _check(self.L.wbx_filter_phase_ms(self.h, out.ctypes.data), "wbx_filter_phase_ms", self.h)
         return tuple(float(v) for v in out)
+
+    def clip_convolve(self, src_clip: int, ir_clip: int, dst_clip: int, first_frame: int, n_frames: int, ir_first: int,
+                      ir_frames: int, out_first: int = 0, out_frames: Optional[int] = None, gain: float = 1.0,
+                      stats_channels: int = 0):
+        """wbx_clip_convolve: `dst_clip` becomes a new F32 clip holding frames [out_first, out_first + out_frames) of the
+        convolution of `src_clip`'s range with `ir_clip`'s (the impulse response), times `gain` (linear); out_frames
+        defaults to the rest of the full result, n_frames + ir_frames - 1 - out_first.  Returns the result's statistics
+        when `stats_channels` (its channel count) is given, else None"""
+        if out_frames is None:
+            out_frames = n_frames + ir_frames - 1 - out_first
+        st = _ffi.ClipStats()
+        _check(self.L.wbx_clip_convolve(self.h, src_clip, ir_clip, dst_clip, first_frame, n_frames, ir_first, ir_frames, out_first,
+                                        out_frames, float(gain), C.byref(st) if stats_channels else None), "wbx_clip_convolve", self.h)
+        return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def convolve_ms(self) -> float:
+        """wbx_convolve_ms: device milliseconds of the last convolution's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_convolve_ms(self.h, C.byref(out)), "wbx_convolve_ms", self.h)
+        return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
                       energies: bool = False):
@@ -950,6 +986,40 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return new.value
+
+    def add_fir(self, rate: int, taps) -> int:
+        """fir_design(...)'s taps (or any fp32 response) as a mono F32 sample: the `ir_sample` of convolve_sample"""
+        return self.add_sample("f32", rate, [np.ascontiguousarray(taps, dtype=np.float32)])
+
+    def convolve_sample(self, sample: int, ir_sample: int, gain_db: float = 0.0, out_first: int = 0,
+                        out_frames: Optional[int] = None, first_frame: int = 0, n_frames: Optional[int] = None, ir_first: int = 0,
+                        ir_frames: Optional[int] = None, channels: Optional[int] = None, frames: Optional[int] = None,
+                        ir_channels: Optional[int] = None, ir_length: Optional[int] = None, stats: bool = False):
+        """wbx_engine_convolve_sample: a new sample = the range of `sample` convolved with the range of `ir_sample` (the
+        impulse response; add_fir makes one of designed taps), times 10 ** (gain_db / 20) — see MixContext.clip_convolve.
+        The window defaults to the full ring-out from `out_first` on; out_first = (taps - 1) // 2 with out_frames = n_frames
+        drops a linear-phase FIR's delay.  `frames` / `channels` (`ir_length` / `ir_channels`) as in export_sample, for
+        samples this object did not make.  Both samples are pinned against delete_sample for the call's length; may be called
+        while another thread runs process().  Returns the new id, with `stats` (id, statistics of the result)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        ir_length, ir_channels = self._shape_of(ir_sample, ir_length, ir_channels)
+        if n_frames is None:
+            assert frames is not None, "convolve_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        if ir_frames is None:
+            assert ir_length is not None, "convolve_sample: give ir_frames, or ir_length (the response's length)"
+            ir_frames = ir_length - ir_first
+        if out_frames is None:
+            out_frames = n_frames + ir_frames - 1 - out_first
+        new, st = C.c_uint32(), _ffi.ClipStats()
+        _check(self.L.wbx_engine_convolve_sample(self.h, sample, ir_sample, first_frame, n_frames, ir_first, ir_frames, out_first,
+                                                 out_frames, 10.0 ** (float(gain_db) / 20.0), C.byref(new),
+                                                 C.byref(st) if stats else None), "wbx_engine_convolve_sample", self.h, True)
+        out_channels = max(channels, ir_channels)
+        self._sample_shape[new.value] = (out_frames, out_channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return (new.value, _clip_stats(st, out_channels)) if stats else new.value
 
     def splice_samples(self, channels: int, n_frames: int, parts) -> int:
         """wbx_engine_splice_samples: a new sample of `channels` x `n_frames` frames made of the parts (splice_part(...),
