@@ -576,6 +576,73 @@ wbx_status wbx_clip_convolve(wbx_ctx* ctx, uint32_t src_clip, uint32_t ir_clip, 
                              uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
                              uint64_t out_frames, double gain, wbx_clip_stats* stats_of_result);
 
+/* Limiting a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels through a
+ * look-ahead peak limiter into a NEW F32 clip of n_frames frames, without the samples leaving HBM: the last step of a
+ * mastering chain, which lets a clip reach a loudness target under a ceiling without being turned down as a whole for a few
+ * tall peaks.  Purely feed-forward: the gain curve is a sliding minimum, a slope-limited release written in closed form as
+ * a (min, +) convolution, and a moving average.  No reference counterpart.  This text is the specification;
+ * tests/limit_model.py restates it in numpy, and the ramp table, the statistics and every output frame equal that BIT FOR
+ * BIT.  n = n_frames, A = lookahead_frames (0 .. 4096), H = hold_frames (0 .. 65536), R = release_frames (1 .. 2^20);
+ * ceiling is linear, a float, finite and >= FLT_MIN; drive is a linear pre-gain, finite with 0 < |drive| <= 2^32.  Every
+ * operator below is one IEEE fp64 operation and nothing is fused.
+ *   input     d[c][i] = drive * (double)x[c][i], i in [0, n).  A sample that is not finite enters as 0.0 (the filter's
+ *             rule).  Nothing beside the range counts or is ever read
+ *   detector  (channels linked) p[i] = the maximum over the channels of |d[c][i]|;  need[i] = p[i] > c ? c / p[i] : 1.0
+ *             with c = (double)ceiling.  need is 1.0 for every i outside [0, n)
+ *   ramp      s = 1.0 / (double)R;  for k = -A .. H + R - 1: ramp[k] = 0.0 when k <= H, else (double)(k - H) * s.  The
+ *             host builds it as a table of A + H + R doubles, table[k + A] (wbx_limit_ramp): no fma(k, s, ..) can arise
+ *   curve     for j = -A .. n - 1: y[j] = 1.0, then y[j] = min(y[j], need[j - k] + ramp[k]) for every k.  Every value is
+ *             finite and positive, so the minimum is the same in any order and grouping; a run of terms whose need values
+ *             are all 1.0 contributes nothing below 1.0 and may be skipped.  This is look-ahead A, then hold H, then a
+ *             release that rises linearly in gain by 1 / R per frame — in exact arithmetic y[j] = min(m[j], y[j-1] + s)
+ *             with m the sliding minimum — written so that no frame depends on another
+ *   gain      acc = 0.0;  for j = i - A .. i ascending: acc = acc + y[j];  g[i] = min(acc / (double)(A + 1), need[i]).
+ *             Every y[j] of that window has need[i] inside its own look-ahead, so the average reaches need[i] at a peak
+ *             and ramps down to it over A frames; the final min makes the guarantee immune to the rounding of the sum
+ *   output    out[c][i] = (float)(d[c][i] * g[i]), rounded once; a NaN is stored as 0x7FC00000 (none can arise).  The
+ *             result has n frames, the source's channels and rate and NO delay.  GUARANTEE: |out[c][i]| <= ceiling for
+ *             every sample.  Where g[i] == 1.0, out is (float)d: with drive == 1.0 a clip that never exceeds the ceiling
+ *             comes back bit for bit
+ *   wbx_limit_stats (may be NULL; every field independent of order): peak_in = the maximum of p; min_gain and
+ *             min_gain_frame = the smallest g and the first frame that has it (1.0 and 0 where nothing was limited);
+ *             limited_frames = the count of g[i] < 1.0
+ * dst_clip becomes a new F32 pool clip of n frames (plus the pool's 16 zero frames of padding), replaced or allocated as
+ * wbx_clip_derive does it, on the same stream and behind the same ordering; one edit, conversion, filter, convolution or
+ * limit runs at a time.  The curve lives in a stage of (2^20 + A) doubles whatever the clip's length: the call is issued
+ * in bands of 2^20 output frames, each recomputing its A frames of halo.  stats_of_result (may be NULL):
+ * wbx_clip_measure of the whole result, a second pass over the output only.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: an unknown source clip,
+ * n_frames of 0, a range past the clip, dst_clip equal to the source, a ceiling, drive, lookahead_frames, hold_frames or
+ * release_frames outside the ranges above, n_frames >= 2^31 - 16; WBX_ERR_UNSUPPORTED: a source that is not F32 or has
+ * more than 2 channels, n_frames * (A + H + R) > 2^44 terms (a stated cap of the interface, not a measurement; one hour
+ * of 48 kHz with 100 ms of release lies under it).  The sizes are judged before the clip is looked at.  WBX_ERR_OOM as for
+ * wbx_clip_derive.
+ * Host-only, no device (wbx_limit.h, which a C++ compiler takes alone): wbx_limit_ramp writes the A + H + R doubles of the
+ * table (WBX_ERR_INVALID: NULL out, A, H or R out of range, cap_doubles below A + H + R); wbx_limit_tile_frames (2048, the
+ * frames one workgroup owns), wbx_limit_segment_terms (2048, the ramp terms walked per staging) and
+ * wbx_limit_band_frames (2^20) — the kernels' shape constants.
+ * wbx_limit_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed limit (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_limit.py; nothing else reads it.
+ * Not offered: a detector on the oversampled signal (a true-peak limiter; wbx_clip_loudness reports the result's true
+ * peak), unlinked stereo, compressors, expanders and gates (their gain is computed in dB: log and pow), the gain curve as
+ * a clip of its own, limiting at render time or on the master bus, more than 2 channels, in-place edits. */
+typedef struct wbx_limit_stats {
+  double peak_in;
+  double min_gain;
+  uint64_t min_gain_frame;
+  uint64_t limited_frames;
+} wbx_limit_stats;
+wbx_status wbx_limit_ramp(uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames, double* out,
+                          size_t cap_doubles);
+uint32_t wbx_limit_tile_frames(void);
+uint32_t wbx_limit_segment_terms(void);
+uint32_t wbx_limit_band_frames(void);
+wbx_status wbx_limit_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_limit(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                          float ceiling, double drive, uint32_t lookahead_frames, uint32_t hold_frames,
+                          uint32_t release_frames, wbx_limit_stats* limit_stats, wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -1015,6 +1082,13 @@ wbx_status wbx_engine_convolve_sample(wbx_engine* e, uint32_t sample, uint32_t i
                                       uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
                                       uint64_t out_frames, double gain, uint32_t* new_sample,
                                       wbx_clip_stats* stats_of_result);
+/* wbx_clip_limit of an engine sample, under wbx_engine_filter_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile ("sample is being edited"); the editor lock is held only to validate, pin,
+ * order the stream, publish and unpin.  *new_sample is a fresh sample id registered at the source's rate with n_frames
+ * frames and the source's channels.  Arguments and refusals are wbx_clip_limit's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_limit_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, float ceiling,
+                                   double drive, uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
+                                   uint32_t* new_sample, wbx_limit_stats* limit_stats, wbx_clip_stats* stats_of_result);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

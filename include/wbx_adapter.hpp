@@ -357,6 +357,17 @@ struct Engine {
                                      gain, &id, stats_of_result), "convolve_sample");
     return id;
   }
+  // A NEW sample holding the range through a look-ahead peak limiter (wbx.h "Limiting a clip"): drive (linear) in, then no
+  // sample above ceiling (linear), with lookahead / hold / release in frames; no delay, the source's length.  The source is
+  // pinned for the call.  Editing thread, like derive_sample.
+  uint32_t limit_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, float ceiling, double drive,
+                        uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
+                        wbx_limit_stats* limit_stats = nullptr, wbx_clip_stats* stats_of_result = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_limit_sample(h, sample, first_frame, n_frames, ceiling, drive, lookahead_frames, hold_frames, release_frames,
+                                  &id, limit_stats, stats_of_result), "limit_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

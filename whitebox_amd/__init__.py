@@ -11,4 +11,5 @@ from .engine import resample_frames, resample_plan, resample_table  # noqa: F401
 from .engine import loudness_coefficients, loudness_gate, loudness_hops  # noqa: F401
 from .engine import filter_design, filter_transition  # noqa: F401
 from .engine import convolve_frames, fir_design  # noqa: F401
+from .engine import limit_frames, limit_ramp  # noqa: F401
 from .engine import splice_part, splice_plan  # noqa: F401

@@ -78,6 +78,10 @@ class Loudness(C.Structure):           # wbx_loudness, 80 bytes
                 ("blocks", C.c_uint64), ("blocks_gated", C.c_uint64), ("hop_frames", C.c_uint32), ("oversampling", C.c_uint32)]
 
 
+class LimitStats(C.Structure):         # wbx_limit_stats, 32 bytes
+    _fields_ = [("peak_in", C.c_double), ("min_gain", C.c_double), ("min_gain_frame", C.c_uint64), ("limited_frames", C.c_uint64)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -162,6 +166,13 @@ SYMBOLS = {
     "wbx_convolve_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_convolve": (C.c_int, [_vp, _u32, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                     _d, C.POINTER(ClipStats)]),
+    "wbx_limit_ramp": (C.c_int, [_u32, _u32, _u32, _vp, _sz]),
+    "wbx_limit_tile_frames": (_u32, []),
+    "wbx_limit_segment_terms": (_u32, []),
+    "wbx_limit_band_frames": (_u32, []),
+    "wbx_limit_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_limit": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _f, _d, _u32, _u32, _u32, C.POINTER(LimitStats),
+                                 C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -257,6 +268,8 @@ SYMBOLS = {
     "wbx_engine_filter_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, C.POINTER(_u32)]),
     "wbx_engine_convolve_sample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                              C.c_uint64, _d, C.POINTER(_u32), C.POINTER(ClipStats)]),
+    "wbx_engine_limit_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, _d, _u32, _u32, _u32, C.POINTER(_u32),
+                                          C.POINTER(LimitStats), C.POINTER(ClipStats)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

@@ -20,6 +20,7 @@
 #include "wbx_shape.h"
 #include "wbx_convolve.h"
 #include "wbx_filter.h"
+#include "wbx_limit.h"
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
 #include "wbx_splice.h"
@@ -173,6 +174,30 @@ struct ConvolveArgs {
 };
 void launch_convolve_taps(const ConvolveArgs& a, hipStream_t s);
 void launch_convolve(const ConvolveArgs& a, uint32_t n_tiles, hipStream_t s);   // tiles [tile0, tile0 + n_tiles)
+// limiting a clip (wbx_limit.hip): per band the gain curve into the fp64 stage, then gain, product and partial statistics
+struct LimitPartial {          // what one tile (or the whole call so far) knows of wbx_limit_stats; every field merges in any order
+  double peak_in;              // the largest p
+  double min_gain;             // the smallest g ...
+  uint64_t min_gain_frame;     // ... and the first frame that has it
+  uint64_t limited_frames;     // frames with g < 1.0
+};
+struct LimitArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const double* ramp;          // device: [l_pad + 8] — the ramp table, kLimitRampPad from its last term on
+  double* y;                   // device: the stage, curve frame band0 - A + q at [q], q < band_n + A
+  LimitPartial* part;          // device: [apply tiles of a band]
+  LimitPartial* total;         // device: the call's record, merged band by band
+  double ceiling, drive;
+  uint32_t n;                  // frames of the range (< 2^31 - 16)
+  uint32_t band0, band_n;      // this band's first output frame and its output frames
+  uint32_t A;                  // look-ahead
+  uint32_t l_pad;              // A + H + R rounded up to a multiple of 32
+  uint32_t channels;           // 1 or 2
+};
+void launch_limit_curve(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);
+void launch_limit_apply(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);
+void launch_limit_reduce(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);   // part[0 .. n_tiles) into *total
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -298,6 +323,19 @@ struct FilterStage {
 struct ConvolveStage {
   DevBuf<double> d_taps;
   Event mark[2];               // (timing events) around the launches of the last run: wbx_convolve_ms
+  bool timed = false;          // the last run completed
+};
+
+// wbx_clip_limit's ramp table (at most (4096 + 65536 + 2^20 + 40) x 8 bytes, kept while A, H and R stay the same), the fp64
+// curve of one band ((2^20 + 4096) x 8 bytes = 8.4 MB, whatever the clip's length) and the statistics — grown on demand,
+// freed with the context
+struct LimitStage {
+  PinnedBuf<double> h_ramp;
+  DevBuf<double> d_ramp, d_y;
+  DevBuf<LimitPartial> d_part;   // a band's tiles, and behind them the call's record
+  PinnedBuf<LimitPartial> h_total;
+  uint32_t ramp_of[3] = {0, 0, 0};   // A, H, R of the table d_ramp holds (R == 0: none)
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_limit_ms
   bool timed = false;          // the last run completed
 };
 
@@ -454,6 +492,7 @@ struct wbx_ctx {
   LoudnessStage loud;                     // wbx_clip_loudness (under fx_mu, on fx.side.stream)
   FilterStage filt;                       // wbx_clip_filter (under fx_mu, on fx.side.stream)
   ConvolveStage conv;                     // wbx_clip_convolve (under fx_mu, on fx.side.stream)
+  LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -633,6 +672,11 @@ wbx_status convolve_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc& 
                           uint32_t* out_channels, const char** why);
 wbx_status convolve_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& ir, uint32_t rate, const ConvolveCall& k, ClipSlot& slot,
                         wbx_clip_stats* stats, std::string* why);
+// limiting a clip (wbx_limit.hip), cut the same way: the check makes no device call (wbx_limit.h's limit_check_args first,
+// then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status limit_check(const ClipSrc& src, const LimitCall& k, const char** why);
+wbx_status limit_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const LimitCall& k, ClipSlot& slot, wbx_limit_stats* out,
+                     wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -196,6 +196,26 @@ def convolve_frames(n_frames: int, ir_frames: int) -> int:
     return int(_ffi.lib().wbx_convolve_frames(n_frames, ir_frames))
 
 
+def limit_ramp(lookahead_frames: int, hold_frames: int, release_frames: int) -> np.ndarray:
+    """wbx_limit_ramp (host-only): the A + H + R doubles of the limiter's ramp table, table[k + A] = ramp[k]: 0.0 through the
+    look-ahead and the hold, then (k - H) / R.  WbxError (-4) where the library refuses the shape"""
+    n = max(int(lookahead_frames) + int(hold_frames) + int(release_frames), 1)
+    out = np.zeros(n, dtype=np.float64)
+    _check(_ffi.lib().wbx_limit_ramp(lookahead_frames, hold_frames, release_frames, out.ctypes.data, out.size), "wbx_limit_ramp")
+    return out
+
+
+def limit_frames(rate: int, lookahead_ms: float = 1.5, hold_ms: float = 0.0, release_ms: float = 100.0) -> tuple:
+    """(lookahead_frames, hold_frames, release_frames) of the times at `rate`, rounded to the nearest frame; the release is
+    at least one frame.  A convenience of this module: not part of the bit-exact contract"""
+    f = lambda ms: int(round(float(ms) * rate / 1000.0))
+    return f(lookahead_ms), f(hold_ms), max(1, f(release_ms))
+
+
+def _limit_stats(st) -> dict:
+    return {"peak_in": st.peak_in, "min_gain": st.min_gain, "min_gain_frame": st.min_gain_frame, "limited_frames": st.limited_frames}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -371,6 +391,24 @@ class MixContext:
         """wbx_convolve_ms: device milliseconds of the last convolution's launches"""
         out = C.c_double()
         _check(self.L.wbx_convolve_ms(self.h, C.byref(out)), "wbx_convolve_ms", self.h)
+        return out.value
+
+    def clip_limit(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, ceiling: float, drive: float = 1.0,
+                   lookahead_frames: int = 72, hold_frames: int = 0, release_frames: int = 4800, stats_channels: int = 0):
+        """wbx_clip_limit: `dst_clip` becomes a new F32 clip of n_frames frames = the range of `src_clip` times `drive`
+        (linear) through the look-ahead peak limiter: no sample above `ceiling` (linear, taken as a float32), no delay.
+        Returns the limiter's statistics {"peak_in", "min_gain", "min_gain_frame", "limited_frames"}, and with
+        `stats_channels` (the clip's channel count) the pair (those, the result's wbx_clip_measure statistics)"""
+        ls, st = _ffi.LimitStats(), _ffi.ClipStats()
+        _check(self.L.wbx_clip_limit(self.h, src_clip, dst_clip, first_frame, n_frames, np.float32(ceiling), float(drive),
+                                     lookahead_frames, hold_frames, release_frames, C.byref(ls),
+                                     C.byref(st) if stats_channels else None), "wbx_clip_limit", self.h)
+        return (_limit_stats(ls), _clip_stats(st, stats_channels)) if stats_channels else _limit_stats(ls)
+
+    def limit_ms(self) -> float:
+        """wbx_limit_ms: device milliseconds of the last limit's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_limit_ms(self.h, C.byref(out)), "wbx_limit_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1020,6 +1058,55 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _clip_stats(st, out_channels)) if stats else new.value
+
+    def limit_sample(self, sample: int, ceiling_db: float = -1.0, lookahead_ms: float = 1.5, hold_ms: float = 0.0,
+                     release_ms: float = 100.0, drive_db: float = 0.0, first_frame: int = 0, n_frames: Optional[int] = None,
+                     channels: Optional[int] = None, frames: Optional[int] = None, rate: Optional[int] = None,
+                     shape: Optional[tuple] = None, stats: bool = False):
+        """wbx_engine_limit_sample: a new sample = the range of `sample` times 10 ** (drive_db / 20) through the look-ahead
+        peak limiter — see MixContext.clip_limit: no sample above 10 ** (ceiling_db / 20) (rounded to float32), the source's
+        length, no delay.  The times become frames at the sample's rate (`rate` where this object did not make it) through
+        limit_frames; `shape` = (lookahead, hold, release) in frames overrides them.  These conversions happen here and are
+        not part of the bit-exact contract.  `frames` / `channels` as in export_sample.  The source is pinned against
+        delete_sample for the call's length; may be called while another thread runs process().  Returns (new id, the
+        limiter's statistics), with `stats` (id, those, the result's statistics)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "limit_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        A, H, R = shape if shape is not None else limit_frames(rate, lookahead_ms, hold_ms, release_ms)
+        new, ls, st = C.c_uint32(), _ffi.LimitStats(), _ffi.ClipStats()
+        _check(self.L.wbx_engine_limit_sample(self.h, sample, first_frame, n_frames, np.float32(10.0 ** (float(ceiling_db) / 20.0)),
+                                              10.0 ** (float(drive_db) / 20.0), A, H, R, C.byref(new), C.byref(ls),
+                                              C.byref(st) if stats else None), "wbx_engine_limit_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return (new.value, _limit_stats(ls), _clip_stats(st, channels)) if stats else (new.value, _limit_stats(ls))
+
+    def maximize_sample(self, sample: int, target_lufs: float, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
+                        hold_ms: float = 0.0, release_ms: float = 100.0, first_frame: int = 0, n_frames: Optional[int] = None,
+                        channels: Optional[int] = None, frames: Optional[int] = None, rate: Optional[int] = None):
+        """Loudness maximizing in one pass, no iteration: loudness_sample measures the range, the drive is what takes its
+        integrated loudness to `target_lufs`, limit_sample limits the driven range under `ceiling_db`, and loudness_sample
+        (with the true peak) measures the result.  Returns (new id, {"loudness": the result's integrated LUFS, "true_peak":
+        per channel, linear, "drive_db", "limit": the limiter's statistics}).  Where the limiter has work to do the result
+        comes out under the target by what it took away.  A range without an integrated loudness raises WbxError (-4)"""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "maximize_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        before = self.loudness_sample(sample, first_frame, n_frames, channels=channels, frames=frames, rate=rate)
+        if not np.isfinite(before["integrated"]):
+            raise WbxError(-4, "maximize_sample", "the range has no integrated loudness (silent, or shorter than 400 ms)")
+        drive_db = float(target_lufs) - before["integrated"]
+        new, ls = self.limit_sample(sample, ceiling_db, lookahead_ms, hold_ms, release_ms, drive_db, first_frame, n_frames,
+                                    channels=channels, frames=frames, rate=rate)
+        if rate is not None:
+            self._sample_rate[new] = rate
+        after = self.loudness_sample(new, true_peak=True, rate=rate)
+        return new, {"loudness": after["integrated"], "true_peak": after["true_peak"], "drive_db": drive_db, "limit": ls}
 
     def splice_samples(self, channels: int, n_frames: int, parts) -> int:
         """wbx_engine_splice_samples: a new sample of `channels` x `n_frames` frames made of the parts (splice_part(...),
