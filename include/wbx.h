@@ -625,8 +625,9 @@ wbx_status wbx_clip_convolve(wbx_ctx* ctx, uint32_t src_clip, uint32_t ir_clip, 
  * completed limit (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
  * tools/bench_limit.py; nothing else reads it.
  * Not offered: a detector on the oversampled signal (a true-peak limiter; wbx_clip_loudness reports the result's true
- * peak), unlinked stereo, compressors, expanders and gates (their gain is computed in dB: log and pow), the gain curve as
- * a clip of its own, limiting at render time or on the master bus, more than 2 channels, in-place edits. */
+ * peak), unlinked stereo, the gain curve as a clip of its own, limiting at render time or on the master bus, more than 2
+ * channels, in-place edits.  Compressors, expanders, gates and ducking are "Dynamics of a clip" below: their curve in dB is
+ * a table the host builds, so the device needs no log and no pow. */
 typedef struct wbx_limit_stats {
   double peak_in;
   double min_gain;
@@ -642,6 +643,97 @@ wbx_status wbx_limit_ms(wbx_ctx* ctx, double* out);
 wbx_status wbx_clip_limit(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                           float ceiling, double drive, uint32_t lookahead_frames, uint32_t hold_frames,
                           uint32_t release_frames, wbx_limit_stats* limit_stats, wbx_clip_stats* stats_of_result);
+
+/* Dynamics of a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels through a
+ * table-driven dynamics processor into a NEW F32 clip of n_frames frames, the source's channels and rate and NO delay,
+ * without the samples leaving HBM: a compressor of any ratio and knee, a downward expander or gate, ducking from a
+ * sidechain, or any hand-drawn transfer curve, between the EQ and the limiter of a mastering chain.  The gain follows the
+ * level of the clip itself, or of a second resident clip (the key), through a transfer table the HOST builds — a gain per
+ * level, so the device needs no log and no pow: it looks the table up and interpolates — and through the limiter's purely
+ * feed-forward look-ahead / hold / release curve, so no frame depends on another.  No reference counterpart.  This text is
+ * the specification; tests/dynamics_model.py restates it in numpy, and the table, the statistics and every output frame
+ * equal that BIT FOR BIT.  n = n_frames, A = lookahead_frames (0 .. 4096), H = hold_frames (0 .. 65536), R = release_frames
+ * (1 .. 2^20): "Limiting a clip"'s ranges and its wbx_limit_ramp table, unchanged.  sense is WBX_DYN_COMPRESS or
+ * WBX_DYN_GATE.  drive and key_gain are linear, finite with 0 < |.| <= 2^32 (key_gain is not looked at without a key);
+ * makeup is linear, finite and >= 0.  Every operator below is one IEEE fp64 operation and nothing is fused.
+ *   input     d[c][i] = drive * (double)x[c][i], i in [0, n).  A sample that is not finite enters as 0.0.  Nothing beside
+ *             the range counts or is ever read
+ *   level     without a key (key_clip == WBX_DYN_NO_KEY): p[i] = the maximum over the channels of |d[c][i]|.  With a key:
+ *             p[i] = the maximum over the KEY's channels of |key_gain * (double)key[c][key_first + i]|, what is not finite
+ *             entering as 0.0.  The key has 1 or 2 channels of its own, whatever the source has, and the source's rate
+ *   table     WBX_DYN_TABLE = 48 * 64 + 1 = 3073 doubles over the levels 2^-40 .. 2^8, 64 cells per octave, linear in the
+ *             mantissa: entry (e + 40) * 64 + k belongs to the level 2^e * (1 + k / 64).  Every entry is finite, its sign
+ *             bit clear, and <= 1.0 (wbx_dynamics_check).  lo = the smallest entry
+ *   lookup    want = tab(p):  p < 2^-40 (0 included): tab[0];  p >= 2^8: tab[3072];  otherwise, with e the unbiased
+ *             exponent and m the 52 mantissa bits of p:  idx = (e + 40) * 64 + (m >> 46);
+ *             f = (double)(m & (2^46 - 1)) * 2^-46 (exact);  want = tab[idx] + f * (tab[idx + 1] - tab[idx]).
+ *             want lies between its two entries (f <= 1 - 2^-46, and two roundings cannot carry the sum past
+ *             tab[idx + 1]), so want is in [lo, 1.0]
+ *   rest      the gain of a level that asks for nothing: 1.0 in the compress sense, lo in the gate sense.  want is rest for
+ *             every frame outside [0, n)
+ *   curve     for j = -A .. n - 1, with ramp[k], k = -A .. H + R - 1, the limiter's (0.0 when k <= H, else (k - H) * (1 / R)):
+ *             compress: y[j] = 1.0, then y[j] = min(y[j], want[j - k] + ramp[k]) for every k — the limiter's curve with want
+ *             in place of need: the gain falls A frames ahead of a loud passage, is held H frames and recovers by 1 / R per
+ *             frame.  gate: y[j] = lo, then y[j] = max(y[j], want[j - k] - ramp[k]) for every k — the mirror image: the gate
+ *             opens A frames before the signal arrives, is held H frames and closes by 1 / R per frame.  No -0.0 can arise
+ *             (the entries carry no sign, x - x is +0.0), so minimum and maximum are the same in any order and grouping; a
+ *             run of terms whose want values all equal rest changes nothing and may be skipped
+ *   gain      acc = 0.0;  for j = i - A .. i ascending: acc = acc + y[j];  g[i] = acc / (double)(A + 1).  No final minimum:
+ *             there is no guarantee to keep here, that is the limiter's job.  g <= 1.0 (a sum of A + 1 values <= 1.0 cannot
+ *             round above A + 1); g may round below lo by a few units in the last place
+ *   output    out[c][i] = (float)((d[c][i] * g[i]) * makeup), rounded once to fp32; a NaN is stored as 0x7FC00000
+ *   wbx_dynamics_stats (may be NULL; every field independent of order): min_gain and min_gain_frame = the smallest g and
+ *             the first frame that has it; reduced_frames = the count of g[i] < 1.0
+ * dst_clip becomes a new F32 pool clip of n frames (plus the pool's 16 zero frames of padding), replaced or allocated as
+ * wbx_clip_derive does it, on the same stream and behind the same ordering; one edit, conversion, filter, convolution,
+ * limit or dynamics call runs at a time.  The call is issued in the limiter's bands of 2^20 output frames over the
+ * limiter's stage.  stats_of_result (may be NULL): wbx_clip_measure of the whole result, a second pass over
+ * the output only.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: an unknown source or key clip,
+ * n_frames of 0, a range past either clip, dst_clip equal to the source or the key, a NULL table or one wbx_dynamics_check
+ * refuses, an unknown sense, a drive, key_gain, makeup, lookahead_frames, hold_frames or release_frames outside the ranges
+ * above, n_frames >= 2^31 - 16, a key whose sample rate differs from the source's; WBX_ERR_UNSUPPORTED: a source or key
+ * that is not F32 or has more than 2 channels, n_frames * (A + H + R) > 2^44 terms (the limiter's stated cap).  The sizes
+ * are judged before the clips are looked at.  WBX_ERR_OOM as for wbx_clip_derive.
+ * Host-only, no device (wbx_dynamics.h, which a C++ compiler takes alone):
+ * wbx_dynamics_table writes the 3073 entries of the usual static curve.  kind WBX_DYN_COMPRESS: above the threshold the
+ *             gain in dB is (1 / ratio - 1) * (L - T), L the level and T the threshold in dB; kind WBX_DYN_GATE (a downward
+ *             expander; a gate is one of high ratio): below the threshold it is (ratio - 1) * (L - T).  ratio >= 1, +inf
+ *             allowed for the compressor only.  knee_db (0 .. 1000) blends quadratically over [T - knee / 2, T + knee / 2]:
+ *             (1 / ratio - 1) * (L - T + knee / 2)^2 / (2 knee), the expander -(ratio - 1) * (L - T - knee / 2)^2 / (2 knee).
+ *             The gain is never below range_db (<= 0; -inf: no floor, and an entry below 2^-1021 is 0.0).  |T| <= 1000.
+ *             On the side of the knee where the curve asks for nothing the entry is EXACTLY 1.0, by a branch.  Computed in
+ *             octaves (a dB figure divided by 20 log10(2) = 6.020599913279624) with a log2 and an exp2 made of + - * /
+ *             and floor in a fixed number of steps — no libm, so the table is the same on every host.  WBX_ERR_INVALID:
+ *             NULL out, cap_doubles below WBX_DYN_TABLE, an unknown kind, a parameter outside the ranges above or a NaN;
+ *             nothing is written then
+ * wbx_dynamics_check judges any table, designed or hand-drawn (WBX_ERR_INVALID: NULL, an unknown sense, an entry that is
+ *             not finite, carries a sign bit or exceeds 1.0); lo (may be NULL) receives the smallest entry
+ * wbx_dynamics_lookup the lookup above for one level (WBX_ERR_INVALID: NULL table or out, a level that is negative or a NaN).
+ * wbx_dynamics_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed dynamics call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_dynamics.py; nothing else reads it.
+ * Not offered: an RMS or true-peak detector, unlinked stereo, upward compression (entries above 1.0), multiband, a release
+ * that is exponential in dB, the gain curve as a clip of its own, dynamics at render time or on buses, more than 2
+ * channels, in-place edits. */
+enum { WBX_DYN_COMPRESS = 0, WBX_DYN_GATE = 1 };
+#define WBX_DYN_TABLE 3073
+#define WBX_DYN_NO_KEY 0xFFFFFFFFu
+typedef struct wbx_dynamics_stats {
+  double min_gain;
+  uint64_t min_gain_frame;
+  uint64_t reduced_frames;
+} wbx_dynamics_stats;
+wbx_status wbx_dynamics_table(int kind, double threshold_db, double ratio, double knee_db, double range_db, double* out,
+                              size_t cap_doubles);
+wbx_status wbx_dynamics_check(const double* table, int sense, double* lo);
+wbx_status wbx_dynamics_lookup(const double* table, double level, double* out);
+wbx_status wbx_dynamics_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_dynamics(wbx_ctx* ctx, uint32_t src_clip, uint32_t key_clip /* WBX_DYN_NO_KEY: the source keys itself */,
+                             uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames, uint64_t key_first, int sense,
+                             const double* table /* [WBX_DYN_TABLE] */, double drive, double key_gain, double makeup,
+                             uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
+                             wbx_dynamics_stats* dynamics_stats, wbx_clip_stats* stats_of_result);
 
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
@@ -1089,6 +1181,16 @@ wbx_status wbx_engine_convolve_sample(wbx_engine* e, uint32_t sample, uint32_t i
 wbx_status wbx_engine_limit_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, float ceiling,
                                    double drive, uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
                                    uint32_t* new_sample, wbx_limit_stats* limit_stats, wbx_clip_stats* stats_of_result);
+/* wbx_clip_dynamics of an engine sample, keyed by itself (key_sample == WBX_DYN_NO_KEY) or by another sample, under
+ * wbx_engine_convolve_sample's rules: the source and the key are pinned for the call (one id where they are the same
+ * sample), so wbx_engine_delete_sample refuses them meanwhile; the editor lock is held only to validate, pin, order the
+ * stream, publish and unpin.  *new_sample is a fresh sample id registered at the source's rate with n_frames frames and the
+ * source's channels.  Arguments and refusals are wbx_clip_dynamics' (there is no dst_clip to collide with). */
+wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t key_sample, uint64_t first_frame,
+                                      uint64_t n_frames, uint64_t key_first, int sense, const double* table, double drive,
+                                      double key_gain, double makeup, uint32_t lookahead_frames, uint32_t hold_frames,
+                                      uint32_t release_frames, uint32_t* new_sample, wbx_dynamics_stats* dynamics_stats,
+                                      wbx_clip_stats* stats_of_result);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

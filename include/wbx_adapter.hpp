@@ -368,6 +368,21 @@ struct Engine {
                                   &id, limit_stats, stats_of_result), "limit_sample");
     return id;
   }
+  // A NEW sample holding the range through a table-driven compressor, expander, gate or ducker (wbx.h "Dynamics of a
+  // clip"): table = WBX_DYN_TABLE gains over level (wbx_dynamics_table, or hand-drawn), sense WBX_DYN_COMPRESS or
+  // WBX_DYN_GATE, the level taken from the sample itself or from key_sample (WBX_DYN_NO_KEY: itself), lookahead / hold /
+  // release in frames; no delay, the source's length.  Source and key are pinned for the call.  Editing thread, like
+  // derive_sample.
+  uint32_t dynamics_sample(uint32_t sample, uint32_t key_sample, uint64_t first_frame, uint64_t n_frames, uint64_t key_first,
+                           int sense, const double* table, double drive, double key_gain, double makeup,
+                           uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
+                           wbx_dynamics_stats* dynamics_stats = nullptr, wbx_clip_stats* stats_of_result = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_dynamics_sample(h, sample, key_sample, first_frame, n_frames, key_first, sense, table, drive, key_gain, makeup,
+                                     lookahead_frames, hold_frames, release_frames, &id, dynamics_stats, stats_of_result),
+          "dynamics_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

@@ -82,6 +82,10 @@ class LimitStats(C.Structure):         # wbx_limit_stats, 32 bytes
     _fields_ = [("peak_in", C.c_double), ("min_gain", C.c_double), ("min_gain_frame", C.c_uint64), ("limited_frames", C.c_uint64)]
 
 
+class DynamicsStats(C.Structure):      # wbx_dynamics_stats, 24 bytes
+    _fields_ = [("min_gain", C.c_double), ("min_gain_frame", C.c_uint64), ("reduced_frames", C.c_uint64)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -116,6 +120,8 @@ SRC_QUALITY = {"fast": 0, "good": 1, "best": 2}         # WBX_SRC_*
 LOUD_TRUE_PEAK = 1                                      # WBX_LOUD_TRUE_PEAK
 FILTER_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass": 4, "peak": 5, "lowshelf": 6,
                "highshelf": 7}                          # WBX_FILT_*
+DYN_SENSE = {"compress": 0, "gate": 1}                    # WBX_DYN_COMPRESS / WBX_DYN_GATE (a table's kind, a call's sense)
+DYN_TABLE, DYN_NO_KEY = 3073, 0xFFFFFFFF                # WBX_DYN_TABLE, WBX_DYN_NO_KEY
 FIR_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # WBX_FIR_*
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
@@ -173,6 +179,12 @@ SYMBOLS = {
     "wbx_limit_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_limit": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _f, _d, _u32, _u32, _u32, C.POINTER(LimitStats),
                                  C.POINTER(ClipStats)]),
+    "wbx_dynamics_table": (C.c_int, [C.c_int, _d, _d, _d, _d, _vp, _sz]),
+    "wbx_dynamics_check": (C.c_int, [_vp, C.c_int, C.POINTER(_d)]),
+    "wbx_dynamics_lookup": (C.c_int, [_vp, _d, C.POINTER(_d)]),
+    "wbx_dynamics_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_dynamics": (C.c_int, [_vp, _u32, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
+                                    _u32, _u32, C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -270,6 +282,8 @@ SYMBOLS = {
                                              C.c_uint64, _d, C.POINTER(_u32), C.POINTER(ClipStats)]),
     "wbx_engine_limit_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _f, _d, _u32, _u32, _u32, C.POINTER(_u32),
                                           C.POINTER(LimitStats), C.POINTER(ClipStats)]),
+    "wbx_engine_dynamics_sample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
+                                             _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

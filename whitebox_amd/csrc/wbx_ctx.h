@@ -20,6 +20,7 @@
 #include "wbx_shape.h"
 #include "wbx_convolve.h"
 #include "wbx_filter.h"
+#include "wbx_dynamics.h"
 #include "wbx_limit.h"
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
@@ -198,6 +199,35 @@ struct LimitArgs {
 void launch_limit_curve(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_limit_apply(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_limit_reduce(const LimitArgs& a, uint32_t n_tiles, hipStream_t s);   // part[0 .. n_tiles) into *total
+// dynamics of a clip (wbx_dynamics.hip): the limiter's shape — per band the gain curve into the limiter's fp64 stage, then
+// gain, product and partial statistics — with a table lookup where the limiter divides
+struct DynPartial {            // what one tile (or the whole call so far) knows of wbx_dynamics_stats; every field merges in any order
+  double min_gain;             // the smallest g ...
+  uint64_t min_gain_frame;     // ... and the first frame that has it
+  uint64_t reduced_frames;     // frames with g < 1.0
+};
+struct DynArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  const float* det[2];         // the detector's rows at its first frame: the key's, or the source's again
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const double* ramp;          // device: [l_pad + 8] — the limiter's ramp table, kLimitRampPad from its last term on
+  const double* tab;           // device: [kDynTable] — the transfer table
+  double* y;                   // device: the stage, curve frame band0 - A + q at [q], q < band_n + A
+  DynPartial* part;            // device: [apply tiles of a band]
+  DynPartial* total;           // device: the call's record, merged band by band
+  double drive, det_gain, makeup;   // det_gain: key_gain, or the drive again
+  double rest;                 // 1.0 (compress) or the table's smallest entry (gate)
+  uint32_t n;                  // frames of the range (< 2^31 - 16)
+  uint32_t band0, band_n;      // this band's first output frame and its output frames
+  uint32_t A;                  // look-ahead
+  uint32_t l_pad;              // A + H + R rounded up to a multiple of 32
+  uint32_t channels;           // the source's: 1 or 2
+  uint32_t det_channels;       // the detector's: 1 or 2
+  int sense;                   // WBX_DYN_COMPRESS or WBX_DYN_GATE
+};
+void launch_dynamics_curve(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
+void launch_dynamics_apply(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
+void launch_dynamics_reduce(const DynArgs& a, uint32_t n_tiles, hipStream_t s);   // part[0 .. n_tiles) into *total
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -323,6 +353,17 @@ struct FilterStage {
 struct ConvolveStage {
   DevBuf<double> d_taps;
   Event mark[2];               // (timing events) around the launches of the last run: wbx_convolve_ms
+  bool timed = false;          // the last run completed
+};
+
+// wbx_clip_dynamics' own buffers: the transfer table (3073 doubles, uploaded per call), the statistics and the timing
+// events.  The curve's stage and the cached ramp are LimitStage's — one edit runs at a time
+struct DynStage {
+  PinnedBuf<double> h_tab;
+  DevBuf<double> d_tab;
+  DevBuf<DynPartial> d_part;     // a band's tiles, and behind them the call's record
+  PinnedBuf<DynPartial> h_total;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_dynamics_ms
   bool timed = false;          // the last run completed
 };
 
@@ -493,6 +534,7 @@ struct wbx_ctx {
   FilterStage filt;                       // wbx_clip_filter (under fx_mu, on fx.side.stream)
   ConvolveStage conv;                     // wbx_clip_convolve (under fx_mu, on fx.side.stream)
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
+  DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -677,6 +719,13 @@ wbx_status convolve_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& ir, uint3
 wbx_status limit_check(const ClipSrc& src, const LimitCall& k, const char** why);
 wbx_status limit_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const LimitCall& k, ClipSlot& slot, wbx_limit_stats* out,
                      wbx_clip_stats* stats, std::string* why);
+// dynamics of a clip (wbx_dynamics.hip), beside their limiter twins: the check makes no device call (wbx_dynamics.h's
+// dynamics_check_args first, then the clips; `key` is NULL for a call that keys itself) and yields the table's smallest
+// entry; the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status dynamics_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc* key, uint32_t key_rate, const DynCall& k, double* lo,
+                          const char** why);
+wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint32_t rate, const DynCall& k, double lo, ClipSlot& slot,
+                        wbx_dynamics_stats* out, wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

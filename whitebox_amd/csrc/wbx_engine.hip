@@ -833,6 +833,50 @@ extern "C" wbx_status wbx_engine_limit_sample(wbx_engine* e, uint32_t sample, ui
   return st;
 }
 
+// wbx_clip_dynamics of engine samples (wbx.h "Dynamics of a clip"), under wbx_engine_convolve_sample's rules and with its
+// pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the source and the key (one id
+// where they are the same sample, or where there is no key), ordering the stream, registering the new sample — at the
+// source's rate — and unpinning; it is never held across the device wait.  No transport state is touched, no edit is counted.
+extern "C" wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t key_sample, uint64_t first_frame,
+                                                 uint64_t n_frames, uint64_t key_first, int sense, const double* table, double drive,
+                                                 double key_gain, double makeup, uint32_t lookahead_frames, uint32_t hold_frames,
+                                                 uint32_t release_frames, uint32_t* new_sample, wbx_dynamics_stats* dynamics_stats,
+                                                 wbx_clip_stats* stats_of_result) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "dynamics_sample: new_sample is NULL");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const bool keyed = key_sample != WBX_DYN_NO_KEY;
+  const DynCall k{first_frame, n_frames, key_first, keyed, sense, table, drive, key_gain, makeup, lookahead_frames, hold_frames, release_frames};
+  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
+  if (keyed && key_sample != sample) distinct.push_back(key_sample);
+  ClipSrc key{};
+  double lo = 1.0;
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "dynamics_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    uint32_t key_rate = p.rate;
+    if (keyed) {
+      const ClipSlot* r = e->hs.valid_sample(key_sample) ? find_clip(e->ctx, key_sample) : nullptr;
+      if (!r) return efail(e, WBX_ERR_INVALID, "dynamics_sample: unknown key sample");
+      key = clip_src(*r);
+      key_rate = r->d.sample_rate;
+    }
+    const char* msg = "";
+    st = dynamics_check(p.src, p.rate, keyed ? &key : nullptr, key_rate, k, &lo, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "dynamics_sample: the pool's sample ids (2^24) would run out");
+    p.pin_set_locked(distinct);
+  }
+  std::string why;
+  ClipSlot slot;
+  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = dynamics_run(e->ctx, p.src, keyed ? &key : nullptr, p.rate, k, lo, slot, dynamics_stats, stats_of_result, &why);
+  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, n_frames, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
 // wbx_clip_loudness of an engine sample (wbx.h "Measuring a clip's loudness"), beside wbx_engine_measure_sample and under its
 // rules: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,

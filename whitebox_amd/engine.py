@@ -216,6 +216,42 @@ def _limit_stats(st) -> dict:
     return {"peak_in": st.peak_in, "min_gain": st.min_gain, "min_gain_frame": st.min_gain_frame, "limited_frames": st.limited_frames}
 
 
+def dynamics_table(kind, threshold_db: float, ratio: float, knee_db: float = 0.0, range_db: float = -np.inf) -> np.ndarray:
+    """wbx_dynamics_table (host-only): the WBX_DYN_TABLE = 3073 gains over level of the usual static curve — kind "compress"
+    (above the threshold the gain in dB is (1 / ratio - 1) * (L - T)) or "gate" (a downward expander: below it,
+    (ratio - 1) * (L - T)), with a quadratic knee of knee_db and never below range_db.  WbxError (-4) where the library
+    refuses the design"""
+    out = np.zeros(_ffi.DYN_TABLE, dtype=np.float64)
+    _check(_ffi.lib().wbx_dynamics_table(_ffi.DYN_SENSE.get(kind, kind), float(threshold_db), float(ratio), float(knee_db),
+                                         float(range_db), out.ctypes.data, out.size), "wbx_dynamics_table")
+    return out
+
+
+def _dyn_table(table) -> np.ndarray:
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    assert t.shape == (_ffi.DYN_TABLE,), "a dynamics table has 3073 entries"
+    return t
+
+
+def dynamics_check(table, sense="compress") -> float:
+    """wbx_dynamics_check (host-only): the smallest entry of a table the library accepts; WbxError (-4) for one it refuses
+    (an entry that is not finite, carries a sign bit or exceeds 1.0)"""
+    t, lo = _dyn_table(table), C.c_double()
+    _check(_ffi.lib().wbx_dynamics_check(t.ctypes.data, _ffi.DYN_SENSE.get(sense, sense), C.byref(lo)), "wbx_dynamics_check")
+    return lo.value
+
+
+def dynamics_lookup(table, level: float) -> float:
+    """wbx_dynamics_lookup (host-only): the gain the table gives one level (linear, >= 0), as the device interpolates it"""
+    t, out = _dyn_table(table), C.c_double()
+    _check(_ffi.lib().wbx_dynamics_lookup(t.ctypes.data, float(level), C.byref(out)), "wbx_dynamics_lookup")
+    return out.value
+
+
+def _dynamics_stats(st) -> dict:
+    return {"min_gain": st.min_gain, "min_gain_frame": st.min_gain_frame, "reduced_frames": st.reduced_frames}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -409,6 +445,28 @@ class MixContext:
         """wbx_limit_ms: device milliseconds of the last limit's launches"""
         out = C.c_double()
         _check(self.L.wbx_limit_ms(self.h, C.byref(out)), "wbx_limit_ms", self.h)
+        return out.value
+
+    def clip_dynamics(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, table, sense="compress",
+                      key_clip: Optional[int] = None, key_first: int = 0, drive: float = 1.0, key_gain: float = 1.0,
+                      makeup: float = 1.0, lookahead_frames: int = 72, hold_frames: int = 0, release_frames: int = 4800,
+                      stats_channels: int = 0):
+        """wbx_clip_dynamics: `dst_clip` becomes a new F32 clip of n_frames frames = the range of `src_clip` times `drive`,
+        times the gain that `table` (dynamics_table(...), or any 3073 gains over level) gives the level of the clip itself
+        or of `key_clip` from `key_first` on, shaped by look-ahead, hold and release in the `sense` "compress" or "gate",
+        times `makeup` (all linear); no delay.  Returns the statistics {"min_gain", "min_gain_frame", "reduced_frames"},
+        and with `stats_channels` (the clip's channel count) the pair (those, the result's wbx_clip_measure statistics)"""
+        t, ds, st = _dyn_table(table), _ffi.DynamicsStats(), _ffi.ClipStats()
+        _check(self.L.wbx_clip_dynamics(self.h, src_clip, _ffi.DYN_NO_KEY if key_clip is None else key_clip, dst_clip, first_frame,
+                                        n_frames, key_first, _ffi.DYN_SENSE.get(sense, sense), t.ctypes.data, float(drive),
+                                        float(key_gain), float(makeup), lookahead_frames, hold_frames, release_frames,
+                                        C.byref(ds), C.byref(st) if stats_channels else None), "wbx_clip_dynamics", self.h)
+        return (_dynamics_stats(ds), _clip_stats(st, stats_channels)) if stats_channels else _dynamics_stats(ds)
+
+    def dynamics_ms(self) -> float:
+        """wbx_dynamics_ms: device milliseconds of the last dynamics call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_dynamics_ms(self.h, C.byref(out)), "wbx_dynamics_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1084,6 +1142,65 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _limit_stats(ls), _clip_stats(st, channels)) if stats else (new.value, _limit_stats(ls))
+
+    def dynamics_sample(self, sample: int, table, sense="compress", key_sample: Optional[int] = None, key_first: int = 0,
+                        drive: float = 1.0, key_gain: float = 1.0, makeup: float = 1.0, shape: tuple = (72, 0, 4800),
+                        first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                        frames: Optional[int] = None, stats: bool = False):
+        """wbx_engine_dynamics_sample: a new sample = the range of `sample` through the table-driven dynamics processor —
+        see MixContext.clip_dynamics; `shape` = (lookahead, hold, release) in frames, gains linear.  `frames` / `channels` as
+        in export_sample.  The source and the key are pinned against delete_sample for the call's length; may be called
+        while another thread runs process().  Returns (new id, the statistics), with `stats` (id, those, the result's
+        statistics)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "dynamics_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        A, H, R = shape
+        t, new, ds, st = _dyn_table(table), C.c_uint32(), _ffi.DynamicsStats(), _ffi.ClipStats()
+        _check(self.L.wbx_engine_dynamics_sample(self.h, sample, _ffi.DYN_NO_KEY if key_sample is None else key_sample, first_frame,
+                                                 n_frames, key_first, _ffi.DYN_SENSE.get(sense, sense), t.ctypes.data, float(drive),
+                                                 float(key_gain), float(makeup), A, H, R, C.byref(new), C.byref(ds),
+                                                 C.byref(st) if stats else None), "wbx_engine_dynamics_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return (new.value, _dynamics_stats(ds), _clip_stats(st, channels)) if stats else (new.value, _dynamics_stats(ds))
+
+    def _dynamics_shape(self, sample, rate, attack_ms, hold_ms, release_ms):
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        return limit_frames(rate, attack_ms, hold_ms, release_ms)
+
+    def compress_sample(self, sample: int, threshold_db: float = -18.0, ratio: float = 4.0, knee_db: float = 6.0,
+                        makeup_db: float = 0.0, attack_ms: float = 5.0, hold_ms: float = 0.0, release_ms: float = 100.0,
+                        range_db: float = -np.inf, rate: Optional[int] = None, **call):
+        """A compressor: dynamics_sample in the compress sense with dynamics_table("compress", ...); the attack is the
+        look-ahead (the gain is down when the loud passage arrives).  dB and ms are converted here (limit_frames): a
+        convenience outside the bit-exact contract.  `call`: dynamics_sample's first_frame, n_frames, frames, channels,
+        stats, drive"""
+        return self.dynamics_sample(sample, dynamics_table("compress", threshold_db, ratio, knee_db, range_db), "compress",
+                                    makeup=10.0 ** (float(makeup_db) / 20.0),
+                                    shape=self._dynamics_shape(sample, rate, attack_ms, hold_ms, release_ms), **call)
+
+    def gate_sample(self, sample: int, threshold_db: float = -40.0, ratio: float = 10.0, knee_db: float = 0.0,
+                    range_db: float = -80.0, attack_ms: float = 1.0, hold_ms: float = 20.0, release_ms: float = 100.0,
+                    rate: Optional[int] = None, **call):
+        """A downward expander or gate: dynamics_sample in the gate sense with dynamics_table("gate", ...): open `attack_ms`
+        before the signal crosses the threshold, held, closed over `release_ms`, never below `range_db`.  Conversions as in
+        compress_sample"""
+        return self.dynamics_sample(sample, dynamics_table("gate", threshold_db, ratio, knee_db, range_db), "gate",
+                                    shape=self._dynamics_shape(sample, rate, attack_ms, hold_ms, release_ms), **call)
+
+    def duck_sample(self, sample: int, key_sample: int, amount_db: float = 12.0, threshold_db: float = -30.0,
+                    knee_db: float = 6.0, attack_ms: float = 10.0, hold_ms: float = 50.0, release_ms: float = 300.0,
+                    key_first: int = 0, key_gain_db: float = 0.0, rate: Optional[int] = None, **call):
+        """Sidechain ducking: `sample` turned down by up to `amount_db` while `key_sample` (a voice-over, a kick) is above
+        `threshold_db`: the compress sense, keyed, with an infinite ratio and range_db = -amount_db.  Conversions as in
+        compress_sample"""
+        table = dynamics_table("compress", threshold_db, np.inf, knee_db, -abs(float(amount_db)))
+        return self.dynamics_sample(sample, table, "compress", key_sample=key_sample, key_first=key_first,
+                                    key_gain=10.0 ** (float(key_gain_db) / 20.0),
+                                    shape=self._dynamics_shape(sample, rate, attack_ms, hold_ms, release_ms), **call)
 
     def maximize_sample(self, sample: int, target_lufs: float, ceiling_db: float = -1.0, lookahead_ms: float = 1.5,
                         hold_ms: float = 0.0, release_ms: float = 100.0, first_frame: int = 0, n_frames: Optional[int] = None,
