@@ -735,6 +735,78 @@ wbx_status wbx_clip_dynamics(wbx_ctx* ctx, uint32_t src_clip, uint32_t key_clip 
                              uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
                              wbx_dynamics_stats* dynamics_stats, wbx_clip_stats* stats_of_result);
 
+/* Stretching a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels time-stretched
+ * into a NEW F32 clip of out_frames frames — another LENGTH at the same PITCH — without the samples leaving HBM, by WSOLA
+ * (waveform-similarity overlap-add): fitting a loop or a take to the session's tempo.  The result plays at speed 1.0 through
+ * the unity row mode; the reference's own `stretch` resize only changes the playback speed (pitch moves with tempo).  No
+ * reference counterpart.  Purely time-domain: no FFT, no log, no sqrt.  This text is the specification;
+ * tests/stretch_model.py restates it in numpy, and the positions, the window table and every output sample equal that BIT
+ * FOR BIT.  Every operator below is one IEEE fp64 operation in the order written and nothing is fused; where both factors
+ * are fp32 values the product is exact in fp64, so an fma there is the same thing.
+ *   input     x[c][i], i in [0, n), n = n_frames: the (double) of the range's fp32 sample; a value that is not finite enters
+ *             as 0.0.  x is zero outside [0, n), whatever the clip holds beside the range; nothing beside it is ever read
+ *   detector  linked channels, one set of positions for all: mono d[i] = x[0][i]; stereo d[i] = (float)(0.5 * (x[0][i] +
+ *             x[1][i])), one rounding to fp32 (it cannot overflow).  d is an fp32 value, so every product below is exact
+ *   shape     N = window_frames, a multiple of 8 in [32, 8192]; Hs = N / 2; D = tolerance_frames in [0, 4096];
+ *             m = out_frames; K = ceil(m / Hs) steps (wbx_stretch_steps)
+ *   anchors   a_k = floor(k * Hs * n / m) in 64-bit integers (wbx_stretch_anchor); a_k <= n - 1
+ *   positions with p_{-1} = -Hs, for k = 0 .. K - 1: c_k = p_{k-1} + Hs, the natural continuation; lo = max(a_k - D, 0);
+ *             hi = min(a_k + D, n - 1).  If lo <= c_k <= hi, p_k = c_k with no search (so p_0 = 0).  Otherwise every
+ *             candidate q in [lo, hi] is scored:
+ *                 s = 0.0; E = 0.0; for i = 0 .. Hs - 1 ascending: s = s + d[c_k + i] * d[q + i]; E = E + d[q + i] * d[q + i]
+ *                 score = (E == 0.0) ? 0.0 : (s * |s|) / E
+ *             — a signed, energy-normalised correlation without a square root; it stays below 2^540, so nothing overflows
+ *             and no NaN can arise — and p_k is the candidate with the greatest score, the LOWEST q among equals.  A
+ *             template past the end of the range is all zeros: every score is 0 and p_k = lo.  Positions are int32
+ *   window    wbx_stretch_window (host-only, no libm): for i in [0, Hs): t = sinpi((double)i / (double)N) ("Converting a
+ *             clip's sample rate"'s sinpi); w_up[i] = t * t; w_dn[i] = 1.0 - w_up[i].  out receives w_up[0 .. Hs), then
+ *             w_dn[0 .. Hs): N doubles
+ *   output    frame j = k * Hs + i, i in [0, Hs), j < m, each channel: if p_k == c_k, y = (float)x[c][p_k + i] — the
+ *             source's sample unchanged, so a range stretched to its own length is a copy, bit for bit; otherwise
+ *             y = (float)((w_up[i] * x[c][p_k + i]) + (w_dn[i] * x[c][c_k + i])).  A NaN cannot arise
+ * dst_clip becomes a new F32 pool clip of m frames (plus the pool's 16 zero frames of padding) with the source's channels
+ * and rate, replaced or allocated as wbx_clip_derive does it, on the same stream and behind the same ordering; one edit,
+ * conversion, filter, convolution, limit, dynamics or stretch call runs at a time.  positions_out (may be NULL): the K
+ * positions (a caller who asks for them makes the call wait band by band).  info (may be NULL): steps = K; searched_steps,
+ * the steps that scored candidates; candidates, the total scored; max_shift, the maximum of |p_k - a_k|; launches, the
+ * kernel launches of the call.  stats_of_result (may be NULL): wbx_clip_measure of the whole result.
+ * The search is a chain (step k needs p_{k-1}): ONE workgroup walks the steps of a launch in order; a launch takes the steps
+ * whose scored terms (candidates x Hs, and wbx_stretch_step_terms more per step for what a searched step costs besides)
+ * stay within wbx_stretch_launch_terms if every one searched its whole span (wbx_stretch_launch_steps, at least 1), and the positions are staged in bands of wbx_stretch_band_steps steps.
+ * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: an unknown source, n_frames or
+ * out_frames of 0, a range past the clip, dst_clip equal to the source, n_frames or out_frames >= 2^31 - 16, a
+ * window_frames that is not a multiple of 8 or lies outside [32, 8192], tolerance_frames > 4096, a non-NULL positions_out
+ * with positions_cap < K; WBX_ERR_UNSUPPORTED: a clip that is not F32 or has more than 2 channels, out_frames > 8 n_frames
+ * or n_frames > 8 out_frames.  The sizes are judged before the clip is looked at.  WBX_ERR_OOM as for wbx_clip_derive.
+ * Host-only, no device (wbx_stretch.h, which a C++ compiler takes alone): wbx_stretch_steps (0 for a window the call refuses),
+ * wbx_stretch_anchor (any k, n and m; 0 for such a window or m == 0), wbx_stretch_window (WBX_ERR_INVALID: NULL out, such a
+ * window, cap_doubles < N; nothing is written then), wbx_stretch_band_steps, wbx_stretch_launch_terms, wbx_stretch_step_terms,
+ * wbx_stretch_launch_steps (0 for such a window or n_frames == 0).
+ * wbx_stretch_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed stretch call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_stretch.py; nothing else reads it.
+ * Not offered: pitch shifting (a resample whose result keeps the source's rate label), transient or formant preservation,
+ * unlinked stereo, a phase vocoder or anything with an FFT, stretching at render time, several clips in one call, more than
+ * 2 channels, in-place edits; the reference's `stretch` resize is unchanged. */
+typedef struct wbx_stretch_info {       /* 32 bytes */
+  uint64_t steps;
+  uint64_t searched_steps;
+  uint64_t candidates;
+  uint32_t max_shift;
+  uint32_t launches;
+} wbx_stretch_info;
+uint64_t wbx_stretch_steps(uint64_t out_frames, uint32_t window_frames);
+uint64_t wbx_stretch_anchor(uint64_t k, uint64_t n_frames, uint64_t out_frames, uint32_t window_frames);
+wbx_status wbx_stretch_window(uint32_t window_frames, double* out /* [window_frames] */, size_t cap_doubles);
+uint32_t wbx_stretch_band_steps(void);
+uint64_t wbx_stretch_launch_terms(void);
+uint64_t wbx_stretch_step_terms(void);
+uint32_t wbx_stretch_launch_steps(uint64_t n_frames, uint32_t window_frames, uint32_t tolerance_frames);
+wbx_status wbx_stretch_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_stretch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                            uint64_t out_frames, uint32_t window_frames, uint32_t tolerance_frames, int32_t* positions_out,
+                            size_t positions_cap, wbx_stretch_info* info, wbx_clip_stats* stats_of_result);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -1191,6 +1263,13 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
                                       double key_gain, double makeup, uint32_t lookahead_frames, uint32_t hold_frames,
                                       uint32_t release_frames, uint32_t* new_sample, wbx_dynamics_stats* dynamics_stats,
                                       wbx_clip_stats* stats_of_result);
+/* wbx_clip_stretch of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_stretch's (there is no dst_clip to collide with, and no positions). */
+wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
+                                     uint32_t window_frames, uint32_t tolerance_frames, wbx_stretch_info* info,
+                                     uint32_t* new_sample);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -383,6 +383,16 @@ struct Engine {
           "dynamics_sample");
     return id;
   }
+  // A NEW sample of out_frames frames holding the range time-stretched by WSOLA (wbx.h "Stretching a clip"): another
+  // length at the same pitch; window_frames a multiple of 8 in 32 .. 8192, tolerance_frames 0 .. 4096.  The source is
+  // pinned for the call.  Editing thread, like derive_sample.
+  uint32_t stretch_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames, uint32_t window_frames,
+                          uint32_t tolerance_frames, wbx_stretch_info* info = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_stretch_sample(h, sample, first_frame, n_frames, out_frames, window_frames, tolerance_frames, info, &id),
+          "stretch_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

@@ -86,6 +86,11 @@ class DynamicsStats(C.Structure):      # wbx_dynamics_stats, 24 bytes
     _fields_ = [("min_gain", C.c_double), ("min_gain_frame", C.c_uint64), ("reduced_frames", C.c_uint64)]
 
 
+class StretchInfo(C.Structure):        # wbx_stretch_info, 32 bytes
+    _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("max_shift", C.c_uint32),
+                ("launches", C.c_uint32)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -185,6 +190,16 @@ SYMBOLS = {
     "wbx_dynamics_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_dynamics": (C.c_int, [_vp, _u32, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
                                     _u32, _u32, C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
+    "wbx_stretch_steps": (C.c_uint64, [C.c_uint64, _u32]),
+    "wbx_stretch_anchor": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, _u32]),
+    "wbx_stretch_window": (C.c_int, [_u32, _vp, _sz]),
+    "wbx_stretch_band_steps": (_u32, []),
+    "wbx_stretch_launch_terms": (C.c_uint64, []),
+    "wbx_stretch_step_terms": (C.c_uint64, []),
+    "wbx_stretch_launch_steps": (_u32, [C.c_uint64, _u32, _u32]),
+    "wbx_stretch_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_stretch": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, _vp, _sz, C.POINTER(StretchInfo),
+                                   C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -284,6 +299,8 @@ SYMBOLS = {
                                           C.POINTER(LimitStats), C.POINTER(ClipStats)]),
     "wbx_engine_dynamics_sample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
+    "wbx_engine_stretch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.POINTER(StretchInfo),
+                                            C.POINTER(_u32)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

@@ -25,6 +25,7 @@
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
 #include "wbx_splice.h"
+#include "wbx_stretch.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
 
@@ -228,6 +229,30 @@ struct DynArgs {
 void launch_dynamics_curve(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_dynamics_apply(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_dynamics_reduce(const DynArgs& a, uint32_t n_tiles, hipStream_t s);   // part[0 .. n_tiles) into *total
+// stretching a clip (wbx_stretch.hip): per band of steps the positions — stretch_search_kernel, ONE workgroup walking the
+// steps of a launch in order — then the overlap-add over the band's frames
+struct StretchCarry {          // what one search launch hands the next, and the call's record so far (a device word block)
+  int32_t p;                   // the last position found: p_{k0 - 1} of the next launch
+  uint32_t max_shift;          // the largest |p_k - a_k|
+  uint64_t searched;           // steps that searched
+  uint64_t candidates;         // candidates scored
+};
+struct StretchArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  int32_t* pos;                // device: the stage — pos[0] = p_{band0 - 1}, pos[1 + k - band0] = p_k
+  StretchCarry* carry;         // device
+  const double* win;           // device: [N] — w_up[Hs], then w_dn[Hs]
+  uint64_t a0, r0;             // anchor and remainder of step k0: k0 Hs n = a0 m + r0
+  uint32_t qn, rn;             // an anchor's advance per step: Hs n = qn m + rn
+  uint32_t n, m;               // frames of the range and of the result (< 2^31 - 16)
+  uint32_t Hs, D;              // N / 2, the tolerance
+  uint32_t band0, band_steps;  // the band's first step and its steps
+  uint32_t k0, k1;             // the steps of this search launch: [k0, k1)
+  uint32_t channels;           // 1 or 2
+};
+void launch_stretch_search(const StretchArgs& a, hipStream_t s);
+void launch_stretch_ola(const StretchArgs& a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -364,6 +389,21 @@ struct DynStage {
   DevBuf<DynPartial> d_part;     // a band's tiles, and behind them the call's record
   PinnedBuf<DynPartial> h_total;
   Event mark[2];               // (timing events) around the launches of the last run: wbx_dynamics_ms
+  bool timed = false;          // the last run completed
+};
+
+// wbx_clip_stretch's own buffers: the positions of one band (2^16 + 1 words, whatever the clip's length) with their pinned
+// twin (filled only for a caller who asks for positions), the carry, the window table (kept while N stays the same) and
+// the timing events
+struct StretchStage {
+  DevBuf<int32_t> d_pos;
+  PinnedBuf<int32_t> h_pos;
+  DevBuf<StretchCarry> d_carry;
+  PinnedBuf<StretchCarry> h_carry;
+  PinnedBuf<double> h_win;
+  DevBuf<double> d_win;
+  uint32_t win_of = 0;         // the N the device table was built for (0: none)
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_stretch_ms
   bool timed = false;          // the last run completed
 };
 
@@ -535,6 +575,7 @@ struct wbx_ctx {
   ConvolveStage conv;                     // wbx_clip_convolve (under fx_mu, on fx.side.stream)
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
   DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
+  StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -726,6 +767,11 @@ wbx_status dynamics_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc* 
                           const char** why);
 wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint32_t rate, const DynCall& k, double lo, ClipSlot& slot,
                         wbx_dynamics_stats* out, wbx_clip_stats* stats, std::string* why);
+// stretching a clip (wbx_stretch.hip), cut the same way: the check makes no device call (wbx_stretch.h's
+// stretch_check_args first, then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** why);
+wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const StretchCall& k, ClipSlot& slot, int32_t* positions_out,
+                       wbx_stretch_info* info, wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

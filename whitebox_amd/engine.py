@@ -252,6 +252,29 @@ def _dynamics_stats(st) -> dict:
     return {"min_gain": st.min_gain, "min_gain_frame": st.min_gain_frame, "reduced_frames": st.reduced_frames}
 
 
+def stretch_steps(out_frames: int, window_frames: int) -> int:
+    """wbx_stretch_steps (host-only): K = ceil(out_frames / (window_frames / 2)); 0 for a window a stretch refuses"""
+    return int(_ffi.lib().wbx_stretch_steps(out_frames, window_frames))
+
+
+def stretch_anchor(k: int, n_frames: int, out_frames: int, window_frames: int) -> int:
+    """wbx_stretch_anchor (host-only): a_k = floor(k * (window_frames / 2) * n_frames / out_frames)"""
+    return int(_ffi.lib().wbx_stretch_anchor(k, n_frames, out_frames, window_frames))
+
+
+def stretch_window(window_frames: int) -> tuple:
+    """wbx_stretch_window (host-only): (w_up, w_dn), the two halves of the overlap-add window, window_frames / 2 doubles
+    each.  WbxError (-4) where the library refuses the window"""
+    out = np.zeros(max(int(window_frames), 1), dtype=np.float64)
+    _check(_ffi.lib().wbx_stretch_window(window_frames, out.ctypes.data, out.size), "wbx_stretch_window")
+    return out[:window_frames // 2].copy(), out[window_frames // 2:].copy()
+
+
+def _stretch_info(si) -> dict:
+    return {"steps": si.steps, "searched_steps": si.searched_steps, "candidates": si.candidates, "max_shift": si.max_shift,
+            "launches": si.launches}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -467,6 +490,27 @@ class MixContext:
         """wbx_dynamics_ms: device milliseconds of the last dynamics call's launches"""
         out = C.c_double()
         _check(self.L.wbx_dynamics_ms(self.h, C.byref(out)), "wbx_dynamics_ms", self.h)
+        return out.value
+
+    def clip_stretch(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int,
+                     window_frames: int = 2048, tolerance_frames: int = 512, positions: bool = False, stats_channels: int = 0):
+        """wbx_clip_stretch: `dst_clip` becomes a new F32 clip of out_frames frames = the range of `src_clip` time-stretched
+        by WSOLA: another length, the same pitch.  Returns the call's info {"steps", "searched_steps", "candidates",
+        "max_shift", "launches"}; with `positions` the pair (info, the int32 positions p_k); with `stats_channels` (the
+        clip's channel count) the result's wbx_clip_measure statistics as the last element"""
+        si, st = _ffi.StretchInfo(), _ffi.ClipStats()
+        K = stretch_steps(out_frames, window_frames) if positions else 0
+        pos = np.zeros(max(K, 1), dtype=np.int32)
+        _check(self.L.wbx_clip_stretch(self.h, src_clip, dst_clip, first_frame, n_frames, out_frames, window_frames, tolerance_frames,
+                                       pos.ctypes.data if positions else None, pos.size if positions else 0, C.byref(si),
+                                       C.byref(st) if stats_channels else None), "wbx_clip_stretch", self.h)
+        out = (_stretch_info(si),) + ((pos[:K],) if positions else ()) + ((_clip_stats(st, stats_channels),) if stats_channels else ())
+        return out[0] if len(out) == 1 else out
+
+    def stretch_ms(self) -> float:
+        """wbx_stretch_ms: device milliseconds of the last stretch call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_stretch_ms(self.h, C.byref(out)), "wbx_stretch_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1142,6 +1186,41 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _limit_stats(ls), _clip_stats(st, channels)) if stats else (new.value, _limit_stats(ls))
+
+    def stretch_sample(self, sample: int, out_frames: int, window_frames: int = 2048, tolerance_frames: int = 512,
+                       first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                       frames: Optional[int] = None):
+        """wbx_engine_stretch_sample: a new sample of out_frames frames = the range of `sample` time-stretched by WSOLA —
+        see MixContext.clip_stretch.  `frames` / `channels` as in export_sample.  The source is pinned against
+        delete_sample for the call's length; may be called while another thread runs process().  Returns (new id, info)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "stretch_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        new, si = C.c_uint32(), _ffi.StretchInfo()
+        _check(self.L.wbx_engine_stretch_sample(self.h, sample, first_frame, n_frames, out_frames, window_frames, tolerance_frames,
+                                                C.byref(si), C.byref(new)), "wbx_engine_stretch_sample", self.h, True)
+        self._sample_shape[new.value] = (out_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return new.value, _stretch_info(si)
+
+    def stretch_to_tempo(self, sample: int, bpm_from: float, bpm_to: float, window_ms: float = 40.0, tolerance_ms: float = 10.0,
+                         rate: Optional[int] = None, **call):
+        """A sample recorded at `bpm_from` fitted to `bpm_to`: stretch_sample to round(n_frames * bpm_from / bpm_to) frames
+        (at least 1), the window rounded to a multiple of 8 frames in 32 .. 8192 and the tolerance to a frame in 0 .. 4096 at
+        the sample's rate (`rate` where this object did not make it).  These conversions happen here: a convenience
+        outside the bit-exact contract.  `call`: stretch_sample's first_frame, n_frames, frames, channels"""
+        frames, _ = self._shape_of(sample, call.get("frames"), call.get("channels"))
+        n = call.get("n_frames")
+        if n is None:
+            assert frames is not None, "stretch_to_tempo: give n_frames, or frames (the sample's length)"
+            n = frames - call.get("first_frame", 0)
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        out_frames = max(1, int(round(n * float(bpm_from) / float(bpm_to))))
+        window = min(8192, max(32, 8 * int(round(float(window_ms) * rate / 8000.0))))
+        tolerance = min(4096, max(0, int(round(float(tolerance_ms) * rate / 1000.0))))
+        return self.stretch_sample(sample, out_frames, window, tolerance, **call)
 
     def dynamics_sample(self, sample: int, table, sense="compress", key_sample: Optional[int] = None, key_first: int = 0,
                         drive: float = 1.0, key_gain: float = 1.0, makeup: float = 1.0, shape: tuple = (72, 0, 4800),
