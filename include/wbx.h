@@ -785,7 +785,7 @@ wbx_status wbx_clip_dynamics(wbx_ctx* ctx, uint32_t src_clip, uint32_t key_clip 
  * wbx_stretch_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
  * completed stretch call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
  * tools/bench_stretch.py; nothing else reads it.
- * Not offered: pitch shifting (a resample whose result keeps the source's rate label), transient or formant preservation,
+ * Not offered (pitch shifting is "Pitch-shifting a clip" below): transient or formant preservation,
  * unlinked stereo, a phase vocoder or anything with an FFT, stretching at render time, several clips in one call, more than
  * 2 channels, in-place edits; the reference's `stretch` resize is unchanged. */
 typedef struct wbx_stretch_info {       /* 32 bytes */
@@ -806,6 +806,64 @@ wbx_status wbx_stretch_ms(wbx_ctx* ctx, double* out);
 wbx_status wbx_clip_stretch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                             uint64_t out_frames, uint32_t window_frames, uint32_t tolerance_frames, int32_t* positions_out,
                             size_t positions_cap, wbx_stretch_info* info, wbx_clip_stats* stats_of_result);
+
+/* Pitch-shifting a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels transposed
+ * into a NEW F32 clip of out_frames frames — another PITCH, by the ratio num / den (above 1: up), at a length of the
+ * caller's choice (out_frames = n_frames is the plain transposition) — without the samples leaving HBM.  The result keeps
+ * the source's RATE, so it plays at speed 1.0 through the unity row mode.  No reference counterpart.  The result is, by
+ * definition and BIT FOR BIT, the composition of two texts above; tests/pitch_model.py is their two models one after the
+ * other.
+ *   ratio     g = gcd(num, den), L = den / g, M = num / g: the plan of wbx_resample_plan(num, den, quality) (H, T, table)
+ *   length    m = out_frames; the intermediate has m' = ceil(m * M / L) frames (wbx_pitch_mid_frames)
+ *   stretch   y'[c][g], g in [0, m'), is what "Stretching a clip" STORES for wbx_clip_stretch(the range, out_frames = m',
+ *             window_frames, tolerance_frames): fp32 values, the same positions p_k, k < K' = ceil(m' / Hs), the copy
+ *             branch or the blend rounded once to fp32
+ *   output    frame j in [0, m), each channel: what "Converting a clip's sample rate" STORES for frame j of converting the
+ *             m'-frame intermediate with (L, M, quality): t = j * M, i = t div L, p = t mod L, T fp64 multiply-adds in
+ *             ascending tap order over y'[c][i - (H - 1) + k], y' zero outside [0, m'), one rounding to fp32, a NaN as
+ *             0x7FC00000.  Only the first m of that conversion's frames are kept; floor((m - 1) * M / L) < m' always
+ *             holds, so every kept frame lies inside the intermediate
+ * The intermediate is never stored: the searches fill one buffer of all K' positions, and ONE further launch feeds the filter
+ * straight from the overlap-add; nothing of m' frames is allocated in the pool.
+ * dst_clip becomes a new F32 pool clip of m frames (plus the pool's 16 zero frames of padding) with the source's channels
+ * and rate, replaced or allocated as wbx_clip_derive does it, on the same stream and behind the same ordering; one edit,
+ * conversion, filter, convolution, limit, dynamics, stretch or pitch call runs at a time.  positions_out (may be NULL): the
+ * K' positions, copied once after the last search launch.  info (may be NULL): steps = K', searched_steps, candidates and
+ * max_shift of the stretch to m' frames as in wbx_stretch_info; mid_frames = m'; launches, the kernel launches of the call
+ * (the searches and one more); L, M.  stats_of_result (may be NULL): wbx_clip_measure of the whole result.
+ * Refused before any device call, nothing allocated, dst_clip untouched; the sizes are judged before the clip is looked at,
+ * in this order.  WBX_ERR_INVALID: an unknown source, dst_clip equal to the source; n_frames or out_frames of 0, num or den
+ * of 0, num == den after reduction (a ratio of 1 is wbx_clip_stretch's job: the filter is no identity), an unknown quality,
+ * out_frames >= 2^31 - 16.  WBX_ERR_UNSUPPORTED: num > 4 den or den > 4 num (two octaves either way), what
+ * wbx_resample_plan refuses (L > 1280, T > 512).  Then everything wbx_clip_stretch refuses for (n_frames, m', window_frames,
+ * tolerance_frames), with its status — WBX_ERR_INVALID: n_frames or m' >= 2^31 - 16, the window, the tolerance, a non-NULL
+ * positions_out with positions_cap < K'; WBX_ERR_UNSUPPORTED: m' > 8 n_frames or n_frames > 8 m'.  WBX_ERR_UNSUPPORTED:
+ * K' > wbx_pitch_max_steps() (2^22: the positions take at most 16 MB + 4 B).  Then the clip — WBX_ERR_UNSUPPORTED: not F32
+ * or more than 2 channels; WBX_ERR_INVALID: a range past the clip.  WBX_ERR_OOM as for wbx_clip_derive.
+ * Host-only, no device (wbx_pitch.h, which a C++ compiler takes alone): wbx_pitch_mid_frames (any out_frames: the product
+ * in 128 bits, 2^64 - 1 where it does not fit; 0 where the call would refuse the RATIO), wbx_pitch_max_steps.
+ * wbx_pitch_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed pitch call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_pitch.py; nothing else reads it.
+ * Not offered: formant preservation, pitch correction or detection, a pitch curve over time, ratios beyond two octaves,
+ * pitch shifting at render time, unlinked stereo, more than 2 channels, in-place edits. */
+typedef struct wbx_pitch_info {         /* 48 bytes */
+  uint64_t steps;
+  uint64_t searched_steps;
+  uint64_t candidates;
+  uint64_t mid_frames;
+  uint32_t max_shift;
+  uint32_t launches;
+  uint32_t L;
+  uint32_t M;
+} wbx_pitch_info;
+uint64_t wbx_pitch_mid_frames(uint64_t out_frames, uint32_t num, uint32_t den);
+uint32_t wbx_pitch_max_steps(void);
+wbx_status wbx_pitch_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_pitch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                          uint64_t out_frames, uint32_t num, uint32_t den, int quality, uint32_t window_frames,
+                          uint32_t tolerance_frames, int32_t* positions_out, size_t positions_cap, wbx_pitch_info* info,
+                          wbx_clip_stats* stats_of_result);
 
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
@@ -1270,6 +1328,13 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
 wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
                                      uint32_t window_frames, uint32_t tolerance_frames, wbx_stretch_info* info,
                                      uint32_t* new_sample);
+/* wbx_clip_pitch of an engine sample, under wbx_engine_stretch_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_pitch's (there is no dst_clip to collide with, and no positions). */
+wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
+                                   uint32_t num, uint32_t den, int quality, uint32_t window_frames, uint32_t tolerance_frames,
+                                   wbx_pitch_info* info, uint32_t* new_sample);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -393,6 +393,17 @@ struct Engine {
           "stretch_sample");
     return id;
   }
+  // A NEW sample of out_frames frames holding the range transposed by num / den (wbx.h "Pitch-shifting a clip"): another
+  // pitch at the source's rate, out_frames = n_frames keeping the length; quality one of WBX_SRC_*, window and tolerance
+  // as for stretch_sample.  The source is pinned for the call.  Editing thread, like derive_sample.
+  uint32_t pitch_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames, uint32_t num, uint32_t den,
+                        int quality, uint32_t window_frames, uint32_t tolerance_frames, wbx_pitch_info* info = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_pitch_sample(h, sample, first_frame, n_frames, out_frames, num, den, quality, window_frames, tolerance_frames,
+                                  info, &id),
+          "pitch_sample");
+    return id;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

@@ -14,4 +14,5 @@ from .engine import convolve_frames, fir_design  # noqa: F401
 from .engine import limit_frames, limit_ramp  # noqa: F401
 from .engine import dynamics_check, dynamics_lookup, dynamics_table  # noqa: F401
 from .engine import stretch_anchor, stretch_steps, stretch_window  # noqa: F401
+from .engine import pitch_mid_frames, pitch_ratio  # noqa: F401
 from .engine import splice_part, splice_plan  # noqa: F401

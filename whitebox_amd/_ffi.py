@@ -91,6 +91,11 @@ class StretchInfo(C.Structure):        # wbx_stretch_info, 32 bytes
                 ("launches", C.c_uint32)]
 
 
+class PitchInfo(C.Structure):          # wbx_pitch_info, 48 bytes
+    _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("mid_frames", C.c_uint64),
+                ("max_shift", C.c_uint32), ("launches", C.c_uint32), ("L", C.c_uint32), ("M", C.c_uint32)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -200,6 +205,11 @@ SYMBOLS = {
     "wbx_stretch_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_stretch": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, _vp, _sz, C.POINTER(StretchInfo),
                                    C.POINTER(ClipStats)]),
+    "wbx_pitch_mid_frames": (C.c_uint64, [C.c_uint64, _u32, _u32]),
+    "wbx_pitch_max_steps": (_u32, []),
+    "wbx_pitch_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_pitch": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32, _vp, _sz,
+                                 C.POINTER(PitchInfo), C.POINTER(ClipStats)]),
     "wbx_mip_levels": (_u32, [C.c_uint64]),
     "wbx_mip_data_count": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_clip_build_mipmaps": (C.c_int, [_vp, _u32, C.c_int]),
@@ -301,6 +311,8 @@ SYMBOLS = {
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_engine_stretch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.POINTER(StretchInfo),
                                             C.POINTER(_u32)]),
+    "wbx_engine_pitch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32,
+                                          C.POINTER(PitchInfo), C.POINTER(_u32)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

@@ -26,6 +26,7 @@
 #include "wbx_resample.h"
 #include "wbx_splice.h"
 #include "wbx_stretch.h"
+#include "wbx_pitch.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
 
@@ -253,6 +254,21 @@ struct StretchArgs {
 };
 void launch_stretch_search(const StretchArgs& a, hipStream_t s);
 void launch_stretch_ola(const StretchArgs& a, hipStream_t s);
+// pitch-shifting a clip (wbx_pitch.hip): the stretch's searches fill ALL positions of the call, then one pitch_kernel launch —
+// resample_kernel's tile, staged from the overlap-add of the range instead of from a clip
+struct PitchArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const float* table;          // device: the conversion's coefficients in phase-visit order, [T][L] (resample_table_device)
+  const int32_t* pos;          // device: [K' + 1] — pos[0] = p_{-1} = -Hs, pos[1 + k] = p_k
+  const double* win;           // device: [N] — w_up[Hs], then w_dn[Hs]
+  uint32_t n, mid, n_out;      // frames of the range, of the intermediate (m') and of the result (m), all < 2^31 - 16
+  uint32_t Hs;                 // N / 2
+  uint32_t L, M, H, T;         // the plan (wbx_resample.h)
+  uint32_t channels;           // 1 or 2
+  uint32_t tile, span, n_tiles;   // filled by launch_pitch: outputs per tile, floats staged per channel and tile, tiles
+};
+void launch_pitch(PitchArgs a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -404,6 +420,16 @@ struct StretchStage {
   DevBuf<double> d_win;
   uint32_t win_of = 0;         // the N the device table was built for (0: none)
   Event mark[2];               // (timing events) around the launches of the last run: wbx_stretch_ms
+  bool timed = false;          // the last run completed
+};
+
+// wbx_clip_pitch's own buffers: ALL positions of a call behind p_{-1} (K' + 1 words, K' <= 2^22: at most 16 MB + 4 B) with
+// their pinned twin (filled only for a caller who asks for positions) and the timing events.  The window table and the
+// carry are StretchStage's — one edit runs at a time
+struct PitchStage {
+  DevBuf<int32_t> d_pos;
+  PinnedBuf<int32_t> h_pos;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_pitch_ms
   bool timed = false;          // the last run completed
 };
 
@@ -576,6 +602,7 @@ struct wbx_ctx {
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
   DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
   StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
+  PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
   Event ready_ev;                      // wbx_master_ready: results of an in-stream sum, for a foreign stream
@@ -772,6 +799,12 @@ wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint
 wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** why);
 wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const StretchCall& k, ClipSlot& slot, int32_t* positions_out,
                        wbx_stretch_info* info, wbx_clip_stats* stats, std::string* why);
+// pitch-shifting a clip (wbx_pitch.hip), beside its stretch twin: the check makes no device call (wbx_pitch.h's
+// pitch_check_args first, then the clip) and yields the conversion's plan and the stretch the call performs; the run works
+// under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status pitch_check(const ClipSrc& src, const PitchCall& k, ResamplePlan* plan, StretchCall* stretch, const char** why);
+wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchCall& k, const ResamplePlan& plan, const StretchCall& stretch,
+                     ClipSlot& slot, int32_t* positions_out, wbx_pitch_info* info, wbx_clip_stats* stats, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -906,6 +906,37 @@ extern "C" wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, 
   return st;
 }
 
+// wbx_clip_pitch of an engine sample (wbx.h "Pitch-shifting a clip"), beside wbx_engine_stretch_sample and under its rules:
+// the editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
+// out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.
+extern "C" wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                              uint64_t out_frames, uint32_t num, uint32_t den, int quality, uint32_t window_frames,
+                                              uint32_t tolerance_frames, wbx_pitch_info* info, uint32_t* new_sample) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "pitch_sample: new_sample is NULL");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const PitchCall k{first_frame, n_frames, out_frames, num, den, quality, window_frames, tolerance_frames, false, 0};
+  ResamplePlan plan;
+  StretchCall sk{};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "pitch_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = pitch_check(p.src, k, &plan, &sk, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "pitch_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  ClipSlot slot;
+  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = pitch_run(e->ctx, p.src, p.rate, k, plan, sk, slot, nullptr, info, nullptr, &why);
+  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, out_frames, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
 // wbx_clip_loudness of an engine sample (wbx.h "Measuring a clip's loudness"), beside wbx_engine_measure_sample and under its
 // rules: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,

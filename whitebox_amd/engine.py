@@ -13,6 +13,7 @@ All arithmetic happens in libwbx.so on the GPU; this file only marshals.
 from __future__ import annotations
 
 import ctypes as C
+from fractions import Fraction
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -275,6 +276,26 @@ def _stretch_info(si) -> dict:
             "launches": si.launches}
 
 
+def pitch_mid_frames(out_frames: int, num: int, den: int) -> int:
+    """wbx_pitch_mid_frames (host-only): m' = ceil(out_frames * M / L), the frames of the stretched intermediate of a pitch
+    shift by num / den (M / L in lowest terms); 0 where the call would refuse the ratio"""
+    return int(_ffi.lib().wbx_pitch_mid_frames(out_frames, num, den))
+
+
+def pitch_ratio(semitones: float, cents: float = 0.0) -> tuple:
+    """(num, den) for a transposition by `semitones` and `cents` in equal temperament: the fraction with a denominator of
+    at most 1280 nearest to 2 ** ((100 * semitones + cents) / 1200) — within 0.4 cent for every whole cent of two octaves
+    either way.  A convenience outside the bit-exact contract.  ValueError where the fraction is 1 (nothing to shift)"""
+    f = Fraction(2.0 ** ((100.0 * float(semitones) + float(cents)) / 1200.0)).limit_denominator(1280)
+    if f == 1:
+        raise ValueError("pitch_ratio: the ratio is 1 (use stretch_sample to change the length alone)")
+    return f.numerator, f.denominator
+
+
+def _pitch_info(pi) -> dict:
+    return {k: getattr(pi, k) for k, _ in _ffi.PitchInfo._fields_}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -511,6 +532,31 @@ class MixContext:
         """wbx_stretch_ms: device milliseconds of the last stretch call's launches"""
         out = C.c_double()
         _check(self.L.wbx_stretch_ms(self.h, C.byref(out)), "wbx_stretch_ms", self.h)
+        return out.value
+
+    def clip_pitch(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int, num: int, den: int,
+                   quality="good", window_frames: int = 2048, tolerance_frames: int = 512, positions: bool = False,
+                   stats_channels: int = 0):
+        """wbx_clip_pitch: `dst_clip` becomes a new F32 clip of out_frames frames = the range of `src_clip` transposed by
+        num / den (above 1: up) at the source's rate: a stretch to pitch_mid_frames(out_frames, num, den) frames fed
+        straight into a conversion by that ratio.  Returns the call's info {"steps", "searched_steps", "candidates",
+        "mid_frames", "max_shift", "launches", "L", "M"}; with `positions` the pair (info, the int32 positions p_k of the
+        stretch); with `stats_channels` (the clip's channel count) the result's wbx_clip_measure statistics as the last
+        element"""
+        pi, st = _ffi.PitchInfo(), _ffi.ClipStats()
+        K = stretch_steps(pitch_mid_frames(out_frames, num, den), window_frames) if positions else 0
+        pos = np.zeros(max(K, 1), dtype=np.int32)
+        _check(self.L.wbx_clip_pitch(self.h, src_clip, dst_clip, first_frame, n_frames, out_frames, num, den,
+                                     _ffi.SRC_QUALITY.get(quality, quality), window_frames, tolerance_frames,
+                                     pos.ctypes.data if positions else None, pos.size if positions else 0, C.byref(pi),
+                                     C.byref(st) if stats_channels else None), "wbx_clip_pitch", self.h)
+        out = (_pitch_info(pi),) + ((pos[:K],) if positions else ()) + ((_clip_stats(st, stats_channels),) if stats_channels else ())
+        return out[0] if len(out) == 1 else out
+
+    def pitch_ms(self) -> float:
+        """wbx_pitch_ms: device milliseconds of the last pitch call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_pitch_ms(self.h, C.byref(out)), "wbx_pitch_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1221,6 +1267,40 @@ class Engine:
         window = min(8192, max(32, 8 * int(round(float(window_ms) * rate / 8000.0))))
         tolerance = min(4096, max(0, int(round(float(tolerance_ms) * rate / 1000.0))))
         return self.stretch_sample(sample, out_frames, window, tolerance, **call)
+
+    def pitch_sample(self, sample: int, num: int, den: int, out_frames: Optional[int] = None, quality="good",
+                     window_frames: int = 2048, tolerance_frames: int = 512, first_frame: int = 0,
+                     n_frames: Optional[int] = None, channels: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_pitch_sample: a new sample of out_frames frames (default: the range's own length) = the range of
+        `sample` transposed by num / den at the sample's rate — see MixContext.clip_pitch.  `frames` / `channels` as in
+        export_sample.  The source is pinned against delete_sample for the call's length; may be called while another thread
+        runs process().  Returns (new id, info)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "pitch_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        out_frames = n_frames if out_frames is None else out_frames
+        new, pi = C.c_uint32(), _ffi.PitchInfo()
+        _check(self.L.wbx_engine_pitch_sample(self.h, sample, first_frame, n_frames, out_frames, num, den,
+                                              _ffi.SRC_QUALITY.get(quality, quality), window_frames, tolerance_frames,
+                                              C.byref(pi), C.byref(new)), "wbx_engine_pitch_sample", self.h, True)
+        self._sample_shape[new.value] = (out_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return new.value, _pitch_info(pi)
+
+    def transpose_sample(self, sample: int, semitones: float, cents: float = 0.0, window_ms: float = 40.0,
+                         tolerance_ms: float = 10.0, quality="good", rate: Optional[int] = None, **call):
+        """A sample transposed by `semitones` and `cents` at its own length: pitch_sample with pitch_ratio(semitones, cents),
+        the window rounded to a multiple of 8 frames in 32 .. 8192 and the tolerance to a frame in 0 .. 4096 at the sample's
+        rate (`rate` where this object did not make it), as stretch_to_tempo rounds them.  These conversions happen here: a
+        convenience outside the bit-exact contract.  `call`: pitch_sample's out_frames, first_frame, n_frames, frames,
+        channels"""
+        num, den = pitch_ratio(semitones, cents)
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        window = min(8192, max(32, 8 * int(round(float(window_ms) * rate / 8000.0))))
+        tolerance = min(4096, max(0, int(round(float(tolerance_ms) * rate / 1000.0))))
+        return self.pitch_sample(sample, num, den, quality=quality, window_frames=window, tolerance_frames=tolerance, **call)
 
     def dynamics_sample(self, sample: int, table, sense="compress", key_sample: Optional[int] = None, key_first: int = 0,
                         drive: float = 1.0, key_gain: float = 1.0, makeup: float = 1.0, shape: tuple = (72, 0, 4800),
