@@ -845,8 +845,8 @@ wbx_status wbx_clip_stretch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, 
  * wbx_pitch_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
  * completed pitch call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
  * tools/bench_pitch.py; nothing else reads it.
- * Not offered: formant preservation, pitch correction or detection, a pitch curve over time, ratios beyond two octaves,
- * pitch shifting at render time, unlinked stereo, more than 2 channels, in-place edits. */
+ * Not offered: formant preservation, pitch correction over time (detection is "Tracking a clip's pitch" below), ratios
+ * beyond two octaves, pitch shifting at render time, unlinked stereo, more than 2 channels, in-place edits. */
 typedef struct wbx_pitch_info {         /* 48 bytes */
   uint64_t steps;
   uint64_t searched_steps;
@@ -864,6 +864,79 @@ wbx_status wbx_clip_pitch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, ui
                           uint64_t out_frames, uint32_t num, uint32_t den, int quality, uint32_t window_frames,
                           uint32_t tolerance_frames, int32_t* positions_out, size_t positions_cap, wbx_pitch_info* info,
                           wbx_clip_stats* stats_of_result);
+
+/* Tracking a clip's pitch: the period of frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2
+ * channels, one record per hop, by YIN's cumulative-mean-normalized difference in the time domain — without the samples
+ * leaving HBM.  A MEASUREMENT, like wbx_clip_loudness: nothing is allocated in the pool and no clip is created.  No
+ * reference counterpart.  The arithmetic is part of the interface; tests/f0_model.py restates it in numpy, operation for
+ * operation, and the records equal it BIT FOR BIT.  Every operator below is ONE IEEE fp64 operation in the order written;
+ * nothing is fused (where both factors are fp32 values the product is exact, so an fma there is the same thing).
+ *   input     x and the detector d exactly as in "Stretching a clip": x[c][g] the range's fp32 samples as doubles, what is
+ *             not finite entering as 0.0, zero outside [0, n), nothing beside the range ever read; mono d = x[0], stereo
+ *             d = (float)(0.5 * (x[0] + x[1]))
+ *   shape     W = window_frames, a multiple of 8 in [64, 8192]; tau_max in [8, 4095]; tau_min in [2, tau_max - 1];
+ *             H = hop_frames in [1, 2^20]; threshold finite, in (0, 1].
+ *             hops = n >= W + tau_max ? (n - W - tau_max) / H + 1 : 0 (wbx_f0_hops): only complete frames count, and
+ *             hops == 0 is no error
+ *   per hop h with t = h * H, for every lag tau in [0, tau_max]:
+ *             r = 0; E = 0; for j = 0 .. W - 1 ascending: r = r + d[t+j] * d[t+j+tau]; E = E + d[t+j+tau] * d[t+j+tau]
+ *             E0 = E(0) (which equals r(0) bit for bit)
+ *             dd(tau) = (E0 + E(tau)) - (2.0 * r(tau)); a dd < 0.0 becomes 0.0; dd(0) is 0.0
+ *   mean      the cumulative mean in runs of 8 lags — the two-level order IS the definition, not an approximation of a flat
+ *             sum (it is what a lane that owns 8 lags computes, and it shortens the serial chain eightfold): tau = 8 g + i,
+ *             lags above tau_max counting 0.0; P(g,0) = dd(8g), P(g,i) = P(g,i-1) + dd(8g+i); T(g) = P(g,7); B(0) = 0.0,
+ *             B(g) = B(g-1) + T(g-1); S(tau) = B(g) + P(g,i).
+ *             c(0) = 1.0; for tau >= 1: c(tau) = (S(tau) == 0.0) ? 1.0 : (dd(tau) * (double)tau) / S(tau)
+ *   pick      lag = the lowest tau in [tau_min, tau_max - 1] with c(tau) < threshold and c(tau+1) >= c(tau); then
+ *             voiced = 1 (YIN's "first dip below the threshold, walked down to its minimum", as a predicate that needs no
+ *             walk).  If there is none: voiced = 0 and lag = the tau of that interval with the least c, the lowest among
+ *             equals
+ *   refine    a = c(lag-1), b = c(lag), g = c(lag+1); den = (a + g) - (2.0 * b);
+ *             off = (den > 0.0 && a >= b && g >= b) ? (0.5 * (a - g)) / den : 0.0; period = (double)lag + off
+ *   record    wbx_f0_frame: period, dip = b, energy = E0, lag, voiced
+ * No NaN can arise and nothing overflows.  Silence gives c == 1 everywhere, voiced = 0, lag = tau_min, off = 0.  The
+ * frequency is rate / period: the caller's division, not part of the contract.
+ * The call runs on the edits' stream behind wbx_clip_derive's ordering, one edit or measurement at a time, in launches of
+ * at most wbx_f0_launch_hops(window_frames, tau_max) hops — max(1, wbx_f0_launch_terms() / (W * (tau_max + 1))), whole
+ * eights where there are 8 or more — and returns when frames_out holds all hops records, copied once after the last launch.
+ * info (may be NULL): hops; voiced_hops; terms = hops * W * (tau_max + 1); launches.
+ * Refused before any device call, frames_out untouched; the sizes are judged before the clip is looked at, in this order.
+ * WBX_ERR_INVALID: an unknown clip; n_frames of 0 or >= 2^31 - 16; a window, lag bound, hop or threshold outside the ranges
+ * above (a NaN threshold included); a NULL frames_out with hops > 0; frames_cap < hops.  WBX_ERR_UNSUPPORTED:
+ * hops > wbx_f0_max_hops() (2^20: the records take at most 32 MB).  Then the clip — WBX_ERR_UNSUPPORTED: not F32 or more
+ * than 2 channels; WBX_ERR_INVALID: a range past the clip.
+ * Host-only, no device (wbx_f0.h, which a C++ compiler takes alone): wbx_f0_hops (0 for a shape the call refuses),
+ * wbx_f0_check (the argument check above without the clip: its status), wbx_f0_max_hops, wbx_f0_launch_terms,
+ * wbx_f0_launch_hops (at least 1; 0 for a shape the call refuses).
+ * wbx_f0_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed f0 call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_f0.py; nothing else reads it.
+ * Not offered: polyphonic material, pitch correction over time, a smoothed or Viterbi track, onset or tempo detection,
+ * tracking at render time, unlinked stereo, more than 2 channels. */
+typedef struct wbx_f0_frame {           /* 32 bytes */
+  double period;
+  double dip;
+  double energy;
+  uint32_t lag;
+  uint32_t voiced;
+} wbx_f0_frame;
+typedef struct wbx_f0_info {            /* 32 bytes */
+  uint64_t hops;
+  uint64_t voiced_hops;
+  uint64_t terms;
+  uint32_t launches;
+  uint32_t _pad;
+} wbx_f0_info;
+uint64_t wbx_f0_hops(uint64_t n_frames, uint32_t window_frames, uint32_t hop_frames, uint32_t tau_max);
+wbx_status wbx_f0_check(uint64_t n_frames, uint32_t window_frames, uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max,
+                        double threshold, int has_frames_out, size_t frames_cap);
+uint64_t wbx_f0_max_hops(void);
+uint64_t wbx_f0_launch_terms(void);
+uint32_t wbx_f0_launch_hops(uint32_t window_frames, uint32_t tau_max);
+wbx_status wbx_f0_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_f0(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
+                       uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold, wbx_f0_frame* frames_out,
+                       size_t frames_cap, wbx_f0_info* info);
 
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
@@ -1335,6 +1408,13 @@ wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, uint64_t fi
 wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
                                    uint32_t num, uint32_t den, int quality, uint32_t window_frames, uint32_t tolerance_frames,
                                    wbx_pitch_info* info, uint32_t* new_sample);
+/* wbx_clip_f0 of an engine sample, beside wbx_engine_loudness_sample and under its rules: the sample is pinned for the
+ * call, so wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream
+ * and unpin, never across the device wait, so the call may run beside the audio thread.  Arguments and refusals are
+ * wbx_clip_f0's. */
+wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
+                                uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold,
+                                wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

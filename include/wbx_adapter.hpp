@@ -404,6 +404,23 @@ struct Engine {
           "pitch_sample");
     return id;
   }
+  // The period track of a sample's range where it lives (wbx.h "Tracking a clip's pitch"): one wbx_f0_frame per hop — the
+  // period in frames (the frequency is the sample's rate over it), the dip, the energy, whether the hop is voiced.  Lags
+  // tau_min .. tau_max bound the periods looked for; threshold in (0, 1], 0.15 being YIN's.  The sample is pinned for the
+  // call.  Editing thread, like measure_sample.
+  std::vector<wbx_f0_frame> f0_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
+                                      uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold = 0.15,
+                                      wbx_f0_info* info = nullptr) {
+    const uint64_t hops = wbx_f0_hops(n_frames, window_frames, hop_frames, tau_max);
+    // the call's own argument check first, so that a refused call (2^31 hops of one frame, say) allocates no records
+    const wbx_status pre = wbx_f0_check(n_frames, window_frames, hop_frames, tau_min, tau_max, threshold, 1, (size_t)hops);
+    if (pre != WBX_OK) throw Error(pre, std::string("f0_sample: ") + wbx_status_string(pre));
+    std::vector<wbx_f0_frame> out((size_t)hops);
+    check(wbx_engine_f0_sample(h, sample, first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold,
+                               out.empty() ? nullptr : out.data(), out.size(), info),
+          "f0_sample");
+    return out;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

@@ -96,6 +96,15 @@ class PitchInfo(C.Structure):          # wbx_pitch_info, 48 bytes
                 ("max_shift", C.c_uint32), ("launches", C.c_uint32), ("L", C.c_uint32), ("M", C.c_uint32)]
 
 
+class F0Frame(C.Structure):            # wbx_f0_frame, 32 bytes
+    _fields_ = [("period", C.c_double), ("dip", C.c_double), ("energy", C.c_double), ("lag", C.c_uint32), ("voiced", C.c_uint32)]
+
+
+class F0Info(C.Structure):             # wbx_f0_info, 32 bytes
+    _fields_ = [("hops", C.c_uint64), ("voiced_hops", C.c_uint64), ("terms", C.c_uint64), ("launches", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -168,6 +177,13 @@ SYMBOLS = {
     "wbx_loudness_hops": (C.c_uint64, [_u32, C.c_uint64]),
     "wbx_loudness_coefficients": (C.c_int, [_u32, _vp]),
     "wbx_loudness_gate": (C.c_int, [_u32, C.c_uint64, _u32, _vp, C.POINTER(Loudness)]),
+    "wbx_f0_hops": (C.c_uint64, [C.c_uint64, _u32, _u32, _u32]),
+    "wbx_f0_check": (C.c_int, [C.c_uint64, _u32, _u32, _u32, _u32, _d, C.c_int, _sz]),
+    "wbx_f0_max_hops": (C.c_uint64, []),
+    "wbx_f0_launch_terms": (C.c_uint64, []),
+    "wbx_f0_launch_hops": (_u32, [_u32, _u32]),
+    "wbx_f0_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_f0": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
     "wbx_clip_loudness": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_filter_design": (C.c_int, [_u32, C.c_int, _d, _d, _d, _vp]),
     "wbx_filter_check": (C.c_int, [_vp, _u32]),
@@ -313,6 +329,7 @@ SYMBOLS = {
                                             C.POINTER(_u32)]),
     "wbx_engine_pitch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32,
                                           C.POINTER(PitchInfo), C.POINTER(_u32)]),
+    "wbx_engine_f0_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

@@ -27,6 +27,7 @@
 #include "wbx_splice.h"
 #include "wbx_stretch.h"
 #include "wbx_pitch.h"
+#include "wbx_f0.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
 
@@ -269,6 +270,19 @@ struct PitchArgs {
   uint32_t tile, span, n_tiles;   // filled by launch_pitch: outputs per tile, floats staged per channel and tile, tiles
 };
 void launch_pitch(PitchArgs a, hipStream_t s);
+// tracking a clip's pitch (wbx_f0.hip): one launch scores hops [hop0, hop1) of the call, F consecutive hops per workgroup
+struct F0Args {
+  const float* src[2];         // the clip's channel rows at the RANGE's first frame (mono: src[1] unused)
+  wbx_f0_frame* out;           // device: the call's records, [hops]
+  double threshold;
+  uint32_t n;                  // frames of the range (< 2^31 - 16)
+  uint32_t W, H;               // window and hop
+  uint32_t tau_min, tau_max;
+  uint32_t hop0, hop1;         // the hops of this launch
+  uint32_t G, F;               // waves per hop (1, 2, 4 or 8), hops per workgroup (wbx_f0.h f0_shape)
+  uint32_t channels;           // 1 or 2
+};
+void launch_f0(const F0Args& a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -430,6 +444,15 @@ struct PitchStage {
   DevBuf<int32_t> d_pos;
   PinnedBuf<int32_t> h_pos;
   Event mark[2];               // (timing events) around the launches of the last run: wbx_pitch_ms
+  bool timed = false;          // the last run completed
+};
+
+// wbx_clip_f0's records on the device and in pinned memory (at most 2^20 x 32 bytes) — grown on demand, freed with the
+// context — and the timing events
+struct F0Stage {
+  DevBuf<wbx_f0_frame> d_rec;
+  PinnedBuf<wbx_f0_frame> h_rec;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_f0_ms
   bool timed = false;          // the last run completed
 };
 
@@ -602,6 +625,7 @@ struct wbx_ctx {
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
   DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
   StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
+  F0Stage f0;                             // wbx_clip_f0 (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -805,6 +829,11 @@ wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const Stre
 wbx_status pitch_check(const ClipSrc& src, const PitchCall& k, ResamplePlan* plan, StretchCall* stretch, const char** why);
 wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchCall& k, const ResamplePlan& plan, const StretchCall& stretch,
                      ClipSlot& slot, int32_t* positions_out, wbx_pitch_info* info, wbx_clip_stats* stats, std::string* why);
+// tracking a clip's pitch (wbx_f0.hip), cut as the loudness measurement is: the check makes no device call (wbx_f0.h's
+// f0_check first, then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order and
+// waits for the device
+wbx_status f0_check_call(const ClipSrc& src, const F0Call& k, const char** why);
+wbx_status f0_run(wbx_ctx* c, const ClipSrc& src, const F0Call& k, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -606,6 +606,11 @@ struct SamplePin {
     if (st == WBX_OK) st = loudness_run(e->ctx, src, plan, first_frame, n_frames, out, hop_energy, why);
     return st;
   }
+  wbx_status f0(const F0Call& k, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = f0_run(e->ctx, src, k, frames_out, info, why);
+    return st;
+  }
   wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
     wbx_status st = order(clipfx_prepare, clipfx_order, why);
     ClipSlot slot;
@@ -955,6 +960,29 @@ extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample,
   }
   std::string why;
   const wbx_status st = p.loudness(plan, first_frame, n_frames, out, hop_energy, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// wbx_clip_f0 of an engine sample (wbx.h "Tracking a clip's pitch"), beside wbx_engine_loudness_sample and under its rules:
+// the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
+extern "C" wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                           uint32_t window_frames, uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max,
+                                           double threshold, wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const F0Call k{first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold, frames_out != nullptr, frames_cap};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "f0_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = f0_check_call(p.src, k, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.f0(k, frames_out, info, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }

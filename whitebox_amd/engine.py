@@ -296,6 +296,27 @@ def _pitch_info(pi) -> dict:
     return {k: getattr(pi, k) for k, _ in _ffi.PitchInfo._fields_}
 
 
+# wbx_f0_frame as a numpy record: what clip_f0 and f0_sample return, one per hop
+F0_DTYPE = np.dtype([("period", "<f8"), ("dip", "<f8"), ("energy", "<f8"), ("lag", "<u4"), ("voiced", "<u4")])
+
+
+def f0_hops(n_frames: int, window_frames: int, hop_frames: int, tau_max: int) -> int:
+    """wbx_f0_hops (host-only): the complete analysis frames of n_frames — (n - W - tau_max) // H + 1, or 0 where the range
+    is shorter than W + tau_max or the call would refuse the shape"""
+    return int(_ffi.lib().wbx_f0_hops(n_frames, window_frames, hop_frames, tau_max))
+
+
+def _run_f0(fn, what, h, engine, ident, first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold):
+    hops = f0_hops(n_frames, window_frames, hop_frames, tau_max)
+    # the call's own argument check first, so that a refused call (2^31 hops of one frame, say) allocates no records
+    _check(_ffi.lib().wbx_f0_check(n_frames, window_frames, hop_frames, tau_min, tau_max, threshold, 1, hops), "wbx_f0_check")
+    rec = np.zeros(hops, dtype=F0_DTYPE)
+    fi = _ffi.F0Info()
+    _check(fn(h, ident, first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold,
+              rec.ctypes.data if rec.size else None, rec.size, C.byref(fi)), what, h, engine)
+    return rec, {k: getattr(fi, k) for k, _ in _ffi.F0Info._fields_ if k != "_pad"}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -557,6 +578,21 @@ class MixContext:
         """wbx_pitch_ms: device milliseconds of the last pitch call's launches"""
         out = C.c_double()
         _check(self.L.wbx_pitch_ms(self.h, C.byref(out)), "wbx_pitch_ms", self.h)
+        return out.value
+
+    def clip_f0(self, clip: int, first_frame: int, n_frames: int, window_frames: int = 1024, hop_frames: int = 256,
+                tau_min: int = 24, tau_max: int = 1024, threshold: float = 0.15):
+        """wbx_clip_f0: the period track of frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2
+        channels, by YIN on the device: (records, info) — a structured array (F0_DTYPE: "period" in frames, "dip",
+        "energy", "lag", "voiced"), one record per complete hop, and {"hops", "voiced_hops", "terms", "launches"}.  The
+        frequency of a hop is the clip's rate over its period"""
+        return _run_f0(self.L.wbx_clip_f0, "wbx_clip_f0", self.h, False, clip, first_frame, n_frames, window_frames, hop_frames,
+                       tau_min, tau_max, threshold)
+
+    def f0_ms(self) -> float:
+        """wbx_f0_ms: device milliseconds of the last f0 call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_f0_ms(self.h, C.byref(out)), "wbx_f0_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1301,6 +1337,57 @@ class Engine:
         window = min(8192, max(32, 8 * int(round(float(window_ms) * rate / 8000.0))))
         tolerance = min(4096, max(0, int(round(float(tolerance_ms) * rate / 1000.0))))
         return self.pitch_sample(sample, num, den, quality=quality, window_frames=window, tolerance_frames=tolerance, **call)
+
+    def f0_sample(self, sample: int, window_frames: int = 1024, hop_frames: int = 256, tau_min: int = 24, tau_max: int = 1024,
+                  threshold: float = 0.15, first_frame: int = 0, n_frames: Optional[int] = None,
+                  channels: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_f0_sample — see MixContext.clip_f0; `frames` / `channels` as in export_sample.  Returns (records, info).
+        May be called while another thread runs process(); delete_sample of the sample is refused meanwhile."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "f0_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        return _run_f0(self.L.wbx_engine_f0_sample, "wbx_engine_f0_sample", self.h, True, sample, first_frame, n_frames,
+                       window_frames, hop_frames, tau_min, tau_max, threshold)
+
+    def detect_note_sample(self, sample: int, rate: Optional[int] = None, floor_db: float = 40.0, a4_hz: float = 440.0, **call):
+        """The note of a sample: f0_sample (`call`: its arguments), then the MEDIAN period of the voiced hops whose energy
+        lies within `floor_db` of the loudest hop's.  Returns {"hz", "midi" (the nearest note, 69 = A4 at `a4_hz`), "cents"
+        (off that note, -50 .. 50), "voiced" (the share of hops that are voiced), "period", "hops"}; hz, midi, cents and
+        period are None where no such hop is voiced.  `rate` where this object did not make the sample.  The median, the
+        logarithm and the rounding happen here: a convenience outside the bit-exact contract."""
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        rec, info = self.f0_sample(sample, **call)
+        out = {"hz": None, "midi": None, "cents": None, "period": None, "hops": int(info["hops"]),
+               "voiced": float(info["voiced_hops"]) / info["hops"] if info["hops"] else 0.0}
+        if rec.size == 0:
+            return out
+        keep = (rec["voiced"] != 0) & (rec["energy"] >= rec["energy"].max() * 10.0 ** (-float(floor_db) / 10.0))
+        if not keep.any():
+            return out
+        period = float(np.median(rec["period"][keep]))
+        hz = float(rate) / period
+        note = 69.0 + 12.0 * float(np.log2(hz / float(a4_hz)))
+        midi = int(np.floor(note + 0.5))
+        out.update(hz=hz, midi=midi, cents=100.0 * (note - midi), period=period)
+        return out
+
+    def tune_sample(self, sample: int, to_midi: Optional[int] = None, a4_hz: float = 440.0, detect: Optional[dict] = None,
+                    **transpose):
+        """A sample tuned to a note: detect_note_sample (`detect`: its arguments), then transpose_sample by the cents that
+        bring the detected frequency to MIDI note `to_midi` (default: the nearest note) through pitch_ratio (`transpose`:
+        transpose_sample's arguments).  Returns (new id, info, the detected note).  ValueError where no hop is voiced, or
+        where the correction rounds to a ratio of 1 (the sample is in tune within pitch_ratio's grid)."""
+        detect = dict(detect or {})
+        if "rate" in transpose:
+            detect.setdefault("rate", transpose["rate"])
+        note = self.detect_note_sample(sample, a4_hz=a4_hz, **detect)
+        if note["hz"] is None:
+            raise ValueError("tune_sample: no voiced hop, so no pitch to tune")
+        target = note["midi"] if to_midi is None else int(to_midi)
+        cents = 100.0 * (target - note["midi"]) - note["cents"]
+        new, info = self.transpose_sample(sample, 0.0, cents, **transpose)   # (pitch_ratio raises for a ratio of 1)
+        return new, info, note
 
     def dynamics_sample(self, sample: int, table, sense="compress", key_sample: Optional[int] = None, key_first: int = 0,
                         drive: float = 1.0, key_gain: float = 1.0, makeup: float = 1.0, shape: tuple = (72, 0, 4800),
