@@ -909,10 +909,11 @@ wbx_status wbx_clip_pitch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, ui
  * wbx_f0_check (the argument check above without the clip: its status), wbx_f0_max_hops, wbx_f0_launch_terms,
  * wbx_f0_launch_hops (at least 1; 0 for a shape the call refuses).
  * wbx_f0_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
- * completed f0 call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
- * tools/bench_f0.py; nothing else reads it.
- * Not offered: polyphonic material, pitch correction over time, a smoothed or Viterbi track, onset or tempo detection,
- * tracking at render time, unlinked stereo, more than 2 channels. */
+ * completed f0 call (layer 1's or layer 2's).  A completed wbx_clip_tempo counts as one: after it the figure is that of the
+ * tempo call's f0 launches over the novelty, without its energy and novelty passes.  WBX_ERR_INVALID for NULL arguments
+ * or when none has completed.  For tools/bench_f0.py and tools/bench_onsets.py; nothing else reads it.
+ * Not offered: polyphonic material, pitch correction over time, a smoothed or Viterbi track, tracking at render time,
+ * unlinked stereo, more than 2 channels (onsets and tempo are "Finding a clip's onsets and tempo" below). */
 typedef struct wbx_f0_frame {           /* 32 bytes */
   double period;
   double dip;
@@ -937,6 +938,85 @@ wbx_status wbx_f0_ms(wbx_ctx* ctx, double* out);
 wbx_status wbx_clip_f0(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
                        uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold, wbx_f0_frame* frames_out,
                        size_t frames_cap, wbx_f0_info* info);
+
+/* Finding a clip's onsets and tempo: an onset-strength curve (the "novelty") of frames [first_frame, first_frame + n_frames)
+ * of a resident F32 clip of 1 or 2 channels, one value per hop, from the rise of two hop energies — the signal's and its
+ * first difference's, which weighs the high end — the onsets picked from it, and its period tracked by "Tracking a clip's
+ * pitch" with hops in the place of frames: the tempo.  MEASUREMENTS, like wbx_clip_loudness and wbx_clip_f0: nothing is
+ * allocated in the pool and no clip is created.  No reference counterpart.  The arithmetic is part of the interface;
+ * tests/onset_model.py restates it in numpy, operation for operation, and the records equal it BIT FOR BIT.  Every operator
+ * below is ONE IEEE fp64 operation in the order written; nothing is fused unless stated.
+ *   input     x and the detector d exactly as in "Stretching a clip": what is not finite enters as 0.0; mono d = x[0],
+ *             stereo d = (float)(0.5 * (x[0] + x[1])).  d[-1] = 0.0: the frame before the range is never read, and neither is
+ *             anything after it
+ *   shape     H = hop_frames, a multiple of 64 in [64, 16384]; q = H / 64.  floor_power finite, in [1e-30, 1];
+ *             floor = (double)H * floor_power.  hops = n / H (wbx_onset_hops): only complete hops count, and hops == 0 is no
+ *             error.  n in [1, 2^31 - 16); hops at most wbx_onset_max_hops() = 2^20
+ *   energies  per hop h and run i = 0 .. 63, over frames t = h H + i q + j, j ascending, from a = b = 0.0:
+ *             a = a + d[t] * d[t] (the product is exact, so an fma is the same thing);
+ *             e = d[t] - d[t-1]; b = b + (e * e) (the product rounded before the addition: NOT an fma).
+ *             The 64 run sums are added as a balanced tree of adjacent pairs: s0[i] = a_i, s(k+1)[i] = sk[2i] + sk[2i+1],
+ *             A(h) = s6[0]; B(h) the same way from b_i (an xor butterfly over a wave computes exactly this)
+ *   novelty   for X in {A, B}: ref = max(X(h-1), X(h-2), X(h-3)), hops before 0 counting 0.0; up = X(h) - ref, an up that
+ *             is not > 0.0 becoming 0.0; rise = up / ((X(h) + ref) + floor).  o(h) = (float)(rise_A + rise_B), in [0, 2]: below 2 before
+ *             the roundings, 2.0 where the floor vanishes beside both energies.
+ *             ((a - b) / (a + b) is tanh of half the log ratio: a rise measure that does not depend on the level and needs
+ *             no log.)  No NaN can arise; silence gives o == 0
+ *   pick      on the host, from the records (wbx_onset_pick is this alone).  onset(h) = 1 iff o(h) >= threshold; no
+ *             o(g) >= o(h) for g in [h-w, h); no o(g) > o(h) for g in (h, h+w] (the earliest of equals wins); and
+ *             (double)o(h) >= m / cnt + delta, m the ascending fp64 sum of o over [max(0, h-a), min(hops-1, h+a)] and cnt
+ *             its length.  threshold in (0, 2], delta in [0, 2], w in [0, 64], a in [0, 256]
+ *   record    wbx_onset_frame: energy = A, edge_energy = B, novelty = o as a double, onset.  An onset's frame is h H
+ *   tempo     wbx_clip_tempo computes o on the device and runs wbx_clip_f0's arithmetic over it as a mono F32 range of
+ *             `hops` frames: window window_hops, hop step_hops, lags lag_min .. lag_max, threshold; wbx_f0_frame records
+ *             whose periods are in hops, bit-equal to that arithmetic on o.  The novelty never visits the host.
+ *             bpm = 60 rate / (H period): the caller's division.  The lag range decides the octave, as it does for any
+ *             autocorrelation tempo estimate
+ * Both calls run on the edits' stream behind wbx_clip_derive's ordering, one edit or measurement at a time, and return
+ * when the records are in frames_out.  wbx_onset_info: hops; onsets (the records with onset = 1); launches (2 where there
+ * are hops).  wbx_clip_tempo's info is wbx_clip_f0's.
+ * Refused before any device call, outputs untouched; the sizes are judged before the clip is looked at, in this order.
+ * WBX_ERR_INVALID: an unknown clip; n_frames of 0 or >= 2^31 - 16; hop_frames, floor_power, threshold, delta, w or a outside
+ * the ranges above (NaNs included); a NULL frames_out with hops > 0; frames_cap < hops.  WBX_ERR_UNSUPPORTED:
+ * hops > wbx_onset_max_hops().  Then the clip — WBX_ERR_UNSUPPORTED: not F32 or more than 2 channels; WBX_ERR_INVALID: a
+ * range past the clip.  wbx_clip_tempo judges n_frames, hop_frames, floor_power and the number of hops first, then
+ * wbx_f0_check's rules with n = hops (a range without a complete hop: the shape alone), then the clip; zero hops give
+ * WBX_OK and no records.
+ * Host-only, no device (wbx_onset.h, which a C++ compiler takes alone): wbx_onset_hops (0 for a hop length the call
+ * refuses), wbx_onset_check (the argument check above without the clip: its status), wbx_onset_max_hops, wbx_onset_pick
+ * (sets frames[h].onset from frames[h].novelty and counts into *onsets, which may be NULL; WBX_ERR_INVALID for pick
+ * arguments out of range or NULL frames with hops > 0).
+ * wbx_onset_ms: device milliseconds between two events on the edits' stream around the energy pass of the context's last
+ * completed onsets or tempo call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.
+ * For tools/bench_onsets.py; nothing else reads it.
+ * Not offered: beat phase or downbeats, a tempo prior against octave errors, sample-accurate onset refinement, detection
+ * at render time, unlinked stereo, more than 2 channels. */
+typedef struct wbx_onset_frame {        /* 32 bytes */
+  double energy;
+  double edge_energy;
+  double novelty;
+  uint32_t onset;
+  uint32_t _pad;
+} wbx_onset_frame;
+typedef struct wbx_onset_info {         /* 24 bytes */
+  uint64_t hops;
+  uint64_t onsets;
+  uint32_t launches;
+  uint32_t _pad;
+} wbx_onset_info;
+uint64_t wbx_onset_hops(uint64_t n_frames, uint32_t hop_frames);
+wbx_status wbx_onset_check(uint64_t n_frames, uint32_t hop_frames, double floor_power, double threshold, double delta, uint32_t w,
+                           uint32_t a, int has_frames_out, size_t frames_cap);
+uint64_t wbx_onset_max_hops(void);
+wbx_status wbx_onset_pick(wbx_onset_frame* frames, uint64_t hops, double threshold, double delta, uint32_t w, uint32_t a,
+                          uint64_t* onsets);
+wbx_status wbx_onset_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_onsets(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
+                           double floor_power, double threshold, double delta, uint32_t w, uint32_t a,
+                           wbx_onset_frame* frames_out, size_t frames_cap, wbx_onset_info* info);
+wbx_status wbx_clip_tempo(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
+                          double floor_power, uint32_t window_hops, uint32_t step_hops, uint32_t lag_min, uint32_t lag_max,
+                          double threshold, wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info);
 
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
@@ -1415,6 +1495,15 @@ wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t firs
 wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
                                 uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold,
                                 wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info);
+/* wbx_clip_onsets and wbx_clip_tempo of an engine sample, under wbx_engine_f0_sample's rules: pinned for the call, the
+ * editor lock held only to validate and pin.  Arguments and refusals are the clip calls'. */
+wbx_status wbx_engine_onsets_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
+                                    double floor_power, double threshold, double delta, uint32_t w, uint32_t a,
+                                    wbx_onset_frame* frames_out, size_t frames_cap, wbx_onset_info* info);
+wbx_status wbx_engine_tempo_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
+                                   double floor_power, uint32_t window_hops, uint32_t step_hops, uint32_t lag_min,
+                                   uint32_t lag_max, double threshold, wbx_f0_frame* frames_out, size_t frames_cap,
+                                   wbx_f0_info* info);
 /* Upper bound in bytes on what the clip pool reserves from the driver (slabs and clips with an allocation of their own);
  * 0 = none (the default).  A clip that would take the pool past it fails with WBX_ERR_OOM. */
 wbx_status wbx_clip_pool_limit(wbx_ctx* ctx, uint64_t max_bytes_reserved);

@@ -421,6 +421,36 @@ struct Engine {
           "f0_sample");
     return out;
   }
+  // The onsets of a sample's range where it lives (wbx.h "Finding a clip's onsets and tempo"): one wbx_onset_frame per hop
+  // of hop_frames frames (a multiple of 64) — the two energies, the onset strength and whether the hop is an onset, whose
+  // frame is then first_frame + h * hop_frames.  The sample is pinned for the call.  Editing thread, like measure_sample.
+  std::vector<wbx_onset_frame> onsets_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames = 256,
+                                             double floor_power = 1e-9, double threshold = 0.3, double delta = 0.1, uint32_t w = 3,
+                                             uint32_t a = 8, wbx_onset_info* info = nullptr) {
+    const uint64_t hops = wbx_onset_hops(n_frames, hop_frames);
+    // the call's own argument check first, so that a refused call allocates no records
+    const wbx_status pre = wbx_onset_check(n_frames, hop_frames, floor_power, threshold, delta, w, a, 1, (size_t)hops);
+    if (pre != WBX_OK) throw Error(pre, std::string("onsets_sample: ") + wbx_status_string(pre));
+    std::vector<wbx_onset_frame> out((size_t)hops);
+    check(wbx_engine_onsets_sample(h, sample, first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a,
+                                   out.empty() ? nullptr : out.data(), out.size(), info),
+          "onsets_sample");
+    return out;
+  }
+  // ... and the period track of its onset strength, which stays on the device: one wbx_f0_frame per window of window_hops
+  // hops every step_hops, with the period in hops — bpm = 60 * rate / (hop_frames * period).  Lags lag_min .. lag_max bound
+  // the tempi looked for and decide the octave.
+  std::vector<wbx_f0_frame> tempo_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
+                                         uint32_t window_hops, uint32_t step_hops, uint32_t lag_min, uint32_t lag_max,
+                                         double threshold = 0.5, double floor_power = 1e-9, wbx_f0_info* info = nullptr) {
+    const uint64_t hops = wbx_onset_hops(n_frames, hop_frames);
+    const uint64_t windows = hops <= wbx_onset_max_hops() ? wbx_f0_hops(hops, window_hops, step_hops, lag_max) : 0;
+    std::vector<wbx_f0_frame> out((size_t)windows);
+    check(wbx_engine_tempo_sample(h, sample, first_frame, n_frames, hop_frames, floor_power, window_hops, step_hops, lag_min,
+                                  lag_max, threshold, out.empty() ? nullptr : out.data(), out.size(), info),
+          "tempo_sample");
+    return out;
+  }
   // BS.1770 loudness of a sample's range where it lives (wbx.h "Measuring a clip's loudness"): integrated, momentary and
   // short-term maxima, loudness range, with WBX_LOUD_TRUE_PEAK the oversampled peak — and a NEW sample brought to a target
   // (-14, -16, -23 LUFS) under a true-peak ceiling (linear, 0 = none; *gain_used: the factor).  Editing thread, like

@@ -105,6 +105,15 @@ class F0Info(C.Structure):             # wbx_f0_info, 32 bytes
                 ("_pad", C.c_uint32)]
 
 
+class OnsetFrame(C.Structure):         # wbx_onset_frame, 32 bytes
+    _fields_ = [("energy", C.c_double), ("edge_energy", C.c_double), ("novelty", C.c_double), ("onset", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class OnsetInfo(C.Structure):          # wbx_onset_info, 24 bytes
+    _fields_ = [("hops", C.c_uint64), ("onsets", C.c_uint64), ("launches", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -184,6 +193,13 @@ SYMBOLS = {
     "wbx_f0_launch_hops": (_u32, [_u32, _u32]),
     "wbx_f0_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_f0": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
+    "wbx_onset_hops": (C.c_uint64, [C.c_uint64, _u32]),
+    "wbx_onset_check": (C.c_int, [C.c_uint64, _u32, _d, _d, _d, _u32, _u32, C.c_int, _sz]),
+    "wbx_onset_max_hops": (C.c_uint64, []),
+    "wbx_onset_pick": (C.c_int, [_vp, C.c_uint64, _d, _d, _u32, _u32, C.POINTER(C.c_uint64)]),
+    "wbx_onset_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_onsets": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _d, _d, _u32, _u32, _vp, _sz, C.POINTER(OnsetInfo)]),
+    "wbx_clip_tempo": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
     "wbx_clip_loudness": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_filter_design": (C.c_int, [_u32, C.c_int, _d, _d, _d, _vp]),
     "wbx_filter_check": (C.c_int, [_vp, _u32]),
@@ -330,6 +346,10 @@ SYMBOLS = {
     "wbx_engine_pitch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32,
                                           C.POINTER(PitchInfo), C.POINTER(_u32)]),
     "wbx_engine_f0_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
+    "wbx_engine_onsets_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _d, _d, _u32, _u32, _vp, _sz,
+                                           C.POINTER(OnsetInfo)]),
+    "wbx_engine_tempo_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _u32, _u32, _u32, _u32, _d, _vp, _sz,
+                                          C.POINTER(F0Info)]),
     "wbx_engine_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.POINTER(Loudness), _vp, _sz]),
     "wbx_engine_normalize_loudness_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _d, _f, C.POINTER(_u32),
                                                        C.POINTER(_f)]),

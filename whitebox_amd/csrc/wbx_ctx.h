@@ -28,6 +28,7 @@
 #include "wbx_stretch.h"
 #include "wbx_pitch.h"
 #include "wbx_f0.h"
+#include "wbx_onset.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
 
@@ -283,6 +284,25 @@ struct F0Args {
   uint32_t channels;           // 1 or 2
 };
 void launch_f0(const F0Args& a, hipStream_t s);
+// finding a clip's onsets (wbx_onset.hip): the energy pass — a wave per hop, striding over the hops by the grid — and the
+// novelty pass, a lane per hop
+struct alignas(16) OnsetEnergy {   // what the energy pass leaves per hop: one 16-byte store
+  double a, b;                 // A(h), B(h)
+};
+struct OnsetArgs {
+  const float* src[2];         // the clip's channel rows at the RANGE's first frame (mono: src[1] unused)
+  OnsetEnergy* energy;         // device: [hops]
+  float* novelty;              // device: o(h) as floats, [hops] — the "clip" a tempo call tracks
+  wbx_onset_frame* rec;        // device: the call's records, [hops] (onset = 0: the pick runs on the host)
+  double floor;                // (double)H * floor_power
+  uint32_t hops;               // complete hops of the range (<= 2^20)
+  uint32_t H, q;               // hop length, a lane's run H / 64
+  uint32_t row;                // words between the lanes' rows of a wave's staged chunk (wbx_onset.h; 0: no LDS)
+  uint32_t channels;           // 1 or 2
+  uint32_t aligned;            // both rows lie on 4 q bytes: a lane's run is one load (q = 1, 2 or 4)
+};
+void launch_onset_energy(const OnsetArgs& a, hipStream_t s);
+void launch_onset_novelty(const OnsetArgs& a, hipStream_t s);
 // splicing clips (wbx_splice.hip): parts of planar F32 clips placed, faded and added into a new planar F32 clip
 struct SplicePartDev {         // 48 bytes, read with wave-uniform loads
   const float* src[2];         // the rows output channel 0 / 1 reads (MONO_MIX: L and R), at the PART's first source frame
@@ -456,6 +476,17 @@ struct F0Stage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_onsets' and wbx_clip_tempo's energies (16 bytes per hop), novelty (4) and records (32) on the device, the records'
+// pinned twin (at most 2^20 hops each) — grown on demand, freed with the context — and the timing events
+struct OnsetStage {
+  DevBuf<OnsetEnergy> d_energy;
+  DevBuf<float> d_nov;
+  DevBuf<wbx_onset_frame> d_rec;
+  PinnedBuf<wbx_onset_frame> h_rec;
+  Event mark[2];               // (timing events) around the energy pass of the last run: wbx_onset_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_limit's ramp table (at most (4096 + 65536 + 2^20 + 40) x 8 bytes, kept while A, H and R stay the same), the fp64
 // curve of one band ((2^20 + 4096) x 8 bytes = 8.4 MB, whatever the clip's length) and the statistics — grown on demand,
 // freed with the context
@@ -625,7 +656,8 @@ struct wbx_ctx {
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
   DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
   StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
-  F0Stage f0;                             // wbx_clip_f0 (under fx_mu, on fx.side.stream)
+  F0Stage f0;                             // wbx_clip_f0 and wbx_clip_tempo's track (under fx_mu, on fx.side.stream)
+  OnsetStage ons;                         // wbx_clip_onsets, wbx_clip_tempo (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -834,6 +866,15 @@ wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchC
 // waits for the device
 wbx_status f0_check_call(const ClipSrc& src, const F0Call& k, const char** why);
 wbx_status f0_run(wbx_ctx* c, const ClipSrc& src, const F0Call& k, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why);
+// finding a clip's onsets and tempo (wbx_onset.hip), cut the same way: the checks make no device call (wbx_onset.h's
+// onset_check / tempo_check first, then the clip); the runs work under fx_mu on the edit stream behind clipfx_prepare /
+// clipfx_order and wait for the device.  tempo_run leaves the novelty on the device and hands it to f0_run as a mono F32
+// range of `hops` frames: the stream orders the two
+wbx_status onset_check_call(const ClipSrc& src, const OnsetCall& k, const char** why);
+wbx_status tempo_check_call(const ClipSrc& src, const OnsetCall& k, F0Call* track, const char** why);   // (sets track's range: the hops)
+wbx_status onset_run(wbx_ctx* c, const ClipSrc& src, const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why);
+wbx_status tempo_run(wbx_ctx* c, const ClipSrc& src, const OnsetCall& k, const F0Call& track, wbx_f0_frame* frames_out, wbx_f0_info* info,
+                     std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -611,6 +611,16 @@ struct SamplePin {
     if (st == WBX_OK) st = f0_run(e->ctx, src, k, frames_out, info, why);
     return st;
   }
+  wbx_status onsets(const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = onset_run(e->ctx, src, k, frames_out, info, why);
+    return st;
+  }
+  wbx_status tempo(const OnsetCall& k, const F0Call& track, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = tempo_run(e->ctx, src, k, track, frames_out, info, why);
+    return st;
+  }
   wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
     wbx_status st = order(clipfx_prepare, clipfx_order, why);
     ClipSlot slot;
@@ -983,6 +993,52 @@ extern "C" wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint6
   }
   std::string why;
   const wbx_status st = p.f0(k, frames_out, info, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// wbx_clip_onsets and wbx_clip_tempo of an engine sample (wbx.h "Finding a clip's onsets and tempo"), wbx_engine_f0_sample's
+// shape: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
+extern "C" wbx_status wbx_engine_onsets_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                               uint32_t hop_frames, double floor_power, double threshold, double delta, uint32_t w,
+                                               uint32_t a, wbx_onset_frame* frames_out, size_t frames_cap, wbx_onset_info* info) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a, frames_out != nullptr, frames_cap};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "onsets_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = onset_check_call(p.src, k, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.onsets(k, frames_out, info, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+extern "C" wbx_status wbx_engine_tempo_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                              uint32_t hop_frames, double floor_power, uint32_t window_hops, uint32_t step_hops,
+                                              uint32_t lag_min, uint32_t lag_max, double threshold, wbx_f0_frame* frames_out,
+                                              size_t frames_cap, wbx_f0_info* info) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, 0.0, 0.0, 0u, 0u, false, 0};
+  F0Call track{0, 0, window_hops, step_hops, lag_min, lag_max, threshold, frames_out != nullptr, frames_cap};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "tempo_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = tempo_check_call(p.src, k, &track, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_locked(sample);
+  }
+  std::string why;
+  const wbx_status st = p.tempo(k, track, frames_out, info, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }

@@ -317,6 +317,37 @@ def _run_f0(fn, what, h, engine, ident, first_frame, n_frames, window_frames, ho
     return rec, {k: getattr(fi, k) for k, _ in _ffi.F0Info._fields_ if k != "_pad"}
 
 
+# wbx_onset_frame as a numpy record: what clip_onsets and onsets_sample return, one per hop
+ONSET_DTYPE = np.dtype([("energy", "<f8"), ("edge_energy", "<f8"), ("novelty", "<f8"), ("onset", "<u4"), ("_pad", "<u4")])
+
+
+def onset_hops(n_frames: int, hop_frames: int) -> int:
+    """wbx_onset_hops (host-only): the complete hops of n_frames — n // H, or 0 where the call would refuse the hop length"""
+    return int(_ffi.lib().wbx_onset_hops(n_frames, hop_frames))
+
+
+def _run_onsets(fn, what, h, engine, ident, first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a):
+    hops = onset_hops(n_frames, hop_frames)
+    # the call's own argument check first, so that a refused call allocates no records
+    _check(_ffi.lib().wbx_onset_check(n_frames, hop_frames, floor_power, threshold, delta, w, a, 1, hops), "wbx_onset_check")
+    rec = np.zeros(hops, dtype=ONSET_DTYPE)
+    oi = _ffi.OnsetInfo()
+    _check(fn(h, ident, first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a,
+              rec.ctypes.data if rec.size else None, rec.size, C.byref(oi)), what, h, engine)
+    return rec, {k: getattr(oi, k) for k, _ in _ffi.OnsetInfo._fields_ if k != "_pad"}
+
+
+def _run_tempo(fn, what, h, engine, ident, first_frame, n_frames, hop_frames, floor_power, window_hops, step_hops, lag_min, lag_max,
+               threshold):
+    cap = f0_hops(onset_hops(n_frames, hop_frames), window_hops, step_hops, lag_max)   # (at most 2^20 / step_hops, or the call refuses)
+    cap = min(cap, 1 << 20)
+    rec = np.zeros(cap, dtype=F0_DTYPE)
+    fi = _ffi.F0Info()
+    _check(fn(h, ident, first_frame, n_frames, hop_frames, floor_power, window_hops, step_hops, lag_min, lag_max, threshold,
+              rec.ctypes.data if rec.size else None, rec.size, C.byref(fi)), what, h, engine)
+    return rec, {k: getattr(fi, k) for k, _ in _ffi.F0Info._fields_ if k != "_pad"}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -593,6 +624,29 @@ class MixContext:
         """wbx_f0_ms: device milliseconds of the last f0 call's launches"""
         out = C.c_double()
         _check(self.L.wbx_f0_ms(self.h, C.byref(out)), "wbx_f0_ms", self.h)
+        return out.value
+
+    def clip_onsets(self, clip: int, first_frame: int, n_frames: int, hop_frames: int = 256, floor_power: float = 1e-9,
+                    threshold: float = 0.3, delta: float = 0.1, w: int = 3, a: int = 8):
+        """wbx_clip_onsets: the onset-strength curve of frames [first_frame, first_frame + n_frames) of a resident F32 clip
+        of 1 or 2 channels and the onsets picked from it: (records, info) — a structured array (ONSET_DTYPE: "energy",
+        "edge_energy", "novelty", "onset"), one record per complete hop, and {"hops", "onsets", "launches"}.  An onset's frame
+        is its hop times hop_frames"""
+        return _run_onsets(self.L.wbx_clip_onsets, "wbx_clip_onsets", self.h, False, clip, first_frame, n_frames, hop_frames,
+                           floor_power, threshold, delta, w, a)
+
+    def clip_tempo(self, clip: int, first_frame: int, n_frames: int, hop_frames: int = 256, floor_power: float = 1e-9,
+                   window_hops: int = 1024, step_hops: int = 64, lag_min: int = 56, lag_max: int = 188, threshold: float = 0.5):
+        """wbx_clip_tempo: the period track of the range's onset-strength curve, which never leaves the device: (records,
+        info) as clip_f0's, with periods in hops — bpm = 60 * rate / (hop_frames * period).  The default lags are 200 .. 60
+        bpm at 48 kHz and hop_frames = 256"""
+        return _run_tempo(self.L.wbx_clip_tempo, "wbx_clip_tempo", self.h, False, clip, first_frame, n_frames, hop_frames,
+                          floor_power, window_hops, step_hops, lag_min, lag_max, threshold)
+
+    def onsets_ms(self) -> float:
+        """wbx_onset_ms: device milliseconds of the energy pass of the last onsets or tempo call"""
+        out = C.c_double()
+        _check(self.L.wbx_onset_ms(self.h, C.byref(out)), "wbx_onset_ms", self.h)
         return out.value
 
     def clip_loudness(self, clip: int, channels: int, rate: int, first_frame: int, n_frames: int, true_peak=False,
@@ -1388,6 +1442,79 @@ class Engine:
         cents = 100.0 * (target - note["midi"]) - note["cents"]
         new, info = self.transpose_sample(sample, 0.0, cents, **transpose)   # (pitch_ratio raises for a ratio of 1)
         return new, info, note
+
+    def _range_of(self, what, sample, first_frame, n_frames, frames, channels):
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, what + ": give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        return n_frames
+
+    def onsets_sample(self, sample: int, hop_frames: int = 256, floor_power: float = 1e-9, threshold: float = 0.3,
+                      delta: float = 0.1, w: int = 3, a: int = 8, first_frame: int = 0, n_frames: Optional[int] = None,
+                      channels: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_onsets_sample — see MixContext.clip_onsets; `frames` / `channels` as in export_sample.  Returns
+        (records, info).  May be called while another thread runs process(); delete_sample of the sample is refused
+        meanwhile."""
+        n_frames = self._range_of("onsets_sample", sample, first_frame, n_frames, frames, channels)
+        return _run_onsets(self.L.wbx_engine_onsets_sample, "wbx_engine_onsets_sample", self.h, True, sample, first_frame, n_frames,
+                           hop_frames, floor_power, threshold, delta, w, a)
+
+    def tempo_sample(self, sample: int, hop_frames: int = 256, floor_power: float = 1e-9, window_hops: int = 1024,
+                     step_hops: int = 64, lag_min: int = 56, lag_max: int = 188, threshold: float = 0.5, first_frame: int = 0,
+                     n_frames: Optional[int] = None, channels: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_tempo_sample — see MixContext.clip_tempo.  Returns (records, info); pinned like onsets_sample."""
+        n_frames = self._range_of("tempo_sample", sample, first_frame, n_frames, frames, channels)
+        return _run_tempo(self.L.wbx_engine_tempo_sample, "wbx_engine_tempo_sample", self.h, True, sample, first_frame, n_frames,
+                          hop_frames, floor_power, window_hops, step_hops, lag_min, lag_max, threshold)
+
+    def detect_tempo_sample(self, sample: int, bpm_min: float = 70.0, bpm_max: float = 180.0, rate: Optional[int] = None,
+                            hop_frames: int = 256, window_hops: int = 1024, step_hops: int = 64, threshold: float = 0.5, **call):
+        """The tempo of a sample: tempo_sample with the lags of bpm_max .. bpm_min at the sample's rate (`rate` where this
+        object did not make it; `call`: tempo_sample's other arguments), then the MEDIAN period of the voiced windows.
+        Returns {"bpm", "period" (in hops), "voiced" (the share of windows that are voiced), "windows"}; bpm and period are
+        None where no window is voiced.  The lag range decides the octave: a loop at half of bpm_max or below may come out
+        doubled.  The lags, the median and the division happen here: a convenience outside the bit-exact contract."""
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        per_minute = 60.0 * float(rate) / float(hop_frames)          # hops per minute: bpm = per_minute / period
+        lag_min = max(2, int(np.floor(per_minute / float(bpm_max))))
+        lag_max = min(4095, max(lag_min + 1, 8, int(np.ceil(per_minute / float(bpm_min)))))
+        rec, info = self.tempo_sample(sample, hop_frames=hop_frames, window_hops=window_hops, step_hops=step_hops, lag_min=lag_min,
+                                      lag_max=lag_max, threshold=threshold, **call)
+        out = {"bpm": None, "period": None, "windows": int(info["hops"]),
+               "voiced": float(info["voiced_hops"]) / info["hops"] if info["hops"] else 0.0}
+        keep = rec["voiced"] != 0
+        if keep.any():
+            period = float(np.median(rec["period"][keep]))
+            out.update(bpm=per_minute / period, period=period)
+        return out
+
+    def fit_sample_to_tempo(self, sample: int, bpm_to: float, detect: Optional[dict] = None, **stretch):
+        """A sample of unknown tempo fitted to `bpm_to`: detect_tempo_sample (`detect`: its arguments), then stretch_to_tempo
+        from the detected bpm (`stretch`: its arguments).  Returns (new id, info, the detected tempo).  ValueError where no
+        window is voiced."""
+        detect = dict(detect or {})
+        for k in ("rate", "first_frame", "n_frames", "frames", "channels"):
+            if k in stretch:
+                detect.setdefault(k, stretch[k])
+        tempo = self.detect_tempo_sample(sample, **detect)
+        if tempo["bpm"] is None:
+            raise ValueError("fit_sample_to_tempo: no voiced window, so no tempo to fit")
+        new, info = self.stretch_to_tempo(sample, tempo["bpm"], bpm_to, **stretch)
+        return new, info, tempo
+
+    def slice_sample(self, sample: int, first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                     frames: Optional[int] = None, **onsets):
+        """A sample cut at its onsets: onsets_sample (`onsets`: its arguments), then one derive_sample trim per stretch
+        between consecutive onset frames h * hop_frames, the last reaching the end of the range.  Returns (the new ids, the
+        (first frame, frames) of each piece): the pieces concatenate to the range from the first onset on.  No onset: no
+        piece."""
+        n_frames = self._range_of("slice_sample", sample, first_frame, n_frames, frames, channels)
+        rec, _ = self.onsets_sample(sample, first_frame=first_frame, n_frames=n_frames, channels=channels, frames=frames, **onsets)
+        H = int(onsets.get("hop_frames", 256))
+        cuts = [first_frame + int(h) * H for h in np.flatnonzero(rec["onset"])] + [first_frame + n_frames]
+        pieces = [(cuts[i], cuts[i + 1] - cuts[i]) for i in range(len(cuts) - 1)]
+        return [self.derive_sample(sample, edit_desc(at, n), channels=channels) for at, n in pieces], pieces
 
     def dynamics_sample(self, sample: int, table, sense="compress", key_sample: Optional[int] = None, key_first: int = 0,
                         drive: float = 1.0, key_gain: float = 1.0, makeup: float = 1.0, shape: tuple = (72, 0, 4800),
