@@ -1,6 +1,7 @@
-"""Sample life scripts on the device (tests/sample_scripts.py): uploads, derived, normalized, resampled, spliced and
-loudness-normalized samples, recorder takes, bounces and deletes chained at random in ONE clip pool, with placements,
-playback, measure, loudness, export and mip-maps in between.  Every feature's own test checks its own result; this one
+"""Sample life scripts on the device (tests/sample_scripts.py): uploads, derived, normalized, resampled, spliced,
+loudness-normalized, filtered, convolved, limited, dynamics-processed, stretched and pitch-shifted samples, recorder takes,
+bounces and deletes chained at random in ONE clip pool, with placements, playback, measure, loudness, f0, onsets, tempo,
+export and mip-maps in between.  Every feature's own test checks its own result; this one
 checks THE OTHERS: after every op every live sample is downloaded and compared bit for bit (uint32 views) with the model —
 an extent handed to two clips, or a store past a row, corrupts whoever lies beside the clip a feature test looks at — and
 the padding behind every producer's result shows when a clip of another rate plays to its end against the oracle engine,
@@ -14,9 +15,18 @@ energies and the true peak bit for bit) and, being a consumer, must leave every 
 splice (an i16 source: -3, two rates: -4) or normalization (fewer than 4 hops: -4) returns its status, makes no sample id
 and changes nothing; the script often deletes one of its sources next, which a pin left behind would refuse.
 
-Measured on an MI355X: 0.84 - 1.7 s per case, 15.3 s for the module's twelve cases (0.07 - 0.45 s and 2.2 - 2.5 s before
-splice and loudness joined: the time is numpy's twin of the loudness filter; MEASUREMENTS.md "Sample life scripts");
-no time is asserted."""
+The six newer producers (LifeRig.newer_producer) take anybody's result as their source — and a convolution's response and
+a dynamics call's key are a second live sample — in sizes around their kernels' tiles, chunks, segments and windows, ending
+inside a 16-byte word, back to back on one context whose work buffers (taps, gain-curve tables, positions, carried states)
+grow and are reused from call to call.  Each result is compared bit for bit with the feature's model, a limit's and a
+dynamics call's statistics and a stretch's and a pitch shift's info exactly; refused ones (an i16 source, response or key:
+-3; a response or key of another rate: -4; a stretch beyond 8 n or a ratio beyond 4 : 1: -3; a ratio of 1: -4) as above,
+with BOTH samples of a two-source call deleted next.  The consumers f0, onsets and tempo return the model's records (as
+64-bit patterns) and info, and leave every sample and the pool alone.
+
+Measured on an MI355X: 1.6 - 2.9 s per case, 30.5 s for the module's sixteen cases of 160 ops (0.84 - 1.7 s and 15.3 s for
+twelve of 80 ops before these nine joined; the time is still numpy's twin of the loudness filter; MEASUREMENTS.md "Sample
+life scripts"); no time is asserted."""
 import ctypes as C
 
 import numpy as np
@@ -38,6 +48,7 @@ from test_gpu_record import Rig, input_blocks
 
 pytestmark = pytest.mark.gpu
 DT = {"f32": np.float32, "i16": np.int16}
+NEW = object()                                              # LifeRig.refused: where the new id's out-parameter goes
 
 
 class LifeRig(Rig):
@@ -125,7 +136,7 @@ class LifeRig(Rig):
         k, eng, c = op[0], self.eng, self.c
         try:
             if k == "add":
-                _, key, fmt, channels, rate, frames, interleaved, _ = op
+                _, key, fmt, channels, rate, frames, interleaved, _, _ = op
                 c.apply(op)
                 planes = c.s[key][2]
                 sid = eng.add_sample_interleaved(fmt, rate, np.stack(planes, axis=1)) if interleaved else eng.add_sample(fmt, rate, planes)
@@ -181,6 +192,20 @@ class LifeRig(Rig):
                 assert got["oversampling"] == (LM.oversampling(rate) if true_peak else 0)
                 assert BU.bits(np.array(got["true_peak"], dtype=np.float32)).tolist() == BU.bits(np.array(want_peak, dtype=np.float32)).tolist(), \
                     ("true peak", src, got["true_peak"], want_peak)
+            elif k in SS.NEW_PRODUCERS:
+                return self.newer_producer(op)
+            elif k in SS.CONSUMERS:
+                _, rate, planes = c.s[op[1]]
+                sid, first, n = self.sid[op[1]], op[-2], op[-1]
+                shape = dict(first_frame=first, n_frames=n, channels=len(planes), frames=len(planes[0]))
+                got, info = (eng.f0_sample(sid, *op[2:7], **shape) if k == "f0" else
+                             eng.onsets_sample(sid, *op[2:8], **shape) if k == "onsets" else eng.tempo_sample(sid, *op[2:9], **shape))
+                want, want_info = c.analyse(op)
+                # the records as 64-bit patterns (three doubles and two 32-bit counts each), the info exactly
+                assert got.dtype == want.dtype and got.shape == want.shape, (k, op[1], got.shape, want.shape)
+                bad = np.flatnonzero(got.view(np.uint64).reshape(-1, 4) != want.view(np.uint64).reshape(-1, 4))
+                assert bad.size == 0, (k, op[1], "first wrong record", int(bad[0]) // 4, got[int(bad[0]) // 4], want[int(bad[0]) // 4], bad.size)
+                assert {f: info[f] for f in want_info} == want_info, (k, op[1], info, want_info)
             elif k == "take":
                 _, key, track, kind, index, b0, n, beat = op
                 made = len(self.made)
@@ -253,10 +278,71 @@ class LifeRig(Rig):
             return ex.status
         return 0
 
+    def newer_producer(self, op):
+        """filter, convolve, limit, dynamics, stretch, pitch: (kind, key, src, first, n, ..., status) -> the status.  The
+        sample against the feature's model bit for bit (new_sample), the statistics / info beside it exactly; a refused one
+        through the C entry point, whose out-parameter must stay untouched"""
+        k, key, src, first, n, status = op[0], op[1], op[2], op[3], op[4], op[-1]
+        eng, c, L, sid = self.eng, self.c, self.eng.L, self.sid[op[2]]
+        planes = c.s[src][2]
+        shape = dict(first_frame=first, n_frames=n, channels=len(planes), frames=len(planes[0]))
+        info = None
+        if k == "filter":
+            tail, coef = op[5], np.ascontiguousarray(op[6], dtype=np.float64)
+            if status:
+                return self.refused(L.wbx_engine_filter_sample, sid, first, n, tail, coef.ctypes.data, len(coef), NEW)
+            new = eng.filter_sample(sid, coef, tail, **shape)
+        elif k == "convolve":
+            _, _, _, _, _, ir, ir_first, taps, out_first, out_frames, gain_db, _ = op
+            if status:
+                return self.refused(L.wbx_engine_convolve_sample, sid, self.sid[ir], first, n, ir_first, taps, out_first, out_frames,
+                                    10.0 ** (gain_db / 20.0), NEW, None)
+            new = eng.convolve_sample(sid, self.sid[ir], gain_db, out_first, out_frames, ir_first=ir_first, ir_frames=taps,
+                                      ir_channels=len(c.s[ir][2]), ir_length=len(c.s[ir][2][0]), **shape)
+        elif k == "limit":
+            _, _, _, _, _, ceiling_db, drive_db, A, H, R, _ = op
+            if status:
+                ls = _ffi.LimitStats()
+                return self.refused(L.wbx_engine_limit_sample, sid, first, n, np.float32(10.0 ** (ceiling_db / 20.0)),
+                                    10.0 ** (drive_db / 20.0), A, H, R, NEW, C.byref(ls), None)
+            new, info = eng.limit_sample(sid, ceiling_db=ceiling_db, drive_db=drive_db, shape=(A, H, R), rate=c.s[src][1], **shape)
+        elif k == "dynamics":
+            _, _, _, _, _, spec, sense, kkey, key_first, drive, key_gain, makeup, A, H, R, _ = op
+            table = np.ascontiguousarray(SS.dyn_table(spec), dtype=np.float64)
+            if status:
+                ds = _ffi.DynamicsStats()
+                return self.refused(L.wbx_engine_dynamics_sample, sid, self.sid[kkey], first, n, key_first, sense, table.ctypes.data,
+                                    drive, key_gain, makeup, A, H, R, NEW, C.byref(ds), None)
+            new, info = eng.dynamics_sample(sid, table, sense, key_sample=None if kkey is None else self.sid[kkey], key_first=key_first,
+                                            drive=drive, key_gain=key_gain, makeup=makeup, shape=(A, H, R), **shape)
+        elif k == "stretch":
+            _, _, _, _, _, out, N, D, _ = op
+            if status:
+                si = _ffi.StretchInfo()
+                return self.refused(L.wbx_engine_stretch_sample, sid, first, n, out, N, D, C.byref(si), NEW)
+            new, info = eng.stretch_sample(sid, out, N, D, **shape)
+        else:
+            _, _, _, _, _, out, num, den, quality, N, D, _ = op
+            if status:
+                pi = _ffi.PitchInfo()
+                return self.refused(L.wbx_engine_pitch_sample, sid, first, n, out, num, den, quality, N, D, C.byref(pi), NEW)
+            new, info = eng.pitch_sample(sid, num, den, out, quality, N, D, **shape)
+        c.apply(op)
+        if k in ("limit", "dynamics"):                       # the statistics field by field, exactly
+            assert info == c.info, (k, key, info, c.info)
+        elif info is not None:                               # the info, without its launches
+            assert {f: info[f] for f in c.info} == c.info, (k, key, info, c.info)
+        self.new_sample(key, new, len(c.s[key][2][0]), len(c.s[key][2]), c.s[src][1])
+        return 0
+
     def refused(self, fn, *args):
-        """a producer the product must refuse -> its status; no sample id and no gain came back"""
+        """a producer the product must refuse -> its status; no sample id and no gain came back.  NEW among the arguments
+        stands for the new id's out-parameter (where it is not the last one)"""
         new, gain = C.c_uint32(0xFEED), C.c_float(7.0)
-        tail = (C.byref(new), C.byref(gain)) if fn is self.eng.L.wbx_engine_normalize_loudness_sample else (C.byref(new),)
+        if any(a is NEW for a in args):
+            args, tail = [C.byref(new) if a is NEW else a for a in args], ()
+        else:
+            tail = (C.byref(new), C.byref(gain)) if fn is self.eng.L.wbx_engine_normalize_loudness_sample else (C.byref(new),)
         status = fn(self.eng.h, *args, *tail)
         assert status != 0 and new.value == 0xFEED and gain.value == 7.0, ("a refused producer made a sample", status, new.value)
         return status
@@ -276,7 +362,7 @@ def test_every_sample_outlives_its_neighbours(seed):
         for i, op in enumerate(ops):
             try:
                 status = rig.life_op(op)
-                assert status == (op[2] if op[0] == "delete" else op[-1] if op[0] in ("splice", "loudnorm") else 0), ("status", status)
+                assert status == (op[2] if op[0] == "delete" else op[-1] if op[0] in SS.HAVE_A_STATUS else 0), ("status", status)
                 rig.check_bystanders()
             except AssertionError as ex:
                 raise AssertionError((seed, i, op[:3], ex.args)) from ex
