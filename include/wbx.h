@@ -214,7 +214,10 @@ wbx_status wbx_set_export_chunk(wbx_ctx* ctx, uint32_t frames);
  * Refused before any device call, nothing allocated, dst_clip untouched — WBX_ERR_INVALID: unknown source clip, NULL
  * descriptor, n_frames == 0, a range past the clip, dst_clip == src_clip, an unknown flag, mode or shape, a fade longer
  * than n_frames, a channel mode that does not fit the source's channel count; WBX_ERR_UNSUPPORTED: a source whose storage
- * format is not F32.  WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated). */
+ * format is not F32.  WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated).
+ * wbx_clipfx_pass_frames (host-only, no device): the frames ONE pass of the measure / derive kernel's capped grid covers; a
+ * longer range is finished by further passes of the same launch.  For tests that must reach such a pass; nothing else
+ * reads it. */
 enum { WBX_EDIT_REVERSE = 1 };
 enum { WBX_CH_KEEP = 0, WBX_CH_SWAP = 1, WBX_CH_LEFT = 2, WBX_CH_RIGHT = 3, WBX_CH_MONO_MIX = 4, WBX_CH_DUAL_MONO = 5 };
 enum { WBX_FADE_LINEAR = 0, WBX_FADE_SQUARE = 1, WBX_FADE_SMOOTH = 2 };
@@ -237,6 +240,7 @@ typedef struct wbx_clip_edit_desc {   /* 56 bytes */
   uint64_t fade_in, fade_out;   /* frames, each <= n_frames */
   int32_t fade_in_shape, fade_out_shape;   /* WBX_FADE_* */
 } wbx_clip_edit_desc;
+uint64_t wbx_clipfx_pass_frames(void);
 wbx_status wbx_clip_measure(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out);
 wbx_status wbx_clip_derive(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, const wbx_clip_edit_desc* d,
                            wbx_clip_stats* stats_of_result);
@@ -280,7 +284,12 @@ wbx_status wbx_clip_derive(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, c
  * n_frames == 0, a range past the clip, dst_clip == src_clip, unknown quality, dst_rate == 0, dst_rate == the source's
  * rate, n_out >= 2^31 - 16; WBX_ERR_UNSUPPORTED: a source whose storage format is not F32 (bounce a track pre-fader to get
  * one) or with more than 2 channels, L > 1280 (22050 -> 192000 has 1280), T > 512 (192000 -> 32000 at BEST has 576).
- * WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated). */
+ * WBX_ERR_OOM when wbx_clip_pool_limit does not allow the new clip (nothing is left allocated).
+ * wbx_resample_launch_shape (host-only, no device): how a conversion to n_out output frames is launched — a workgroup's
+ * tile of output frames, the source span it stages, the tiles, and the workgroups that share them (fewer than the tiles
+ * once the grid's cap is reached: then a workgroup takes further tiles, one pass of the grid after another).  What
+ * wbx_resample_plan refuses is refused with its status; WBX_ERR_INVALID for n_out of 0 or >= 2^31 - 16 or a NULL pointer.
+ * For tests that must reach a second pass; nothing else reads it. */
 enum { WBX_SRC_FAST = 0, WBX_SRC_GOOD = 1, WBX_SRC_BEST = 2 };
 typedef struct wbx_resample_info {   /* 24 bytes */
   uint32_t L, M;             /* dst_rate / g, src_rate / g */
@@ -291,6 +300,8 @@ typedef struct wbx_resample_info {   /* 24 bytes */
 wbx_status wbx_resample_plan(uint32_t src_rate, uint32_t dst_rate, int quality, wbx_resample_info* out);
 uint64_t wbx_resample_frames(uint32_t src_rate, uint32_t dst_rate, uint64_t n_frames);
 wbx_status wbx_resample_table(uint32_t src_rate, uint32_t dst_rate, int quality, float* out, size_t cap_floats);
+wbx_status wbx_resample_launch_shape(uint32_t src_rate, uint32_t dst_rate, int quality, uint64_t n_out, uint32_t* tile,
+                                     uint32_t* span, uint32_t* n_tiles, uint32_t* grid);
 wbx_status wbx_clip_resample(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                              uint32_t dst_rate, int quality, wbx_clip_stats* stats_of_result);
 
@@ -406,7 +417,11 @@ wbx_status wbx_clip_splice(wbx_ctx* ctx, uint32_t dst_clip, uint32_t channels, u
  * returns when *out is complete.  hop_energy (may be NULL): E as the device wrote it, [channels][hops].
  * Refused before any device call — WBX_ERR_INVALID: unknown clip, NULL out, n_frames == 0, a range past the clip, an unknown
  * flag, cap_doubles below channels*hops when hop_energy is given; WBX_ERR_UNSUPPORTED: a source whose storage format is not
- * F32, more than 2 channels, a rate outside 8000 .. 384000, with true peak factor*n_frames >= 2^31 - 16. */
+ * F32, more than 2 channels, a rate outside 8000 .. 384000, with true peak factor*n_frames >= 2^31 - 16.
+ * wbx_true_peak_launch_shape (host-only, no device): the true peak's factor at `rate`, the tiles of oversampled frames a
+ * range of n_frames has and the workgroups that share them (wbx_resample_launch_shape's meaning; both 0 at factor 1, where
+ * the sample peak is wbx_clip_measure's pass).  WBX_ERR_INVALID: n_frames == 0 or a NULL pointer; WBX_ERR_UNSUPPORTED: the
+ * rate, factor*n_frames >= 2^31 - 16.  For tests that must reach a second pass; nothing else reads it. */
 enum { WBX_LOUD_TRUE_PEAK = 1 };
 typedef struct wbx_loudness {   /* 80 bytes */
   double integrated;         /*  0: LUFS */
@@ -424,6 +439,7 @@ typedef struct wbx_loudness {   /* 80 bytes */
 uint32_t wbx_loudness_hop_frames(uint32_t rate);
 uint64_t wbx_loudness_hops(uint32_t rate, uint64_t n_frames);
 wbx_status wbx_loudness_coefficients(uint32_t rate, double out[10]);
+wbx_status wbx_true_peak_launch_shape(uint32_t rate, uint64_t n_frames, uint32_t* factor, uint32_t* n_tiles, uint32_t* grid);
 wbx_status wbx_loudness_gate(uint32_t channels, uint64_t hops, uint32_t hop_frames, const double* hop_energy, wbx_loudness* out);
 wbx_status wbx_clip_loudness(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t flags,
                              wbx_loudness* out, double* hop_energy, size_t cap_doubles);
@@ -841,7 +857,10 @@ wbx_status wbx_clip_stretch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, 
  * K' > wbx_pitch_max_steps() (2^22: the positions take at most 16 MB + 4 B).  Then the clip — WBX_ERR_UNSUPPORTED: not F32
  * or more than 2 channels; WBX_ERR_INVALID: a range past the clip.  WBX_ERR_OOM as for wbx_clip_derive.
  * Host-only, no device (wbx_pitch.h, which a C++ compiler takes alone): wbx_pitch_mid_frames (any out_frames: the product
- * in 128 bits, 2^64 - 1 where it does not fit; 0 where the call would refuse the RATIO), wbx_pitch_max_steps.
+ * in 128 bits, 2^64 - 1 where it does not fit; 0 where the call would refuse the RATIO), wbx_pitch_max_steps,
+ * wbx_pitch_launch_shape (wbx_resample_launch_shape of the call's last launch: the conversion by M / L to out_frames frames;
+ * WBX_ERR_UNSUPPORTED for a ratio or a plan the call refuses, WBX_ERR_INVALID for out_frames of 0 or >= 2^31 - 16 or a NULL
+ * pointer).
  * wbx_pitch_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
  * completed pitch call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
  * tools/bench_pitch.py; nothing else reads it.
@@ -859,6 +878,8 @@ typedef struct wbx_pitch_info {         /* 48 bytes */
 } wbx_pitch_info;
 uint64_t wbx_pitch_mid_frames(uint64_t out_frames, uint32_t num, uint32_t den);
 uint32_t wbx_pitch_max_steps(void);
+wbx_status wbx_pitch_launch_shape(uint32_t num, uint32_t den, int quality, uint64_t out_frames, uint32_t* tile, uint32_t* span,
+                                  uint32_t* n_tiles, uint32_t* grid);
 wbx_status wbx_pitch_ms(wbx_ctx* ctx, double* out);
 wbx_status wbx_clip_pitch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
                           uint64_t out_frames, uint32_t num, uint32_t den, int quality, uint32_t window_frames,

@@ -15,7 +15,7 @@ import whitebox_amd as W
 from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["wbx_clip_measure", "wbx_clip_derive", "wbx_engine_measure_sample", "wbx_engine_derive_sample", "wbx_engine_normalize_sample"]
+NEW = ["wbx_clipfx_pass_frames", "wbx_clip_measure", "wbx_clip_derive", "wbx_engine_measure_sample", "wbx_engine_derive_sample", "wbx_engine_normalize_sample"]
 
 
 def test_symbols_are_declared_exported_and_bound():
@@ -140,3 +140,20 @@ def test_normalize_gain_is_one_fp32_division():
         g = M.normalize_gain(target, peak)
         assert g.dtype == np.float32 and g == np.float32(target) / np.float32(peak)
         assert g == np.float32(np.float64(np.float32(target)) / np.float64(np.float32(peak)))   # (fp64 then fp32: the same rounding)
+
+
+def test_the_models_exact_sums_are_math_fsum():
+    """measure()'s sum, sum_sq and abs_sum go through exact_sum (binade by binade, for clips of 10^7 frames); it must give
+    math.fsum's correctly rounded value whatever the range of the samples: denormals, 10^-30 beside 10^30, cancellation"""
+    import math
+    rng = np.random.default_rng(0xE5AC7)
+    for t in range(120):
+        n = int(rng.integers(0, 3000))
+        x = [rng.uniform(-1.4, 1.4, n), rng.standard_normal(n) * 10.0 ** rng.integers(-30, 30, n), rng.integers(-2 ** 24, 2 ** 24, n) * 2.0 ** -149,
+             np.where(rng.random(n) < 0.5, 3e38, -3e38) * rng.random(n), np.concatenate([rng.uniform(-1, 1, n), [1e30, -1e30, 1e-30, -0.0, 0.0]]),
+             rng.uniform(-1e-20, 1e-20, n)][t % 6]
+        d = np.asarray(x, dtype=np.float32).astype(np.float64)
+        hi, lo = M.split26(d * d)
+        assert np.array_equal(hi + lo, d * d) and np.all(np.frexp(hi)[0] * 2.0 ** 26 % 1 == 0) and np.all(np.frexp(lo)[0] * 2.0 ** 26 % 1 == 0)
+        assert M.exact_sum(d, bits=24) == math.fsum(d) and M.exact_sum(np.abs(d), bits=24) == math.fsum(np.abs(d)), t
+        assert M.exact_sum(hi, lo, bits=26) == math.fsum(d * d), t

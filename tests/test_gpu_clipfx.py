@@ -13,6 +13,7 @@ import pytest
 import bounce_util as BU
 import clipfx_model as M
 import oracle_ffi as O
+import second_pass as SP
 import whitebox_amd as W
 from whitebox_amd import _ffi, synth
 from whitebox_amd.engine import build_engine
@@ -101,11 +102,11 @@ def test_derive_matrix(ctx, case):
     check_stats(ctx.clip_measure(clip_id(ch, L), ch, first, n), M.measure(src, first, n), n, "measure of the source range")
 
 
-# ---- 2: every workgroup and grid-stride seam -----------------------------------------------------------------------------------
+# ---- 2: every workgroup and wave seam of one pass of the grid (513 workgroups; the second pass is section 2b's) ---------------
 @pytest.fixture(scope="module")
 def big():
     c = W.MixContext(4, block=128)
-    n = (1 << 20) + 3
+    n = SP.CLIPFX_SEAMS_FRAMES
     rng = np.random.default_rng(0x5EA5)
     c.planes = [rng.uniform(-1.1, 1.1, n).astype(np.float32) for _ in range(2)]
     c.clip_upload(1, "f32", 48000, c.planes)
@@ -114,7 +115,7 @@ def big():
 
 
 @pytest.mark.parametrize("rev", [False, True])
-def test_grid_stride_seams(big, rev):
+def test_workgroup_and_wave_seams(big, rev):
     c, n = big
     fi, fo = 300001, 700003                      # overlapping, ending inside waves
     want = M.derive(c.planes, 0, n, rev, M.KEEP, 0.5, fi, fo, M.SMOOTH, M.SQUARE)
@@ -127,8 +128,100 @@ def test_grid_stride_seams(big, rev):
     check_stats(c.clip_measure(1, 2, 5, n - 5), M.measure(c.planes, 5, n - 5), n - 5, "big measure")
 
 
+# ---- 2b: the second pass of the grid ----------------------------------------------------------------------------------------
+# n = one pass of the grid + 1037 frames (tests/second_pass.py, from wbx_clipfx_pass_frames): the first three workgroups run
+# the loop a second time, the range ends inside a wave of that pass and its last lane holds 5 frames.  Every frame and every
+# statistic is compared, so lane statistics that are reset or mis-merged between the iterations show, as does a skipped tile:
+# the pool hands the space of the clip freed last out again (shifted by the few granules of its pseudo-random gap), and that
+# clip was filled by a call with another gain and the other direction; no two cases share first_frame, direction and mode.
+HUGE_SRC, HUGE_MONO, HUGE_SPOIL, HUGE_DST = 1, 2, 3, 4
+HUGE_SLACK = 8                                                  # frames of the source clip behind a range that starts at 0
+
+
+def huge_material(n):
+    """stereo, n + 8 frames.  In the coordinates of the range measured below (first_frame 5), P the frames of one pass:
+    channel 0's peak magnitude 3.5 at frame 995 and again, as -3.5, at P + 600: the first is reported, the signed maximum
+    lies before P and the minimum behind it; channel 1's peak, -3.25, lies only behind P (its minimum; its maximum 2.0 before);
+    NaNs and over-range samples on both sides"""
+    P = W.clipfx_pass_frames()
+    rng = np.random.default_rng(0x2FA55)
+    x = [rng.uniform(-0.9, 0.9, n + HUGE_SLACK).astype(np.float32) for _ in range(2)]
+    x[0][[1000, P + 605]] = [3.5, -3.5]
+    x[1][[4005, P + 782]] = [2.0, -3.25]
+    for k in range(2):
+        x[k][[77 + k, 300_000 + k, P + 905 + k, n - 2 - k]] = np.nan
+        x[k][[500 + k, P - 3 + k, P + 9 + k, P + 1030 + k]] = [1.5, -1.25, 1.75, -1.5]
+    return x
+
+
+@pytest.fixture(scope="module")
+def huge():
+    c = W.MixContext(4, block=128)
+    n = SP.clipfx_frames()
+    assert n > W.clipfx_pass_frames()
+    c.planes = huge_material(n)
+    c.clip_upload(HUGE_SRC, "f32", 48000, c.planes)
+    c.clip_upload(HUGE_MONO, "f32", 48000, c.planes[:1])
+    yield c, n
+    c.close()
+
+
+def huge_cases(n, P):
+    a, b = (P + 300, 700), (300_001, 1037 + 1500)                # the fade layouts: (fade_in, fade_out)
+    return [  # (source channels, first_frame, reversed, mode, fades)
+        (2, 0, False, "keep", a), (2, 0, True, "keep", a),      # the fade-in ends inside the second pass, the fade-out lies in it
+        (2, 5, False, "keep", b), (2, 3, True, "keep", b),      # the fade-out starts before the seam
+        (2, 5, True, "keep", a), (2, 8, True, "keep", b),
+        (2, 3, False, "mono_mix", a), (1, 0, True, "dual_mono", b), (2, 8, False, "swap", b)]
+
+
+@pytest.mark.parametrize("i", range(9))
+def test_derive_across_the_second_pass_of_the_grid(huge, i):
+    """Reversed at first_frame 0 the range's last lane — it runs in the second pass — has top = 4 < 7 and loads its frames one
+    by one, each guarded; at 3 it has top = 7, the first unguarded span, which starts at the clip's frame 0"""
+    c, n = huge
+    P = W.clipfx_pass_frames()
+    cases = huge_cases(n, P)
+    assert len(cases) == 9 and {(k[1], k[2]) for k in cases} >= {(f, True) for f in (0, 3, 5, 8)}
+    assert [k[2] for k in cases[6:]] == [False, True, False] and n - cases[0][4][0] > 0 and cases[2][4][1] > 1037
+    ch, first, rev, mode, (fi, fo) = cases[i]
+    src, planes = (HUGE_SRC, c.planes) if ch == 2 else (HUGE_MONO, c.planes[:1])
+    want = M.derive(planes, first, n, rev, _ffi.CH_MODE[mode], 0.5, fi, fo, M.SMOOTH, M.SQUARE)
+    c.clip_derive(src, HUGE_SPOIL, W.edit_desc(first, n, not rev, mode, -0.25))     # fills the space the result is about to get
+    assert c.L.wbx_clip_free(c.h, HUGE_SPOIL) == 0
+    st = c.clip_derive(src, HUGE_DST, W.edit_desc(first, n, rev, mode, 0.5, fi, fo, "smooth", "square"), stats_channels=len(want))
+    got = download(c, HUGE_DST, len(want), n)
+    assert c.L.wbx_clip_free(c.h, HUGE_DST) == 0
+    for k in range(len(want)):
+        bad = np.flatnonzero(got[k].view(np.uint32) != want[k].view(np.uint32))
+        assert bad.size == 0, (cases[i], k, bad[:8], bad.size)
+    check_stats(st, M.measure(want), n, "second pass stats_of_result")
+
+
+@pytest.mark.parametrize("channels", [2, 1])
+def test_measure_across_the_second_pass_of_the_grid(huge, channels):
+    c, n = huge
+    P = W.clipfx_pass_frames()
+    first, m = 5, n - 5
+    assert m > P
+    planes = c.planes[:channels]
+    want = M.measure(planes, first, m)
+    got = c.clip_measure(HUGE_SRC if channels == 2 else HUGE_MONO, channels, first, m)
+    # the material is what the docstring of huge_material says it is
+    assert want["peak"][0] == 3.5 and want["peak_frame"][0] == 995 and planes[0][first + P + 600] == -3.5
+    assert want["min"][0] == -3.5 and want["max"][0] == 3.5
+    if channels == 2:
+        assert want["peak"][1] == 3.25 and want["peak_frame"][1] == P + 777 and want["min"][1] == -3.25 and want["max"][1] == 2.0
+    for p in planes:
+        r = p[first:first + m]
+        with np.errstate(invalid="ignore"):
+            assert np.isnan(r[:P]).any() and np.isnan(r[P:]).any() and (np.abs(r[:P]) > 1).any() and (np.abs(r[P:]) > 1).any()
+    check_stats(got, want, m, "second pass measure")
+    assert got["peak_frame"][0] == 995
+
+
 # ---- 3: special values ------------------------------------------------------------------------------------------------------
-SPECIALS = np.array([np.inf, -np.inf, np.nan, -0.0, 1e-40, -1.4e-45, 0.0], dtype=np.float32)
+SPECIALS =np.array([np.inf, -np.inf, np.nan, -0.0, 1e-40, -1.4e-45, 0.0], dtype=np.float32)
 
 
 @pytest.mark.parametrize("rot", range(len(SPECIALS)))

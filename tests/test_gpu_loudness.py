@@ -17,6 +17,8 @@ import pytest
 import bounce_util as BU
 import clipfx_model as FX
 import loudness_model as M
+import resample_model as RS
+import second_pass as SP
 import whitebox_amd as W
 from whitebox_amd import _ffi, synth
 from whitebox_amd.engine import build_engine
@@ -160,6 +162,78 @@ def test_true_peak_at_192000_is_the_sample_peak(ctx, channels):
     st = ctx.clip_measure(clip_id(channels, 192000), channels, first, n)
     assert got["oversampling"] == 1 and got["true_peak"] == st["peak"] and all(p > 0 for p in st["peak"])
     assert got["true_peak"] == M.true_peak(ctx.src[(channels, 192000)], first, n, 192000)
+
+
+# ---- 2b: the second pass of true_peak_kernel's grid -------------------------------------------------------------------------
+PAD = 64                                                        # frames of silence kept around a burst: more than H = 24
+
+
+def burst_material(n, seam):
+    """stereo silence with three noise bursts per channel: inside tile 0, straddling source frame `seam` (the first of the
+    second pass), ending on the last frame.  Channel 0's loudest lies on the seam burst's second-pass side, channel 1's in
+    tile 0; (planes, the bursts' [a, b) per channel)"""
+    rng = np.random.default_rng(0x7EA4)
+    planes = [np.zeros(n, dtype=np.float32) for _ in range(2)]
+    spans = [[(40, 140), (seam - 50, seam + 50), (n - 60, n)], [(60, 160), (seam - 40, seam + 60), (n - 70, n)]]
+    amps = [[0.4, None, 0.5], [0.9, 0.4, 0.5]]
+    for p, sp, am in zip(planes, spans, amps):
+        for (a, b), amp in zip(sp, am):
+            p[a:b] = rng.uniform(-1.0, 1.0, b - a) * (amp if amp is not None else np.where(np.arange(a, b) < seam, 0.3, 0.9))
+    return planes, spans
+
+
+def peak_over_windows(plane, first, n, spans):
+    """the model's true peak of the range [first, first + n) of a plane that is silent outside `spans`: the maximum over
+    windows of PAD frames around each burst, cut to the range.  A zero frame adds nothing to any output, and none lies within
+    H frames of a window's ends (tests/test_loudness_host.py holds the model to that)"""
+    best = np.float32(0.0)
+    for a, b in spans:
+        w0, w1 = max(first, a - PAD), min(first + n, b + PAD)
+        if w1 > w0:
+            best = max(best, M.true_peak([plane[w0:w1]], 0, w1 - w0, SP.TRUE_PEAK_RATE)[0])
+    return best
+
+
+def test_true_peak_of_tiles_past_the_grid_cap():
+    """48000 Hz, factor 4: G tiles and 767 frames (tests/second_pass.py, from wbx_true_peak_launch_shape), so workgroups 0, 1 and
+    2 take a second tile; `off` / `row` are computed once outside the tile loop and the lane maxima live across it.  Channel
+    0's peak is found only by the second pass; channel 1's is workgroup 0's FIRST tile's and must survive its second (for
+    that channel removing the second-pass bursts cannot change the expected value — its part is to show that the running
+    maximum is not reset between the iterations; the assertion about removal is made where it can hold, on channel 0)"""
+    n, sh, G, tile_frames = SP.true_peak_case()
+    seam = G * tile_frames
+    assert sh["n_tiles"] == G + 3 > sh["grid"] == G and n - seam == 767
+    planes, spans = burst_material(n, seam)
+    rate = SP.TRUE_PEAK_RATE
+    want = [peak_over_windows(p, 0, n, s) for p, s in zip(planes, spans)]
+    # on the CPU, through the model alone: what each channel's figure depends on
+    cut = [p.copy() for p in planes]
+    for p in cut:
+        p[seam:] = 0.0
+    without = [peak_over_windows(p, 0, n, s) for p, s in zip(cut, spans)]
+    assert without[0] < want[0] and without[1] == want[1]
+    assert want[1] == peak_over_windows(planes[1], 0, n, spans[1][:1]) > peak_over_windows(planes[1], 0, n, spans[1][1:])
+    a, b = spans[0][1]
+    up = RS.resample([planes[0][a - PAD:b + PAD]], 0, b - a + 2 * PAD, rate, 4 * rate, RS.GOOD)[0]
+    at = 4 * (a - PAD) + int(np.argmax(np.abs(up)))
+    assert np.abs(up).max() == want[0] and at >= G * 1024 + 4 * 24, "channel 0's peak is an output of the second pass alone"
+    assert want[0] > max(np.abs(planes[0]).max(), 0.9), "an inter-sample peak"
+
+    c = W.MixContext(4, block=128)
+    c.clip_upload(1, "f32", rate, planes)
+    c.clip_upload(2, "f32", rate, planes[:1])
+    got = c.clip_loudness(1, 2, rate, 0, n, true_peak=True)
+    assert got["oversampling"] == 4
+    assert bits(np.array(got["true_peak"], dtype=np.float32)).tolist() == bits(np.array(want, dtype=np.float32)).tolist(), (got, want)
+    mono = c.clip_loudness(2, 1, rate, 0, n, true_peak=True)
+    assert bits(np.float32(mono["true_peak"][0])) == bits(np.float32(want[0])), (mono, want)
+    # the range from frame 3 on: every tile moves by three source frames, the last still ragged
+    first = 3
+    assert W.true_peak_launch_shape(rate, n - first) == sh
+    want3 = [peak_over_windows(p, first, n - first, s) for p, s in zip(planes, spans)]
+    got3 = c.clip_loudness(1, 2, rate, first, n - first, true_peak=True)
+    assert bits(np.array(got3["true_peak"], dtype=np.float32)).tolist() == bits(np.array(want3, dtype=np.float32)).tolist(), (got3, want3)
+    c.close()
 
 
 # ---- 3: one known answer per family -----------------------------------------------------------------------------------------

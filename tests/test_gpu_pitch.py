@@ -19,6 +19,7 @@ import clipfx_model as FX
 import oracle_ffi as O
 import pitch_model as M
 import resample_model as RS
+import second_pass as SP
 import stretch_model as ST
 import whitebox_amd as W
 from whitebox_amd import _ffi, synth
@@ -265,6 +266,88 @@ def test_one_step_more_than_the_cap_is_refused_without_a_device_call(ctx):
     # ... one step fewer passes the sizes and fails on the clip, which is not that long
     assert L.wbx_clip_pitch(ctx.h, SRC[1], DST + 1, 0, mid // 4, 2 * (mid - 1), 1, 2, 0, 32, 8, None, 0, C.byref(pi), None) == -4
     assert b"past the clip" in bytes(L.wbx_last_error(ctx.h)) and ctx.pool_stats() == before
+
+
+# ---- 4b: the second pass of pitch_kernel's grid -----------------------------------------------------------------------------------
+class Intermediate:
+    """one channel of the stretched intermediate, sliced lazily: ST.overlap_add over the steps a slice touches (and the one
+    before them, whose frames are dropped: a step blends with its predecessor's position), on the frames of the range those
+    steps read — `plane` may be lazy itself.  What lies past the range's n frames is zero, as in the model"""
+
+    def __init__(self, plane, n, pos, N):
+        self.plane, self.n, self.pos, self.N = plane, n, np.asarray(pos, dtype=np.int64), N
+
+    def __getitem__(self, s):
+        Hs = self.N // 2
+        k0, k1 = s.start // Hs, -(-s.stop // Hs)
+        assert s.step is None and 0 <= s.start <= s.stop and k1 <= len(self.pos)
+        lead = 1 if k0 else 0
+        p = self.pos[k0 - lead:k1]
+        reads = np.concatenate([p, p[:-1] + Hs])                  # every step's own frames and its predecessor's continuation
+        lo, hi = int(reads.min()), min(self.n, int(reads.max()) + Hs)
+        x = ST.inputs([self.plane[lo:hi]])[0]
+        y = ST.overlap_add([x], p - lo, (k1 - k0 + lead) * Hs, self.N)[0][lead * Hs:]
+        return y[s.start - k0 * Hs:s.stop - k0 * Hs]
+
+
+def export_window(c, clip, channels, j0, j1):
+    """frames [j0, j1) of a resident clip as [channels] float32 planes, through wbx_clip_export (unclamped f32: the stored bits)"""
+    out, _ = c.clip_export(clip, "f32", channels, j0, j1 - j0, clamp=False)
+    return [np.ascontiguousarray(out.reshape(-1, channels)[:, k]) for k in range(channels)]
+
+
+def test_the_lazy_intermediate_is_the_models():
+    """(no device call) the windowed overlap-add equals ST.overlap_add of every step: at step seams, inside steps, where steps
+    read past the range's end"""
+    for n, mid, N in ((3000, 5000, 64), (700, 5003, 256), (5300, 5000, 64)):
+        plane = source(1, n)[0]
+        pos = np.array([ST.anchor(k, n, mid, N) for k in range(ST.steps(mid, N))], dtype=np.int32)
+        pos[5:9] += [3, -2, 0, 7]                                 # steps moved off their anchors ...
+        pos[7] = pos[6] + N // 2                                 # ... and one that continues its predecessor: a copy, no blend
+        whole = ST.overlap_add(ST.inputs([plane]), pos, mid, N)[0]
+        lazy = Intermediate(plane, n, pos, N)
+        Hs = N // 2
+        for a, b in ((0, 1), (0, 2 * Hs), (Hs - 1, Hs + 1), (Hs * 5 - 1, Hs * 9 + 2), (mid - 1000, mid), (mid - 10, mid)):
+            assert np.array_equal(lazy[a:b].view(np.uint32), whole[a:b].view(np.uint32)), (n, mid, N, a, b)
+
+
+@pytest.mark.parametrize("source_range,channels", [("eighth", 1), ("eighth", 2), ("longer", 2)])
+def test_tiles_past_the_grid_cap(source_range, channels):
+    """Down an octave (L 2, M 1: the tile is 1024) to G + 3 tiles, G the grid's cap (tests/second_pass.py, from
+    wbx_pitch_launch_shape): workgroups 0, 1 and 2 stage and convert a second tile.  With D = 0 the positions are the anchors
+    (test_stretch_host.py pins that for the model), so no search is modelled: the expected frames are ST.overlap_add over the
+    steps a window's span touches, then the conversion's model of that window.  Compared bit for bit: the first three tiles,
+    the frames around tile G's first, everything from tile G - 2 to the end — the whole second pass and the last lane's
+    partial store (m = 1 mod 4).  From the "eighth" range, eight times shorter than the intermediate, the last step runs off
+    the range's end after some 80 frames: most of the second pass stores silence.  From the "longer" range it blends frames of
+    the range to the end, so a tile that is skipped or staged from the wrong step shows.  The same call at another quality
+    is made and freed first: the memory the result then gets is not left as the driver handed it out"""
+    n, m, mid, sh, G = SP.pitch_case(source_range)
+    k = SP.PITCH
+    num, den, q, N, D = k["num"], k["den"], k["quality"], k["window"], k["tolerance"]
+    tile = sh["tile"]
+    assert sh["n_tiles"] == G + 3 > sh["grid"] == G and m % 4 and q == "fast"
+    K = ST.steps(mid, N)
+    c = W.MixContext(4, block=128)
+    seed, track, amp = 0x2D_9A55 + channels, 5, 0.75
+    c.clip_synth(1, "f32", channels, RATE, n, seed, track, amp)
+    c.clip_pitch(1, 2, 0, n, m, num, den, "good", N, D)         # fills the memory the result is about to get
+    assert c.L.wbx_clip_free(c.h, 2) == 0
+    info, pos = c.clip_pitch(1, 3, 0, n, m, num, den, q, N, D, positions=True)
+    want_p = ((np.arange(K, dtype=np.int64) * (N // 2) * n) // mid).astype(np.int32)
+    assert [int(want_p[j]) for j in (1, K // 2, K - 1)] == [ST.anchor(j, n, mid, N) for j in (1, K // 2, K - 1)]
+    bad = np.flatnonzero(pos != want_p)
+    assert pos.shape == want_p.shape and bad.size == 0, (bad[:8], bad.size)
+    assert (info["steps"], info["mid_frames"], info["max_shift"], info["L"], info["M"]) == (K, mid, 0, 2, 1), info
+    mids = [Intermediate(SP.SynthPlane(seed, track, ch, n, amp), n, want_p, N) for ch in range(channels)]
+    tab = M.table(2, 1, RS.FAST)
+    for j0, j1 in ((0, 3 * tile), (G * tile - 2048, G * tile + 2048), ((G - 2) * tile, m)):
+        want = RS.resample(mids, 0, mid, num, den, RS.FAST, window=(j0, j1), tab=tab)
+        if source_range == "longer":
+            assert all(np.count_nonzero(w) > 0.99 * w.size for w in want), "the window holds signal, not silence"
+        got = export_window(c, 3, channels, j0, j1)
+        assert got[0].size == j1 - j0 and first_bad(got, want) is None, (j0, first_bad(got, want))
+    c.close()
 
 
 # ---- 5: around the call -----------------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ import bounce_util as BU
 import clipfx_model as FX
 import oracle_ffi as O
 import resample_model as M
+import second_pass as SP
 import whitebox_amd as W
 from whitebox_amd import _ffi, synth, wav
 from whitebox_amd.engine import build_engine
@@ -122,11 +123,11 @@ def test_resample_matrix(ctx, case):
     check_stats(st, FX.measure(want), n_out, "stats_of_result")
 
 
-# ---- 2: every tile and grid seam ------------------------------------------------------------------------------------------------
+# ---- 2: every tile seam of one pass of the grid (some 280 tiles, each with a workgroup of its own; the second pass is section 3b's)
 @pytest.fixture(scope="module")
 def big():
     c = W.MixContext(4, block=128)
-    n = (1 << 18) + 3
+    n = SP.RESAMPLE_SEAMS_FRAMES
     rng = np.random.default_rng(0x5EA6)
     c.planes = [rng.uniform(-1.1, 1.1, n).astype(np.float32) for _ in range(2)]
     c.clip_upload(1, "f32", 44100, c.planes)
@@ -137,6 +138,8 @@ def big():
 
 @pytest.mark.parametrize("pair", [(44100, 48000), (48000, 44100)], ids=lambda p: "%d-%d" % p)
 def test_tile_seams(big, pair):
+    """the whole result of some 280 tiles, both directions of 44100 <-> 48000: every seam between two tiles.  No workgroup takes
+    a second tile here (tests/test_second_pass_host.py holds that against the launch's own shape)"""
     c, n = big
     rs, rd = pair
     want = model(c.planes, 0, n, rs, rd, M.GOOD)
@@ -152,15 +155,7 @@ def test_tile_seams(big, pair):
 
 
 # ---- 3: positions past 2^32 -----------------------------------------------------------------------------------------------------
-class SynthPlane:
-    """whitebox_amd/synth.py's generator, sliced lazily: the model asks for the frames a window needs"""
-
-    def __init__(self, seed, track, chan, frames, amp):
-        self.seed, self.track, self.chan, self.frames, self.amp = seed, track, chan, frames, amp
-
-    def __getitem__(self, s):
-        assert s.step is None and 0 <= s.start <= s.stop <= self.frames
-        return synth.clip_channel(self.seed, self.track, self.chan, s.stop - s.start, self.amp, first=s.start)
+SynthPlane = SP.SynthPlane
 
 
 def test_positions_past_2_to_the_32():
@@ -180,6 +175,51 @@ def test_positions_past_2_to_the_32():
         want = model([plane], 0, n, rs, rd, q, window=(j0, j1))[0]
         bad = np.flatnonzero(got[j0:j1].view(np.uint32) != want.view(np.uint32))
         assert bad.size == 0, (j0, bad[:8], bad.size)
+    c.close()
+
+
+# ---- 3b: the second pass of the grid ----------------------------------------------------------------------------------------
+def export_window(c, clip, channels, j0, j1):
+    """frames [j0, j1) of a resident clip as [channels] float32 planes, through wbx_clip_export (unclamped f32: the stored bits)"""
+    out, _ = c.clip_export(clip, "f32", channels, j0, j1 - j0, clamp=False)
+    return [np.ascontiguousarray(out.reshape(-1, channels)[:, k]) for k in range(channels)]
+
+
+@pytest.mark.parametrize("rs,rd,q,channels", [(8000, 192000, "good", 1), (22050, 192000, "fast", 2)], ids=["24-1-good-mono", "1280-147-fast-stereo"])
+def test_tiles_past_the_grid_cap(rs, rd, q, channels):
+    """Upsampling, so that the tile is 1024 outputs and the source stays small: n_out has G + 3 tiles, G the grid's cap
+    (tests/second_pass.py, from wbx_resample_launch_shape), so workgroups 0, 1 and 2 take a second tile.  L = 24 and L = 1280
+    are the two ends of the table; the stereo result ends inside a 16-byte word (every result of 24 : 1 is a multiple of 24
+    frames long).  Compared bit for bit: the first three tiles — the same workgroups' first pass —, the frames around tile G's
+    first, and everything from tile G - 2 to the end: the whole second pass and the last lane's partial store.  A conversion of
+    the same range at another quality is made and freed first: the memory the result then gets held other frames, so a
+    skipped tile shows."""
+    n, n_out, sh, G = SP.resample_case(rs, rd, q)
+    tile = sh["tile"]
+    assert sh["n_tiles"] == G + 3 > sh["grid"] == G and (channels == 1 or n_out % 4)
+    qi = _ffi.SRC_QUALITY[q]
+    c = W.MixContext(4, block=128)
+    seed, track, amp = 0x2D_9A55 + channels, 5, 0.75
+    c.clip_synth(1, "f32", channels, rs, n, seed, track, amp)
+    planes = [SynthPlane(seed, track, k, n, amp) for k in range(channels)]
+    c.clip_resample(1, 2, 0, n, rd, "best")                     # fills the memory the result is about to get
+    assert c.L.wbx_clip_free(c.h, 2) == 0
+    st = c.clip_resample(1, 3, 0, n, rd, q, stats_channels=channels if channels == 2 else 0)
+    for j0, j1 in ((0, 3 * tile), (G * tile - 2048, G * tile + 2048), ((G - 2) * tile, n_out)):
+        want = model(planes, 0, n, rs, rd, qi, window=(j0, j1))
+        got = export_window(c, 3, channels, j0, j1)
+        for k in range(channels):
+            bad = np.flatnonzero(got[k].view(np.uint32) != want[k].view(np.uint32))
+            assert bad.size == 0 and got[k].size == j1 - j0, (j0, k, bad[:8], bad.size)
+    if st is not None:                                          # stats_of_result is wbx_clip_measure of the result (pinned by test_gpu_clipfx.py)
+        again = c.clip_measure(3, channels, 0, n_out)
+        assert FX.exact_fields_equal(st, again) and all(p > 0 for p in st["peak"]), (st, again)
+        # two any-order fp64 sums of the same terms: each within check_stats' n * 2^-52 * (sum of magnitudes) of the exact
+        # sum, so within twice that of each other; the magnitudes of sum's terms add up to at most sqrt(n * sum_sq)
+        for k in range(channels):
+            mags = {"sum": math.sqrt(n_out * again["sum_sq"][k]) * (1 + 2.0 ** -40), "sum_sq": again["sum_sq"][k]}
+            for f in ("sum", "sum_sq"):
+                assert abs(st[f][k] - again[f][k]) <= 2 * n_out * 2.0 ** -52 * mags[f], (f, k, st[f][k], again[f][k])
     c.close()
 
 

@@ -18,7 +18,8 @@ import whitebox_amd as W
 from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["wbx_loudness_hop_frames", "wbx_loudness_hops", "wbx_loudness_coefficients", "wbx_loudness_gate", "wbx_clip_loudness",
+NEW = ["wbx_loudness_hop_frames", "wbx_loudness_hops", "wbx_loudness_coefficients", "wbx_loudness_gate", "wbx_true_peak_launch_shape",
+       "wbx_clip_loudness",
        "wbx_engine_loudness_sample", "wbx_engine_normalize_loudness_sample"]
 RATES = (8000, 11025, 22050, 44100, 48000, 96000, 192000)
 FIELDS = ["integrated", "gated_power", "momentary_max", "short_term_max", "range_lu", "true_peak", "hops", "blocks",

@@ -17,7 +17,7 @@ import whitebox_amd as W
 from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["wbx_pitch_mid_frames", "wbx_pitch_max_steps", "wbx_pitch_ms", "wbx_clip_pitch", "wbx_engine_pitch_sample"]
+NEW = ["wbx_pitch_mid_frames", "wbx_pitch_max_steps", "wbx_pitch_launch_shape", "wbx_pitch_ms", "wbx_clip_pitch", "wbx_engine_pitch_sample"]
 EDGE = M.MAX_FRAMES - 1                                        # the longest result
 RATIOS = [(3, 2), (2, 3), (2, 1), (1, 2), (4, 1), (1, 4), (1265, 1194), (1194, 1265), (967, 1024), (6, 4), (1280, 1279), (1279, 1280)]
 REFUSED_RATIOS = [(0, 1), (1, 0), (0, 0), (1, 1), (7, 7), (5, 1), (1, 5), (4001, 1000), (1000, 4001), (1282, 1281), (1281, 1283),
@@ -33,7 +33,7 @@ def test_symbols_are_declared_exported_and_bound():
     for n in NEW:
         assert re.search(r"\b%s\s*\(" % n, header), n
         assert hasattr(L, n) and n in _ffi.SYMBOLS, n
-    assert callable(W.pitch_mid_frames) and callable(W.pitch_ratio)
+    assert callable(W.pitch_mid_frames) and callable(W.pitch_ratio) and callable(W.pitch_launch_shape)
     assert hasattr(W.MixContext, "clip_pitch") and hasattr(W.MixContext, "pitch_ms")
     for m in ("pitch_sample", "transpose_sample"):
         assert hasattr(W.Engine, m), m

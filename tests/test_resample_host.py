@@ -17,7 +17,8 @@ import whitebox_amd as W
 from whitebox_amd import _ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["wbx_resample_plan", "wbx_resample_frames", "wbx_resample_table", "wbx_clip_resample", "wbx_engine_resample_sample"]
+NEW = ["wbx_resample_plan", "wbx_resample_frames", "wbx_resample_table", "wbx_resample_launch_shape", "wbx_clip_resample",
+       "wbx_engine_resample_sample"]
 # (src_rate, dst_rate) -> (L, M, H at GOOD)
 PLANS = {(44100, 48000): (160, 147, 24), (48000, 44100): (147, 160, 27), (96000, 48000): (1, 2, 48), (48000, 96000): (2, 1, 24),
          (48000, 32000): (2, 3, 36), (192000, 44100): (147, 640, 105), (44100, 96000): (320, 147, 24)}
@@ -31,7 +32,7 @@ def test_symbols_are_declared_exported_and_bound():
     for n in NEW:
         assert re.search(r"\b%s\s*\(" % n, header), n
         assert hasattr(L, n) and n in _ffi.SYMBOLS, n
-    assert callable(W.resample_plan) and callable(W.resample_frames) and callable(W.resample_table)
+    assert callable(W.resample_plan) and callable(W.resample_frames) and callable(W.resample_table) and callable(W.resample_launch_shape)
     assert hasattr(W.MixContext, "clip_resample") and hasattr(W.Engine, "resample_sample")
 
 

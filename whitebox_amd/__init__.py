@@ -8,6 +8,7 @@ without a gfx950 device.
 from ._ffi import WbxError, lib, lib_path  # noqa: F401
 from .engine import AudioBuffer, Engine, MixContext, Track, edit_desc  # noqa: F401
 from .engine import resample_frames, resample_plan, resample_table  # noqa: F401
+from .engine import clipfx_pass_frames, pitch_launch_shape, resample_launch_shape, true_peak_launch_shape  # noqa: F401
 from .engine import loudness_coefficients, loudness_gate, loudness_hops  # noqa: F401
 from .engine import filter_design, filter_transition  # noqa: F401
 from .engine import convolve_frames, fir_design  # noqa: F401

@@ -173,11 +173,13 @@ SYMBOLS = {
     "wbx_export_bytes": (C.c_uint64, [C.c_int, _u32, C.c_uint64]),
     "wbx_clip_export": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _vp, C.POINTER(ExportStats)]),
     "wbx_set_export_chunk": (C.c_int, [_vp, _u32]),
+    "wbx_clipfx_pass_frames": (C.c_uint64, []),
     "wbx_clip_measure": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.POINTER(ClipStats)]),
     "wbx_clip_derive": (C.c_int, [_vp, _u32, _u32, C.POINTER(ClipEditDesc), C.POINTER(ClipStats)]),
     "wbx_resample_plan": (C.c_int, [_u32, _u32, C.c_int, C.POINTER(ResampleInfo)]),
     "wbx_resample_frames": (C.c_uint64, [_u32, _u32, C.c_uint64]),
     "wbx_resample_table": (C.c_int, [_u32, _u32, C.c_int, _vp, _sz]),
+    "wbx_resample_launch_shape": (C.c_int, [_u32, _u32, C.c_int, C.c_uint64] + [C.POINTER(_u32)] * 4),
     "wbx_clip_resample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, C.POINTER(ClipStats)]),
     "wbx_splice_plan": (C.c_int, [_u32, C.c_uint64, C.POINTER(SplicePart), _u32, C.POINTER(SpliceSource), _u32,
                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _sz, _vp, _sz]),
@@ -185,6 +187,7 @@ SYMBOLS = {
     "wbx_loudness_hop_frames": (_u32, [_u32]),
     "wbx_loudness_hops": (C.c_uint64, [_u32, C.c_uint64]),
     "wbx_loudness_coefficients": (C.c_int, [_u32, _vp]),
+    "wbx_true_peak_launch_shape": (C.c_int, [_u32, C.c_uint64] + [C.POINTER(_u32)] * 3),
     "wbx_loudness_gate": (C.c_int, [_u32, C.c_uint64, _u32, _vp, C.POINTER(Loudness)]),
     "wbx_f0_hops": (C.c_uint64, [C.c_uint64, _u32, _u32, _u32]),
     "wbx_f0_check": (C.c_int, [C.c_uint64, _u32, _u32, _u32, _u32, _d, C.c_int, _sz]),
@@ -239,6 +242,7 @@ SYMBOLS = {
                                    C.POINTER(ClipStats)]),
     "wbx_pitch_mid_frames": (C.c_uint64, [C.c_uint64, _u32, _u32]),
     "wbx_pitch_max_steps": (_u32, []),
+    "wbx_pitch_launch_shape": (C.c_int, [_u32, _u32, C.c_int, C.c_uint64] + [C.POINTER(_u32)] * 4),
     "wbx_pitch_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_pitch": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32, _vp, _sz,
                                  C.POINTER(PitchInfo), C.POINTER(ClipStats)]),

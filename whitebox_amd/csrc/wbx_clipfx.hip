@@ -197,9 +197,11 @@ void launch_rev(const ClipFxArgs& a, dim3 grid, hipStream_t s) {
 
 }  // namespace
 
+constexpr uint32_t kClipFxGroupFrames = 2048, kClipFxGridMax = 4096;   // 4 waves of 512 frames per workgroup and stride
+
 // 10 instances: (1,1) (2,2) (2,1) (1,2) x forward / reversed with the store, (1,1) (2,2) forward without (measure)
 void launch_clipfx(const ClipFxArgs& a, hipStream_t s) {
-  const dim3 grid(std::min<uint32_t>((a.n_frames + 2047u) / 2048u, 4096u));   // 4 waves of 512 frames per workgroup and stride
+  const dim3 grid(std::min<uint32_t>((a.n_frames + kClipFxGroupFrames - 1u) / kClipFxGroupFrames, kClipFxGridMax));
   if (!a.dst[0]) {
     if (a.src_channels == 2u) launch_rev<2, 2, false>(a, grid, s);
     else launch_rev<1, 1, false>(a, grid, s);
@@ -378,6 +380,8 @@ wbx_status clipfx_derive_run(wbx_ctx* c, const ClipSrc& src, uint32_t sample_rat
 }
 
 }  // namespace wbx
+
+extern "C" uint64_t wbx_clipfx_pass_frames(void) { return (uint64_t)wbx::kClipFxGridMax * wbx::kClipFxGroupFrames; }
 
 extern "C" wbx_status wbx_clip_measure(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out) {
   if (!c) return WBX_ERR_INVALID;

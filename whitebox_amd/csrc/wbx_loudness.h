@@ -24,6 +24,14 @@ inline bool loudness_rate_ok(uint32_t rate) { return rate >= kLoudMinRate && rat
 inline uint32_t loudness_hop_frames(uint32_t rate) { return (rate + 5u) / 10u; }
 inline uint32_t loudness_oversampling(uint32_t rate) { return rate < 96000u ? 4u : rate < 192000u ? 2u : 1u; }
 
+// true_peak_kernel's launch: tiles of kPeakTile oversampled outputs (a multiple of every factor: a tile starts at phase 0),
+// a capped grid that the kernel strides over the tiles by
+constexpr uint32_t kPeakTile = 1024, kPeakGridMax = 1u << 16;
+inline void true_peak_launch_shape(uint32_t factor, uint32_t n_in, uint32_t* n_tiles, uint32_t* grid) {
+  *n_tiles = (n_in * factor + kPeakTile - 1u) / kPeakTile;     // (n_in * factor < 2^31 - 16)
+  *grid = *n_tiles < kPeakGridMax ? *n_tiles : kPeakGridMax;
+}
+
 // K = tan(pi * f0 / rate): y = (pi * f0) / rate; sin and cos as alternating series in Horner form over y*y; one division
 inline double loudness_tan(double f0, uint32_t rate) {
   const double y = (3.141592653589793 * f0) / (double)rate;

@@ -32,7 +32,7 @@ namespace wbx {
 namespace {
 
 constexpr uint32_t kRowWords = 65;                             // a staged row: 64 frames and one word of padding
-constexpr uint32_t kPeakTile = 1024, kPeakSpanMax = 560, kPeakGridMax = 1u << 16;   // span: 1024 / 2 + 48 at factor 2
+constexpr uint32_t kPeakSpanMax = 560;                         // 1024 / 2 + 48 at factor 2 (kPeakTile: wbx_loudness.h)
 
 struct Biquad {
   double x1 = 0.0, x2 = 0.0, y1 = 0.0, y2 = 0.0;
@@ -168,8 +168,9 @@ void launch_loudness(const LoudnessArgs& a, hipStream_t s) {
 }
 
 void launch_true_peak(const TruePeakArgs& a, hipStream_t s) {
-  const uint32_t n_tiles = (a.n_in * a.L + kPeakTile - 1u) / kPeakTile;
-  const dim3 grid(std::min(n_tiles, kPeakGridMax));
+  uint32_t n_tiles = 0, blocks = 0;
+  true_peak_launch_shape(a.L, a.n_in, &n_tiles, &blocks);
+  const dim3 grid(blocks);
   if (a.channels == 2u) hipLaunchKernelGGL((true_peak_kernel<2>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((true_peak_kernel<1>), grid, dim3(256), 0, s, a);
 }
@@ -269,6 +270,17 @@ extern "C" uint32_t wbx_loudness_hop_frames(uint32_t rate) { return loudness_rat
 
 extern "C" uint64_t wbx_loudness_hops(uint32_t rate, uint64_t n_frames) {
   return loudness_rate_ok(rate) ? n_frames / loudness_hop_frames(rate) : 0u;
+}
+
+extern "C" wbx_status wbx_true_peak_launch_shape(uint32_t rate, uint64_t n_frames, uint32_t* factor, uint32_t* n_tiles, uint32_t* grid) {
+  if (!factor || !n_tiles || !grid || n_frames == 0) return WBX_ERR_INVALID;
+  if (!loudness_rate_ok(rate)) return WBX_ERR_UNSUPPORTED;
+  const uint32_t f = loudness_oversampling(rate);
+  if (n_frames * f >= kResampleMaxFrames) return WBX_ERR_UNSUPPORTED;
+  *factor = f;
+  *n_tiles = *grid = 0;                                        // factor 1: the sample peak is the measure pass, no tiles
+  if (f > 1u) true_peak_launch_shape(f, (uint32_t)n_frames, n_tiles, grid);
+  return WBX_OK;
 }
 
 extern "C" wbx_status wbx_loudness_coefficients(uint32_t rate, double out[10]) {

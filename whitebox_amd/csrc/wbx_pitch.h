@@ -70,16 +70,9 @@ inline wbx_status pitch_check_args(const PitchCall& k, ResamplePlan* plan, Stret
   return WBX_OK;
 }
 
-// pitch_kernel's tile, as resample_kernel's: the most outputs (a multiple of 4, <= 1024) whose span of the intermediate,
-// ((L-1) + (tile-1) M) / L + T frames, fits 4096 floats.  T <= 512 bounds M / L by 256 / 12, so tile >= 168
-constexpr uint32_t kPitchTileMax = 1024, kPitchSpanMax = 4096;
-inline uint32_t pitch_tile(uint32_t L, uint32_t M, uint32_t T) {
-  const uint64_t tm1 = (uint64_t)(kPitchSpanMax - T) * L / M;
-  const uint64_t t = (tm1 + 1u) & ~3ull;
-  return (uint32_t)(t < kPitchTileMax ? t : kPitchTileMax);
-}
-inline uint32_t pitch_span(uint32_t L, uint32_t M, uint32_t T, uint32_t tile) {
-  return (uint32_t)(((uint64_t)(L - 1u) + (uint64_t)(tile - 1u) * M) / L) + T;
-}
+// pitch_kernel's tile and its span of the intermediate are the conversion's: one formula, resample_launch_shape
+// (wbx_resample.h), which launch_pitch calls for the grid as well.  The tile depends on (L, M, T) alone
+inline uint32_t pitch_tile(uint32_t L, uint32_t M, uint32_t T) { return resample_launch_shape(L, M, T, 1u).tile; }
+inline uint32_t pitch_span(uint32_t L, uint32_t M, uint32_t T, uint32_t tile) { return resample_span(L, M, T, tile); }
 
 }  // namespace wbx

@@ -24,8 +24,6 @@ namespace wbx {
 
 namespace {
 
-constexpr uint32_t kGridMax = 1u << 16;
-
 __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
 // x[c][g] of the stretch's text: zero outside [0, n), what is not finite as 0.0
 __device__ __forceinline__ double x_at(const float* __restrict__ row, int64_t g, int64_t n) {
@@ -114,10 +112,9 @@ __global__ void __launch_bounds__(256) pitch_kernel(PitchArgs a) {
 }  // namespace
 
 void launch_pitch(PitchArgs a, hipStream_t s) {
-  a.tile = pitch_tile(a.L, a.M, a.T);
-  a.span = pitch_span(a.L, a.M, a.T, a.tile);
-  a.n_tiles = (a.n_out + a.tile - 1u) / a.tile;
-  const dim3 grid(std::min(a.n_tiles, kGridMax));
+  const ResampleShape sh = resample_launch_shape(a.L, a.M, a.T, a.n_out);   // the conversion's own tile, span and grid
+  a.tile = sh.tile, a.span = sh.span, a.n_tiles = sh.n_tiles;
+  const dim3 grid(sh.grid);
   const size_t lds = (size_t)a.channels * a.span * sizeof(float);
   if (a.channels == 2u) hipLaunchKernelGGL((pitch_kernel<2>), grid, dim3(256), lds, s, a);
   else hipLaunchKernelGGL((pitch_kernel<1>), grid, dim3(256), lds, s, a);
@@ -246,6 +243,22 @@ wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchC
 
 extern "C" uint64_t wbx_pitch_mid_frames(uint64_t out_frames, uint32_t num, uint32_t den) { return wbx::pitch_mid_frames(out_frames, num, den); }
 extern "C" uint32_t wbx_pitch_max_steps(void) { return wbx::kPitchMaxSteps; }
+
+extern "C" wbx_status wbx_pitch_launch_shape(uint32_t num, uint32_t den, int quality, uint64_t out_frames, uint32_t* tile, uint32_t* span,
+                                             uint32_t* n_tiles, uint32_t* grid) {
+  using namespace wbx;
+  uint32_t L = 0, M = 0;
+  ResamplePlan p;
+  const char* msg = "";
+  if (out_frames == 0 || out_frames >= kPitchMaxFrames || !tile || !span || !n_tiles || !grid) return WBX_ERR_INVALID;
+  if (num == 0 || den == 0) return WBX_ERR_INVALID;
+  if (!pitch_ratio_ok(num, den, &L, &M)) return L == M ? WBX_ERR_INVALID : WBX_ERR_UNSUPPORTED;   // (a ratio of 1 is the call's INVALID)
+  const wbx_status st = resample_plan(num, den, quality, &p, &msg);
+  if (st != WBX_OK) return st;
+  const ResampleShape sh = resample_launch_shape(p.L, p.M, p.T, (uint32_t)out_frames);
+  *tile = sh.tile, *span = sh.span, *n_tiles = sh.n_tiles, *grid = sh.grid;
+  return WBX_OK;
+}
 
 extern "C" wbx_status wbx_pitch_ms(wbx_ctx* c, double* out) {
   using namespace wbx;

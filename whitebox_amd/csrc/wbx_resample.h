@@ -84,6 +84,27 @@ inline uint64_t resample_out_frames(uint32_t L, uint32_t M, uint64_t n_frames) {
   return n_out < kResampleMaxFrames ? (uint64_t)n_out : 0;
 }
 
+// resample_kernel's launch (pitch_kernel's too): the tile is the most outputs (a multiple of 4, <= 1024) whose source span,
+// ((L-1) + (tile-1) M) / L + T frames, fits 4096 floats — T <= 512 bounds M / L by 256 / 12, so tile >= 168 —; the grid is
+// capped and the kernel strides over the tiles by it
+constexpr uint32_t kResampleTileMax = 1024, kResampleSpanMax = 4096, kResampleGridMax = 1u << 16;
+struct ResampleShape {
+  uint32_t tile, span, n_tiles, grid;
+};
+inline uint32_t resample_span(uint32_t L, uint32_t M, uint32_t T, uint32_t tile) {
+  return (uint32_t)(((uint64_t)(L - 1u) + (uint64_t)(tile - 1u) * M) / L) + T;
+}
+inline ResampleShape resample_launch_shape(uint32_t L, uint32_t M, uint32_t T, uint32_t n_out) {
+  ResampleShape s;
+  const uint64_t tm1 = (uint64_t)(kResampleSpanMax - T) * L / M;
+  const uint64_t t = (tm1 + 1u) & ~3ull;
+  s.tile = (uint32_t)(t < kResampleTileMax ? t : kResampleTileMax);
+  s.span = resample_span(L, M, T, s.tile);
+  s.n_tiles = (uint32_t)(((uint64_t)n_out + s.tile - 1u) / s.tile);
+  s.grid = s.n_tiles < kResampleGridMax ? s.n_tiles : kResampleGridMax;
+  return s;
+}
+
 // sin(pi x): x mod 2 reduced exactly to [0, 1/2], ONE multiplication by pi, the alternating series in Horner form
 inline double resample_sinpi(double x) {
   double sign = 1.0;

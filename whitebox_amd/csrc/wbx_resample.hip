@@ -28,8 +28,6 @@ namespace wbx {
 
 namespace {
 
-constexpr uint32_t kTileMax = 1024, kSpanMax = 4096, kGridMax = 1u << 16;
-
 template <int CH>
 __global__ void __launch_bounds__(256) resample_kernel(ResampleArgs a) {
   extern __shared__ __attribute__((aligned(16))) float xs[];   // [CH][span]
@@ -95,14 +93,11 @@ __global__ void __launch_bounds__(256) resample_kernel(ResampleArgs a) {
 
 }  // namespace
 
-// the tile: the most outputs (a multiple of 4, <= 1024) whose span ((L-1) + (tile-1) * M) / L + T fits kSpanMax floats.
-// T <= 512 bounds M / L by 256 / 12, so tile >= 168.
+// the tile, its span and the capped grid: resample_launch_shape (wbx_resample.h)
 void launch_resample(ResampleArgs a, hipStream_t s) {
-  const uint64_t tm1 = (uint64_t)(kSpanMax - a.T) * a.L / a.M;
-  a.tile = (uint32_t)std::min<uint64_t>(kTileMax, (tm1 + 1u) & ~3ull);
-  a.span = (uint32_t)(((uint64_t)(a.L - 1u) + (uint64_t)(a.tile - 1u) * a.M) / a.L) + a.T;
-  a.n_tiles = (a.n_out + a.tile - 1u) / a.tile;
-  const dim3 grid(std::min(a.n_tiles, kGridMax));
+  const ResampleShape sh = resample_launch_shape(a.L, a.M, a.T, a.n_out);
+  a.tile = sh.tile, a.span = sh.span, a.n_tiles = sh.n_tiles;
+  const dim3 grid(sh.grid);
   const size_t lds = (size_t)a.channels * a.span * sizeof(float);
   if (a.channels == 2u) hipLaunchKernelGGL((resample_kernel<2>), grid, dim3(256), lds, s, a);
   else hipLaunchKernelGGL((resample_kernel<1>), grid, dim3(256), lds, s, a);
@@ -197,6 +192,18 @@ extern "C" wbx_status wbx_resample_plan(uint32_t src_rate, uint32_t dst_rate, in
   const wbx_status st = resample_plan(src_rate, dst_rate, quality, &p, &msg);
   if (st != WBX_OK) return st;
   *out = wbx_resample_info{p.L, p.M, p.H, p.T, (uint64_t)p.L * p.T};
+  return WBX_OK;
+}
+
+extern "C" wbx_status wbx_resample_launch_shape(uint32_t src_rate, uint32_t dst_rate, int quality, uint64_t n_out, uint32_t* tile,
+                                                uint32_t* span, uint32_t* n_tiles, uint32_t* grid) {
+  ResamplePlan p;
+  const char* msg = "";
+  const wbx_status st = resample_plan(src_rate, dst_rate, quality, &p, &msg);
+  if (st != WBX_OK) return st;
+  if (n_out == 0 || n_out >= kResampleMaxFrames || !tile || !span || !n_tiles || !grid) return WBX_ERR_INVALID;
+  const ResampleShape sh = resample_launch_shape(p.L, p.M, p.T, (uint32_t)n_out);
+  *tile = sh.tile, *span = sh.span, *n_tiles = sh.n_tiles, *grid = sh.grid;
   return WBX_OK;
 }
 

@@ -146,6 +146,24 @@ def resample_frames(src_rate: int, dst_rate: int, n_frames: int) -> int:
     return int(_ffi.lib().wbx_resample_frames(src_rate, dst_rate, n_frames))
 
 
+def _launch_shape(fn, what, *args) -> dict:
+    v = [C.c_uint32() for _ in range(4)]
+    _check(fn(*args, *[C.byref(x) for x in v]), what)
+    return dict(zip(("tile", "span", "n_tiles", "grid"), (x.value for x in v)))
+
+
+def clipfx_pass_frames() -> int:
+    """wbx_clipfx_pass_frames (host-only): the frames one pass of the measure / derive kernel's capped grid covers"""
+    return int(_ffi.lib().wbx_clipfx_pass_frames())
+
+
+def resample_launch_shape(src_rate: int, dst_rate: int, quality, n_out: int) -> dict:
+    """wbx_resample_launch_shape (host-only): {"tile", "span", "n_tiles", "grid"} of the conversion's launch for n_out output
+    frames; n_tiles > grid means the grid's workgroups take a second pass over the tiles"""
+    return _launch_shape(_ffi.lib().wbx_resample_launch_shape, "wbx_resample_launch_shape", src_rate, dst_rate,
+                         _ffi.SRC_QUALITY.get(quality, quality), n_out)
+
+
 def resample_table(src_rate: int, dst_rate: int, quality="good") -> np.ndarray:
     """wbx_resample_table (host-only): the fp32 coefficients in phase order, [L][taps]"""
     p = resample_plan(src_rate, dst_rate, quality)
@@ -282,6 +300,12 @@ def pitch_mid_frames(out_frames: int, num: int, den: int) -> int:
     return int(_ffi.lib().wbx_pitch_mid_frames(out_frames, num, den))
 
 
+def pitch_launch_shape(num: int, den: int, quality, out_frames: int) -> dict:
+    """wbx_pitch_launch_shape (host-only): resample_launch_shape of a pitch call's last launch"""
+    return _launch_shape(_ffi.lib().wbx_pitch_launch_shape, "wbx_pitch_launch_shape", num, den,
+                         _ffi.SRC_QUALITY.get(quality, quality), out_frames)
+
+
 def pitch_ratio(semitones: float, cents: float = 0.0) -> tuple:
     """(num, den) for a transposition by `semitones` and `cents` in equal temperament: the fraction with a denominator of
     at most 1280 nearest to 2 ** ((100 * semitones + cents) / 1200) — within 0.4 cent for every whole cent of two octaves
@@ -352,6 +376,13 @@ def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
     return int(_ffi.lib().wbx_loudness_hops(rate, n_frames))
+
+
+def true_peak_launch_shape(rate: int, n_frames: int) -> dict:
+    """wbx_true_peak_launch_shape (host-only): {"factor", "n_tiles", "grid"} of the true peak's launch over n_frames at `rate`"""
+    v = [C.c_uint32() for _ in range(3)]
+    _check(_ffi.lib().wbx_true_peak_launch_shape(rate, n_frames, *[C.byref(x) for x in v]), "wbx_true_peak_launch_shape")
+    return dict(zip(("factor", "n_tiles", "grid"), (x.value for x in v)))
 
 
 def loudness_coefficients(rate: int) -> np.ndarray:
