@@ -1039,6 +1039,85 @@ wbx_status wbx_clip_tempo(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uin
                           double floor_power, uint32_t window_hops, uint32_t step_hops, uint32_t lag_min, uint32_t lag_max,
                           double threshold, wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info);
 
+/* Seeing a clip's spectrum: the power of frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2
+ * channels at n_bins frequencies, one row of cells per hop, as a DIRECT transform — ascending dot products of the clip's
+ * frames with the rows of a host-built basis that lives in the pool as an ordinary mono F32 clip — without the samples
+ * leaving HBM.  No FFT (its rounding depends on its factorisation), no sin and no log on the device: bins may sit at any
+ * frequencies (linear, logarithmic for a constant-Q view, semitones for a chromagram, a few bands), each with its own window
+ * length, and the cells are reproducible bit for bit.  A MEASUREMENT, like wbx_clip_loudness and wbx_clip_f0: nothing is
+ * allocated in the pool and no clip is created.  No reference counterpart.  The arithmetic is part of the interface;
+ * tests/spectrum_model.py restates it in numpy, operation for operation, and the cells equal it BIT FOR BIT.  Every operator
+ * below is ONE IEEE fp64 operation in the order written; nothing is fused unless stated.
+ *   input     channel 0 or 1: d[g] = the channel's fp32 sample; WBX_SPECTRUM_MID: "Tracking a clip's pitch"'s detector as it
+ *             is — mono the sample, stereo d = (float)(0.5 * ((double)L + (double)R)).  A sample that is not finite reads as
+ *             0 (each channel's before the mid is formed).  Nothing beside the range is ever read
+ *   shape     W = window_frames, a multiple of 4 in [32, 8192]; H = hop_frames in [1, 65536]; B = n_bins in [1, 1024] with
+ *             B * W <= 2^21.  hops = n >= W ? (n - W) / H + 1 : 0 (wbx_spectrum_hops): only complete frames count, and
+ *             hops == 0 is no error.  n in [1, 2^31 - 16)
+ *   basis     a resident MONO F32 clip of exactly 2 * B * W frames (wbx_spectrum_basis_frames; 16 MB at most), i-major:
+ *             frame (i * B + b) * 2 holds C_b[i], the next frame S_b[i] — consecutive lanes that own consecutive bins read
+ *             consecutive words.  The call does not inspect its words: a row with non-finite words gives non-finite or
+ *             otherwise unspecified powers in its own bin, and nothing else is affected
+ *   cell      for hop h and bin b, from re = im = 0.0, for i = 0 .. W - 1 ascending:
+ *             re = re + d[h H + i] * C_b[i];  im = im + d[h H + i] * S_b[i]
+ *             (both factors are fp32 values, so each product is exact in fp64 and an fma IS the same thing);
+ *             p = (re * re) + (im * im): two rounded products and one rounded sum, NOT fused;  power[h][b] = (float)p
+ *   output    hop-major float[hops][B] in host memory.  No sqrt and no log: magnitudes and decibels are the caller's business
+ * wbx_spectrum_basis (host-only, no libm: "Converting a clip's sample rate"'s sinpi and I0) writes such a basis into
+ * out[2 * B * W]: bin b has frequency freqs[b] in [0, 0.5] cycles per frame and its own window of L_b = lengths[b] frames in
+ * [4, W] (lengths NULL: all W), centred in W at offset (W - L_b) / 2 and zero outside.  For j = 0 .. L_b - 1:
+ *             w[j] = 1.0 (WBX_WINDOW_RECT); s * s with s = sinpi(((double)j + 0.5) / (double)L) (WBX_WINDOW_HANN, "Stretching a
+ *             clip"'s form); I0(beta * sqrt(max(0.0, 1.0 - u * u))) / I0(beta) with u = ((double)(2 j + 1) - (double)L) / (double)L
+ *             (WBX_WINDOW_KAISER, kaiser_beta in [0, 20]; ignored by the other kinds);
+ *             sum = the ascending fp64 sum of w; wn = w[j] / sum — so a full-scale sine on a bin has power 0.25;
+ *             t = freqs[b] * (double)j; t = t - floor(t); C = (float)(wn * sinpi(2.0 * t + 0.5)); S = (float)(0.0 - (wn * sinpi(2.0 * t)))
+ *             at i = (W - L_b) / 2 + j.
+ * wbx_spectrum_log_freqs (host-only): out[b] = f_min / exp2(0.0 - ((double)b / bins_per_octave)) with "Dynamics of a clip"'s
+ * plain-fp64 exp2 — f_min * 2^(b / bins_per_octave) without libm; f_min in (0, 0.5], bins_per_octave positive and finite;
+ * what exceeds 0.5 becomes 0.5 and is counted into *clamped (may be NULL).
+ * The call runs on the edits' stream behind wbx_clip_derive's ordering, one edit or measurement at a time, in launches of
+ * at most wbx_spectrum_launch_hops(window_frames, n_bins) hops — whole thirty-twos such that hops * W * 2 B stays within
+ * wbx_spectrum_launch_terms() and the device-side stage for a launch's cells within 2^22 cells — each launch's cells copied
+ * out before the next; it returns when power_out holds all of them.  info (may be NULL): hops; bins; launches.
+ * Refused before any device call, power_out and info untouched; the sizes are judged before the clips are looked at, in this
+ * order.  WBX_ERR_INVALID: an unknown clip; n_frames of 0 or >= 2^31 - 16; a channel that is none of the three; a window,
+ * bin count, product or hop outside the ranges above; a NULL power_out with hops > 0; cells_cap < hops * B.
+ * WBX_ERR_UNSUPPORTED: hops > 2^20; hops * B > wbx_spectrum_max_cells() (2^25: 128 MB at the host).  Then the source —
+ * WBX_ERR_UNSUPPORTED: not F32 or more than 2 channels; WBX_ERR_INVALID: channel 1 of a mono clip, a range past the clip.
+ * Then the basis — WBX_ERR_INVALID: an unknown clip; WBX_ERR_UNSUPPORTED: not F32 or not mono; WBX_ERR_INVALID: a length
+ * other than 2 * B * W frames.
+ * Host-only, no device (wbx_spectrum.h, which a C++ compiler takes alone): wbx_spectrum_hops (0 for a window or hop the
+ * call refuses), wbx_spectrum_check (the argument check above without the clips: its status), wbx_spectrum_max_cells,
+ * wbx_spectrum_launch_terms, wbx_spectrum_launch_hops and wbx_spectrum_basis_frames (0 for a shape the call refuses),
+ * wbx_spectrum_basis and wbx_spectrum_log_freqs (WBX_ERR_INVALID for arguments outside the ranges above, NaNs and NULL
+ * included; out untouched).
+ * wbx_spectrum_ms: device milliseconds of the launches of the context's last completed spectrum call (layer 1's or layer
+ * 2's), each between two events on the edits' stream, added up; the copies between them do not count.  WBX_ERR_INVALID for
+ * NULL arguments or when none has completed.  For tools/bench_spectrum.py; nothing else reads it.
+ * Not offered: phase output or complex cells, a reassigned or phase-vocoder spectrum, anything with an FFT, a spectrum at
+ * render time or on live tracks, more than 2 channels, per-channel spectra in one call. */
+#define WBX_SPECTRUM_MID 2u
+enum { WBX_WINDOW_RECT = 0, WBX_WINDOW_HANN = 1, WBX_WINDOW_KAISER = 2 };
+typedef struct wbx_spectrum_info {      /* 16 bytes */
+  uint64_t hops;
+  uint32_t bins;
+  uint32_t launches;
+} wbx_spectrum_info;
+uint64_t wbx_spectrum_hops(uint64_t n_frames, uint32_t window_frames, uint32_t hop_frames);
+wbx_status wbx_spectrum_check(uint64_t n_frames, uint32_t channel, uint32_t window_frames, uint32_t n_bins, uint32_t hop_frames,
+                              int has_power_out, size_t cells_cap);
+uint64_t wbx_spectrum_max_cells(void);
+uint64_t wbx_spectrum_launch_terms(void);
+uint32_t wbx_spectrum_launch_hops(uint32_t window_frames, uint32_t n_bins);
+uint64_t wbx_spectrum_basis_frames(uint32_t window_frames, uint32_t n_bins);
+wbx_status wbx_spectrum_basis(uint32_t window_frames, uint32_t n_bins, const double* freqs, const uint32_t* lengths,
+                              int window_kind, double kaiser_beta, float* out);
+wbx_status wbx_spectrum_log_freqs(double f_min, double bins_per_octave, uint32_t n_bins, double* out, uint32_t* clamped);
+wbx_status wbx_spectrum_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_spectrum(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t channel,
+                             uint32_t basis_clip, uint32_t window_frames, uint32_t n_bins, uint32_t hop_frames, float* power_out,
+                             size_t cells_cap, wbx_spectrum_info* info);
+
 /* Waveform peak mip-maps of a resident clip: WaveformVisual::create + summarize_for_mipmaps_impl<T>
  * (src/gfx/waveform_visual.cpp:9-246).  quality: 0 = Low (int8_t), 1 = High (int16_t) (waveform_visual.h:11-14).
  * Level l holds, per channel, mip_data_count(l) values = ordered (first, second) min/max pairs of chunks of
@@ -1516,6 +1595,13 @@ wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t firs
 wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
                                 uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold,
                                 wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info);
+/* wbx_clip_spectrum of engine samples, under wbx_engine_f0_sample's rules: the sample AND the basis sample are pinned for
+ * the call (one id where they are the same), so wbx_engine_delete_sample refuses either meanwhile; the editor lock is held
+ * only to validate, pin, order the stream and unpin, never across the device waits, so the call may run beside the audio
+ * thread.  Arguments and refusals are wbx_clip_spectrum's. */
+wbx_status wbx_engine_spectrum_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t channel,
+                                      uint32_t basis_sample, uint32_t window_frames, uint32_t n_bins, uint32_t hop_frames,
+                                      float* power_out, size_t cells_cap, wbx_spectrum_info* info);
 /* wbx_clip_onsets and wbx_clip_tempo of an engine sample, under wbx_engine_f0_sample's rules: pinned for the call, the
  * editor lock held only to validate and pin.  Arguments and refusals are the clip calls'. */
 wbx_status wbx_engine_onsets_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,

@@ -421,6 +421,21 @@ struct Engine {
           "f0_sample");
     return out;
   }
+  // The spectrum of a sample's range where it lives (wbx.h "Seeing a clip's spectrum"): hop-major power[hops][n_bins] at the
+  // frequencies of basis_sample, a mono F32 sample of wbx_spectrum_basis's 2 * n_bins * window_frames words.  channel 0, 1
+  // or WBX_SPECTRUM_MID.  Both samples are pinned for the call.  Editing thread, like measure_sample.
+  std::vector<float> spectrum_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t channel, uint32_t basis_sample,
+                                     uint32_t window_frames, uint32_t n_bins, uint32_t hop_frames, wbx_spectrum_info* info = nullptr) {
+    const uint64_t hops = wbx_spectrum_hops(n_frames, window_frames, hop_frames);
+    // the call's own argument check first, so that a refused call allocates no cells
+    const wbx_status pre = wbx_spectrum_check(n_frames, channel, window_frames, n_bins, hop_frames, 1, (size_t)(hops * n_bins));
+    if (pre != WBX_OK) throw Error(pre, std::string("spectrum_sample: ") + wbx_status_string(pre));
+    std::vector<float> out((size_t)(hops * n_bins));
+    check(wbx_engine_spectrum_sample(h, sample, first_frame, n_frames, channel, basis_sample, window_frames, n_bins, hop_frames,
+                                     out.empty() ? nullptr : out.data(), out.size(), info),
+          "spectrum_sample");
+    return out;
+  }
   // The onsets of a sample's range where it lives (wbx.h "Finding a clip's onsets and tempo"): one wbx_onset_frame per hop
   // of hop_frames frames (a multiple of 64) — the two energies, the onset strength and whether the hop is an onset, whose
   // frame is then first_frame + h * hop_frames.  The sample is pinned for the call.  Editing thread, like measure_sample.

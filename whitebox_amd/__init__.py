@@ -17,5 +17,6 @@ from .engine import dynamics_check, dynamics_lookup, dynamics_table  # noqa: F40
 from .engine import stretch_anchor, stretch_steps, stretch_window  # noqa: F401
 from .engine import pitch_mid_frames, pitch_ratio  # noqa: F401
 from .engine import F0_DTYPE, f0_hops  # noqa: F401
+from .engine import SPECTRUM_MID, spectrum_basis, spectrum_hops, spectrum_log_freqs  # noqa: F401
 from .engine import ONSET_DTYPE, onset_hops  # noqa: F401
 from .engine import splice_part, splice_plan  # noqa: F401

@@ -114,6 +114,14 @@ class OnsetInfo(C.Structure):          # wbx_onset_info, 24 bytes
     _fields_ = [("hops", C.c_uint64), ("onsets", C.c_uint64), ("launches", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class SpectrumInfo(C.Structure):       # wbx_spectrum_info, 16 bytes
+    _fields_ = [("hops", C.c_uint64), ("bins", C.c_uint32), ("launches", C.c_uint32)]
+
+
+SPECTRUM_MID = 2
+WINDOW_KIND = {"rect": 0, "hann": 1, "kaiser": 2}
+
+
 class SplicePart(C.Structure):         # wbx_splice_part, 64 bytes
     _fields_ = [("src_clip", C.c_uint32), ("flags", C.c_uint32), ("first_frame", C.c_uint64), ("n_frames", C.c_uint64),
                 ("at", C.c_uint64), ("channel_mode", C.c_int32), ("gain", C.c_float), ("fade_in", C.c_uint64),
@@ -196,6 +204,16 @@ SYMBOLS = {
     "wbx_f0_launch_hops": (_u32, [_u32, _u32]),
     "wbx_f0_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_f0": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
+    "wbx_spectrum_hops": (C.c_uint64, [C.c_uint64, _u32, _u32]),
+    "wbx_spectrum_check": (C.c_int, [C.c_uint64, _u32, _u32, _u32, _u32, C.c_int, _sz]),
+    "wbx_spectrum_max_cells": (C.c_uint64, []),
+    "wbx_spectrum_launch_terms": (C.c_uint64, []),
+    "wbx_spectrum_launch_hops": (_u32, [_u32, _u32]),
+    "wbx_spectrum_basis_frames": (C.c_uint64, [_u32, _u32]),
+    "wbx_spectrum_basis": (C.c_int, [_u32, _u32, _vp, _vp, C.c_int, _d, _vp]),
+    "wbx_spectrum_log_freqs": (C.c_int, [_d, _d, _u32, _vp, C.POINTER(_u32)]),
+    "wbx_spectrum_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_spectrum": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _u32, _vp, _sz, C.POINTER(SpectrumInfo)]),
     "wbx_onset_hops": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_onset_check": (C.c_int, [C.c_uint64, _u32, _d, _d, _d, _u32, _u32, C.c_int, _sz]),
     "wbx_onset_max_hops": (C.c_uint64, []),
@@ -350,6 +368,8 @@ SYMBOLS = {
     "wbx_engine_pitch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32,
                                           C.POINTER(PitchInfo), C.POINTER(_u32)]),
     "wbx_engine_f0_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
+    "wbx_engine_spectrum_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _u32, _vp, _sz,
+                                             C.POINTER(SpectrumInfo)]),
     "wbx_engine_onsets_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _d, _d, _u32, _u32, _vp, _sz,
                                            C.POINTER(OnsetInfo)]),
     "wbx_engine_tempo_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _u32, _u32, _u32, _u32, _d, _vp, _sz,

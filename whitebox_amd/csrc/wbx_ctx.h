@@ -28,6 +28,7 @@
 #include "wbx_stretch.h"
 #include "wbx_pitch.h"
 #include "wbx_f0.h"
+#include "wbx_spectrum.h"
 #include "wbx_onset.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
@@ -284,6 +285,20 @@ struct F0Args {
   uint32_t channels;           // 1 or 2
 };
 void launch_f0(const F0Args& a, hipStream_t s);
+// seeing a clip's spectrum (wbx_spectrum.hip): one launch computes the cells of hops [hop0, hop1) of the call, F consecutive
+// hops x 64 K G bins per workgroup
+struct SpecArgs {
+  const float* src[2];         // the row(s) the detector reads, at the RANGE's first frame (src[1] only where mid is set)
+  const float* basis;          // the basis clip's row: [W][B][2]
+  float* out;                  // device: the cells of THIS launch, [hop1 - hop0][B]
+  uint32_t n;                  // frames of the range (< 2^31 - 16)
+  uint32_t W, B, H;            // window, bins, hop
+  uint32_t hop0, hop1;         // the hops of this launch
+  uint32_t K, G, F;            // bins per lane (1 or 2), waves over the bins (1, 2 or 4), hops per workgroup (wbx_spectrum.h spectrum_shape)
+  uint32_t chunk, stride;      // terms staged at a time, words between the workgroup's hops in LDS
+  uint32_t mid;                // 1: d = (float)(0.5 * (src[0] + src[1])); 0: d = src[0]
+};
+void launch_spectrum(const SpecArgs& a, hipStream_t s);
 // finding a clip's onsets (wbx_onset.hip): the energy pass — a wave per hop, striding over the hops by the grid — and the
 // novelty pass, a lane per hop
 struct alignas(16) OnsetEnergy {   // what the energy pass leaves per hop: one 16-byte store
@@ -476,6 +491,16 @@ struct F0Stage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_spectrum's cells of one launch on the device and in pinned memory (at most 2^22 x 4 bytes each) — grown on
+// demand, freed with the context — and the timing events of a launch, whose times are summed
+struct SpecStage {
+  DevBuf<float> d_cells;
+  PinnedBuf<float> h_cells;
+  Event mark[2];               // (timing events) around each launch of the last run: wbx_spectrum_ms adds them up
+  double ms = 0.0;
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_onsets' and wbx_clip_tempo's energies (16 bytes per hop), novelty (4) and records (32) on the device, the records'
 // pinned twin (at most 2^20 hops each) — grown on demand, freed with the context — and the timing events
 struct OnsetStage {
@@ -658,6 +683,7 @@ struct wbx_ctx {
   StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
   F0Stage f0;                             // wbx_clip_f0 and wbx_clip_tempo's track (under fx_mu, on fx.side.stream)
   OnsetStage ons;                         // wbx_clip_onsets, wbx_clip_tempo (under fx_mu, on fx.side.stream)
+  SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -875,6 +901,12 @@ wbx_status tempo_check_call(const ClipSrc& src, const OnsetCall& k, F0Call* trac
 wbx_status onset_run(wbx_ctx* c, const ClipSrc& src, const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why);
 wbx_status tempo_run(wbx_ctx* c, const ClipSrc& src, const OnsetCall& k, const F0Call& track, wbx_f0_frame* frames_out, wbx_f0_info* info,
                      std::string* why);
+// seeing a clip's spectrum (wbx_spectrum.hip), cut the same way: the check makes no device call (wbx_spectrum.h's
+// spectrum_check first, then the source, then the basis); the run works under fx_mu on the edit stream behind
+// clipfx_prepare / clipfx_order and waits for the device after every launch, whose cells it copies out
+wbx_status spectrum_check_call(const ClipSrc& src, const ClipSrc* basis, const SpecCall& k, const char** why);
+wbx_status spectrum_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& basis, const SpecCall& k, float* power_out, wbx_spectrum_info* info,
+                        std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -611,6 +611,11 @@ struct SamplePin {
     if (st == WBX_OK) st = f0_run(e->ctx, src, k, frames_out, info, why);
     return st;
   }
+  wbx_status spectrum(const ClipSrc& basis, const SpecCall& k, float* power_out, wbx_spectrum_info* info, std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = spectrum_run(e->ctx, src, basis, k, power_out, info, why);
+    return st;
+  }
   wbx_status onsets(const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why) {
     wbx_status st = order(clipfx_prepare, clipfx_order, why);
     if (st == WBX_OK) st = onset_run(e->ctx, src, k, frames_out, info, why);
@@ -993,6 +998,35 @@ extern "C" wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint6
   }
   std::string why;
   const wbx_status st = p.f0(k, frames_out, info, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// wbx_clip_spectrum of engine samples (wbx.h "Seeing a clip's spectrum"), under wbx_engine_f0_sample's rules and with
+// wbx_engine_dynamics_sample's pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the
+// source and the basis (one id where they are the same sample) and ordering the stream, and is never held across a device wait.
+extern "C" wbx_status wbx_engine_spectrum_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                 uint32_t channel, uint32_t basis_sample, uint32_t window_frames, uint32_t n_bins,
+                                                 uint32_t hop_frames, float* power_out, size_t cells_cap, wbx_spectrum_info* info) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const SpecCall k{first_frame, n_frames, channel, window_frames, n_bins, hop_frames, power_out != nullptr, cells_cap};
+  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
+  if (basis_sample != sample) distinct.push_back(basis_sample);
+  ClipSrc basis{};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "spectrum_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const ClipSlot* b = e->hs.valid_sample(basis_sample) ? find_clip(e->ctx, basis_sample) : nullptr;
+    if (b) basis = clip_src(*b);
+    const char* msg = "";
+    st = spectrum_check_call(p.src, b ? &basis : nullptr, k, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_set_locked(distinct);
+  }
+  std::string why;
+  const wbx_status st = p.spectrum(basis, k, power_out, info, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }

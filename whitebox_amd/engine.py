@@ -372,6 +372,53 @@ def _run_tempo(fn, what, h, engine, ident, first_frame, n_frames, hop_frames, fl
     return rec, {k: getattr(fi, k) for k, _ in _ffi.F0Info._fields_ if k != "_pad"}
 
 
+SPECTRUM_MID = _ffi.SPECTRUM_MID   # clip_spectrum's channel: f0's detector (mono the sample, stereo the rounded mean)
+
+
+def spectrum_hops(n_frames: int, window_frames: int, hop_frames: int) -> int:
+    """wbx_spectrum_hops (host-only): the complete analysis frames of n_frames — (n - W) // H + 1, or 0 where the range is
+    shorter than W or the call would refuse the window or the hop length"""
+    return int(_ffi.lib().wbx_spectrum_hops(n_frames, window_frames, hop_frames))
+
+
+def spectrum_basis(window_frames: int, freqs, lengths=None, window="hann", kaiser_beta: float = 8.6) -> np.ndarray:
+    """wbx_spectrum_basis (host-only): the 2 * B * W fp32 words of a basis for clip_spectrum — bin b at freqs[b] cycles per
+    frame (0 .. 0.5) with its own window of lengths[b] frames (4 .. W; None: all W) centred in W; window "rect" / "hann" /
+    "kaiser" (or WBX_WINDOW_*), normalised so that a full-scale sine on a bin has power 0.25.  WbxError (-4) where the
+    library refuses the design"""
+    f = np.ascontiguousarray(freqs, dtype=np.float64)
+    ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint32)
+    assert f.ndim == 1 and (ln is None or ln.shape == f.shape)
+    frames = int(_ffi.lib().wbx_spectrum_basis_frames(window_frames, f.size))
+    out = np.zeros(max(frames, 1), dtype=np.float32)
+    _check(_ffi.lib().wbx_spectrum_basis(window_frames, f.size, f.ctypes.data, None if ln is None else ln.ctypes.data,
+                                         _ffi.WINDOW_KIND.get(window, window), float(kaiser_beta), out.ctypes.data),
+           "wbx_spectrum_basis")
+    return out
+
+
+def spectrum_log_freqs(f_min: float, bins_per_octave: float, n_bins: int):
+    """wbx_spectrum_log_freqs (host-only): (f_min * 2 ** (b / bins_per_octave) for b in 0 .. n_bins - 1 in cycles per frame,
+    without libm; how many were clamped at 0.5)"""
+    out = np.zeros(max(int(n_bins), 1), dtype=np.float64)
+    clamped = C.c_uint32()
+    _check(_ffi.lib().wbx_spectrum_log_freqs(float(f_min), float(bins_per_octave), n_bins, out.ctypes.data, C.byref(clamped)),
+           "wbx_spectrum_log_freqs")
+    return out, clamped.value
+
+
+def _run_spectrum(fn, what, h, engine, ident, first_frame, n_frames, channel, basis, window_frames, n_bins, hop_frames):
+    channel = SPECTRUM_MID if channel in ("mid", None) else channel
+    hops = spectrum_hops(n_frames, window_frames, hop_frames)
+    # the call's own argument check first, so that a refused call allocates no cells
+    _check(_ffi.lib().wbx_spectrum_check(n_frames, channel, window_frames, n_bins, hop_frames, 1, hops * n_bins), "wbx_spectrum_check")
+    power = np.zeros((hops, n_bins), dtype=np.float32)
+    si = _ffi.SpectrumInfo()
+    _check(fn(h, ident, first_frame, n_frames, channel, basis, window_frames, n_bins, hop_frames,
+              power.ctypes.data if power.size else None, power.size, C.byref(si)), what, h, engine)
+    return power, {k: getattr(si, k) for k, _ in _ffi.SpectrumInfo._fields_}
+
+
 def loudness_hops(rate: int, n_frames: int) -> int:
     """wbx_loudness_hops (host-only): complete 100 ms hops of n_frames at `rate` (hop = (rate + 5) // 10 frames); 0 outside
     the supported rates 8000 .. 384000"""
@@ -673,6 +720,21 @@ class MixContext:
         bpm at 48 kHz and hop_frames = 256"""
         return _run_tempo(self.L.wbx_clip_tempo, "wbx_clip_tempo", self.h, False, clip, first_frame, n_frames, hop_frames,
                           floor_power, window_hops, step_hops, lag_min, lag_max, threshold)
+
+    def clip_spectrum(self, clip: int, first_frame: int, n_frames: int, basis_clip: int, window_frames: int, n_bins: int,
+                      hop_frames: int, channel="mid"):
+        """wbx_clip_spectrum: the power of frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2
+        channels at the n_bins frequencies of `basis_clip` (a resident mono F32 clip of spectrum_basis's words), one row per
+        complete hop, as a direct transform on the device: (power float32[hops][n_bins], {"hops", "bins", "launches"}).
+        channel 0, 1 or "mid" (SPECTRUM_MID).  Nothing is allocated in the pool."""
+        return _run_spectrum(self.L.wbx_clip_spectrum, "wbx_clip_spectrum", self.h, False, clip, first_frame, n_frames, channel,
+                             basis_clip, window_frames, n_bins, hop_frames)
+
+    def spectrum_ms(self) -> float:
+        """wbx_spectrum_ms: device milliseconds of the last spectrum call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_spectrum_ms(self.h, C.byref(out)), "wbx_spectrum_ms", self.h)
+        return out.value
 
     def onsets_ms(self) -> float:
         """wbx_onset_ms: device milliseconds of the energy pass of the last onsets or tempo call"""
@@ -1498,6 +1560,60 @@ class Engine:
         n_frames = self._range_of("tempo_sample", sample, first_frame, n_frames, frames, channels)
         return _run_tempo(self.L.wbx_engine_tempo_sample, "wbx_engine_tempo_sample", self.h, True, sample, first_frame, n_frames,
                           hop_frames, floor_power, window_hops, step_hops, lag_min, lag_max, threshold)
+
+    def add_spectrum_basis(self, window_frames: int, freqs, lengths=None, window="hann", kaiser_beta: float = 8.6,
+                           rate: Optional[int] = None) -> int:
+        """spectrum_basis(...)'s words as a mono F32 sample: the `basis_sample` of spectrum_sample, as add_fir makes a
+        response (`rate` is a label only: frequencies are in cycles per frame)"""
+        words = spectrum_basis(window_frames, freqs, lengths, window, kaiser_beta)
+        return self.add_sample("f32", self.audio_sample_rate if rate is None else rate, [words])
+
+    def spectrum_sample(self, sample: int, basis_sample: int, window_frames: int, n_bins: int, hop_frames: int, channel="mid",
+                        first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                        frames: Optional[int] = None):
+        """wbx_engine_spectrum_sample — see MixContext.clip_spectrum; `frames` / `channels` as in export_sample.  Returns
+        (power float32[hops][n_bins], info).  May be called while another thread runs process(); delete_sample of the
+        sample or of the basis sample is refused meanwhile."""
+        n_frames = self._range_of("spectrum_sample", sample, first_frame, n_frames, frames, channels)
+        return _run_spectrum(self.L.wbx_engine_spectrum_sample, "wbx_engine_spectrum_sample", self.h, True, sample, first_frame,
+                             n_frames, channel, basis_sample, window_frames, n_bins, hop_frames)
+
+    def spectrogram_sample(self, sample: int, f_min: float, bins_per_octave: float, n_bins: int, window: int = 2048,
+                           hop: int = 512, constant_q: bool = False, cycles: Optional[float] = None, window_kind="hann",
+                           channel="mid", **call):
+        """A logarithmic spectrogram of a sample: a basis of n_bins frequencies from f_min (cycles per frame) upwards,
+        bins_per_octave to the octave (spectrum_log_freqs: what would pass 0.5 sits at 0.5), designed, uploaded, measured by
+        spectrum_sample (`call`: its first_frame, n_frames, frames, channels) and deleted again.  With constant_q each bin's
+        window holds `cycles` of its periods (default: as many as the lowest bin has in `window`), a multiple of 4 frames in
+        4 .. window.  Returns (power [hops][n_bins], freqs, info).  The lengths and their rounding happen here: a
+        convenience outside the bit-exact contract — the cells equal the model's for the basis this designs."""
+        freqs, _ = spectrum_log_freqs(f_min, bins_per_octave, n_bins)
+        lengths = None
+        if constant_q:
+            cycles = float(window) * float(freqs[0]) if cycles is None else float(cycles)
+            lengths = []
+            for f in freqs:
+                L = int(round(cycles / f))
+                lengths.append(max(4, min(int(window), L - L % 4)))
+        basis = self.add_spectrum_basis(window, freqs, lengths, window_kind)
+        try:
+            power, info = self.spectrum_sample(sample, basis, window, n_bins, hop, channel=channel, **call)
+        finally:
+            self.delete_sample(basis)
+        return power, freqs, info
+
+    def chroma_sample(self, sample: int, f_c: float, octaves: int = 5, window: int = 4096, hop: int = 1024, constant_q: bool = True,
+                      **call):
+        """A chromagram of a sample: spectrogram_sample over a semitone basis of 12 * octaves bins from f_c upwards (cycles
+        per frame: the lowest C, or whichever pitch class 0 shall be), each hop's powers folded into 12 pitch classes on the
+        host in fp64, the octaves added in ascending order from 0.0 (tests/spectrum_model.py chroma_fold).  Returns
+        (chroma float64[hops][12], info)."""
+        power, _, info = self.spectrogram_sample(sample, f_c, 12.0, 12 * int(octaves), window, hop, constant_q=constant_q, **call)
+        cells = power.astype(np.float64)
+        chroma = np.zeros((cells.shape[0], 12), dtype=np.float64)
+        for o in range(int(octaves)):
+            chroma = chroma + cells[:, 12 * o:12 * o + 12]
+        return chroma, info
 
     def detect_tempo_sample(self, sample: int, bpm_min: float = 70.0, bpm_max: float = 180.0, rate: Optional[int] = None,
                             hop_frames: int = 256, window_hops: int = 1024, step_hops: int = 64, threshold: float = 0.5, **call):
