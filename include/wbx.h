@@ -823,6 +823,87 @@ wbx_status wbx_clip_stretch(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, 
                             uint64_t out_frames, uint32_t window_frames, uint32_t tolerance_frames, int32_t* positions_out,
                             size_t positions_cap, wbx_stretch_info* info, wbx_clip_stats* stats_of_result);
 
+/* Warping a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels warped along time
+ * markers into a NEW F32 clip of out_frames frames at the same PITCH — quantizing a take to the grid, conforming it to a
+ * tempo map.  A marker is a promise that source frame src_frame sounds at output frame out_frame; between two markers the
+ * clip is stretched by WSOLA exactly as "Stretching a clip" does it.  No reference counterpart.  This text is the
+ * specification; tests/warp_model.py restates it in numpy, and the positions, the info and every output sample equal that BIT
+ * FOR BIT.  Everything not said here is "Stretching a clip" word for word: x, the non-finite rule and zero outside [0, n) of
+ * the RANGE, the linked detector d, N, Hs = N / 2, D, the score and the lowest candidate among equals, wbx_stretch_window,
+ * one IEEE fp64 operation per operator and nothing fused.
+ *   markers   M = n_markers pairs (src_frame, out_frame), 0 <= M <= 65535; both columns strictly ascending, 0 < src_frame <
+ *             n, 0 < out_frame < m.  With (s_0, t_0) = (0, 0) and (s_{M+1}, t_{M+1}) = (n, m) they bound S = M + 1
+ *             segments; segment j has n_j = s_{j+1} - s_j source frames and m_j = t_{j+1} - t_j output frames
+ *   steps     segment j has K_j = ceil(m_j / Hs) steps; its step i starts at output frame o = t_j + i * Hs and is
+ *             l = min(Hs, t_{j+1} - o) frames long (only a segment's last step may be short).  The global step index is
+ *             k = base_j + i, base_j = the sum of K_j' over j' < j; K = the sum of all K_j (wbx_warp_steps)
+ *   anchors   a_k = s_j + floor(i * Hs * n_j / m_j) in 64-bit integers
+ *   continuation  c_k = p_{k-1} + l_{k-1}, with p_{-1} = -Hs and l_{-1} = Hs, so c_0 = 0
+ *   positions i = 0 (pinned): p_k = s_j, never scored, counted in neither searched_steps nor candidates.  i >= 1: the
+ *             stretch's rule as it is, with lo = max(a_k - D, 0) and hi = min(a_k + D, n - 1) — the clamp is the range's,
+ *             not the segment's: candidates may lie beyond a marker, nothing outside the range is read.  p_k = c_k where
+ *             lo <= c_k <= hi; otherwise every q in [lo, hi] is scored over Hs terms against the template d[c_k + .]
+ *   output    frame o + i', i' < l, each channel: (float)x[p_k + i'] where p_k == c_k; otherwise
+ *             (float)((w_up[i'] * x[p_k + i']) + (w_dn[i'] * x[c_k + i'])).  A pinned step is blended like any other step
+ *             that left its continuation: a marker is a crossfade over one hop into s_j, not a cut
+ * Consequences: with M = 0 the call IS wbx_clip_stretch — positions, info and samples, bit for bit.  A segment's positions
+ * depend on nothing outside it but the source: the chain starts at the pinned s_j (its first step's blend partner c_k comes
+ * from the segment before).  A marker cuts the chain, so the segments are searched side by side, one workgroup each.
+ * dst_clip, positions_out (the K positions, copied at the end of the call), stats_of_result and the ordering are
+ * wbx_clip_stretch's.  info (may be NULL): steps = K; searched_steps; candidates; max_shift = max |p_k - a_k|; segments = S;
+ * longest_segment_steps = max K_j; launches, the kernel launches of the call (= wbx_warp_launches).
+ * Launches: round r walks steps [r S_r, (r + 1) S_r) of every segment that has them, S_r = wbx_stretch_launch_steps(n, N,
+ * D), one 512-lane workgroup per such segment, in slices of at most wbx_warp_launch_segments() workgroups; one overlap-add
+ * launch covers the call after all searches.
+ * Refused before any device call, nothing allocated, dst_clip and the outputs untouched.  First everything
+ * wbx_clip_stretch refuses for (n, m, N, D, dst == src), with the same statuses.  Next WBX_ERR_INVALID: NULL markers with
+ * n_markers > 0, n_markers > 65535, a column that is not strictly ascending, a frame that is 0 or not below n / m, a
+ * non-NULL positions_out with positions_cap < K.  Next WBX_ERR_UNSUPPORTED: a segment with m_j > 8 n_j or n_j > 8 m_j, K >
+ * 2^22.  Last the clip, as wbx_clip_stretch judges it.  The whole-range ratio rule of the stretch is not applied on its own;
+ * the segments' rule replaces it (with M = 0 they are the same rule).
+ * Host-only, no device (wbx_warp.h, which a C++ compiler takes alone): wbx_warp_check, the status a call gets before its
+ * clip is looked at; wbx_warp_steps (0 for a window or markers the call refuses); wbx_warp_segments (fills S records;
+ * WBX_ERR_INVALID for NULL out, cap < S, such a window or markers); wbx_warp_max_markers (65535); wbx_warp_max_steps (2^22);
+ * wbx_warp_launch_segments; wbx_warp_launches (0 for a call wbx_warp_check refuses).
+ * wbx_warp_ms: as wbx_stretch_ms, for the context's last completed warp call.  For tools/bench_warp.py.
+ * Not offered: transient detection inside the call, holding more than the natural continuation after a marker, a
+ * time-varying pitch, warping at render time, more than 2 channels. */
+typedef struct wbx_warp_marker {        /* 16 bytes */
+  uint64_t src_frame;
+  uint64_t out_frame;
+} wbx_warp_marker;
+typedef struct wbx_warp_info {          /* 40 bytes */
+  uint64_t steps;
+  uint64_t searched_steps;
+  uint64_t candidates;
+  uint32_t max_shift;
+  uint32_t launches;
+  uint32_t segments;
+  uint32_t longest_segment_steps;
+} wbx_warp_info;
+typedef struct wbx_warp_segment {       /* 32 bytes */
+  uint64_t src_frame;                   /* s_j */
+  uint64_t out_frame;                   /* t_j */
+  uint64_t first_step;                  /* base_j */
+  uint64_t steps;                       /* K_j */
+} wbx_warp_segment;
+wbx_status wbx_warp_check(uint64_t n_frames, uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
+                          uint32_t window_frames, uint32_t tolerance_frames);
+uint64_t wbx_warp_steps(uint64_t n_frames, uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
+                        uint32_t window_frames);
+wbx_status wbx_warp_segments(uint64_t n_frames, uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
+                             uint32_t window_frames, wbx_warp_segment* out /* [n_markers + 1] */, size_t cap_segments);
+uint32_t wbx_warp_max_markers(void);
+uint64_t wbx_warp_max_steps(void);
+uint32_t wbx_warp_launch_segments(void);
+uint64_t wbx_warp_launches(uint64_t n_frames, uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
+                           uint32_t window_frames, uint32_t tolerance_frames);
+wbx_status wbx_warp_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_warp(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                         uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers, uint32_t window_frames,
+                         uint32_t tolerance_frames, int32_t* positions_out, size_t positions_cap, wbx_warp_info* info,
+                         wbx_clip_stats* stats_of_result);
+
 /* Pitch-shifting a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels transposed
  * into a NEW F32 clip of out_frames frames — another PITCH, by the ratio num / den (above 1: up), at a length of the
  * caller's choice (out_frames = n_frames is the plain transposition) — without the samples leaving HBM.  The result keeps
@@ -1581,6 +1662,13 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
 wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
                                      uint32_t window_frames, uint32_t tolerance_frames, wbx_stretch_info* info,
                                      uint32_t* new_sample);
+/* wbx_clip_warp of an engine sample, under wbx_engine_stretch_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_warp's (there is no dst_clip to collide with, and no positions). */
+wbx_status wbx_engine_warp_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
+                                  const wbx_warp_marker* markers, uint32_t n_markers, uint32_t window_frames,
+                                  uint32_t tolerance_frames, wbx_warp_info* info, uint32_t* new_sample);
 /* wbx_clip_pitch of an engine sample, under wbx_engine_stretch_sample's rules: the source is pinned for the call, so
  * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
  * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's

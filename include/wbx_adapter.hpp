@@ -393,6 +393,18 @@ struct Engine {
           "stretch_sample");
     return id;
   }
+  // A NEW sample of out_frames frames holding the range warped along time markers (wbx.h "Warping a clip"): source frame
+  // markers[i].src_frame of the range sounds at output frame markers[i].out_frame, WSOLA in between.  Pinned and threaded
+  // as for stretch_sample.
+  uint32_t warp_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames,
+                       const std::vector<wbx_warp_marker>& markers, uint32_t window_frames, uint32_t tolerance_frames,
+                       wbx_warp_info* info = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_warp_sample(h, sample, first_frame, n_frames, out_frames, markers.empty() ? nullptr : markers.data(),
+                                 (uint32_t)markers.size(), window_frames, tolerance_frames, info, &id),
+          "warp_sample");
+    return id;
+  }
   // A NEW sample of out_frames frames holding the range transposed by num / den (wbx.h "Pitch-shifting a clip"): another
   // pitch at the source's rate, out_frames = n_frames keeping the length; quality one of WBX_SRC_*, window and tolerance
   // as for stretch_sample.  The source is pinned for the call.  Editing thread, like derive_sample.

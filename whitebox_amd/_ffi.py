@@ -91,6 +91,19 @@ class StretchInfo(C.Structure):        # wbx_stretch_info, 32 bytes
                 ("launches", C.c_uint32)]
 
 
+class WarpMarker(C.Structure):         # wbx_warp_marker, 16 bytes
+    _fields_ = [("src_frame", C.c_uint64), ("out_frame", C.c_uint64)]
+
+
+class WarpInfo(C.Structure):           # wbx_warp_info, 40 bytes
+    _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("max_shift", C.c_uint32),
+                ("launches", C.c_uint32), ("segments", C.c_uint32), ("longest_segment_steps", C.c_uint32)]
+
+
+class WarpSegment(C.Structure):        # wbx_warp_segment, 32 bytes
+    _fields_ = [("src_frame", C.c_uint64), ("out_frame", C.c_uint64), ("first_step", C.c_uint64), ("steps", C.c_uint64)]
+
+
 class PitchInfo(C.Structure):          # wbx_pitch_info, 48 bytes
     _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("mid_frames", C.c_uint64),
                 ("max_shift", C.c_uint32), ("launches", C.c_uint32), ("L", C.c_uint32), ("M", C.c_uint32)]
@@ -258,6 +271,16 @@ SYMBOLS = {
     "wbx_stretch_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_stretch": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, _vp, _sz, C.POINTER(StretchInfo),
                                    C.POINTER(ClipStats)]),
+    "wbx_warp_check": (C.c_int, [C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32]),
+    "wbx_warp_steps": (C.c_uint64, [C.c_uint64, C.c_uint64, _vp, _u32, _u32]),
+    "wbx_warp_segments": (C.c_int, [C.c_uint64, C.c_uint64, _vp, _u32, _u32, _vp, _sz]),
+    "wbx_warp_max_markers": (_u32, []),
+    "wbx_warp_max_steps": (C.c_uint64, []),
+    "wbx_warp_launch_segments": (_u32, []),
+    "wbx_warp_launches": (C.c_uint64, [C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32]),
+    "wbx_warp_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_warp": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32, _vp, _sz,
+                                C.POINTER(WarpInfo), C.POINTER(ClipStats)]),
     "wbx_pitch_mid_frames": (C.c_uint64, [C.c_uint64, _u32, _u32]),
     "wbx_pitch_max_steps": (_u32, []),
     "wbx_pitch_launch_shape": (C.c_int, [_u32, _u32, C.c_int, C.c_uint64] + [C.POINTER(_u32)] * 4),
@@ -365,6 +388,8 @@ SYMBOLS = {
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_engine_stretch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.POINTER(StretchInfo),
                                             C.POINTER(_u32)]),
+    "wbx_engine_warp_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32, C.POINTER(WarpInfo),
+                                         C.POINTER(_u32)]),
     "wbx_engine_pitch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.c_int, _u32, _u32,
                                           C.POINTER(PitchInfo), C.POINTER(_u32)]),
     "wbx_engine_f0_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),

@@ -26,6 +26,7 @@
 #include "wbx_resample.h"
 #include "wbx_splice.h"
 #include "wbx_stretch.h"
+#include "wbx_warp.h"
 #include "wbx_pitch.h"
 #include "wbx_f0.h"
 #include "wbx_spectrum.h"
@@ -257,6 +258,31 @@ struct StretchArgs {
 };
 void launch_stretch_search(const StretchArgs& a, hipStream_t s);
 void launch_stretch_ola(const StretchArgs& a, hipStream_t s);
+// warping a clip (wbx_warp.hip): the segments between markers are independent chains — warp_search_kernel, one workgroup
+// per live segment of a launch walking its steps of the round in order — then one overlap-add over the whole result
+struct WarpRecord {            // the call's record, added to by every search workgroup (integer atomics: free of order)
+  unsigned long long searched;    // steps that searched
+  unsigned long long candidates;  // candidates scored
+  uint32_t max_shift;          // the largest |p_k - a_k|
+  uint32_t pad;
+};
+struct WarpArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  int32_t* pos;                // device: [K] — all positions of the call
+  const wbx_warp_segment* seg; // device: [S + 1] — the segments, then (n, m, K, 0)
+  const uint32_t* ids;         // device: the segment ids of this search launch, one per workgroup
+  WarpRecord* rec;             // device
+  const double* win;           // device: [N] — w_up[Hs], then w_dn[Hs]
+  uint32_t n, m;               // frames of the range and of the result (< 2^31 - 16)
+  uint32_t Hs, D;              // N / 2, the tolerance
+  uint32_t S;                  // segments
+  uint32_t round, round_steps; // this search launch walks steps [round * round_steps, (round + 1) * round_steps) of its segments
+  uint32_t count;              // workgroups of this search launch
+  uint32_t channels;           // 1 or 2
+};
+void launch_warp_search(const WarpArgs& a, hipStream_t s);
+void launch_warp_ola(const WarpArgs& a, hipStream_t s);
 // pitch-shifting a clip (wbx_pitch.hip): the stretch's searches fill ALL positions of the call, then one pitch_kernel launch —
 // resample_kernel's tile, staged from the overlap-add of the range instead of from a clip
 struct PitchArgs {
@@ -472,6 +498,22 @@ struct StretchStage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_warp's own buffers: ALL positions of a call (K <= 2^22: at most 16 MB) with their pinned twin (filled only for a
+// caller who asks for positions), the segment table (S + 1 records), the segment ids of all search launches, the record and
+// the timing events.  The window table is StretchStage's — one edit runs at a time
+struct WarpStage {
+  DevBuf<int32_t> d_pos;
+  PinnedBuf<int32_t> h_pos;
+  DevBuf<wbx_warp_segment> d_seg;
+  PinnedBuf<wbx_warp_segment> h_seg;
+  DevBuf<uint32_t> d_ids;
+  PinnedBuf<uint32_t> h_ids;
+  DevBuf<WarpRecord> d_rec;
+  PinnedBuf<WarpRecord> h_rec;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_warp_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_pitch's own buffers: ALL positions of a call behind p_{-1} (K' + 1 words, K' <= 2^22: at most 16 MB + 4 B) with
 // their pinned twin (filled only for a caller who asks for positions) and the timing events.  The window table and the
 // carry are StretchStage's — one edit runs at a time
@@ -681,6 +723,7 @@ struct wbx_ctx {
   LimitStage lim;                         // wbx_clip_limit (under fx_mu, on fx.side.stream)
   DynStage dyn;                           // wbx_clip_dynamics (under fx_mu, on fx.side.stream; shares lim's stage and ramp)
   StretchStage str;                       // wbx_clip_stretch (under fx_mu, on fx.side.stream)
+  WarpStage wrp;                          // wbx_clip_warp (under fx_mu, on fx.side.stream)
   F0Stage f0;                             // wbx_clip_f0 and wbx_clip_tempo's track (under fx_mu, on fx.side.stream)
   OnsetStage ons;                         // wbx_clip_onsets, wbx_clip_tempo (under fx_mu, on fx.side.stream)
   SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
@@ -881,6 +924,11 @@ wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint
 wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** why);
 wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const StretchCall& k, ClipSlot& slot, int32_t* positions_out,
                        wbx_stretch_info* info, wbx_clip_stats* stats, std::string* why);
+// warping a clip (wbx_warp.hip), beside its stretch twin: the check makes no device call (wbx_warp.h's warp_check_args
+// first, then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status warp_check(const ClipSrc& src, const WarpCall& k, const char** why);
+wbx_status warp_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const WarpCall& k, ClipSlot& slot, int32_t* positions_out,
+                    wbx_warp_info* info, wbx_clip_stats* stats, std::string* why);
 // pitch-shifting a clip (wbx_pitch.hip), beside its stretch twin: the check makes no device call (wbx_pitch.h's
 // pitch_check_args first, then the clip) and yields the conversion's plan and the stretch the call performs; the run works
 // under fx_mu on the edit stream behind clipfx_prepare / clipfx_order

@@ -926,6 +926,36 @@ extern "C" wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, 
   return st;
 }
 
+// wbx_clip_warp of an engine sample (wbx.h "Warping a clip"), beside wbx_engine_stretch_sample and under its rules: the
+// editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
+// out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.
+extern "C" wbx_status wbx_engine_warp_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                             uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
+                                             uint32_t window_frames, uint32_t tolerance_frames, wbx_warp_info* info,
+                                             uint32_t* new_sample) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "warp_sample: new_sample is NULL");
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const WarpCall k{first_frame, n_frames, out_frames, markers, n_markers, window_frames, tolerance_frames, false, 0};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(sample, "warp_sample: unknown sample");
+    if (st != WBX_OK) return st;
+    const char* msg = "";
+    st = warp_check(p.src, k, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "warp_sample: the pool's sample ids (2^24) would run out");
+    p.pin_locked(sample);
+  }
+  std::string why;
+  ClipSlot slot;
+  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
+  if (st == WBX_OK) st = warp_run(e->ctx, p.src, p.rate, k, slot, nullptr, info, nullptr, &why);
+  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, out_frames, new_sample, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
 // wbx_clip_pitch of an engine sample (wbx.h "Pitch-shifting a clip"), beside wbx_engine_stretch_sample and under its rules:
 // the editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
 // out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.

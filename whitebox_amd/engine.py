@@ -294,6 +294,48 @@ def _stretch_info(si) -> dict:
             "launches": si.launches}
 
 
+def _warp_markers(markers):
+    """(ctypes array or None, M) for a sequence of (src_frame, out_frame) pairs"""
+    pairs = [(int(a), int(b)) for a, b in markers] if markers is not None else []
+    if not pairs:
+        return None, 0
+    arr = (_ffi.WarpMarker * len(pairs))()
+    for i, (a, b) in enumerate(pairs):
+        arr[i].src_frame, arr[i].out_frame = a, b
+    return arr, len(pairs)
+
+
+def warp_check(n_frames: int, out_frames: int, markers, window_frames: int = 2048, tolerance_frames: int = 512) -> int:
+    """wbx_warp_check (host-only): the status a warp call gets before its clip is looked at (0: none)"""
+    arr, M = _warp_markers(markers)
+    return int(_ffi.lib().wbx_warp_check(n_frames, out_frames, arr, M, window_frames, tolerance_frames))
+
+
+def warp_steps(n_frames: int, out_frames: int, markers, window_frames: int = 2048) -> int:
+    """wbx_warp_steps (host-only): K, the sum of the segments' ceil(m_j / Hs); 0 for a window or markers the call refuses"""
+    arr, M = _warp_markers(markers)
+    return int(_ffi.lib().wbx_warp_steps(n_frames, out_frames, arr, M, window_frames))
+
+
+def warp_segments(n_frames: int, out_frames: int, markers, window_frames: int = 2048) -> list:
+    """wbx_warp_segments (host-only): the S = M + 1 segments as (src_frame, out_frame, first_step, steps)"""
+    arr, M = _warp_markers(markers)
+    out = (_ffi.WarpSegment * (M + 1))()
+    _check(_ffi.lib().wbx_warp_segments(n_frames, out_frames, arr, M, window_frames, out, M + 1), "wbx_warp_segments")
+    return [(g.src_frame, g.out_frame, g.first_step, g.steps) for g in out]
+
+
+def warp_launches(n_frames: int, out_frames: int, markers, window_frames: int = 2048, tolerance_frames: int = 512) -> int:
+    """wbx_warp_launches (host-only): the kernel launches a warp call makes; 0 for a call wbx_warp_check refuses"""
+    arr, M = _warp_markers(markers)
+    return int(_ffi.lib().wbx_warp_launches(n_frames, out_frames, arr, M, window_frames, tolerance_frames))
+
+
+def _warp_info(wi) -> dict:
+    return {"steps": wi.steps, "searched_steps": wi.searched_steps, "candidates": wi.candidates, "max_shift": wi.max_shift,
+            "launches": wi.launches, "segments": wi.segments, "longest_segment_steps": wi.longest_segment_steps}
+
+
 def pitch_mid_frames(out_frames: int, num: int, den: int) -> int:
     """wbx_pitch_mid_frames (host-only): m' = ceil(out_frames * M / L), the frames of the stretched intermediate of a pitch
     shift by num / den (M / L in lowest terms); 0 where the call would refuse the ratio"""
@@ -662,6 +704,29 @@ class MixContext:
         """wbx_stretch_ms: device milliseconds of the last stretch call's launches"""
         out = C.c_double()
         _check(self.L.wbx_stretch_ms(self.h, C.byref(out)), "wbx_stretch_ms", self.h)
+        return out.value
+
+    def clip_warp(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int, markers,
+                  window_frames: int = 2048, tolerance_frames: int = 512, positions: bool = False, stats_channels: int = 0):
+        """wbx_clip_warp: `dst_clip` becomes a new F32 clip of out_frames frames = the range of `src_clip` warped along
+        `markers`, a sequence of (src_frame, out_frame) pairs relative to the range: each source frame sounds at its
+        output frame, the stretches between them are WSOLA.  Returns the call's info {"steps", "searched_steps",
+        "candidates", "max_shift", "launches", "segments", "longest_segment_steps"}; `positions` and `stats_channels` as
+        in clip_stretch"""
+        arr, M = _warp_markers(markers)
+        wi, st = _ffi.WarpInfo(), _ffi.ClipStats()
+        K = warp_steps(n_frames, out_frames, markers, window_frames) if positions else 0
+        pos = np.zeros(max(K, 1), dtype=np.int32)
+        _check(self.L.wbx_clip_warp(self.h, src_clip, dst_clip, first_frame, n_frames, out_frames, arr, M, window_frames,
+                                    tolerance_frames, pos.ctypes.data if positions else None, pos.size if positions else 0,
+                                    C.byref(wi), C.byref(st) if stats_channels else None), "wbx_clip_warp", self.h)
+        out = (_warp_info(wi),) + ((pos[:K],) if positions else ()) + ((_clip_stats(st, stats_channels),) if stats_channels else ())
+        return out[0] if len(out) == 1 else out
+
+    def warp_ms(self) -> float:
+        """wbx_warp_ms: device milliseconds of the last warp call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_warp_ms(self.h, C.byref(out)), "wbx_warp_ms", self.h)
         return out.value
 
     def clip_pitch(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int, num: int, den: int,
@@ -1433,6 +1498,76 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return new.value, _stretch_info(si)
+
+    def warp_sample(self, sample: int, out_frames: int, markers, window_frames: int = 2048, tolerance_frames: int = 512,
+                    first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                    frames: Optional[int] = None):
+        """wbx_engine_warp_sample: a new sample of out_frames frames = the range of `sample` warped along `markers`
+        ((src_frame, out_frame) pairs relative to the range) — see MixContext.clip_warp.  `frames` / `channels` as in
+        export_sample.  The source is pinned against delete_sample for the call's length; may be called while another
+        thread runs process().  Returns (new id, info)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "warp_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        arr, M = _warp_markers(markers)
+        new, wi = C.c_uint32(), _ffi.WarpInfo()
+        _check(self.L.wbx_engine_warp_sample(self.h, sample, first_frame, n_frames, out_frames, arr, M, window_frames,
+                                             tolerance_frames, C.byref(wi), C.byref(new)), "wbx_engine_warp_sample", self.h, True)
+        self._sample_shape[new.value] = (out_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return new.value, _warp_info(wi)
+
+    def warp_to_markers(self, sample: int, events, targets, out_frames: Optional[int] = None, lead: Optional[int] = None,
+                        window_frames: int = 2048, tolerance_frames: int = 512, **call):
+        """A sample warped so that the event at source frame events[i] sounds at output frame targets[i] (both relative to
+        the range; out_frames defaults to the range's length).  Each pair becomes the marker (event - lead, target - lead),
+        lead = window_frames / 2 by default: a marker a hop early leaves the hop behind it to the natural continuation, so
+        an attack stays intact.  The pairs are taken in ascending order of their event; a pair is DROPPED where its marker
+        would break a rule of the call given the markers kept so far: a frame that is not above the last kept marker's (or
+        0) in either column, a source frame not below n_frames or an output frame not below out_frames, or a ratio beyond
+        8 either way of the segment from the last kept marker to it or of the segment from it to the end.  These choices
+        happen here: a convenience outside the bit-exact contract; the samples are the model's for the markers reported
+        back.  `call`: warp_sample's first_frame, n_frames, frames, channels.  Returns (new id, info, the markers used)."""
+        frames, _ = self._shape_of(sample, call.get("frames"), call.get("channels"))
+        n = call.get("n_frames")
+        if n is None:
+            assert frames is not None, "warp_to_markers: give n_frames, or frames (the sample's length)"
+            n = frames - call.get("first_frame", 0)
+        m = n if out_frames is None else int(out_frames)
+        lead = window_frames // 2 if lead is None else int(lead)
+
+        def fits(a, b):                      # a segment of a source frames into b output frames
+            return a > 0 and b > 0 and b <= 8 * a and a <= 8 * b
+
+        kept, last = [], (0, 0)
+        for ev, tg in sorted((int(e), int(t)) for e, t in zip(events, targets)):
+            s, t = ev - lead, tg - lead
+            if s >= n or t >= m or not fits(s - last[0], t - last[1]) or not fits(n - s, m - t):
+                continue
+            kept.append((s, t))
+            last = (s, t)
+        new, info = self.warp_sample(sample, m, kept, window_frames, tolerance_frames, **call)
+        return new, info, kept
+
+    def quantize_sample(self, sample: int, bpm: float, division: int = 4, strength: float = 1.0, onsets: Optional[dict] = None,
+                        rate: Optional[int] = None, **warp):
+        """A sample with its onsets moved towards the grid: onsets_sample (`onsets`: its arguments), each onset frame moved
+        by `strength` of the way to the nearest line of a grid of 60 * rate / (bpm * division) frames, then warp_to_markers
+        at the range's own length (`warp`: its arguments).  Outside the bit-exact contract, like warp_to_markers.  Returns
+        (new id, info, the markers used)."""
+        onsets = dict(onsets or {})
+        for k in ("first_frame", "n_frames", "frames", "channels"):
+            if k in warp:
+                onsets.setdefault(k, warp[k])
+        rec, _ = self.onsets_sample(sample, **onsets)
+        H = int(onsets.get("hop_frames", 256))
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        grid = 60.0 * rate / (float(bpm) * float(division))
+        events = [int(h) * H for h in np.flatnonzero(rec["onset"])]
+        targets = [int(round(e + float(strength) * (round(e / grid) * grid - e))) for e in events]
+        return self.warp_to_markers(sample, events, targets, **warp)
 
     def stretch_to_tempo(self, sample: int, bpm_from: float, bpm_to: float, window_ms: float = 40.0, tolerance_ms: float = 10.0,
                          rate: Optional[int] = None, **call):
