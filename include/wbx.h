@@ -1041,6 +1041,93 @@ wbx_status wbx_clip_f0(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64
                        uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max, double threshold, wbx_f0_frame* frames_out,
                        size_t frames_cap, wbx_f0_info* info);
 
+/* Aligning two clips: by how many frames clip B lags clip A, and whether its polarity is flipped, from the cross-correlation
+ * of a template of A — frames [a_first, a_first + n) of the reference clip — with frames [b_first, b_first + m) of the
+ * clip to be aligned, over signed lags, without the samples leaving HBM.  A MEASUREMENT, like wbx_clip_loudness and
+ * wbx_clip_f0: nothing is allocated in the pool and no clip is created.  No reference counterpart.  The arithmetic is part
+ * of the interface; tests/align_model.py restates it in numpy, operation for operation, and info and the curve equal it
+ * BIT FOR BIT.  Every operator below is ONE IEEE fp64 operation in the order written; nothing is fused (where both factors
+ * are fp32 values the product is exact, so an fma there is the same thing).
+ *   input     each clip a resident F32 clip of 1 or 2 channels (the counts may differ), each through "Stretching a clip"'s
+ *             linked detector on its own: mono d = x[0], stereo d = (float)(0.5 * (x[0] + x[1])), what is not finite
+ *             entering as 0.0.  da[i] for i in [0, n); db[i] is zero outside [0, m); nothing beside either range is ever read
+ *   shape     n a multiple of 8 in [64, 2^24]; m in [1, 2^31 - 16); lags are signed, lag_min <= lag_max, both in
+ *             [-2^24, 2^24]; lags = lag_max - lag_min + 1 <= 2^17 (wbx_align_max_lags).  C = 2048 terms per chunk
+ *             (wbx_align_chunk_frames); chunks = ceil(n / C) (wbx_align_chunks); the last chunk has n - (chunks - 1) * C
+ *             terms, a multiple of 8
+ *   per lag L, per chunk k — a partial, from rest:
+ *             pr = 0; pE = 0; for i = k*C .. min((k+1)*C, n) - 1 ascending:
+ *             pr = pr + da[i] * db[i+L]; pE = pE + db[i+L] * db[i+L]
+ *   per lag L — the fold:
+ *             r = 0; E = 0; for k = 0 .. chunks - 1 ascending: r = r + pr(L,k); E = E + pE(L,k)
+ *             The two-level order IS the definition, not an approximation of a flat sum, as the cumulative mean of
+ *             "Tracking a clip's pitch" is: it is what lets the chunks of a long template run side by side.
+ *             Ea is the same two-level sum of da[i] * da[i]
+ *   score     score(L) = (E == 0.0) ? 0.0 : (r * |r|) / E — square-root free, its arg-max that of r / sqrt(E);
+ *             with WBX_ALIGN_EITHER_POLARITY in flags: score(L) = (E == 0.0) ? 0.0 : (r * r) / E
+ *   pick      lag = the L with the greatest score, the LOWEST L among equals; silence gives lag = lag_min.
+ *             inverted = r(lag) < 0.0
+ *   refine    only when lag - 1 and lag + 1 both lie in [lag_min, lag_max]: a = score(lag-1), b = score(lag),
+ *             g = score(lag+1); den = (2.0 * b) - (a + g);
+ *             offset = (den > 0.0 && b >= a && b >= g) ? (0.5 * (g - a)) / den : 0.0.  Otherwise offset = 0.0.
+ *             offset is an estimate whose magnitude is at most 0.5; the contract is that it equals the model, and no
+ *             sub-sample accuracy is claimed
+ *   info      wbx_align_info: lag, inverted, offset, score, r, energy = E at the lag, ref_energy = Ea,
+ *             confidence = (Ea == 0.0) ? 0.0 : score / Ea, which lies in [-1, 1] up to rounding (Cauchy-Schwarz);
+ *             lags, chunks, terms = lags * n, launches
+ *   curve     curve_out (may be NULL): records of 16 bytes {r, energy}, one per lag from lag_min upward;
+ *             curve_cap >= lags where it is not NULL
+ * No NaN can arise and nothing overflows.  A and B may be the same clip.
+ * The call runs on the edits' stream behind wbx_clip_derive's ordering, one edit or measurement at a time, in bands of at
+ * most wbx_align_band_chunks(lags) chunks — what a device stage of 2^22 partials (64 MB, made at first use) holds, and at
+ * most 2^39 terms — each band one launch for the partials and one that folds them onto the running r and E, the bands
+ * continuing the same ascending chain, so that the cut into bands does not change a bit.  wbx_align_launches(n, lags) =
+ * 2 * bands + 2: Ea's partials first, the pick last.  info and the curve are copied out once at the end.
+ * Refused before any device call, info and curve_out untouched; the sizes are judged before the clips are looked at, in
+ * this order.  WBX_ERR_INVALID: an unknown clip (the reference first); n_frames not a multiple of 8 in [64, 2^24];
+ * m_frames of 0 or >= 2^31 - 16; lag_min, then lag_max, outside [-2^24, 2^24]; lag_min > lag_max; unknown flag bits; info
+ * and curve_out both NULL; curve_cap < lags with a curve_out.  WBX_ERR_UNSUPPORTED: lags > 2^17.  Then the clips —
+ * WBX_ERR_UNSUPPORTED: the reference, then the clip, not F32 or of more than 2 channels; different sample rates;
+ * WBX_ERR_INVALID: the reference's range, then the clip's, past its clip.
+ * Host-only, no device (wbx_align.h, which a C++ compiler takes alone): wbx_align_check (the argument check above without
+ * the clips: its status), wbx_align_chunks (0 for an n the call refuses), wbx_align_max_lags, wbx_align_chunk_frames,
+ * wbx_align_band_chunks (at least 1; 0 for lags of 0 or above 2^17), wbx_align_launches (0 for a refused shape).
+ * wbx_align_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed align call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_align.py; nothing else reads it.
+ * Not offered: more than 2 channels, unlinked stereo, an alignment that drifts over time, alignment at render time. */
+#define WBX_ALIGN_EITHER_POLARITY 1u
+typedef struct wbx_align_info {         /* 80 bytes */
+  int32_t lag;
+  uint32_t inverted;
+  double offset;
+  double score;
+  double r;
+  double energy;
+  double ref_energy;
+  double confidence;
+  uint32_t lags;
+  uint32_t chunks;
+  uint64_t terms;
+  uint32_t launches;
+  uint32_t _pad;
+} wbx_align_info;
+typedef struct wbx_align_point {        /* 16 bytes */
+  double r;
+  double energy;
+} wbx_align_point;
+wbx_status wbx_align_check(uint64_t n_frames, uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags, int has_info,
+                           int has_curve_out, size_t curve_cap);
+uint32_t wbx_align_chunks(uint64_t n_frames);
+uint64_t wbx_align_max_lags(void);
+uint32_t wbx_align_chunk_frames(void);
+uint32_t wbx_align_band_chunks(uint64_t lags);
+uint32_t wbx_align_launches(uint64_t n_frames, uint64_t lags);
+wbx_status wbx_align_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_align(wbx_ctx* ctx, uint32_t ref_clip, uint64_t a_first, uint64_t n_frames, uint32_t clip, uint64_t b_first,
+                          uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags, wbx_align_info* info,
+                          wbx_align_point* curve_out, size_t curve_cap);
+
 /* Finding a clip's onsets and tempo: an onset-strength curve (the "novelty") of frames [first_frame, first_frame + n_frames)
  * of a resident F32 clip of 1 or 2 channels, one value per hop, from the rise of two hop energies — the signal's and its
  * first difference's, which weighs the high end — the onsets picked from it, and its period tracked by "Tracking a clip's
@@ -1690,6 +1777,13 @@ wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_f
 wbx_status wbx_engine_spectrum_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t channel,
                                       uint32_t basis_sample, uint32_t window_frames, uint32_t n_bins, uint32_t hop_frames,
                                       float* power_out, size_t cells_cap, wbx_spectrum_info* info);
+/* wbx_clip_align of engine samples, under wbx_engine_spectrum_sample's rules: the reference sample AND the sample to be
+ * aligned are pinned for the call (one id where they are the same), so wbx_engine_delete_sample refuses either meanwhile;
+ * the editor lock is held only to validate, pin, order the stream and unpin, never across the device wait, so the call may
+ * run beside the audio thread.  Arguments and refusals are wbx_clip_align's. */
+wbx_status wbx_engine_align_samples(wbx_engine* e, uint32_t ref_sample, uint64_t a_first, uint64_t n_frames, uint32_t sample,
+                                    uint64_t b_first, uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags,
+                                    wbx_align_info* info, wbx_align_point* curve_out, size_t curve_cap);
 /* wbx_clip_onsets and wbx_clip_tempo of an engine sample, under wbx_engine_f0_sample's rules: pinned for the call, the
  * editor lock held only to validate and pin.  Arguments and refusals are the clip calls'. */
 wbx_status wbx_engine_onsets_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,

@@ -448,6 +448,24 @@ struct Engine {
           "spectrum_sample");
     return out;
   }
+  // By how many frames a sample lags a reference sample, where both live (wbx.h "Aligning two clips"): the template
+  // [a_first, a_first + n_frames) of ref_sample (n_frames a multiple of 8 in 64 .. 2^24) against [b_first, b_first + m_frames)
+  // of sample over the signed lags lag_min .. lag_max; flags 0 or WBX_ALIGN_EITHER_POLARITY.  `curve` (may be NULL) is
+  // resized to one {r, energy} per lag.  Both samples are pinned for the call.  Editing thread, like measure_sample.
+  wbx_align_info align_samples(uint32_t ref_sample, uint64_t a_first, uint64_t n_frames, uint32_t sample, uint64_t b_first,
+                               uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags = 0,
+                               std::vector<wbx_align_point>* curve = nullptr) {
+    const size_t lags = lag_max >= lag_min ? (size_t)(lag_max - lag_min) + 1u : 0u;
+    // the call's own argument check first, so that a refused call allocates no curve
+    const wbx_status pre = wbx_align_check(n_frames, m_frames, lag_min, lag_max, flags, 1, curve != nullptr, lags);
+    if (pre != WBX_OK) throw Error(pre, std::string("align_samples: ") + wbx_status_string(pre));
+    if (curve) curve->assign(lags, wbx_align_point{0.0, 0.0});
+    wbx_align_info info{};
+    check(wbx_engine_align_samples(h, ref_sample, a_first, n_frames, sample, b_first, m_frames, lag_min, lag_max, flags, &info,
+                                   curve ? curve->data() : nullptr, curve ? curve->size() : 0),
+          "align_samples");
+    return info;
+  }
   // The onsets of a sample's range where it lives (wbx.h "Finding a clip's onsets and tempo"): one wbx_onset_frame per hop
   // of hop_frames frames (a multiple of 64) — the two energies, the onset strength and whether the hop is an onset, whose
   // frame is then first_frame + h * hop_frames.  The sample is pinned for the call.  Editing thread, like measure_sample.

@@ -18,6 +18,7 @@ from .engine import stretch_anchor, stretch_steps, stretch_window  # noqa: F401
 from .engine import warp_check, warp_launches, warp_segments, warp_steps  # noqa: F401
 from .engine import pitch_mid_frames, pitch_ratio  # noqa: F401
 from .engine import F0_DTYPE, f0_hops  # noqa: F401
+from .engine import ALIGN_CURVE_DTYPE, ALIGN_EITHER_POLARITY, align_check, align_chunks  # noqa: F401
 from .engine import SPECTRUM_MID, spectrum_basis, spectrum_hops, spectrum_log_freqs  # noqa: F401
 from .engine import ONSET_DTYPE, onset_hops  # noqa: F401
 from .engine import splice_part, splice_plan  # noqa: F401

@@ -118,6 +118,19 @@ class F0Info(C.Structure):             # wbx_f0_info, 32 bytes
                 ("_pad", C.c_uint32)]
 
 
+class AlignInfo(C.Structure):          # wbx_align_info, 80 bytes
+    _fields_ = [("lag", C.c_int32), ("inverted", C.c_uint32), ("offset", C.c_double), ("score", C.c_double), ("r", C.c_double),
+                ("energy", C.c_double), ("ref_energy", C.c_double), ("confidence", C.c_double), ("lags", C.c_uint32),
+                ("chunks", C.c_uint32), ("terms", C.c_uint64), ("launches", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class AlignPoint(C.Structure):         # wbx_align_point, 16 bytes
+    _fields_ = [("r", C.c_double), ("energy", C.c_double)]
+
+
+ALIGN_EITHER_POLARITY = 1
+
+
 class OnsetFrame(C.Structure):         # wbx_onset_frame, 32 bytes
     _fields_ = [("energy", C.c_double), ("edge_energy", C.c_double), ("novelty", C.c_double), ("onset", C.c_uint32),
                 ("_pad", C.c_uint32)]
@@ -217,6 +230,15 @@ SYMBOLS = {
     "wbx_f0_launch_hops": (_u32, [_u32, _u32]),
     "wbx_f0_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_f0": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
+    "wbx_align_check": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _u32, C.c_int, C.c_int, _sz]),
+    "wbx_align_chunks": (_u32, [C.c_uint64]),
+    "wbx_align_max_lags": (C.c_uint64, []),
+    "wbx_align_chunk_frames": (_u32, []),
+    "wbx_align_band_chunks": (_u32, [C.c_uint64]),
+    "wbx_align_launches": (_u32, [C.c_uint64, C.c_uint64]),
+    "wbx_align_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_align": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, _u32,
+                                 C.POINTER(AlignInfo), _vp, _sz]),
     "wbx_spectrum_hops": (C.c_uint64, [C.c_uint64, _u32, _u32]),
     "wbx_spectrum_check": (C.c_int, [C.c_uint64, _u32, _u32, _u32, _u32, C.c_int, _sz]),
     "wbx_spectrum_max_cells": (C.c_uint64, []),
@@ -395,6 +417,8 @@ SYMBOLS = {
     "wbx_engine_f0_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _d, _vp, _sz, C.POINTER(F0Info)]),
     "wbx_engine_spectrum_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _u32, _u32, _vp, _sz,
                                              C.POINTER(SpectrumInfo)]),
+    "wbx_engine_align_samples": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_uint64, C.c_uint64, C.c_int64, C.c_int64,
+                                           _u32, C.POINTER(AlignInfo), _vp, _sz]),
     "wbx_engine_onsets_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _d, _d, _u32, _u32, _vp, _sz,
                                            C.POINTER(OnsetInfo)]),
     "wbx_engine_tempo_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _d, _u32, _u32, _u32, _u32, _d, _vp, _sz,

@@ -29,6 +29,7 @@
 #include "wbx_warp.h"
 #include "wbx_pitch.h"
 #include "wbx_f0.h"
+#include "wbx_align.h"
 #include "wbx_spectrum.h"
 #include "wbx_onset.h"
 #include "wbx_pool.h"
@@ -325,6 +326,40 @@ struct SpecArgs {
   uint32_t mid;                // 1: d = (float)(0.5 * (src[0] + src[1])); 0: d = src[0]
 };
 void launch_spectrum(const SpecArgs& a, hipStream_t s);
+// aligning two clips (wbx_align.hip): the partials of one band — a workgroup per (block of 4096 lags, chunk) —, the fold of a
+// band onto the running curve with the scores and the workgroups' best after the last, Ea's partials, and the pick
+struct alignas(16) AlignPartial {  // what a chunk leaves per lag: one 16-byte store
+  double pr, pE;
+};
+struct alignas(8) AlignBest {      // a fold workgroup's greatest score and the lowest lag index that has it
+  double score;
+  uint32_t q, _pad;
+};
+struct AlignPick {                 // what the pick leaves for the host
+  double offset, score, r, energy, ref_energy, confidence;
+  uint32_t q, inverted;            // the lag's index from lag_min
+};
+struct AlignArgs {
+  const float* a[2];           // the reference's channel rows at a_first (mono: a[1] unused)
+  const float* b[2];           // the clip's channel rows at b_first (mono: b[1] unused)
+  AlignPartial* stage;         // device: [chunks of the band][lags]
+  wbx_align_point* curve;      // device: [lags], the running r and E
+  AlignBest* best;             // device: [ceil(lags / 256)]
+  double* ea_part;             // device: [chunks]
+  AlignPick* pick;             // device: the record
+  uint32_t n, m;               // frames of the template (<= 2^24) and of B's range (< 2^31 - 16)
+  int32_t lag_min;
+  uint32_t lags;
+  uint32_t chunks;             // of the call
+  uint32_t chunk0, chunk1;     // the chunks of this band
+  uint32_t waves;              // of a partial workgroup (wbx_align.h align_shape)
+  uint32_t cha, chb;           // channels, 1 or 2
+  uint32_t either;             // WBX_ALIGN_EITHER_POLARITY
+};
+void launch_align_ref(const AlignArgs& a, hipStream_t s);
+void launch_align_partial(const AlignArgs& a, hipStream_t s);
+void launch_align_fold(const AlignArgs& a, hipStream_t s);
+void launch_align_pick(const AlignArgs& a, hipStream_t s);
 // finding a clip's onsets (wbx_onset.hip): the energy pass — a wave per hop, striding over the hops by the grid — and the
 // novelty pass, a lane per hop
 struct alignas(16) OnsetEnergy {   // what the energy pass leaves per hop: one 16-byte store
@@ -533,6 +568,22 @@ struct F0Stage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_align's buffers: the stage of one band's partials (at most 2^22 x 16 bytes = 64 MB, made at first use), the
+// running curve (at most 2^17 x 16 bytes) with its pinned twin (filled only for a caller who asks for the curve), the fold
+// workgroups' best, Ea's partials (at most 8192), the record with its pinned twin — grown on demand, freed with the context
+// — and the timing events
+struct AlignStage {
+  DevBuf<AlignPartial> d_part;
+  DevBuf<wbx_align_point> d_curve;
+  PinnedBuf<wbx_align_point> h_curve;
+  DevBuf<AlignBest> d_best;
+  DevBuf<double> d_ea;
+  DevBuf<AlignPick> d_pick;
+  PinnedBuf<AlignPick> h_pick;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_align_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_spectrum's cells of one launch on the device and in pinned memory (at most 2^22 x 4 bytes each) — grown on
 // demand, freed with the context — and the timing events of a launch, whose times are summed
 struct SpecStage {
@@ -727,6 +778,7 @@ struct wbx_ctx {
   F0Stage f0;                             // wbx_clip_f0 and wbx_clip_tempo's track (under fx_mu, on fx.side.stream)
   OnsetStage ons;                         // wbx_clip_onsets, wbx_clip_tempo (under fx_mu, on fx.side.stream)
   SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
+  AlignStage aln;                         // wbx_clip_align (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -955,6 +1007,12 @@ wbx_status tempo_run(wbx_ctx* c, const ClipSrc& src, const OnsetCall& k, const F
 wbx_status spectrum_check_call(const ClipSrc& src, const ClipSrc* basis, const SpecCall& k, const char** why);
 wbx_status spectrum_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& basis, const SpecCall& k, float* power_out, wbx_spectrum_info* info,
                         std::string* why);
+// aligning two clips (wbx_align.hip), cut the same way: the check makes no device call (wbx_align.h's align_check first,
+// then the reference, then the clip; NULL for an unknown one); the run works under fx_mu on the edit stream behind
+// clipfx_prepare / clipfx_order and waits for the device once, at the end
+wbx_status align_check_call(const ClipSrc* ref, uint32_t ref_rate, const ClipSrc* src, uint32_t src_rate, const AlignCall& k, const char** why);
+wbx_status align_run(wbx_ctx* c, const ClipSrc& ref, const ClipSrc& src, const AlignCall& k, wbx_align_info* info, wbx_align_point* curve_out,
+                     std::string* why);
 // splicing clips (wbx_splice.hip), cut the same way: the plan is wbx_splice.h's (no device call); the run works under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order and measures its result through clipfx_measure_run.  srcs[i] is
 // the storage of parts[i]'s source (layer 2 copies it out of the pool under the editor lock)

@@ -616,6 +616,11 @@ struct SamplePin {
     if (st == WBX_OK) st = spectrum_run(e->ctx, src, basis, k, power_out, info, why);
     return st;
   }
+  wbx_status align(const ClipSrc& other, const AlignCall& k, wbx_align_info* info, wbx_align_point* curve_out, std::string* why) {
+    wbx_status st = order(clipfx_prepare, clipfx_order, why);
+    if (st == WBX_OK) st = align_run(e->ctx, src, other, k, info, curve_out, why);
+    return st;
+  }
   wbx_status onsets(const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why) {
     wbx_status st = order(clipfx_prepare, clipfx_order, why);
     if (st == WBX_OK) st = onset_run(e->ctx, src, k, frames_out, info, why);
@@ -1057,6 +1062,35 @@ extern "C" wbx_status wbx_engine_spectrum_sample(wbx_engine* e, uint32_t sample,
   }
   std::string why;
   const wbx_status st = p.spectrum(basis, k, power_out, info, &why);
+  if (st != WBX_OK) tls_err = why;
+  return st;
+}
+
+// wbx_clip_align of engine samples (wbx.h "Aligning two clips"), wbx_engine_spectrum_sample's shape: the editor lock covers
+// validating, copying BOTH storage descriptions out, pinning the reference and the sample (one id where they are the same
+// sample) and ordering the stream, and is never held across the device wait.
+extern "C" wbx_status wbx_engine_align_samples(wbx_engine* e, uint32_t ref_sample, uint64_t a_first, uint64_t n_frames, uint32_t sample,
+                                               uint64_t b_first, uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags,
+                                               wbx_align_info* info, wbx_align_point* curve_out, size_t curve_cap) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  const AlignCall k{a_first, n_frames, b_first, m_frames, lag_min, lag_max, flags, info != nullptr, curve_out != nullptr, curve_cap};
+  std::vector<uint32_t> distinct{ref_sample};                  // (made before the lock, like a splice's)
+  if (sample != ref_sample) distinct.push_back(sample);
+  ClipSrc other{};
+  {
+    LockGuard g(e->hs.editor_lock);
+    wbx_status st = p.begin_locked(ref_sample, "align_samples: unknown reference sample");
+    if (st != WBX_OK) return st;
+    const ClipSlot* b = e->hs.valid_sample(sample) ? find_clip(e->ctx, sample) : nullptr;
+    if (b) other = clip_src(*b);
+    const char* msg = "";
+    st = align_check_call(&p.src, p.rate, b ? &other : nullptr, b ? b->d.sample_rate : 0u, k, &msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    p.pin_set_locked(distinct);
+  }
+  std::string why;
+  const wbx_status st = p.align(other, k, info, curve_out, &why);
   if (st != WBX_OK) tls_err = why;
   return st;
 }

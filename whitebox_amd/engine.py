@@ -414,6 +414,34 @@ def _run_tempo(fn, what, h, engine, ident, first_frame, n_frames, hop_frames, fl
     return rec, {k: getattr(fi, k) for k, _ in _ffi.F0Info._fields_ if k != "_pad"}
 
 
+# wbx_align_point as a numpy record: what clip_align and align_samples return as the curve, one per lag from lag_min upward
+ALIGN_CURVE_DTYPE = np.dtype([("r", "<f8"), ("energy", "<f8")])
+ALIGN_EITHER_POLARITY = _ffi.ALIGN_EITHER_POLARITY
+
+
+def align_chunks(n_frames: int) -> int:
+    """wbx_align_chunks (host-only): ceil(n_frames / 2048), or 0 where the call would refuse the template's length"""
+    return int(_ffi.lib().wbx_align_chunks(n_frames))
+
+
+def align_check(n_frames: int, m_frames: int, lag_min: int, lag_max: int, flags: int = 0, has_info: bool = True,
+                has_curve: bool = False, curve_cap: int = 0) -> int:
+    """wbx_align_check (host-only): the status a call of these sizes gets before its clips are looked at (0: none)"""
+    return int(_ffi.lib().wbx_align_check(n_frames, m_frames, lag_min, lag_max, flags, int(has_info), int(has_curve), curve_cap))
+
+
+def _run_align(fn, what, h, engine, ref, a_first, n_frames, ident, b_first, m_frames, lag_min, lag_max, either_polarity, curve):
+    flags = ALIGN_EITHER_POLARITY if either_polarity is True else int(either_polarity)
+    lags = lag_max - lag_min + 1
+    # the call's own argument check first, so that a refused call allocates no curve
+    _check(align_check(n_frames, m_frames, lag_min, lag_max, flags, True, bool(curve), max(lags, 0)), "wbx_align_check")
+    pts = np.zeros(lags, dtype=ALIGN_CURVE_DTYPE) if curve else None
+    ai = _ffi.AlignInfo()
+    _check(fn(h, ref, a_first, n_frames, ident, b_first, m_frames, lag_min, lag_max, flags, C.byref(ai),
+              pts.ctypes.data if curve else None, lags if curve else 0), what, h, engine)
+    return {k: getattr(ai, k) for k, _ in _ffi.AlignInfo._fields_ if k != "_pad"}, pts
+
+
 SPECTRUM_MID = _ffi.SPECTRUM_MID   # clip_spectrum's channel: f0's detector (mono the sample, stereo the rounded mean)
 
 
@@ -794,6 +822,23 @@ class MixContext:
         channel 0, 1 or "mid" (SPECTRUM_MID).  Nothing is allocated in the pool."""
         return _run_spectrum(self.L.wbx_clip_spectrum, "wbx_clip_spectrum", self.h, False, clip, first_frame, n_frames, channel,
                              basis_clip, window_frames, n_bins, hop_frames)
+
+    def clip_align(self, ref_clip: int, a_first: int, n_frames: int, clip: int, b_first: int, m_frames: int, lag_min: int,
+                   lag_max: int, either_polarity=False, curve: bool = False):
+        """wbx_clip_align: by how many frames `clip`'s range [b_first, b_first + m_frames) lags the template
+        [a_first, a_first + n_frames) of `ref_clip` (n_frames a multiple of 8 in 64 .. 2^24), over the signed lags
+        lag_min .. lag_max, by a chunked cross-correlation on the device: (info, curve) — {"lag", "inverted", "offset",
+        "score", "r", "energy", "ref_energy", "confidence", "lags", "chunks", "terms", "launches"} and, with curve=True, a
+        structured array (ALIGN_CURVE_DTYPE: "r", "energy") per lag, else None.  either_polarity: score r * r / E, so that
+        an inverted copy is found (info["inverted"]).  Nothing is allocated in the pool."""
+        return _run_align(self.L.wbx_clip_align, "wbx_clip_align", self.h, False, ref_clip, a_first, n_frames, clip, b_first,
+                          m_frames, lag_min, lag_max, either_polarity, curve)
+
+    def align_ms(self) -> float:
+        """wbx_align_ms: device milliseconds of the last align call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_align_ms(self.h, C.byref(out)), "wbx_align_ms", self.h)
+        return out.value
 
     def spectrum_ms(self) -> float:
         """wbx_spectrum_ms: device milliseconds of the last spectrum call's launches"""
@@ -1712,6 +1757,47 @@ class Engine:
         n_frames = self._range_of("spectrum_sample", sample, first_frame, n_frames, frames, channels)
         return _run_spectrum(self.L.wbx_engine_spectrum_sample, "wbx_engine_spectrum_sample", self.h, True, sample, first_frame,
                              n_frames, channel, basis_sample, window_frames, n_bins, hop_frames)
+
+    def align_samples(self, ref_sample: int, sample: int, lag_min: int, lag_max: int, n_frames: Optional[int] = None,
+                      a_first: int = 0, b_first: int = 0, m_frames: Optional[int] = None, either_polarity=False, curve: bool = False,
+                      ref_frames: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_align_samples — see MixContext.clip_align: by how many frames `sample` lags `ref_sample`.  `n_frames`
+        None: the reference from a_first to its end, rounded DOWN to a multiple of 8; `m_frames` None: the sample from
+        b_first to its end; `ref_frames` / `frames`: the samples' lengths where this object did not make them.  Returns
+        (info, curve or None).  May be called while another thread runs process(); delete_sample of either sample is refused
+        meanwhile."""
+        if n_frames is None:
+            n_frames = min(self._range_of("align_samples", ref_sample, a_first, None, ref_frames, None), 1 << 24) & ~7
+        m_frames = self._range_of("align_samples", sample, b_first, m_frames, frames, None)
+        return _run_align(self.L.wbx_engine_align_samples, "wbx_engine_align_samples", self.h, True, ref_sample, a_first, n_frames,
+                          sample, b_first, m_frames, lag_min, lag_max, either_polarity, curve)
+
+    def aligned_sample(self, ref_sample: int, sample: int, max_lag: int, either_polarity: bool = True, ref_frames: Optional[int] = None,
+                       frames: Optional[int] = None, channels: Optional[int] = None, **call):
+        """A NEW sample: `sample` moved by the lag align_samples finds within -max_lag .. max_lag of `ref_sample` (`call`: its
+        further arguments), so that its frame i is what lines up with the reference's frame i — its head trimmed (a derive)
+        where it lags, silence put in front (a splice) where it leads — and its polarity flipped (gain -1) when
+        either_polarity finds it inverted.  Built from existing calls, outside the bit-exact contract.  Returns
+        (new sample, info)."""
+        info, _ = self.align_samples(ref_sample, sample, -max_lag, max_lag, either_polarity=either_polarity, ref_frames=ref_frames,
+                                     frames=frames, **call)
+        total, channels = self._shape_of(sample, frames, channels)
+        assert total is not None, "aligned_sample: give frames (the sample's length)"
+        lag, gain = info["lag"], -1.0 if info["inverted"] else 1.0
+        assert -total < lag < total, "aligned_sample: the lag leaves nothing of the sample"
+        if lag >= 0:
+            new = self.derive_sample(sample, edit_desc(lag, total - lag, gain=gain), channels)
+        else:
+            new = self.splice_samples(channels, total - lag, [splice_part(sample, 0, total, at=-lag, gain=gain)])
+        return new, info
+
+    def measure_latency(self, played: int, recorded: int, max_frames: int, played_frames: Optional[int] = None,
+                        recorded_frames: Optional[int] = None, **call) -> int:
+        """The round-trip latency of a loopback in frames: the lag in 0 .. max_frames at which the take `recorded` matches
+        `played` best (align_samples over the whole of `played`, rounded down to a multiple of 8; `call`: its further
+        arguments).  A take's length is record_info()["frames"]: pass it as recorded_frames."""
+        info, _ = self.align_samples(played, recorded, 0, max_frames, ref_frames=played_frames, frames=recorded_frames, **call)
+        return info["lag"]
 
     def spectrogram_sample(self, sample: int, f_min: float, bins_per_octave: float, n_bins: int, window: int = 2048,
                            hop: int = 512, constant_q: bool = False, cycles: Optional[float] = None, window_kind="hann",
