@@ -359,15 +359,7 @@ extern "C" uint32_t wbx_align_band_chunks(uint64_t lags) { return wbx::align_ban
 extern "C" uint32_t wbx_align_launches(uint64_t n_frames, uint64_t lags) { return wbx::align_launches(n_frames, lags); }
 
 extern "C" wbx_status wbx_align_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  AlignStage& z = c->aln;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, "align time: no align call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::aln, "align time: no align call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_align(wbx_ctx* c, uint32_t ref_clip, uint64_t a_first, uint64_t n_frames, uint32_t clip, uint64_t b_first,
@@ -382,13 +374,7 @@ extern "C" wbx_status wbx_clip_align(wbx_ctx* c, uint32_t ref_clip, uint64_t a_f
   if (rb) src = clip_src(*rb);
   const AlignCall k{a_first, n_frames, b_first, m_frames, lag_min, lag_max, flags, info != nullptr, curve_out != nullptr, curve_cap};
   const char* msg = "";
-  wbx_status st = align_check_call(ra ? &ref : nullptr, ra ? ra->d.sample_rate : 0u, rb ? &src : nullptr, rb ? rb->d.sample_rate : 0u, k, &msg);
+  const wbx_status st = align_check_call(ra ? &ref : nullptr, ra ? ra->d.sample_rate : 0u, rb ? &src : nullptr, rb ? rb->d.sample_rate : 0u, k, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = align_run(c, ref, src, k, info, curve_out, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return align_run(c, ref, src, k, info, curve_out, why); });
 }

@@ -346,10 +346,8 @@ wbx_status clipfx_measure_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_fra
 // `slot` becomes the new clip (built on the edit stream; complete when this returns WBX_OK, released otherwise)
 wbx_status clipfx_derive_run(wbx_ctx* c, const ClipSrc& src, uint32_t sample_rate, const wbx_clip_edit_desc& d,
                              uint32_t out_channels, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, out_channels, sample_rate, d.n_frames, fill, c->fx.side.stream);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, out_channels, sample_rate, d.n_frames, why);
+  if (st != WBX_OK) return st;
   ClipFxArgs a{};
   const float* row[2] = {clip_row(src, 0), clip_row(src, 1)};
   switch (d.channel_mode) {
@@ -390,15 +388,9 @@ extern "C" wbx_status wbx_clip_measure(wbx_ctx* c, uint32_t clip, uint64_t first
   if (!s) return fail(c, WBX_ERR_INVALID, "clip measure: unknown clip");
   const ClipSrc src = clip_src(*s);
   const char* msg = "";
-  wbx_status st = clipfx_check_range(src, first_frame, n_frames, &msg);
+  const wbx_status st = clipfx_check_range(src, first_frame, n_frames, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = clipfx_measure_run(c, src, first_frame, n_frames, out, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return clipfx_measure_run(c, src, first_frame, n_frames, out, why); });
 }
 
 extern "C" wbx_status wbx_clip_derive(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, const wbx_clip_edit_desc* d,

@@ -224,10 +224,8 @@ wbx_status convolve_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& ir, uint3
                         wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
   const uint32_t ch = std::max(src.channels, ir.channels);
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, ch, rate, k.out_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, ch, rate, k.out_frames, why);
+  if (st != WBX_OK) return st;
   ConvolveStage& x = c->conv;
   ConvolveArgs a{};
   for (uint32_t i = 0; i < 2; i++) {
@@ -270,11 +268,7 @@ wbx_status convolve_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc& ir, uint3
     return stage_fail(why, WBX_ERR_DEVICE, "clip convolve", e);
   }
   x.timed = true;
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, k.out_frames, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, k.out_frames, stats, why);
 }
 
 }  // namespace wbx
@@ -289,14 +283,7 @@ extern "C" wbx_status wbx_fir_design(uint32_t rate, int kind, double f1_hz, doub
 }
 
 extern "C" wbx_status wbx_convolve_ms(wbx_ctx* c, double* out) {
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  ConvolveStage& x = c->conv;
-  if (!x.timed) return fail(c, WBX_ERR_INVALID, "convolve time: no convolution has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, x.mark[0], x.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::conv, "convolve time: no convolution has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_convolve(wbx_ctx* c, uint32_t src_clip, uint32_t ir_clip, uint32_t dst_clip, uint64_t first_frame,

@@ -921,6 +921,48 @@ wbx_status clipfx_into_clip(wbx_ctx* c, uint32_t dst_clip, Run run) {
   if (st != WBX_OK) return c->err = why, st;
   return clip_publish(c, dst_clip, slot);   // (may reallocate the pool's table: references into it are dead from here)
 }
+// ... and its twin for layer 1's calls that make no clip (wbx_clip_measure, _loudness, _f0, _onsets, _tempo, _spectrum,
+// _align): "prepare, order, run(why)" under fx_mu
+template <class Run>
+wbx_status clipfx_reading(wbx_ctx* c, Run run) {
+  std::lock_guard<std::mutex> g(c->fx_mu);
+  std::string why;
+  wbx_status st = clipfx_prepare(c, &why);
+  if (st == WBX_OK) st = clipfx_order(c, &why);
+  if (st == WBX_OK) st = run(&why);
+  if (st != WBX_OK) c->err = why;
+  return st;
+}
+// how the runs that make a clip open: `slot` becomes a blank planar F32 clip on the edit stream — the kernel writes every
+// frame; clip_build clears the 16 padding frames (and the row's slack)
+inline wbx_status clipfx_blank_clip(wbx_ctx* c, ClipSlot& slot, uint32_t channels, uint32_t sample_rate, uint64_t frames, std::string* why) {
+  ClipFill fill{};
+  fill.kind = CLIP_SRC_NONE;
+  const wbx_status st = clip_build(c, slot, WBX_FMT_F32, channels, sample_rate, frames, fill, c->fx.side.stream);
+  if (st != WBX_OK) *why = c->err;
+  return st;
+}
+// ... and close: the measure pass over the finished result, on the same stream, where `stats` asks for it; a failure
+// releases the slot
+inline wbx_status clipfx_measure_result(wbx_ctx* c, ClipSlot& slot, uint64_t frames, wbx_clip_stats* stats, std::string* why) {
+  if (!stats) return WBX_OK;
+  const wbx_status st = clipfx_measure_run(c, clip_src(slot), 0, frames, stats, why);
+  if (st != WBX_OK) clip_release(c, slot);
+  return st;
+}
+// the device time of a stage's last run, between its two events (the wbx_*_ms accessors; Z has mark[2] and timed); `none`:
+// what is said where no run has completed
+template <class Z>
+wbx_status stage_ms(wbx_ctx* c, Z wbx_ctx::*stage, const char* none, double* out) {
+  if (!c || !out) return WBX_ERR_INVALID;
+  std::lock_guard<std::mutex> g(c->fx_mu);
+  Z& z = c->*stage;
+  if (!z.timed) return fail(c, WBX_ERR_INVALID, none);
+  float ms = 0.0f;
+  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
+  *out = (double)ms;
+  return WBX_OK;
+}
 // converting a clip's sample rate (wbx_resample.hip), cut the same way; it runs under fx_mu on the edit stream, behind
 // clipfx_prepare / clipfx_order, and measures its result through clipfx_measure_run
 wbx_status resample_check(const ClipSrc& src, uint32_t src_rate, uint64_t first_frame, uint64_t n_frames, uint32_t dst_rate,

@@ -126,10 +126,8 @@ wbx_status dynamics_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc* 
 wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint32_t rate, const DynCall& k, double lo, ClipSlot& slot,
                         wbx_dynamics_stats* out, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  const wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, k.n_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, k.n_frames, why);
+  if (st != WBX_OK) return st;
   DynStage& z = c->dyn;
   DynArgs a{};
   for (uint32_t i = 0; i < 2; i++) {
@@ -177,7 +175,7 @@ extern "C" wbx_status wbx_dynamics_lookup(const double* table, double level, dou
 }
 
 extern "C" wbx_status wbx_dynamics_ms(wbx_ctx* c, double* out) {
-  return gain_ms(c, &wbx_ctx::dyn, "dynamics time: no dynamics call has completed on this context", out);
+  return stage_ms(c, &wbx_ctx::dyn, "dynamics time: no dynamics call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_dynamics(wbx_ctx* c, uint32_t src_clip, uint32_t key_clip, uint32_t dst_clip, uint64_t first_frame,

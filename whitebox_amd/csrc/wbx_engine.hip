@@ -525,14 +525,12 @@ extern "C" wbx_status wbx_engine_delete_sample(wbx_engine* e, uint32_t sample) {
   return WBX_OK;
 }
 
-// Side calls on engine samples: wbx_engine_export_sample (wbx_clip_export; wbx.h), and measuring and editing them
-// (wbx_clip_measure / wbx_clip_derive; wbx.h "Editing clips").  Editing thread; the audio thread may be in
-// wbx_engine_process* all the while.  The editor lock covers validating the sample, copying its storage description out of
-// the pool (the pool's table may be reallocated by a later add_sample), pinning it against wbx_engine_delete_sample,
-// ordering the call's side stream behind what is enqueued (stream calls only), dropping the pin and registering a new
-// sample; the stream's and the staging slots' creation, a new clip's allocation, the kernels, the device waits and the
-// host copies run without the lock (the rule of wbx_engine_levels).  Nothing here touches the transport or counts as an
-// edit (no note_edit_locked): a render sees a new sample only once a clip names it.
+// Side calls on engine samples: wbx_engine_export_sample (wbx_clip_export; wbx.h), and measuring and editing them (the
+// wbx_clip_* calls of wbx.h "Editing clips" and after, each on an engine sample).  Editing thread; the audio thread may be
+// in wbx_engine_process* all the while.  Nothing here touches the transport or counts as an edit (no note_edit_locked): a
+// render sees a new sample only once a clip names it.  Every entry point is the same pinned call, written once in
+// SamplePin below; what stands in an entry point is what is its own: the call struct, the samples it names, its check, its
+// run and, for a producer, what the new sample is registered as.
 namespace {
 
 // (editor lock held) `slot` becomes the pool's next sample, an F32 one, known to the session's sample table
@@ -547,17 +545,36 @@ wbx_status register_sample_locked(wbx_engine* e, ClipSlot& slot, uint32_t channe
   return WBX_OK;
 }
 
-// `mu` (export_mu or fx_mu) held for its life; begin_locked() validates, pin_locked() writes the pin word (export_pin or
-// edit_pin), the destructor clears it.  A splice pins a SET: pin_set_locked() fills edit_pins, the destructor empties it
+// One pinned call on engine samples: THE statement of its rules.
+//   * The call's mutex — export_mu for an export, fx_mu for everything else — is held for the object's life: one call
+//     at a time on its side stream.  hipSetDevice happens on entry.
+//   * begin() is the locked half.  Under the editor lock: the sample is validated and its storage description copied out
+//     (the pool's table may be reallocated by a later add_sample), check(&msg) judges the call (no device call; it looks
+//     up and copies out further samples through slot_locked()), a producer is refused where the pool's 2^24 ids would run
+//     out, and only then the pin is written — export_pin or edit_pin, or for a call of several samples the set
+//     edit_pins — against wbx_engine_delete_sample.  A refusal pins nothing and goes through efail.
+//   * What needs the heap is made by the caller BEFORE begin() and freed after the lock is released: the distinct ids
+//     of a set (begin() swaps them in, the destructor swaps them out again).
+//   * read() and make() are the unlocked half: the side stream and its staging are created without the lock, the stream is
+//     ordered behind what is enqueued under it, and run() — kernels, device waits, host copies, a new clip's allocation —
+//     works without it: the editor lock is NEVER held across a device wait (the rule of wbx_engine_levels, what the
+//     *_beside_the_audio_thread tests hold).  make() then registers the new sample under the lock.  A failure's text goes
+//     to tls_err.  A call may run more than once under its one pin (the normalizations measure, then derive).
+//   * The destructor drops the pin on every path out.
 struct SamplePin {
   using Step = wbx_status(wbx_ctx*, std::string*);
   wbx_engine* e;
   std::lock_guard<std::mutex> one;
   uint32_t wbx_engine::* word;
+  Step *prepare, *order_side;
   bool pinned = false, pinned_set = false;
   ClipSrc src;
   uint32_t rate = 0;
-  SamplePin(wbx_engine* e_, std::mutex& mu, uint32_t wbx_engine::* word_) : e(e_), one(mu), word(word_) {
+  enum Side { kEdit, kExport };
+  explicit SamplePin(wbx_engine* e_, Side side = kEdit)
+      : e(e_), one(side == kExport ? e_->ctx->export_mu : e_->ctx->fx_mu),
+        word(side == kExport ? &wbx_engine::export_pin : &wbx_engine::edit_pin),
+        prepare(side == kExport ? export_prepare : clipfx_prepare), order_side(side == kExport ? export_order : clipfx_order) {
     (void)hipSetDevice(e->ctx->cfg.device);
   }
   ~SamplePin() {
@@ -567,301 +584,217 @@ struct SamplePin {
     if (pinned) e->*word = wbx_engine::kNoExport;
     if (pinned_set) gone.swap(e->edit_pins);
   }
-  // (editor lock held) the sample's storage
-  wbx_status begin_locked(uint32_t sample, const char* what) {
-    const ClipSlot* s = e->hs.valid_sample(sample) ? find_clip(e->ctx, sample) : nullptr;
-    if (!s) return efail(e, WBX_ERR_INVALID, what);
-    src = clip_src(*s);
-    rate = s->d.sample_rate;
+  // (editor lock held) a sample's slot in the pool, null for an id that names none
+  const ClipSlot* slot_locked(uint32_t id) const { return e->hs.valid_sample(id) ? find_clip(e->ctx, id) : nullptr; }
+  // `unknown`: what an id that names no sample is told (null: the call names its samples in its check alone, a splice);
+  // `full`: what a producer is told where the ids would run out (null: a measurer); `set`: the distinct ids to pin (null:
+  // `sample` alone)
+  template <class Check>
+  wbx_status begin(uint32_t sample, const char* unknown, const char* full, std::vector<uint32_t>* set, Check&& check) {
+    LockGuard g(e->hs.editor_lock);
+    if (unknown) {
+      const ClipSlot* s = slot_locked(sample);
+      if (!s) return efail(e, WBX_ERR_INVALID, unknown);
+      src = clip_src(*s);
+      rate = s->d.sample_rate;
+    }
+    const char* msg = "";
+    const wbx_status st = check(&msg);
+    if (st != WBX_OK) return efail(e, st, msg);
+    if (full && e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, full);
+    if (set) {
+      e->edit_pins.swap(*set);
+      pinned_set = true;
+    } else {
+      e->*word = sample;
+      pinned = true;
+    }
     return WBX_OK;
   }
-  void pin_locked(uint32_t sample) {
-    e->*word = sample;
-    pinned = true;
+  // a run that makes no sample: run(&why)
+  template <class Run>
+  wbx_status read(Run&& run) {
+    std::string why;
+    wbx_status st = order(&why);
+    if (st == WBX_OK) st = run(&why);
+    if (st != WBX_OK) tls_err = why;
+    return st;
   }
-  void pin_set_locked(std::vector<uint32_t>& distinct) {   // the distinct sources, listed by the caller before it took the lock
-    e->edit_pins.swap(distinct);
-    pinned_set = true;
+  // a run that fills a new clip, run(slot, &why), which becomes the pool's next sample of `channels` x `frames` at `new_rate`
+  template <class Run>
+  wbx_status make(uint32_t channels, uint32_t new_rate, uint64_t frames, uint32_t* new_sample, Run&& run) {
+    ClipSlot slot;
+    return read([&](std::string* why) {
+      wbx_status st = run(slot, why);
+      if (st != WBX_OK) return st;
+      LockGuard g(e->hs.editor_lock);
+      st = register_sample_locked(e, slot, channels, new_rate, frames, new_sample);
+      if (st != WBX_OK) *why = e->ctx->err;
+      return st;
+    });
   }
-  wbx_status order(Step* prepare, Step* order_side, std::string* why) {   // the side stream: made without the lock, ordered under it
+
+ private:
+  wbx_status order(std::string* why) {                     // the side stream: made without the lock, ordered under it
     const wbx_status st = prepare(e->ctx, why);
     if (st != WBX_OK) return st;
     LockGuard g(e->hs.editor_lock);
     return order_side(e->ctx, why);
   }
-  wbx_status publish(ClipSlot& slot, uint32_t channels, uint32_t new_rate, uint64_t frames, uint32_t* new_sample, std::string* why) {
-    LockGuard g(e->hs.editor_lock);
-    const wbx_status st = register_sample_locked(e, slot, channels, new_rate, frames, new_sample);
-    if (st != WBX_OK) *why = e->ctx->err;
-    return st;
-  }
-  wbx_status measure(uint64_t first_frame, uint64_t n_frames, wbx_clip_stats* out, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = clipfx_measure_run(e->ctx, src, first_frame, n_frames, out, why);
-    return st;
-  }
-  wbx_status loudness(const LoudnessPlan& plan, uint64_t first_frame, uint64_t n_frames, wbx_loudness* out, double* hop_energy,
-                      std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = loudness_run(e->ctx, src, plan, first_frame, n_frames, out, hop_energy, why);
-    return st;
-  }
-  wbx_status f0(const F0Call& k, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = f0_run(e->ctx, src, k, frames_out, info, why);
-    return st;
-  }
-  wbx_status spectrum(const ClipSrc& basis, const SpecCall& k, float* power_out, wbx_spectrum_info* info, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = spectrum_run(e->ctx, src, basis, k, power_out, info, why);
-    return st;
-  }
-  wbx_status align(const ClipSrc& other, const AlignCall& k, wbx_align_info* info, wbx_align_point* curve_out, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = align_run(e->ctx, src, other, k, info, curve_out, why);
-    return st;
-  }
-  wbx_status onsets(const OnsetCall& k, wbx_onset_frame* frames_out, wbx_onset_info* info, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = onset_run(e->ctx, src, k, frames_out, info, why);
-    return st;
-  }
-  wbx_status tempo(const OnsetCall& k, const F0Call& track, wbx_f0_frame* frames_out, wbx_f0_info* info, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    if (st == WBX_OK) st = tempo_run(e->ctx, src, k, track, frames_out, info, why);
-    return st;
-  }
-  wbx_status derive(const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample, std::string* why) {
-    wbx_status st = order(clipfx_prepare, clipfx_order, why);
-    ClipSlot slot;
-    if (st == WBX_OK) st = clipfx_derive_run(e->ctx, src, rate, d, out_channels, slot, nullptr, why);
-    return st == WBX_OK ? publish(slot, out_channels, rate, d.n_frames, new_sample, why) : st;
-  }
 };
+
+// the ids a call of two samples pins, made before the lock: one id where both are the same sample
+std::vector<uint32_t> distinct_pair(uint32_t a, uint32_t b) {
+  std::vector<uint32_t> ids{a};
+  if (b != a) ids.push_back(b);
+  return ids;
+}
+
+// what derive_sample and the two normalizations end in: the range derived by `d`, registered at the source's rate
+wbx_status derive_pinned(SamplePin& p, const wbx_clip_edit_desc& d, uint32_t out_channels, uint32_t* new_sample) {
+  return p.make(out_channels, p.rate, d.n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return clipfx_derive_run(p.e->ctx, p.src, p.rate, d, out_channels, slot, nullptr, why);
+  });
+}
 
 }  // namespace
 
+// the one call on the export's mutex, pin and stream
 extern "C" wbx_status wbx_engine_export_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                int out_format, uint32_t flags, void* dst, wbx_export_stats* stats) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->export_mu, &wbx_engine::export_pin);
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "export: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = export_check(p.src, first_frame, n_frames, out_format, flags, dst, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  wbx_status st = p.order(export_prepare, export_order, &why);
-  if (st == WBX_OK) st = export_run(e->ctx, p.src, first_frame, n_frames, out_format, flags, dst, stats, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  SamplePin p(e, SamplePin::kExport);
+  const wbx_status st = p.begin(sample, "export: unknown sample", nullptr, nullptr, [&](const char** msg) {
+    return export_check(p.src, first_frame, n_frames, out_format, flags, dst, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return export_run(e->ctx, p.src, first_frame, n_frames, out_format, flags, dst, stats, why); });
 }
 
 extern "C" wbx_status wbx_engine_measure_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                 wbx_clip_stats* stats) {
   if (!e) return WBX_ERR_INVALID;
   if (!stats) return efail(e, WBX_ERR_INVALID, "measure_sample: stats is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "measure_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = clipfx_check_range(p.src, first_frame, n_frames, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.measure(first_frame, n_frames, stats, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  SamplePin p(e);
+  const wbx_status st = p.begin(sample, "measure_sample: unknown sample", nullptr, nullptr,
+                                [&](const char** msg) { return clipfx_check_range(p.src, first_frame, n_frames, msg); });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return clipfx_measure_run(e->ctx, p.src, first_frame, n_frames, stats, why); });
 }
 
 extern "C" wbx_status wbx_engine_derive_sample(wbx_engine* e, uint32_t sample, const wbx_clip_edit_desc* desc, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "derive_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   uint32_t out_channels = 0;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "derive_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = clipfx_check_derive(p.src, desc, &out_channels, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "derive_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.derive(*desc, out_channels, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "derive_sample: unknown sample", "derive_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) { return clipfx_check_derive(p.src, desc, &out_channels, msg); });
+  if (st != WBX_OK) return st;
+  return derive_pinned(p, *desc, out_channels, new_sample);
 }
 
+// two runs under one pin: the range's peak, then the range derived at target_peak over it
 extern "C" wbx_status wbx_engine_normalize_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                   float target_peak, uint32_t* new_sample, float* gain_used) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "normalize_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   wbx_clip_edit_desc d{};
   d.first_frame = first_frame;
   d.n_frames = n_frames;
   d.channel_mode = WBX_CH_KEEP;
   uint32_t out_channels = 0;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "normalize_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = clipfx_check_derive(p.src, &d, &out_channels, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "normalize_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
+  wbx_status st = p.begin(sample, "normalize_sample: unknown sample", "normalize_sample: the pool's sample ids (2^24) would run out", nullptr,
+                          [&](const char** msg) { return clipfx_check_derive(p.src, &d, &out_channels, msg); });
+  if (st != WBX_OK) return st;
   wbx_clip_stats m{};
-  wbx_status st = p.measure(first_frame, n_frames, &m, &why);
-  if (st != WBX_OK) return tls_err = why, st;
+  st = p.read([&](std::string* why) { return clipfx_measure_run(e->ctx, p.src, first_frame, n_frames, &m, why); });
+  if (st != WBX_OK) return st;
   const float peak = out_channels > 1 && m.peak[1] > m.peak[0] ? m.peak[1] : m.peak[0];
   if (!(peak > 0.0f) || !std::isfinite(peak)) return efail(e, WBX_ERR_INVALID, "normalize_sample: the range is silent, or its peak is not finite");
   d.gain = target_peak / peak;   // one IEEE fp32 division (no fast-math in this build)
-  st = p.derive(d, out_channels, new_sample, &why);
-  if (st != WBX_OK) return tls_err = why, st;
+  st = derive_pinned(p, d, out_channels, new_sample);
+  if (st != WBX_OK) return st;
   if (gain_used) *gain_used = d.gain;
   return WBX_OK;
 }
 
-// wbx_clip_resample of an engine sample (wbx.h "Converting a clip's sample rate"), beside wbx_engine_derive_sample and under
-// its rules: the editor lock covers validating, the pin, ordering the stream and registering the new sample — at dst_rate —
-// and is never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at dst_rate, with the conversion's n_out frames
 extern "C" wbx_status wbx_engine_resample_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                  uint32_t dst_rate, int quality, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "resample_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   ResamplePlan plan;
   uint64_t n_out = 0;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "resample_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = resample_check(p.src, p.rate, first_frame, n_frames, dst_rate, quality, &plan, &n_out, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "resample_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = resample_run(e->ctx, p.src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, dst_rate, n_out, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "resample_sample: unknown sample", "resample_sample: the pool's sample ids (2^24) would run out",
+                                nullptr, [&](const char** msg) {
+    return resample_check(p.src, p.rate, first_frame, n_frames, dst_rate, quality, &plan, &n_out, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, dst_rate, n_out, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return resample_run(e->ctx, p.src, plan, quality, first_frame, n_frames, n_out, dst_rate, slot, nullptr, why);
+  });
 }
 
-// wbx_clip_filter of an engine sample (wbx.h "Filtering a clip"), beside wbx_engine_resample_sample and under its rules: the
-// editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate — and is
-// never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at the source's rate, with the range's frames and the tail's
 extern "C" wbx_status wbx_engine_filter_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                uint64_t tail_frames, const double* coef, uint32_t n_stages, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "filter_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "filter_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = filter_check_call(p.src, first_frame, n_frames, tail_frames, coef, n_stages, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "filter_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = filter_run(e->ctx, p.src, p.rate, first_frame, n_frames, tail_frames, coef, n_stages, slot, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, n_frames + tail_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  SamplePin p(e);
+  const wbx_status st = p.begin(sample, "filter_sample: unknown sample", "filter_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) {
+    return filter_check_call(p.src, first_frame, n_frames, tail_frames, coef, n_stages, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, n_frames + tail_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return filter_run(e->ctx, p.src, p.rate, first_frame, n_frames, tail_frames, coef, n_stages, slot, nullptr, why);
+  });
 }
 
-// wbx_clip_convolve of two engine samples (wbx.h "Convolving a clip"), under wbx_engine_filter_sample's rules with
-// wbx_engine_splice_samples' pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the
-// source and the response (one id where they are the same sample), ordering the stream, registering the new sample — at
-// the source's rate — and unpinning; it is never held across the device wait.  No transport state is touched, no edit is
-// counted.
+// pins the source and the response; registered at the source's rate, with the check's channels and the window's frames
 extern "C" wbx_status wbx_engine_convolve_sample(wbx_engine* e, uint32_t sample, uint32_t ir_sample, uint64_t first_frame,
                                                  uint64_t n_frames, uint64_t ir_first, uint64_t ir_frames, uint64_t out_first,
                                                  uint64_t out_frames, double gain, uint32_t* new_sample, wbx_clip_stats* stats_of_result) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "convolve_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const ConvolveCall k{first_frame, n_frames, ir_first, ir_frames, out_first, out_frames, gain};
-  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
-  if (ir_sample != sample) distinct.push_back(ir_sample);
+  std::vector<uint32_t> distinct = distinct_pair(sample, ir_sample);
   ClipSrc ir;
   uint32_t ch = 0;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "convolve_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const ClipSlot* r = e->hs.valid_sample(ir_sample) ? find_clip(e->ctx, ir_sample) : nullptr;
-    if (!r) return efail(e, WBX_ERR_INVALID, "convolve_sample: unknown response sample");
+  const wbx_status st = p.begin(sample, "convolve_sample: unknown sample", "convolve_sample: the pool's sample ids (2^24) would run out",
+                                &distinct, [&](const char** msg) -> wbx_status {
+    const ClipSlot* r = p.slot_locked(ir_sample);
+    if (!r) return *msg = "convolve_sample: unknown response sample", WBX_ERR_INVALID;
     ir = clip_src(*r);
-    const char* msg = "";
-    st = convolve_check(p.src, p.rate, ir, r->d.sample_rate, k, &ch, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "convolve_sample: the pool's sample ids (2^24) would run out");
-    p.pin_set_locked(distinct);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = convolve_run(e->ctx, p.src, ir, p.rate, k, slot, stats_of_result, &why);
-  if (st == WBX_OK) st = p.publish(slot, ch, p.rate, out_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+    return convolve_check(p.src, p.rate, ir, r->d.sample_rate, k, &ch, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.make(ch, p.rate, out_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return convolve_run(e->ctx, p.src, ir, p.rate, k, slot, stats_of_result, why);
+  });
 }
 
-// wbx_clip_limit of an engine sample (wbx.h "Limiting a clip"), beside wbx_engine_filter_sample and under its rules: the
-// editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate — and is
-// never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at the source's rate, with the range's frames
 extern "C" wbx_status wbx_engine_limit_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, float ceiling,
                                               double drive, uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
                                               uint32_t* new_sample, wbx_limit_stats* limit_stats, wbx_clip_stats* stats_of_result) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "limit_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const LimitCall k{first_frame, n_frames, ceiling, drive, lookahead_frames, hold_frames, release_frames};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "limit_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = limit_check(p.src, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "limit_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = limit_run(e->ctx, p.src, p.rate, k, slot, limit_stats, stats_of_result, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, n_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "limit_sample: unknown sample", "limit_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) { return limit_check(p.src, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return limit_run(e->ctx, p.src, p.rate, k, slot, limit_stats, stats_of_result, why);
+  });
 }
 
-// wbx_clip_dynamics of engine samples (wbx.h "Dynamics of a clip"), under wbx_engine_convolve_sample's rules and with its
-// pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the source and the key (one id
-// where they are the same sample, or where there is no key), ordering the stream, registering the new sample — at the
-// source's rate — and unpinning; it is never held across the device wait.  No transport state is touched, no edit is counted.
+// pins the source and the key (no key with WBX_DYN_NO_KEY: the source alone); registered at the source's rate, with the
+// range's frames
 extern "C" wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t key_sample, uint64_t first_frame,
                                                  uint64_t n_frames, uint64_t key_first, int sense, const double* table, double drive,
                                                  double key_gain, double makeup, uint32_t lookahead_frames, uint32_t hold_frames,
@@ -869,253 +802,150 @@ extern "C" wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample,
                                                  wbx_clip_stats* stats_of_result) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "dynamics_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const bool keyed = key_sample != WBX_DYN_NO_KEY;
   const DynCall k{first_frame, n_frames, key_first, keyed, sense, table, drive, key_gain, makeup, lookahead_frames, hold_frames, release_frames};
-  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
-  if (keyed && key_sample != sample) distinct.push_back(key_sample);
+  std::vector<uint32_t> distinct = distinct_pair(sample, keyed ? key_sample : sample);
   ClipSrc key{};
   double lo = 1.0;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "dynamics_sample: unknown sample");
-    if (st != WBX_OK) return st;
+  const wbx_status st = p.begin(sample, "dynamics_sample: unknown sample", "dynamics_sample: the pool's sample ids (2^24) would run out",
+                                &distinct, [&](const char** msg) -> wbx_status {
     uint32_t key_rate = p.rate;
     if (keyed) {
-      const ClipSlot* r = e->hs.valid_sample(key_sample) ? find_clip(e->ctx, key_sample) : nullptr;
-      if (!r) return efail(e, WBX_ERR_INVALID, "dynamics_sample: unknown key sample");
+      const ClipSlot* r = p.slot_locked(key_sample);
+      if (!r) return *msg = "dynamics_sample: unknown key sample", WBX_ERR_INVALID;
       key = clip_src(*r);
       key_rate = r->d.sample_rate;
     }
-    const char* msg = "";
-    st = dynamics_check(p.src, p.rate, keyed ? &key : nullptr, key_rate, k, &lo, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "dynamics_sample: the pool's sample ids (2^24) would run out");
-    p.pin_set_locked(distinct);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = dynamics_run(e->ctx, p.src, keyed ? &key : nullptr, p.rate, k, lo, slot, dynamics_stats, stats_of_result, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, n_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+    return dynamics_check(p.src, p.rate, keyed ? &key : nullptr, key_rate, k, &lo, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return dynamics_run(e->ctx, p.src, keyed ? &key : nullptr, p.rate, k, lo, slot, dynamics_stats, stats_of_result, why);
+  });
 }
 
-// wbx_clip_stretch of an engine sample (wbx.h "Stretching a clip"), beside wbx_engine_limit_sample and under its rules: the
-// editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
-// out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at the source's rate, with out_frames frames
 extern "C" wbx_status wbx_engine_stretch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                 uint64_t out_frames, uint32_t window_frames, uint32_t tolerance_frames,
                                                 wbx_stretch_info* info, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "stretch_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const StretchCall k{first_frame, n_frames, out_frames, window_frames, tolerance_frames, false, 0};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "stretch_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = stretch_check(p.src, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "stretch_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = stretch_run(e->ctx, p.src, p.rate, k, slot, nullptr, info, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, out_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "stretch_sample: unknown sample", "stretch_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) { return stretch_check(p.src, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, out_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return stretch_run(e->ctx, p.src, p.rate, k, slot, nullptr, info, nullptr, why);
+  });
 }
 
-// wbx_clip_warp of an engine sample (wbx.h "Warping a clip"), beside wbx_engine_stretch_sample and under its rules: the
-// editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
-// out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at the source's rate, with out_frames frames
 extern "C" wbx_status wbx_engine_warp_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                              uint64_t out_frames, const wbx_warp_marker* markers, uint32_t n_markers,
                                              uint32_t window_frames, uint32_t tolerance_frames, wbx_warp_info* info,
                                              uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "warp_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const WarpCall k{first_frame, n_frames, out_frames, markers, n_markers, window_frames, tolerance_frames, false, 0};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "warp_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = warp_check(p.src, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "warp_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = warp_run(e->ctx, p.src, p.rate, k, slot, nullptr, info, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, out_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "warp_sample: unknown sample", "warp_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) { return warp_check(p.src, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, out_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return warp_run(e->ctx, p.src, p.rate, k, slot, nullptr, info, nullptr, why);
+  });
 }
 
-// wbx_clip_pitch of an engine sample (wbx.h "Pitch-shifting a clip"), beside wbx_engine_stretch_sample and under its rules:
-// the editor lock covers validating, the pin, ordering the stream and registering the new sample — at the source's rate, with
-// out_frames frames — and is never held across the device wait.  No transport state is touched, no edit is counted.
+// registered at the source's rate, with out_frames frames
 extern "C" wbx_status wbx_engine_pitch_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                               uint64_t out_frames, uint32_t num, uint32_t den, int quality, uint32_t window_frames,
                                               uint32_t tolerance_frames, wbx_pitch_info* info, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "pitch_sample: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const PitchCall k{first_frame, n_frames, out_frames, num, den, quality, window_frames, tolerance_frames, false, 0};
   ResamplePlan plan;
   StretchCall sk{};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "pitch_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = pitch_check(p.src, k, &plan, &sk, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "pitch_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  ClipSlot slot;
-  wbx_status st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = pitch_run(e->ctx, p.src, p.rate, k, plan, sk, slot, nullptr, info, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, p.src.channels, p.rate, out_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "pitch_sample: unknown sample", "pitch_sample: the pool's sample ids (2^24) would run out", nullptr,
+                                [&](const char** msg) { return pitch_check(p.src, k, &plan, &sk, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, out_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return pitch_run(e->ctx, p.src, p.rate, k, plan, sk, slot, nullptr, info, nullptr, why);
+  });
 }
 
-// wbx_clip_loudness of an engine sample (wbx.h "Measuring a clip's loudness"), beside wbx_engine_measure_sample and under its
-// rules: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                  uint32_t flags, wbx_loudness* out, double* hop_energy, size_t cap_doubles) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   LoudnessPlan plan;
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "loudness_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = loudness_check(p.src, p.rate, first_frame, n_frames, flags, out, hop_energy, cap_doubles, &plan, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.loudness(plan, first_frame, n_frames, out, hop_energy, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "loudness_sample: unknown sample", nullptr, nullptr, [&](const char** msg) {
+    return loudness_check(p.src, p.rate, first_frame, n_frames, flags, out, hop_energy, cap_doubles, &plan, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return loudness_run(e->ctx, p.src, plan, first_frame, n_frames, out, hop_energy, why); });
 }
 
-// wbx_clip_f0 of an engine sample (wbx.h "Tracking a clip's pitch"), beside wbx_engine_loudness_sample and under its rules:
-// the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_f0_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                            uint32_t window_frames, uint32_t hop_frames, uint32_t tau_min, uint32_t tau_max,
                                            double threshold, wbx_f0_frame* frames_out, size_t frames_cap, wbx_f0_info* info) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const F0Call k{first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold, frames_out != nullptr, frames_cap};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "f0_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = f0_check_call(p.src, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.f0(k, frames_out, info, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "f0_sample: unknown sample", nullptr, nullptr,
+                                [&](const char** msg) { return f0_check_call(p.src, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return f0_run(e->ctx, p.src, k, frames_out, info, why); });
 }
 
-// wbx_clip_spectrum of engine samples (wbx.h "Seeing a clip's spectrum"), under wbx_engine_f0_sample's rules and with
-// wbx_engine_dynamics_sample's pin: the editor lock covers validating, copying BOTH storage descriptions out, pinning the
-// source and the basis (one id where they are the same sample) and ordering the stream, and is never held across a device wait.
+// pins the source and the basis; an unknown basis is the check's to refuse
 extern "C" wbx_status wbx_engine_spectrum_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                  uint32_t channel, uint32_t basis_sample, uint32_t window_frames, uint32_t n_bins,
                                                  uint32_t hop_frames, float* power_out, size_t cells_cap, wbx_spectrum_info* info) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const SpecCall k{first_frame, n_frames, channel, window_frames, n_bins, hop_frames, power_out != nullptr, cells_cap};
-  std::vector<uint32_t> distinct{sample};                      // (made before the lock, like a splice's)
-  if (basis_sample != sample) distinct.push_back(basis_sample);
+  std::vector<uint32_t> distinct = distinct_pair(sample, basis_sample);
   ClipSrc basis{};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "spectrum_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const ClipSlot* b = e->hs.valid_sample(basis_sample) ? find_clip(e->ctx, basis_sample) : nullptr;
+  const wbx_status st = p.begin(sample, "spectrum_sample: unknown sample", nullptr, &distinct, [&](const char** msg) {
+    const ClipSlot* b = p.slot_locked(basis_sample);
     if (b) basis = clip_src(*b);
-    const char* msg = "";
-    st = spectrum_check_call(p.src, b ? &basis : nullptr, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_set_locked(distinct);
-  }
-  std::string why;
-  const wbx_status st = p.spectrum(basis, k, power_out, info, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+    return spectrum_check_call(p.src, b ? &basis : nullptr, k, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return spectrum_run(e->ctx, p.src, basis, k, power_out, info, why); });
 }
 
-// wbx_clip_align of engine samples (wbx.h "Aligning two clips"), wbx_engine_spectrum_sample's shape: the editor lock covers
-// validating, copying BOTH storage descriptions out, pinning the reference and the sample (one id where they are the same
-// sample) and ordering the stream, and is never held across the device wait.
+// pins the reference and the sample; an unknown sample is the check's to refuse
 extern "C" wbx_status wbx_engine_align_samples(wbx_engine* e, uint32_t ref_sample, uint64_t a_first, uint64_t n_frames, uint32_t sample,
                                                uint64_t b_first, uint64_t m_frames, int64_t lag_min, int64_t lag_max, uint32_t flags,
                                                wbx_align_info* info, wbx_align_point* curve_out, size_t curve_cap) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const AlignCall k{a_first, n_frames, b_first, m_frames, lag_min, lag_max, flags, info != nullptr, curve_out != nullptr, curve_cap};
-  std::vector<uint32_t> distinct{ref_sample};                  // (made before the lock, like a splice's)
-  if (sample != ref_sample) distinct.push_back(sample);
+  std::vector<uint32_t> distinct = distinct_pair(ref_sample, sample);
   ClipSrc other{};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(ref_sample, "align_samples: unknown reference sample");
-    if (st != WBX_OK) return st;
-    const ClipSlot* b = e->hs.valid_sample(sample) ? find_clip(e->ctx, sample) : nullptr;
+  const wbx_status st = p.begin(ref_sample, "align_samples: unknown reference sample", nullptr, &distinct, [&](const char** msg) {
+    const ClipSlot* b = p.slot_locked(sample);
     if (b) other = clip_src(*b);
-    const char* msg = "";
-    st = align_check_call(&p.src, p.rate, b ? &other : nullptr, b ? b->d.sample_rate : 0u, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_set_locked(distinct);
-  }
-  std::string why;
-  const wbx_status st = p.align(other, k, info, curve_out, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+    return align_check_call(&p.src, p.rate, b ? &other : nullptr, b ? b->d.sample_rate : 0u, k, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return align_run(e->ctx, p.src, other, k, info, curve_out, why); });
 }
 
-// wbx_clip_onsets and wbx_clip_tempo of an engine sample (wbx.h "Finding a clip's onsets and tempo"), wbx_engine_f0_sample's
-// shape: the editor lock covers validating, the pin and ordering the stream, and is never held across the device wait.
 extern "C" wbx_status wbx_engine_onsets_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                uint32_t hop_frames, double floor_power, double threshold, double delta, uint32_t w,
                                                uint32_t a, wbx_onset_frame* frames_out, size_t frames_cap, wbx_onset_info* info) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a, frames_out != nullptr, frames_cap};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "onsets_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = onset_check_call(p.src, k, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.onsets(k, frames_out, info, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "onsets_sample: unknown sample", nullptr, nullptr,
+                                [&](const char** msg) { return onset_check_call(p.src, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return onset_run(e->ctx, p.src, k, frames_out, info, why); });
 }
 
 extern "C" wbx_status wbx_engine_tempo_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
@@ -1123,33 +953,24 @@ extern "C" wbx_status wbx_engine_tempo_sample(wbx_engine* e, uint32_t sample, ui
                                               uint32_t lag_min, uint32_t lag_max, double threshold, wbx_f0_frame* frames_out,
                                               size_t frames_cap, wbx_f0_info* info) {
   if (!e) return WBX_ERR_INVALID;
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, 0.0, 0.0, 0u, 0u, false, 0};
   F0Call track{0, 0, window_hops, step_hops, lag_min, lag_max, threshold, frames_out != nullptr, frames_cap};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "tempo_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = tempo_check_call(p.src, k, &track, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    p.pin_locked(sample);
-  }
-  std::string why;
-  const wbx_status st = p.tempo(k, track, frames_out, info, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  const wbx_status st = p.begin(sample, "tempo_sample: unknown sample", nullptr, nullptr,
+                                [&](const char** msg) { return tempo_check_call(p.src, k, &track, msg); });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return tempo_run(e->ctx, p.src, k, track, frames_out, info, why); });
 }
 
-// ... and the range derived at the gain that brings its integrated loudness to target_lufs, under a true-peak ceiling:
-// wbx_engine_normalize_sample with another measurement in front
+// two runs under one pin: the range's loudness (and true peak under a ceiling), then the range derived at the gain that
+// brings its integrated loudness to target_lufs
 extern "C" wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                            double target_lufs, float true_peak_ceiling, uint32_t* new_sample,
                                                            float* gain_used) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: new_sample is NULL");
   if (!(true_peak_ceiling >= 0.0f)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: a negative ceiling, or a NaN");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   wbx_clip_edit_desc d{};
   d.first_frame = first_frame;
   d.n_frames = n_frames;
@@ -1157,21 +978,15 @@ extern "C" wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32
   uint32_t out_channels = 0;
   LoudnessPlan plan;
   wbx_loudness m{};
-  {
-    LockGuard g(e->hs.editor_lock);
-    wbx_status st = p.begin_locked(sample, "normalize_loudness_sample: unknown sample");
-    if (st != WBX_OK) return st;
-    const char* msg = "";
-    st = loudness_check(p.src, p.rate, first_frame, n_frames, true_peak_ceiling > 0.0f ? (uint32_t)WBX_LOUD_TRUE_PEAK : 0u, &m, nullptr,
-                        0, &plan, &msg);
-    if (st == WBX_OK) st = clipfx_check_derive(p.src, &d, &out_channels, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "normalize_loudness_sample: the pool's sample ids (2^24) would run out");
-    p.pin_locked(sample);
-  }
-  std::string why;
-  wbx_status st = p.loudness(plan, first_frame, n_frames, &m, nullptr, &why);
-  if (st != WBX_OK) return tls_err = why, st;
+  wbx_status st = p.begin(sample, "normalize_loudness_sample: unknown sample",
+                          "normalize_loudness_sample: the pool's sample ids (2^24) would run out", nullptr, [&](const char** msg) {
+    const wbx_status ok = loudness_check(p.src, p.rate, first_frame, n_frames, true_peak_ceiling > 0.0f ? (uint32_t)WBX_LOUD_TRUE_PEAK : 0u,
+                                         &m, nullptr, 0, &plan, msg);
+    return ok == WBX_OK ? clipfx_check_derive(p.src, &d, &out_channels, msg) : ok;
+  });
+  if (st != WBX_OK) return st;
+  st = p.read([&](std::string* why) { return loudness_run(e->ctx, p.src, plan, first_frame, n_frames, &m, nullptr, why); });
+  if (st != WBX_OK) return st;
   if (!std::isfinite(m.integrated)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: the range has no integrated loudness (silent, or shorter than 4 hops)");
   float g = (float)std::pow(10.0, (target_lufs - m.integrated) / 20.0);
   if (true_peak_ceiling > 0.0f) {
@@ -1181,26 +996,22 @@ extern "C" wbx_status wbx_engine_normalize_loudness_sample(wbx_engine* e, uint32
   }
   if (!(g > 0.0f) || !std::isfinite(g)) return efail(e, WBX_ERR_INVALID, "normalize_loudness_sample: the gain is not finite and positive");
   d.gain = g;
-  st = p.derive(d, out_channels, new_sample, &why);
-  if (st != WBX_OK) return tls_err = why, st;
+  st = derive_pinned(p, d, out_channels, new_sample);
+  if (st != WBX_OK) return st;
   if (gain_used) *gain_used = g;
   return WBX_OK;
 }
 
-// wbx_clip_splice of engine samples (wbx.h "Splicing clips"), under wbx_engine_derive_sample's rules: the editor lock covers
-// validating the part list against the samples, copying every source's storage description out, pinning every distinct
-// source, ordering the stream, registering the new sample — at the sources' common rate — and unpinning.  The tile table is
-// built, the descriptors are uploaded and the device is waited for without it.  No transport state is touched, no edit is
-// counted.
+// pins every distinct source the parts name (its check names them: no sample of its own); the tile table is built between
+// the locked half and the run, without the lock; registered at the sources' common rate
 extern "C" wbx_status wbx_engine_splice_samples(wbx_engine* e, uint32_t channels, uint64_t n_frames, const wbx_splice_part* parts,
                                                 uint32_t n_parts, uint32_t* new_sample) {
   if (!e) return WBX_ERR_INVALID;
   if (!new_sample) return efail(e, WBX_ERR_INVALID, "splice_samples: new_sample is NULL");
-  SamplePin p(e, e->ctx->fx_mu, &wbx_engine::edit_pin);
+  SamplePin p(e);
   SplicePlan plan;
-  const char* msg = "";
-  // what needs the heap is made before the lock: the distinct source ids (of a list not yet checked: nothing is pinned
-  // where the check refuses it) and room for the storage descriptions
+  // made before the lock: the distinct source ids (of a list not yet checked: nothing is pinned where the check refuses
+  // it) and room for the storage descriptions
   std::vector<uint32_t> distinct;
   std::vector<ClipSrc> srcs;
   if (parts && n_parts && n_parts <= kSpliceMaxParts) {
@@ -1210,30 +1021,26 @@ extern "C" wbx_status wbx_engine_splice_samples(wbx_engine* e, uint32_t channels
     distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
     srcs.resize(n_parts);
   }
-  {
-    LockGuard g(e->hs.editor_lock);
+  wbx_status st = p.begin(0, nullptr, "splice_samples: the pool's sample ids (2^24) would run out", &distinct, [&](const char** msg) {
     wbx_splice_source tmp{};
     const auto source_of = [&](uint32_t id) -> const wbx_splice_source* {
-      const ClipSlot* s = e->hs.valid_sample(id) ? find_clip(e->ctx, id) : nullptr;
+      const ClipSlot* s = p.slot_locked(id);
       if (!s) return nullptr;
       tmp = wbx_splice_source{s->d.channels, s->d.sample_rate, s->d.count, (int32_t)s->d.format, 0u};
       return &tmp;
     };
-    const wbx_status st = splice_check(channels, n_frames, parts, n_parts, source_of, &plan.rate, &msg);
-    if (st != WBX_OK) return efail(e, st, msg);
-    if (e->ctx->clips.size() >= (1u << 24)) return efail(e, WBX_ERR_OVERFLOW, "splice_samples: the pool's sample ids (2^24) would run out");
-    for (uint32_t i = 0; i < n_parts; i++) srcs[i] = clip_src(e->ctx->clips[parts[i].src_clip]);
-    p.pin_set_locked(distinct);
-  }
-  wbx_status st = splice_plan_table(n_frames, parts, n_parts, &plan, &msg);
+    const wbx_status ok = splice_check(channels, n_frames, parts, n_parts, source_of, &plan.rate, msg);
+    if (ok == WBX_OK)
+      for (uint32_t i = 0; i < n_parts; i++) srcs[i] = clip_src(e->ctx->clips[parts[i].src_clip]);
+    return ok;
+  });
+  if (st != WBX_OK) return st;
+  const char* msg = "";
+  st = splice_plan_table(n_frames, parts, n_parts, &plan, &msg);
   if (st != WBX_OK) return efail(e, st, msg);
-  std::string why;
-  ClipSlot slot;
-  st = p.order(clipfx_prepare, clipfx_order, &why);
-  if (st == WBX_OK) st = splice_run(e->ctx, srcs.data(), parts, n_parts, plan, channels, n_frames, slot, nullptr, &why);
-  if (st == WBX_OK) st = p.publish(slot, channels, plan.rate, n_frames, new_sample, &why);
-  if (st != WBX_OK) tls_err = why;
-  return st;
+  return p.make(channels, plan.rate, n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return splice_run(e->ctx, srcs.data(), parts, n_parts, plan, channels, n_frames, slot, nullptr, why);
+  });
 }
 
 // Engine::add_audio_clip -> add_to_cliplist, engine.cpp:293-309, :409-461

@@ -301,15 +301,7 @@ extern "C" uint64_t wbx_f0_launch_terms(void) { return wbx::kF0LaunchTerms; }
 extern "C" uint32_t wbx_f0_launch_hops(uint32_t window_frames, uint32_t tau_max) { return wbx::f0_launch_hops(window_frames, tau_max); }
 
 extern "C" wbx_status wbx_f0_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  F0Stage& z = c->f0;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, "f0 time: no f0 call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::f0, "f0 time: no f0 call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_f0(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
@@ -322,13 +314,7 @@ extern "C" wbx_status wbx_clip_f0(wbx_ctx* c, uint32_t clip, uint64_t first_fram
   const ClipSrc src = clip_src(*s);
   const F0Call k{first_frame, n_frames, window_frames, hop_frames, tau_min, tau_max, threshold, frames_out != nullptr, frames_cap};
   const char* msg = "";
-  wbx_status st = f0_check_call(src, k, &msg);
+  const wbx_status st = f0_check_call(src, k, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = f0_run(c, src, k, frames_out, info, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return f0_run(c, src, k, frames_out, info, why); });
 }

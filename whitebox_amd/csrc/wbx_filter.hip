@@ -242,10 +242,8 @@ wbx_status filter_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, uint64_t fi
                       const double* coef, uint32_t n_stages, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
   const uint64_t n_out = n_frames + tail_frames;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, n_out, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, n_out, why);
+  if (st != WBX_OK) return st;
   FilterStage& x = c->filt;
   const uint32_t D = 2u * n_stages + 2u;
   FilterArgs a{};
@@ -298,11 +296,7 @@ wbx_status filter_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, uint64_t fi
   }
   x.timed = true;
   x.carried = a.n_chunks > 1u;
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, n_out, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, n_out, stats, why);
 }
 
 }  // namespace wbx

@@ -376,25 +376,7 @@ wbx_status gain_run(wbx_ctx* c, Z& z, const char* what, hipError_t e, Args& a, u
   x.ramp_of[0] = A, x.ramp_of[1] = H, x.ramp_of[2] = R;
   z.timed = true;
   report(z.h_total.p[0]);
-  wbx_status st = WBX_OK;
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, n_frames, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
-}
-
-// the device time of the last run between z's two events (wbx_limit_ms, wbx_dynamics_ms); `none`: no run has completed
-template <class Z>
-wbx_status gain_ms(wbx_ctx* c, Z wbx_ctx::*stage, const char* none, double* out) {
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  Z& z = c->*stage;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, none);
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return clipfx_measure_result(c, slot, n_frames, stats, why);
 }
 
 }  // namespace wbx

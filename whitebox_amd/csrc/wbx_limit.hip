@@ -109,10 +109,8 @@ wbx_status limit_check(const ClipSrc& src, const LimitCall& k, const char** why)
 wbx_status limit_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const LimitCall& k, ClipSlot& slot, wbx_limit_stats* out,
                      wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  const wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, k.n_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, k.n_frames, why);
+  if (st != WBX_OK) return st;
   LimitArgs a{};
   for (uint32_t i = 0; i < 2; i++) {
     a.src[i] = clip_row(src, i) + k.first_frame;
@@ -144,7 +142,7 @@ extern "C" uint32_t wbx_limit_segment_terms(void) { return kLimitSegment; }
 extern "C" uint32_t wbx_limit_band_frames(void) { return kLimitBand; }
 
 extern "C" wbx_status wbx_limit_ms(wbx_ctx* c, double* out) {
-  return gain_ms(c, &wbx_ctx::lim, "limit time: no limit has completed on this context", out);
+  return stage_ms(c, &wbx_ctx::lim, "limit time: no limit has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_limit(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,

@@ -304,13 +304,7 @@ extern "C" wbx_status wbx_clip_loudness(wbx_ctx* c, uint32_t clip, uint64_t firs
   const ClipSrc src = clip_src(*s);
   const char* msg = "";
   LoudnessPlan plan;
-  wbx_status st = loudness_check(src, s->d.sample_rate, first_frame, n_frames, flags, out, hop_energy, cap_doubles, &plan, &msg);
+  const wbx_status st = loudness_check(src, s->d.sample_rate, first_frame, n_frames, flags, out, hop_energy, cap_doubles, &plan, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = loudness_run(c, src, plan, first_frame, n_frames, out, hop_energy, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return loudness_run(c, src, plan, first_frame, n_frames, out, hop_energy, why); });
 }

@@ -357,15 +357,7 @@ extern "C" wbx_status wbx_onset_pick(wbx_onset_frame* frames, uint64_t hops, dou
 }
 
 extern "C" wbx_status wbx_onset_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  OnsetStage& z = c->ons;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, "onset time: no onsets or tempo call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::ons, "onset time: no onsets or tempo call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_onsets(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
@@ -378,15 +370,9 @@ extern "C" wbx_status wbx_clip_onsets(wbx_ctx* c, uint32_t clip, uint64_t first_
   const ClipSrc src = clip_src(*s);
   const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, threshold, delta, w, a, frames_out != nullptr, frames_cap};
   const char* msg = "";
-  wbx_status st = onset_check_call(src, k, &msg);
+  const wbx_status st = onset_check_call(src, k, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = onset_run(c, src, k, frames_out, info, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return onset_run(c, src, k, frames_out, info, why); });
 }
 
 extern "C" wbx_status wbx_clip_tempo(wbx_ctx* c, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t hop_frames,
@@ -400,13 +386,7 @@ extern "C" wbx_status wbx_clip_tempo(wbx_ctx* c, uint32_t clip, uint64_t first_f
   const OnsetCall k{first_frame, n_frames, hop_frames, floor_power, 0.0, 0.0, 0u, 0u, false, 0};
   F0Call track{0, 0, window_hops, step_hops, lag_min, lag_max, threshold, frames_out != nullptr, frames_cap};
   const char* msg = "";
-  wbx_status st = tempo_check_call(src, k, &track, &msg);
+  const wbx_status st = tempo_check_call(src, k, &track, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = tempo_run(c, src, k, track, frames_out, info, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return tempo_run(c, src, k, track, frames_out, info, why); });
 }

@@ -138,10 +138,8 @@ wbx_status pitch_check(const ClipSrc& src, const PitchCall& k, ResamplePlan* pla
 wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchCall& k, const ResamplePlan& plan, const StretchCall& sk,
                      ClipSlot& slot, int32_t* positions_out, wbx_pitch_info* info, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, k.out_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, k.out_frames, why);
+  if (st != WBX_OK) return st;
   StretchStage& z = c->str;
   PitchStage& y = c->pit;
   const uint32_t N = sk.window, Hs = N / 2u;
@@ -232,11 +230,7 @@ wbx_status pitch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const PitchC
     info->L = plan.L;
     info->M = plan.M;
   }
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, k.out_frames, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, k.out_frames, stats, why);
 }
 
 }  // namespace wbx
@@ -261,15 +255,7 @@ extern "C" wbx_status wbx_pitch_launch_shape(uint32_t num, uint32_t den, int qua
 }
 
 extern "C" wbx_status wbx_pitch_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  PitchStage& y = c->pit;
-  if (!y.timed) return fail(c, WBX_ERR_INVALID, "pitch time: no pitch call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, y.mark[0], y.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::pit, "pitch time: no pitch call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_pitch(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,

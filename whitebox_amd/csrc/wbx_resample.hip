@@ -149,10 +149,8 @@ hipError_t resample_table_device(wbx_ctx* c, const ResamplePlan& p, int quality,
 // `slot` becomes the new clip (built on the edit stream; complete when this returns WBX_OK, released otherwise)
 wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, int quality, uint64_t first_frame, uint64_t n_frames,
                         uint64_t n_out, uint32_t dst_rate, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, dst_rate, n_out, fill, c->fx.side.stream);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, dst_rate, n_out, why);
+  if (st != WBX_OK) return st;
   ResampleArgs a{};
   bool fresh = false;
   hipError_t e = resample_table_device(c, p, quality, &a.table, &fresh);
@@ -176,11 +174,7 @@ wbx_status resample_run(wbx_ctx* c, const ClipSrc& src, const ResamplePlan& p, i
     clip_release(c, slot);
     return stage_fail(why, WBX_ERR_DEVICE, "clip resample", e);
   }
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, n_out, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, n_out, stats, why);
 }
 
 }  // namespace wbx

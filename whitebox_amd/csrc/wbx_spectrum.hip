@@ -307,13 +307,7 @@ extern "C" wbx_status wbx_clip_spectrum(wbx_ctx* c, uint32_t clip, uint64_t firs
   const ClipSrc basis = bs ? clip_src(*bs) : ClipSrc{};
   const SpecCall k{first_frame, n_frames, channel, window_frames, n_bins, hop_frames, power_out != nullptr, cells_cap};
   const char* msg = "";
-  wbx_status st = spectrum_check_call(src, bs ? &basis : nullptr, k, &msg);
+  const wbx_status st = spectrum_check_call(src, bs ? &basis : nullptr, k, &msg);
   if (st != WBX_OK) return fail(c, st, msg);
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  std::string why;
-  st = clipfx_prepare(c, &why);
-  if (st == WBX_OK) st = clipfx_order(c, &why);
-  if (st == WBX_OK) st = spectrum_run(c, src, basis, k, power_out, info, &why);
-  if (st != WBX_OK) c->err = why;
-  return st;
+  return clipfx_reading(c, [&](std::string* why) { return spectrum_run(c, src, basis, k, power_out, info, why); });
 }

@@ -182,10 +182,8 @@ static SplicePartDev splice_part_dev(const ClipSrc& src, const wbx_splice_part& 
 wbx_status splice_run(wbx_ctx* c, const ClipSrc* srcs, const wbx_splice_part* parts, uint32_t n_parts, const SplicePlan& plan,
                       uint32_t channels, uint64_t n_frames, ClipSlot& slot, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, channels, plan.rate, n_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, channels, plan.rate, n_frames, why);
+  if (st != WBX_OK) return st;
   std::vector<SplicePartDev> dev(n_parts);                   // the uploads' sources: alive until the stream has been waited for
   for (uint32_t i = 0; i < n_parts; i++) dev[i] = splice_part_dev(srcs[i], parts[i]);
   SpliceStage& x = c->splice;
@@ -215,11 +213,7 @@ wbx_status splice_run(wbx_ctx* c, const ClipSrc* srcs, const wbx_splice_part* pa
     clip_release(c, slot);
     return stage_fail(why, WBX_ERR_DEVICE, "clip splice", e);
   }
-  if (stats) {                                               // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, n_frames, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, n_frames, stats, why);
 }
 
 }  // namespace wbx

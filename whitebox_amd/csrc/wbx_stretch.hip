@@ -127,10 +127,8 @@ wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** 
 wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const StretchCall& k, ClipSlot& slot, int32_t* positions_out,
                        wbx_stretch_info* info, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, k.out_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, k.out_frames, why);
+  if (st != WBX_OK) return st;
   StretchStage& z = c->str;
   const uint32_t N = k.window, Hs = N / 2u;
   const uint64_t n = k.n_frames, m = k.out_frames, K = stretch_steps(m, N);
@@ -210,11 +208,7 @@ wbx_status stretch_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const Stre
     info->max_shift = t.max_shift;
     info->launches = (uint32_t)launches;
   }
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, m, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, m, stats, why);
 }
 
 }  // namespace wbx
@@ -234,15 +228,7 @@ extern "C" uint32_t wbx_stretch_launch_steps(uint64_t n_frames, uint32_t window_
 }
 
 extern "C" wbx_status wbx_stretch_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  StretchStage& z = c->str;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, "stretch time: no stretch call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::str, "stretch time: no stretch call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_stretch(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,

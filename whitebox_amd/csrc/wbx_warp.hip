@@ -183,10 +183,8 @@ wbx_status warp_check(const ClipSrc& src, const WarpCall& k, const char** why) {
 wbx_status warp_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const WarpCall& k, ClipSlot& slot, int32_t* positions_out,
                     wbx_warp_info* info, wbx_clip_stats* stats, std::string* why) {
   const hipStream_t on = c->fx.side.stream;
-  ClipFill fill{};
-  fill.kind = CLIP_SRC_NONE;   // the kernel writes every frame; clip_build clears the 16 padding frames (and the row's slack)
-  wbx_status st = clip_build(c, slot, WBX_FMT_F32, src.channels, rate, k.out_frames, fill, on);
-  if (st != WBX_OK) return *why = c->err, st;
+  const wbx_status st = clipfx_blank_clip(c, slot, src.channels, rate, k.out_frames, why);
+  if (st != WBX_OK) return st;
   WarpStage& z = c->wrp;
   StretchStage& zs = c->str;                                   // the window table is the stretch's
   const uint32_t N = k.window, Hs = N / 2u, S = k.n_markers + 1u;
@@ -279,11 +277,7 @@ wbx_status warp_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const WarpCal
     info->segments = S;
     info->longest_segment_steps = (uint32_t)plan.longest;
   }
-  if (stats) {                                                 // the measure pass over the result, on the same stream
-    st = clipfx_measure_run(c, clip_src(slot), 0, m, stats, why);
-    if (st != WBX_OK) clip_release(c, slot);
-  }
-  return st;
+  return clipfx_measure_result(c, slot, m, stats, why);
 }
 
 }  // namespace wbx
@@ -309,15 +303,7 @@ extern "C" uint64_t wbx_warp_launches(uint64_t n_frames, uint64_t out_frames, co
 }
 
 extern "C" wbx_status wbx_warp_ms(wbx_ctx* c, double* out) {
-  using namespace wbx;
-  if (!c || !out) return WBX_ERR_INVALID;
-  std::lock_guard<std::mutex> g(c->fx_mu);
-  WarpStage& z = c->wrp;
-  if (!z.timed) return fail(c, WBX_ERR_INVALID, "warp time: no warp call has completed on this context");
-  float ms = 0.0f;
-  WBX_HIP(c, hipEventElapsedTime(&ms, z.mark[0], z.mark[1]));
-  *out = (double)ms;
-  return WBX_OK;
+  return wbx::stage_ms(c, &wbx_ctx::wrp, "warp time: no warp call has completed on this context", out);
 }
 
 extern "C" wbx_status wbx_clip_warp(wbx_ctx* c, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
