@@ -751,6 +751,96 @@ wbx_status wbx_clip_dynamics(wbx_ctx* ctx, uint32_t src_clip, uint32_t key_clip 
                              uint32_t lookahead_frames, uint32_t hold_frames, uint32_t release_frames,
                              wbx_dynamics_stats* dynamics_stats, wbx_clip_stats* stats_of_result);
 
+/* Saturating a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels through an
+ * OVERSAMPLED table waveshaper into a NEW F32 clip of n_frames frames, the source's channels and rate and NO delay, without
+ * the samples leaving HBM: a soft clipper, tape or tube style saturation, or any hand-drawn transfer curve applied to the
+ * samples themselves, between the compressor and the limiter of a mastering chain.  The limiter and the dynamics only
+ * multiply by a gain curve; this is the memoryless non-linearity, which adds harmonics.  At the clip's own rate a
+ * waveshaper aliases, so the call converts up by os, shapes, and band-limits back, as ONE call whose intermediate is never
+ * stored.  The curve is a table the HOST builds, so the device needs no tanh and no exp.  No reference counterpart.  This
+ * text is the specification; tests/saturate_model.py restates it in numpy (the two conversions are
+ * tests/resample_model.py's), and the table, the statistics and every output sample equal that BIT FOR BIT.
+ * n = n_frames; os is 1, 2, 4 or 8; quality is WBX_SRC_FAST / GOOD / BEST with its Z zero crossings (12 / 24 / 48); drive
+ * is linear, finite with 0 < |drive| <= 2^32; makeup is linear, finite with |makeup| <= 2^32 (0 is allowed); the table has
+ * WBX_SAT_TABLE = 16385 doubles, every entry finite with a magnitude <= 2^32 (wbx_saturate_check).  Every operator below is
+ * one IEEE fp64 operation and nothing is fused, except that the product of two fp32 values added into an fp64 accumulator
+ * may be an fma: that product is exact, as in "Converting a clip's sample rate".
+ *   up        (only when os > 1) that section's conversion with L = os, M = 1 at `quality`, unchanged: its table
+ *             wbx_resample_table(1, os, quality), H = Z, T = 2 Z.  Mid sample j in [0, n os): i = j div os, p = j mod os,
+ *             u[c][j] = (float)(sum over k of h_up[p][k] * x[c][i - (Z - 1) + k]), k ascending from acc = 0.0.  x is ZERO
+ *             outside the range whatever the clip holds there, and nothing beside the range is ever read.  A NaN is
+ *             stored as 0x7FC00000.  With os == 1, u = x
+ *   shape     d = finite(u) ? drive * (double)u : 0.0;  a = d * 1024.0;  a <= -8192: w = tab[0];  a >= 8192: w = tab[16384];
+ *             otherwise fl = floor(a), idx = (int)fl + 8192 (0 .. 16383), f = a - fl (ONE subtraction: it may round to
+ *             1.0 for a tiny negative a), w = tab[idx] + f * (tab[idx + 1] - tab[idx]).  Entry k belongs to the level
+ *             (k - 8192) / 1024: +-8 full scales, 1024 cells per unit.  s[c][j] = (float)(w * makeup)
+ *   down      (only when os > 1) that section's conversion with L = 1, M = os at `quality`, unchanged: one phase,
+ *             H = Z os, T = 2 Z os.  y[c][i] = (float)(sum over k of h_dn[k] * s[c][i os - (H - 1) + k]), ascending.  s is
+ *             ZERO outside [0, n os) — NOT shape(0): the intermediate counts as a whole file, as it does there.  With
+ *             os == 1, y = s
+ * BY DEFINITION the call with os > 1 is these three existing calls in a row: wbx_clip_resample to rate * os, this call with
+ * os = 1, wbx_clip_resample back to rate; every output bit equals that composition.  No NaN and no infinity can appear in
+ * the result: what is not finite enters the shape as 0.0; |f| <= 1 and the entries are at most 2^32, so |w| <= 3 * 2^32 and
+ * |w * makeup| < 2^66, which an fp32 holds — s is always finite; the down filter has at most 768 coefficients, each below 2 in
+ * magnitude, so its sum stays below 2^77, which an fp32 holds as well.
+ * NO CEILING GUARANTEE: the band-limiting overshoots.  A hard table at drive 8 over a half-scale sine gives a peak of 1.156
+ * at os = 4.  Where a ceiling must hold, follow the call with wbx_clip_limit.
+ *   wbx_saturate_stats (may be NULL; every field independent of order): peak_drive = the greatest |d| over all channels and
+ *             mid samples j in [0, n os); peak_index = the lowest such j; beyond = the count over channels and j of
+ *             |a| >= 8192.  Every mid sample counts once.
+ * dst_clip becomes a new F32 pool clip of n frames (plus the pool's 16 zero frames of padding), replaced or allocated as
+ * wbx_clip_derive does it, on the same stream and behind the same ordering; one edit, conversion, filter, convolution,
+ * limit, dynamics or saturate call runs at a time.  Nothing else is allocated in the pool: the oversampled intermediate
+ * lives in the workgroups' LDS.  stats_of_result (may be NULL): wbx_clip_measure of the whole result, a
+ * second pass over the output only.
+ * Refused before any device call, nothing allocated, dst_clip and stats untouched, in this order.  First the sizes and
+ * parameters, before the clips are looked at — WBX_ERR_INVALID: n_frames of 0; an os that is not 1, 2, 4 or 8; an unknown
+ * quality; a NULL table or one wbx_saturate_check refuses; a drive, then a makeup outside the ranges above; n_frames * os
+ * >= 2^31 - 16.  Then what wbx_resample_plan(1, os, quality) or (os, 1, quality) refuses, with its status and reason:
+ * WBX_SRC_BEST at os = 8 has T = 768 > 512 and is WBX_ERR_UNSUPPORTED.  Then the clip — WBX_ERR_INVALID: an unknown source
+ * clip; a range past the clip; dst_clip equal to the source; WBX_ERR_UNSUPPORTED: a source that is not F32 or has more than
+ * 2 channels; last, wbx_clip_derive's rule: WBX_ERR_INVALID for a dst_clip of 2^24 or more.  WBX_ERR_OOM as for
+ * wbx_clip_derive.
+ * Host-only, no device (wbx_saturate.h, which a C++ compiler takes alone):
+ * wbx_saturate_table writes the 16385 entries of a usual curve: entry k = f(v + bias) - f(bias) with v = ((double)k -
+ *             8192.0) / 1024.0 and |bias| <= 4 (a bias gives even harmonics).  WBX_SAT_HARD: f(z) = z clamped to +-1.
+ *             WBX_SAT_CUBIC: +-1 where |z| >= 1.5, else z - (c z) (z z) with c = 4.0 / 27.0.  WBX_SAT_TANH: a = |z|,
+ *             e = exp2((-2.0 a) * 1.4426950408889634) — wbx_dynamics_table's exp2, whose argument is <= 0 —,
+ *             t = (1.0 - e) / (1.0 + e), with the sign of z.  No libm, so the table is the same on every host.  With
+ *             bias == 0 the table is exactly odd and entry 8192 is exactly 0.0.  WBX_ERR_INVALID: NULL out, cap_doubles
+ *             below WBX_SAT_TABLE, an unknown kind, a bias outside the range or a NaN; nothing is written then
+ * wbx_saturate_check judges any table, designed or hand-drawn (WBX_ERR_INVALID: NULL, an entry that is not finite or whose
+ *             magnitude exceeds 2^32)
+ * wbx_saturate_lookup the lookup above for one driven sample d (WBX_ERR_INVALID: NULL table or out, a NaN)
+ * wbx_saturate_launch_shape how a call is launched: the tile (output frames of one workgroup: a multiple of 256, at most
+ *             1024, the greatest whose LDS stays within 64 KB), the mid samples (tile + 2 Z) os and the source frames
+ *             tile + 4 Z - 1 a tile computes and stages per channel, the LDS bytes channels * 4 * ((tile + 2 Z) os + tile +
+ *             4 Z), and the tiles = the grid, ceil(n / tile) <= 2^21.  os == 1: tile 1024, both spans 1024, no LDS.
+ *             Refused as the call refuses os, quality and n_frames; WBX_ERR_INVALID for channels other than 1 or 2 or a
+ *             NULL pointer
+ * wbx_saturate_ms: device milliseconds between two events on the edits' stream around the table's upload (and the filters',
+ * where os or the quality changed) and the two launches of the context's last completed saturate call (layer 1's or layer
+ * 2's).  WBX_ERR_INVALID for NULL arguments or when none has completed.  For
+ * tools/bench_saturate.py; nothing else reads it.
+ * Not offered: waveshaping at render time or on buses, a true-peak-safe clipper (no ceiling guarantee, see above),
+ * oversampling above 8, unlinked per-channel tables, more than 2 channels, in-place edits. */
+enum { WBX_SAT_HARD = 0, WBX_SAT_CUBIC = 1, WBX_SAT_TANH = 2 };
+#define WBX_SAT_TABLE 16385
+typedef struct wbx_saturate_stats { /* 24 bytes */
+  double peak_drive;
+  uint64_t peak_index;
+  uint64_t beyond;
+} wbx_saturate_stats;
+wbx_status wbx_saturate_table(int kind, double bias, double* out, size_t cap_doubles);
+wbx_status wbx_saturate_check(const double* table);
+wbx_status wbx_saturate_lookup(const double* table, double d, double* out);
+wbx_status wbx_saturate_launch_shape(uint32_t os, int quality, uint32_t channels, uint64_t n_frames, uint32_t* tile,
+                                     uint32_t* mid_span, uint32_t* src_span, uint32_t* lds_bytes, uint32_t* n_tiles);
+wbx_status wbx_saturate_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_saturate(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                             uint32_t os, int quality, const double* table /* [WBX_SAT_TABLE] */, double drive,
+                             double makeup, wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result);
+
 /* Stretching a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels time-stretched
  * into a NEW F32 clip of out_frames frames — another LENGTH at the same PITCH — without the samples leaving HBM, by WSOLA
  * (waveform-similarity overlap-add): fitting a loop or a take to the session's tempo.  The result plays at speed 1.0 through
@@ -1742,6 +1832,13 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
                                       double key_gain, double makeup, uint32_t lookahead_frames, uint32_t hold_frames,
                                       uint32_t release_frames, uint32_t* new_sample, wbx_dynamics_stats* dynamics_stats,
                                       wbx_clip_stats* stats_of_result);
+/* wbx_clip_saturate of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with n_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_saturate's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t os,
+                                      int quality, const double* table, double drive, double makeup, uint32_t* new_sample,
+                                      wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result);
 /* wbx_clip_stretch of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
  * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
  * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's

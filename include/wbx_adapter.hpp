@@ -383,6 +383,18 @@ struct Engine {
           "dynamics_sample");
     return id;
   }
+  // A NEW sample holding the range through an oversampled table waveshaper (wbx.h "Saturating a clip"): table =
+  // WBX_SAT_TABLE outputs over the driven level (wbx_saturate_table, or hand-drawn), os 1, 2, 4 or 8 at quality
+  // WBX_SRC_*, drive in and makeup out (linear); no delay, the source's length, NO ceiling guarantee (limit_sample gives
+  // one).  The source is pinned for the call.  Editing thread, like derive_sample.
+  uint32_t saturate_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, const double* table, double drive = 1.0,
+                           double makeup = 1.0, uint32_t os = 4, int quality = WBX_SRC_GOOD,
+                           wbx_saturate_stats* saturate_stats = nullptr, wbx_clip_stats* stats_of_result = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_saturate_sample(h, sample, first_frame, n_frames, os, quality, table, drive, makeup, &id, saturate_stats,
+                                     stats_of_result), "saturate_sample");
+    return id;
+  }
   // A NEW sample of out_frames frames holding the range time-stretched by WSOLA (wbx.h "Stretching a clip"): another
   // length at the same pitch; window_frames a multiple of 8 in 32 .. 8192, tolerance_frames 0 .. 4096.  The source is
   // pinned for the call.  Editing thread, like derive_sample.

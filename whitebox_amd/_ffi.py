@@ -86,6 +86,10 @@ class DynamicsStats(C.Structure):      # wbx_dynamics_stats, 24 bytes
     _fields_ = [("min_gain", C.c_double), ("min_gain_frame", C.c_uint64), ("reduced_frames", C.c_uint64)]
 
 
+class SaturateStats(C.Structure):      # wbx_saturate_stats, 24 bytes
+    _fields_ = [("peak_drive", C.c_double), ("peak_index", C.c_uint64), ("beyond", C.c_uint64)]
+
+
 class StretchInfo(C.Structure):        # wbx_stretch_info, 32 bytes
     _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("max_shift", C.c_uint32),
                 ("launches", C.c_uint32)]
@@ -184,6 +188,8 @@ FILTER_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "notch": 3, "allpass"
                "highshelf": 7}                          # WBX_FILT_*
 DYN_SENSE = {"compress": 0, "gate": 1}                    # WBX_DYN_COMPRESS / WBX_DYN_GATE (a table's kind, a call's sense)
 DYN_TABLE, DYN_NO_KEY = 3073, 0xFFFFFFFF                # WBX_DYN_TABLE, WBX_DYN_NO_KEY
+SAT_KIND = {"hard": 0, "cubic": 1, "tanh": 2}             # WBX_SAT_HARD / CUBIC / TANH
+SAT_TABLE = 16385                                       # WBX_SAT_TABLE
 FIR_KIND = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}   # WBX_FIR_*
 
 # every symbol include/wbx.h declares: name -> (restype, argtypes)
@@ -283,6 +289,14 @@ SYMBOLS = {
     "wbx_dynamics_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_dynamics": (C.c_int, [_vp, _u32, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
                                     _u32, _u32, C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
+    "wbx_saturate_table": (C.c_int, [C.c_int, _d, _vp, _sz]),
+    "wbx_saturate_check": (C.c_int, [_vp]),
+    "wbx_saturate_lookup": (C.c_int, [_vp, _d, C.POINTER(_d)]),
+    "wbx_saturate_launch_shape": (C.c_int, [_u32, C.c_int, _u32, C.c_uint64, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32),
+                                            C.POINTER(_u32), C.POINTER(_u32)]),
+    "wbx_saturate_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_saturate": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(SaturateStats),
+                                    C.POINTER(ClipStats)]),
     "wbx_stretch_steps": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_stretch_anchor": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, _u32]),
     "wbx_stretch_window": (C.c_int, [_u32, _vp, _sz]),
@@ -408,6 +422,8 @@ SYMBOLS = {
                                           C.POINTER(LimitStats), C.POINTER(ClipStats)]),
     "wbx_engine_dynamics_sample": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _vp, _d, _d, _d, _u32,
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
+    "wbx_engine_saturate_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(_u32),
+                                             C.POINTER(SaturateStats), C.POINTER(ClipStats)]),
     "wbx_engine_stretch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.POINTER(StretchInfo),
                                             C.POINTER(_u32)]),
     "wbx_engine_warp_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32, C.POINTER(WarpInfo),

@@ -24,6 +24,7 @@
 #include "wbx_limit.h"
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
+#include "wbx_saturate.h"
 #include "wbx_splice.h"
 #include "wbx_stretch.h"
 #include "wbx_warp.h"
@@ -235,6 +236,26 @@ struct DynArgs {
 void launch_dynamics_curve(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_dynamics_apply(const DynArgs& a, uint32_t n_tiles, hipStream_t s);
 void launch_dynamics_reduce(const DynArgs& a, uint32_t n_tiles, hipStream_t s);   // part[0 .. n_tiles) into *total
+// saturating a clip (wbx_saturate.hip): oversample, shape through a table, band-limit back — one launch over tiles of output
+// frames, the tiles' statistics folded by a second, one-workgroup launch
+struct SatPartial {            // what one tile (or the whole call) knows of wbx_saturate_stats; every field merges in any order
+  double peak_drive;           // the greatest |d|; -1.0: no mid sample yet
+  unsigned long long peak_index, beyond;
+};
+struct SatArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const double* tab;           // device: [kSatTable] — the shape table
+  const double* up;            // device: [2 Z][os] — the up filter, tap-major, as doubles (os > 1)
+  const double* down;          // device: [2 Z + 1][os] — the down filter behind one 0.0, padded with 0.0 (os > 1)
+  SatPartial* part;            // device: [n_tiles], and behind them the call's record
+  double drive, makeup;
+  uint32_t n;                  // frames of the range and of the result; n * os < 2^31 - 16
+  uint32_t os, channels;
+  uint32_t tile, Z, plane, row, n_tiles;   // wbx_saturate.h's SatShape
+};
+void launch_saturate(const SatArgs& a, uint32_t lds_bytes, hipStream_t s);
+void launch_saturate_reduce(const SatArgs& a, hipStream_t s);      // part[0 .. n_tiles) into part[n_tiles]
 // stretching a clip (wbx_stretch.hip): per band of steps the positions — stretch_search_kernel, ONE workgroup walking the
 // steps of a launch in order — then the overlap-add over the band's frames
 struct StretchCarry {          // what one search launch hands the next, and the call's record so far (a device word block)
@@ -618,6 +639,19 @@ struct LimitStage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_saturate's own buffers: the shape table (16385 doubles, uploaded per call), the two filters as doubles (kept
+// while os and the quality stay the same), the tiles' statistics with the call's record behind them — grown on demand, freed
+// with the context — and the timing events
+struct SatStage {
+  PinnedBuf<double> h_tab, h_coef;
+  DevBuf<double> d_tab, d_coef;
+  uint32_t coef_of[2] = {0, 0};  // os and quality + 1 of the filters d_coef holds (os == 0: none)
+  DevBuf<SatPartial> d_part;
+  PinnedBuf<SatPartial> h_total;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_saturate_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
 struct SpliceStage {
   DevBuf<SplicePartDev> parts;
@@ -779,6 +813,7 @@ struct wbx_ctx {
   OnsetStage ons;                         // wbx_clip_onsets, wbx_clip_tempo (under fx_mu, on fx.side.stream)
   SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
   AlignStage aln;                         // wbx_clip_align (under fx_mu, on fx.side.stream)
+  SatStage sat;                           // wbx_clip_saturate (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -1013,6 +1048,12 @@ wbx_status dynamics_check(const ClipSrc& src, uint32_t src_rate, const ClipSrc* 
                           const char** why);
 wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint32_t rate, const DynCall& k, double lo, ClipSlot& slot,
                         wbx_dynamics_stats* out, wbx_clip_stats* stats, std::string* why);
+// saturating a clip (wbx_saturate.hip), cut the same way: the check makes no device call (wbx_saturate.h's
+// saturate_check_args first, then the clip: NULL for an unknown one, `replaces` where dst_clip is the source); the run works
+// under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status saturate_check(const ClipSrc* src, bool replaces, const SatCall& k, const char** why);
+wbx_status saturate_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const SatCall& k, ClipSlot& slot, wbx_saturate_stats* out,
+                        wbx_clip_stats* stats, std::string* why);
 // stretching a clip (wbx_stretch.hip), cut the same way: the check makes no device call (wbx_stretch.h's
 // stretch_check_args first, then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
 wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** why);

@@ -793,6 +793,22 @@ extern "C" wbx_status wbx_engine_limit_sample(wbx_engine* e, uint32_t sample, ui
   });
 }
 
+// registered at the source's rate, with the range's frames
+extern "C" wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t os,
+                                                 int quality, const double* table, double drive, double makeup, uint32_t* new_sample,
+                                                 wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "saturate_sample: new_sample is NULL");
+  SamplePin p(e);
+  const SatCall k{first_frame, n_frames, os, quality, table, drive, makeup};
+  const wbx_status st = p.begin(sample, "saturate_sample: unknown sample", "saturate_sample: the pool's sample ids (2^24) would run out",
+                                nullptr, [&](const char** msg) { return saturate_check(&p.src, false, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return saturate_run(e->ctx, p.src, p.rate, k, slot, saturate_stats, stats_of_result, why);
+  });
+}
+
 // pins the source and the key (no key with WBX_DYN_NO_KEY: the source alone); registered at the source's rate, with the
 // range's frames
 extern "C" wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t key_sample, uint64_t first_frame,

@@ -271,6 +271,48 @@ def _dynamics_stats(st) -> dict:
     return {"min_gain": st.min_gain, "min_gain_frame": st.min_gain_frame, "reduced_frames": st.reduced_frames}
 
 
+def saturate_table(kind="cubic", bias: float = 0.0) -> np.ndarray:
+    """wbx_saturate_table (host-only): the WBX_SAT_TABLE = 16385 outputs over the driven level -8 .. +8 of a usual curve —
+    kind "hard" (a clamp to +-1), "cubic" (z - 4 z^3 / 27, +-1 from |z| = 1.5 on) or "tanh" —, f(v + bias) - f(bias): a bias
+    (|bias| <= 4) gives even harmonics.  WbxError (-4) where the library refuses the design"""
+    out = np.zeros(_ffi.SAT_TABLE, dtype=np.float64)
+    _check(_ffi.lib().wbx_saturate_table(_ffi.SAT_KIND.get(kind, kind), float(bias), out.ctypes.data, out.size), "wbx_saturate_table")
+    return out
+
+
+def _sat_table(table) -> np.ndarray:
+    t = np.ascontiguousarray(table, dtype=np.float64)
+    assert t.shape == (_ffi.SAT_TABLE,), "a saturate table has 16385 entries"
+    return t
+
+
+def saturate_check(table) -> None:
+    """wbx_saturate_check (host-only): WbxError (-4) for a table the library refuses (an entry that is not finite or whose
+    magnitude exceeds 2^32)"""
+    _check(_ffi.lib().wbx_saturate_check(_sat_table(table).ctypes.data), "wbx_saturate_check")
+
+
+def saturate_lookup(table, d: float) -> float:
+    """wbx_saturate_lookup (host-only): what the table gives one driven sample `d`, as the device interpolates it"""
+    t, out = _sat_table(table), C.c_double()
+    _check(_ffi.lib().wbx_saturate_lookup(t.ctypes.data, float(d), C.byref(out)), "wbx_saturate_lookup")
+    return out.value
+
+
+def saturate_launch_shape(os: int, quality, channels: int, n_frames: int) -> dict:
+    """wbx_saturate_launch_shape (host-only): how a wbx_clip_saturate call is launched — the tile (output frames per
+    workgroup), the mid samples and source frames a tile computes and stages per channel, its LDS bytes and the tiles (the
+    grid).  WbxError where the call would be refused for os, quality or n_frames"""
+    v = [C.c_uint32() for _ in range(5)]
+    _check(_ffi.lib().wbx_saturate_launch_shape(os, _ffi.SRC_QUALITY.get(quality, quality), channels, n_frames,
+                                                *[C.byref(x) for x in v]), "wbx_saturate_launch_shape")
+    return dict(zip(("tile", "mid_span", "src_span", "lds_bytes", "n_tiles"), (x.value for x in v)))
+
+
+def _saturate_stats(st) -> dict:
+    return {"peak_drive": st.peak_drive, "peak_index": st.peak_index, "beyond": st.beyond}
+
+
 def stretch_steps(out_frames: int, window_frames: int) -> int:
     """wbx_stretch_steps (host-only): K = ceil(out_frames / (window_frames / 2)); 0 for a window a stretch refuses"""
     return int(_ffi.lib().wbx_stretch_steps(out_frames, window_frames))
@@ -711,6 +753,25 @@ class MixContext:
         """wbx_dynamics_ms: device milliseconds of the last dynamics call's launches"""
         out = C.c_double()
         _check(self.L.wbx_dynamics_ms(self.h, C.byref(out)), "wbx_dynamics_ms", self.h)
+        return out.value
+
+    def clip_saturate(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, table, os: int = 4, quality="good",
+                      drive: float = 1.0, makeup: float = 1.0, stats_channels: int = 0):
+        """wbx_clip_saturate: `dst_clip` becomes a new F32 clip of n_frames frames = the range of `src_clip` converted up by
+        `os` (1, 2, 4 or 8, at "fast" / "good" / "best"), times `drive`, through `table` (saturate_table(...), or any 16385
+        outputs over the level -8 .. +8), times `makeup`, band-limited back; no delay, and NO ceiling guarantee (the
+        band-limiting overshoots: clip_limit gives one).  Returns the statistics {"peak_drive", "peak_index", "beyond"}, and
+        with `stats_channels` (the clip's channel count) the pair (those, the result's wbx_clip_measure statistics)"""
+        t, ss, st = _sat_table(table), _ffi.SaturateStats(), _ffi.ClipStats()
+        _check(self.L.wbx_clip_saturate(self.h, src_clip, dst_clip, first_frame, n_frames, os, _ffi.SRC_QUALITY.get(quality, quality),
+                                        t.ctypes.data, float(drive), float(makeup), C.byref(ss),
+                                        C.byref(st) if stats_channels else None), "wbx_clip_saturate", self.h)
+        return (_saturate_stats(ss), _clip_stats(st, stats_channels)) if stats_channels else _saturate_stats(ss)
+
+    def saturate_ms(self) -> float:
+        """wbx_saturate_ms: device milliseconds of the last saturate call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_saturate_ms(self.h, C.byref(out)), "wbx_saturate_ms", self.h)
         return out.value
 
     def clip_stretch(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int,
@@ -1907,6 +1968,42 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _dynamics_stats(ds), _clip_stats(st, channels)) if stats else (new.value, _dynamics_stats(ds))
+
+    def saturate_sample(self, sample: int, table, os: int = 4, quality="good", drive: float = 1.0, makeup: float = 1.0,
+                        first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                        frames: Optional[int] = None, stats: bool = False):
+        """wbx_engine_saturate_sample: a new sample = the range of `sample` through the oversampled table waveshaper — see
+        MixContext.clip_saturate; gains linear.  `frames` / `channels` as in export_sample.  The source is pinned against
+        delete_sample for the call's length; may be called while another thread runs process().  Returns (new id, the
+        statistics), with `stats` (id, those, the result's statistics)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "saturate_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        t, new, ss, st = _sat_table(table), C.c_uint32(), _ffi.SaturateStats(), _ffi.ClipStats()
+        _check(self.L.wbx_engine_saturate_sample(self.h, sample, first_frame, n_frames, os, _ffi.SRC_QUALITY.get(quality, quality),
+                                                 t.ctypes.data, float(drive), float(makeup), C.byref(new), C.byref(ss),
+                                                 C.byref(st) if stats else None), "wbx_engine_saturate_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return (new.value, _saturate_stats(ss), _clip_stats(st, channels)) if stats else (new.value, _saturate_stats(ss))
+
+    def soft_clip_sample(self, sample: int, ceiling_db: float = -1.0, drive_db: float = 0.0, kind="cubic", oversample: int = 4,
+                         guarantee: bool = True, bias: float = 0.0, quality="good", **call):
+        """A soft clipper: saturate_sample with saturate_table(kind, bias), drive = 10 ** (drive_db / 20) / ceiling and
+        makeup = ceiling, so the curve's +-1 lands on the ceiling.  The band-limiting overshoots it; with `guarantee` a
+        limit_sample at the ceiling follows (the intermediate sample is deleted), so the limiter's promise holds for the
+        overshoot.  dB are converted here: a convenience outside the bit-exact contract.  `call`: saturate_sample's
+        first_frame, n_frames, frames, channels.  Returns (new id, the saturate statistics)"""
+        ceiling = 10.0 ** (float(ceiling_db) / 20.0)
+        new, ss = self.saturate_sample(sample, saturate_table(kind, bias), os=oversample, quality=quality,
+                                       drive=10.0 ** (float(drive_db) / 20.0) / ceiling, makeup=ceiling, **call)
+        if not guarantee:
+            return new, ss
+        out, _ = self.limit_sample(new, ceiling_db=ceiling_db)
+        self.delete_sample(new)
+        return out, ss
 
     def _dynamics_shape(self, sample, rate, attack_ms, hold_ms, release_ms):
         rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
