@@ -841,6 +841,100 @@ wbx_status wbx_clip_saturate(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip,
                              uint32_t os, int quality, const double* table /* [WBX_SAT_TABLE] */, double drive,
                              double makeup, wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result);
 
+/* Reducing a clip's noise: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels through
+ * a SPECTRAL GATE into a NEW F32 clip of n_frames frames, the source's channels and rate and NO delay, without the samples
+ * leaving HBM: hiss, hum or room tone of a recorded take pushed down by `floor` wherever a cell's smoothed power does not
+ * rise above a per-bin threshold, which wbx_clip_denoise_profile measures on a stretch of the noise alone.  The forward
+ * and the inverse transform are DIRECT — ascending fp64 chains of exact fp32 products against host-built tables — so the
+ * device needs no FFT, no sin and no log and every bit is reproducible.  No reference counterpart.  This text is the
+ * specification; tests/denoise_model.py restates it in numpy, and the tables, the threshold, the profile's sums, the
+ * statistics and every output sample equal that BIT FOR BIT.  Every operator below is ONE IEEE fp64 operation in the order
+ * written and nothing is fused, except that the product of two fp32 values added into an fp64 chain may be an fma: that
+ * product is exact.
+ * W = window_frames, a power of two in 64 .. 2048; H = W / 4; B = W / 2 + 1; n = n_frames in [1, 2^31 - 16); S =
+ * smooth_hops in 0 .. 4; F = smooth_bins in 0 .. 8.  Channels are processed independently.  x[c][f] is the range's frame f of
+ * channel c as fp64, what is not finite as 0.0, and 0.0 for f < 0 or f >= n whatever the clip holds there: nothing beside
+ * the range is ever read.  T = ceil(n / H) + 3 hops; hop t starts at range frame (t - 3) H, d_t[j] = x[(t - 3) H + j], so
+ * every output frame lies under exactly four windows.
+ *   tables    (wbx_denoise_tables, host-only, no libm: sinpi is wbx_resample_table's, exact at integers)  s[j] =
+ *             sinpi(((double)j + 0.5) / (double)W) — the square root of a Hann window; its squares over the four
+ *             overlapping windows add up to 2.  m = (k j) mod W in integers, t = (double)m / (double)W, c = sinpi(2.0 t +
+ *             0.5), z = sinpi(2.0 t).  Analysis, [B][W]: AC[k][j] = (float)((s[j] c) / (double)W), AS[k][j] = (float)(0.0 -
+ *             ((s[j] z) / (double)W)).  Synthesis, e_k = 0.5 for k = 0 and k = B - 1, else 1.0 (the Hermitian doubling and
+ *             the overlap's 1/2 folded in): YC[k][j] = (float)(e_k (s[j] c)), YS[k][j] = (float)(0.0 - (e_k (s[j] z))).
+ *             Rows 0 and B - 1 of AS and YS are all +0.0.  The 1 / W sits in the ANALYSIS table, so |re|, |im| <= 0.64
+ *             max|x|: a cell always fits an fp32
+ *   analysis  per hop, channel and bin from re = im = 0.0, j = 0 .. W - 1 ascending: re = re + d[j] AC[k][j], im = im +
+ *             d[j] AS[k][j]; the cell r = (float)re, i = (float)im; its power p = ((double)r (double)r) + ((double)i
+ *             (double)i) — two exact products, one rounded sum, from the STORED fp32 cell
+ *   gate      q = the sum from 0.0 of p[t'][k'] over t' = t - S .. t + S (outer, ascending) and k' = k - F .. k + F (inner,
+ *             ascending), cells with t' outside [0, T) or k' outside [0, B) left out, then divided by (double)count of the
+ *             cells that were present.  With th = thr[c B + k]: if q > th, v = 1.0 - (th / q) and g = v > floor ? v : floor;
+ *             otherwise g = floor.  The masked cell mr = (float)(g (double)r), mi = (float)(g (double)i)
+ *   synthesis per hop, channel and window position j from a = 0.0, k = 0 .. B - 1 ascending: a = a + mr[k] YC[k][j], then
+ *             a = a + mi[k] YS[k][j]
+ *   add       output frame f (0 <= f < n) lies in hops t0 = f div H .. t0 + 3, in hop t0 + u at position f - (t0 + u - 3) H:
+ *             out[c][f] = (float)(((a_0 + a_1) + a_2) + a_3), the chain values as fp64, not rounded on the way.  That last
+ *             rounding may give +-inf only where the sum itself reaches 2^128; no NaN is ever produced
+ *   wbx_denoise_stats (may be NULL; every field an integer independent of order): hops = T; cells = T B channels;
+ *             open_cells = the count over hops, channels and bins of q > th; bands = how many bands the call ran in
+ * thr has channels x B entries, finite and >= 0 (0: always open — with floor anything the call then returns the source
+ * within 1e-7 of its peak; 1e30: all floor); floor is in [0, 1].
+ * dst_clip becomes a new F32 pool clip of n frames (plus the pool's 16 zero frames of padding), replaced or allocated as
+ * wbx_clip_derive does it, on the same stream and behind the same ordering; one edit, conversion, filter, convolution,
+ * limit, dynamics, saturate or denoise call runs at a time.  Nothing else is allocated in the pool: the tables (2 W^2
+ * floats, kept per context while W stays the same) and a band's cells, masked cells and chain values live in the context's
+ * own buffers.  Long ranges run in BANDS of wbx_denoise_band_hops(W, channels) blocks of H output frames;
+ * the band size changes no bit of the result.
+ * Refused before any device call, nothing allocated, dst_clip and stats untouched, in this order.  First the sizes and
+ * parameters, before the clips are looked at — WBX_ERR_INVALID: n_frames of 0 or >= 2^31 - 16; a window_frames that is not
+ * a power of two in 64 .. 2048; smooth_hops above 4; smooth_bins above 8; a NULL thr; a thr entry that is negative or not
+ * finite (the rows of the clip's channels where the clip is known and has 1 or 2, else the first row); a floor outside
+ * [0, 1] or a NaN.  Then the clip — WBX_ERR_INVALID: an unknown source clip; a range past the clip; dst_clip equal to the
+ * source; WBX_ERR_UNSUPPORTED: a source that is not F32 or has more than 2 channels; last, wbx_clip_derive's rule:
+ * WBX_ERR_INVALID for a dst_clip of 2^24 or more.  WBX_ERR_OOM as for wbx_clip_derive.
+ * wbx_clip_denoise_profile is a MEASUREMENT (nothing allocated in the pool): over the COMPLETE windows of the range only —
+ * *hops_out = (n - W) / H + 1, hop h at range frame h H — the cells and p as in the analysis above; sums_out[c B + k] =
+ * the fp64 sum of p over h ascending from 0.0.  Refused, in this order — WBX_ERR_INVALID: n_frames of 0 or >= 2^31 - 16;
+ * the window as above; n_frames < W; a NULL sums_out or hops_out; then the clip as above (no dst_clip).
+ * Host-only, no device (wbx_denoise.h, which a C++ compiler takes alone):
+ * wbx_denoise_tables writes analysis_out = AC then AS and synthesis_out = YC then YS, 2 B W floats each, [k][j] (either
+ *             may be NULL and is left out; WBX_ERR_INVALID for a window as above or both NULL)
+ * wbx_denoise_threshold out[i] = strength * (sums[i] / (double)hops) for i < count (WBX_ERR_INVALID: NULL, hops of 0, a
+ *             strength that is negative or not finite)
+ * wbx_denoise_hops T (0 where n_frames or the window is refused); wbx_denoise_profile_hops the profile's (0 where refused)
+ * wbx_denoise_band_hops the blocks of H output frames of one band: 2^22 / (W channels) - 11, the context's stage of 2^22
+ *             words per buffer less the 3 hops a band's last block reaches on and 4 hops of box on either side (a band
+ *             computes those again instead of keeping them); 0 for a window or channel count as above
+ * wbx_denoise_launches the bands of a call: ceil(ceil(n / H) / band_hops); 0 where refused
+ * wbx_denoise_check the status of the sizes and parameters alone, `channels` rows of thr read (1 or 2)
+ * wbx_denoise_ms: device milliseconds between two events on the edits' stream around the launches of the context's last
+ * completed denoise or profile call (layer 1's or layer 2's); the tables' upload, where W changed, lies before the first.
+ * WBX_ERR_INVALID for NULL arguments or when none has completed.  For tools/bench_denoise.py; nothing else reads it.
+ * Not offered: linked-stereo gating, an adaptive or estimated profile, windows above 2048, other overlaps, attack /
+ * release smoothing of the gains, de-hum by comb, click repair, denoising at render time or on live input. */
+typedef struct wbx_denoise_stats { /* 32 bytes */
+  uint64_t hops;
+  uint64_t cells;
+  uint64_t open_cells;
+  uint32_t bands;
+  uint32_t reserved; /* 0 */
+} wbx_denoise_stats;
+wbx_status wbx_denoise_tables(uint32_t window_frames, float* analysis_out, float* synthesis_out);
+wbx_status wbx_denoise_threshold(const double* sums, uint64_t hops, size_t count, double strength, double* out);
+uint64_t wbx_denoise_hops(uint64_t n_frames, uint32_t window_frames);
+uint64_t wbx_denoise_profile_hops(uint64_t n_frames, uint32_t window_frames);
+uint32_t wbx_denoise_band_hops(uint32_t window_frames, uint32_t channels);
+uint64_t wbx_denoise_launches(uint64_t n_frames, uint32_t window_frames, uint32_t channels);
+wbx_status wbx_denoise_check(uint64_t n_frames, uint32_t window_frames, uint32_t smooth_hops, uint32_t smooth_bins,
+                             const double* thr, uint32_t channels, double floor);
+wbx_status wbx_denoise_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_denoise_profile(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames,
+                                    uint32_t window_frames, double* sums_out /* [channels][B] */, uint64_t* hops_out);
+wbx_status wbx_clip_denoise(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames,
+                            uint32_t smooth_hops, uint32_t smooth_bins, const double* thr /* [channels][B] */, double floor,
+                            uint32_t dst_clip, wbx_denoise_stats* stats);
+
 /* Stretching a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels time-stretched
  * into a NEW F32 clip of out_frames frames — another LENGTH at the same PITCH — without the samples leaving HBM, by WSOLA
  * (waveform-similarity overlap-add): fitting a loop or a take to the session's tempo.  The result plays at speed 1.0 through
@@ -1839,6 +1933,17 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
 wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t os,
                                       int quality, const double* table, double drive, double makeup, uint32_t* new_sample,
                                       wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result);
+/* wbx_clip_denoise of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with n_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_denoise's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_denoise_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                     uint32_t window_frames, uint32_t smooth_hops, uint32_t smooth_bins, const double* thr,
+                                     double floor, uint32_t* new_sample, wbx_denoise_stats* stats);
+/* wbx_clip_denoise_profile of an engine sample, under wbx_engine_spectrum_sample's rules: the sample is pinned for the
+ * call; no sample is made.  Arguments and refusals are wbx_clip_denoise_profile's. */
+wbx_status wbx_engine_denoise_profile_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                             uint32_t window_frames, double* sums_out, uint64_t* hops_out);
 /* wbx_clip_stretch of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
  * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
  * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's

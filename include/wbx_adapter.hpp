@@ -395,6 +395,24 @@ struct Engine {
                                      stats_of_result), "saturate_sample");
     return id;
   }
+  // A NEW sample holding the range through the spectral gate (wbx.h "Reducing a clip's noise"): thr = channels x
+  // (window_frames / 2 + 1) power thresholds (wbx_denoise_threshold of denoise_profile_sample's sums), floor the linear
+  // gain of a closed cell; no delay, the source's length.  The source is pinned for the call.  Editing thread, like
+  // derive_sample.
+  uint32_t denoise_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames, const double* thr,
+                          double floor = 0.1, uint32_t smooth_hops = 2, uint32_t smooth_bins = 1, wbx_denoise_stats* stats = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_denoise_sample(h, sample, first_frame, n_frames, window_frames, smooth_hops, smooth_bins, thr, floor, &id, stats),
+          "denoise_sample");
+    return id;
+  }
+  // The noise profile of the range: sums_out[channels x (window_frames / 2 + 1)] and the number of complete windows they
+  // were added over.  A measurement: no sample is made.  Editing thread.
+  uint64_t denoise_profile_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t window_frames, double* sums_out) {
+    uint64_t hops = 0;
+    check(wbx_engine_denoise_profile_sample(h, sample, first_frame, n_frames, window_frames, sums_out, &hops), "denoise_profile_sample");
+    return hops;
+  }
   // A NEW sample of out_frames frames holding the range time-stretched by WSOLA (wbx.h "Stretching a clip"): another
   // length at the same pitch; window_frames a multiple of 8 in 32 .. 8192, tolerance_frames 0 .. 4096.  The source is
   // pinned for the call.  Editing thread, like derive_sample.

@@ -90,6 +90,11 @@ class SaturateStats(C.Structure):      # wbx_saturate_stats, 24 bytes
     _fields_ = [("peak_drive", C.c_double), ("peak_index", C.c_uint64), ("beyond", C.c_uint64)]
 
 
+class DenoiseStats(C.Structure):       # wbx_denoise_stats, 32 bytes
+    _fields_ = [("hops", C.c_uint64), ("cells", C.c_uint64), ("open_cells", C.c_uint64), ("bands", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class StretchInfo(C.Structure):        # wbx_stretch_info, 32 bytes
     _fields_ = [("steps", C.c_uint64), ("searched_steps", C.c_uint64), ("candidates", C.c_uint64), ("max_shift", C.c_uint32),
                 ("launches", C.c_uint32)]
@@ -297,6 +302,16 @@ SYMBOLS = {
     "wbx_saturate_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_saturate": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(SaturateStats),
                                     C.POINTER(ClipStats)]),
+    "wbx_denoise_tables": (C.c_int, [_u32, _vp, _vp]),
+    "wbx_denoise_threshold": (C.c_int, [_vp, C.c_uint64, _sz, _d, _vp]),
+    "wbx_denoise_hops": (C.c_uint64, [C.c_uint64, _u32]),
+    "wbx_denoise_profile_hops": (C.c_uint64, [C.c_uint64, _u32]),
+    "wbx_denoise_band_hops": (_u32, [_u32, _u32]),
+    "wbx_denoise_launches": (C.c_uint64, [C.c_uint64, _u32, _u32]),
+    "wbx_denoise_check": (C.c_int, [C.c_uint64, _u32, _u32, _u32, _vp, _u32, _d]),
+    "wbx_denoise_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_denoise_profile": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _vp, C.POINTER(C.c_uint64)]),
+    "wbx_clip_denoise": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _vp, _d, _u32, C.POINTER(DenoiseStats)]),
     "wbx_stretch_steps": (C.c_uint64, [C.c_uint64, _u32]),
     "wbx_stretch_anchor": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, _u32]),
     "wbx_stretch_window": (C.c_int, [_u32, _vp, _sz]),
@@ -424,6 +439,9 @@ SYMBOLS = {
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_engine_saturate_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(_u32),
                                              C.POINTER(SaturateStats), C.POINTER(ClipStats)]),
+    "wbx_engine_denoise_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _vp, _d, C.POINTER(_u32),
+                                            C.POINTER(DenoiseStats)]),
+    "wbx_engine_denoise_profile_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _vp, C.POINTER(C.c_uint64)]),
     "wbx_engine_stretch_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _u32, _u32, C.POINTER(StretchInfo),
                                             C.POINTER(_u32)]),
     "wbx_engine_warp_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _u32, _u32, _u32, C.POINTER(WarpInfo),

@@ -32,6 +32,7 @@
 #include "wbx_f0.h"
 #include "wbx_align.h"
 #include "wbx_spectrum.h"
+#include "wbx_denoise.h"
 #include "wbx_onset.h"
 #include "wbx_pool.h"
 #include "wbx_res.h"
@@ -347,6 +348,39 @@ struct SpecArgs {
   uint32_t mid;                // 1: d = (float)(0.5 * (src[0] + src[1])); 0: d = src[0]
 };
 void launch_spectrum(const SpecArgs& a, hipStream_t s);
+// reducing a clip's noise (wbx_denoise.hip): per band of hops the analysis (the transform launch, cells out), the gate (masked
+// cells out, the open cells counted per workgroup and folded), the synthesis (the same launch turned round, chain values
+// out as doubles) and the overlap-add into the new clip; the profile walks the analysis' cells.  Stage rows are
+// [hop - row0][channel][W]
+struct DenArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const float* tab;            // device: [W][W] — the transform launch's table (wbx_denoise.h's A or Y)
+  float* cells;                // device: the band's cell rows
+  float* masked;               // device: the band's masked rows
+  double* chain;               // device: the band's chain values
+  const double* thr;           // device: [channels][B]
+  double* sums;                // device: [channels][B] — the profile's running sums
+  unsigned long long* part;    // device: the gate workgroups' open cells, [n_part]
+  unsigned long long* total;   // device: the call's open cells so far
+  double floor;
+  uint32_t n;                  // frames of the range
+  uint32_t W, H, B, channels;
+  uint32_t S, F;               // the box
+  uint32_t T;                  // hops of the call
+  uint32_t lead;               // hop t starts at range frame (t - lead) H: 3, the profile 0
+  uint32_t row0;               // the hop of the stage's first row
+  uint32_t hop0, hop1;         // the hops of THIS launch (transform, gate, profile)
+  uint32_t own0, own1;         // the hops whose open cells this band counts
+  uint32_t blk0, blk1;         // the blocks of H frames the overlap-add writes
+  uint32_t n_part;
+  uint32_t K, G, hops_wg, chunk, stride;   // wbx_denoise.h's DenShape; stride: words between two hops' staged rows
+};
+void launch_denoise_transform(const DenArgs& a, bool synthesis, hipStream_t s);
+void launch_denoise_gate(const DenArgs& a, hipStream_t s);           // part[0 .. n_part) written
+void launch_denoise_fold(const DenArgs& a, hipStream_t s);           // *total += part[0 .. n_part)
+void launch_denoise_ola(const DenArgs& a, hipStream_t s);
+void launch_denoise_profile(const DenArgs& a, hipStream_t s);        // sums += the power of rows [hop0, hop1), ascending
 // aligning two clips (wbx_align.hip): the partials of one band — a workgroup per (block of 4096 lags, chunk) —, the fold of a
 // band onto the running curve with the scores and the workgroups' best after the last, Ea's partials, and the pick
 struct alignas(16) AlignPartial {  // what a chunk leaves per lag: one 16-byte store
@@ -652,6 +686,22 @@ struct SatStage {
   bool timed = false;          // the last run completed
 };
 
+// wbx_clip_denoise's and wbx_clip_denoise_profile's own buffers: the two tables as the device reads them (W x W floats
+// each, kept while W stays the same; not in the pool), a band's cells, masked cells and chain values, the threshold, the
+// profile's sums, the gate's partial counts with the call's total behind them — grown on demand, freed with the context —
+// and the timing events
+struct DenStage {
+  DevBuf<float> d_tab;         // A, then Y
+  uint32_t tab_w = 0;          // the W of the tables d_tab holds (0: none)
+  DevBuf<float> d_cells, d_masked;
+  DevBuf<double> d_chain, d_thr, d_sums;
+  DevBuf<unsigned long long> d_part;
+  PinnedBuf<double> h_thr, h_sums;
+  PinnedBuf<unsigned long long> h_total;
+  Event mark[2];               // (timing events) around the launches of the last run: wbx_denoise_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_splice's part descriptors and tile table on the device — grown on demand, freed with the context
 struct SpliceStage {
   DevBuf<SplicePartDev> parts;
@@ -814,6 +864,7 @@ struct wbx_ctx {
   SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
   AlignStage aln;                         // wbx_clip_align (under fx_mu, on fx.side.stream)
   SatStage sat;                           // wbx_clip_saturate (under fx_mu, on fx.side.stream)
+  DenStage den;                           // wbx_clip_denoise, wbx_clip_denoise_profile (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
   Stream upload_stream;                // clip uploads of layer 2 run here, outside the engine's editor lock
@@ -1054,6 +1105,16 @@ wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint
 wbx_status saturate_check(const ClipSrc* src, bool replaces, const SatCall& k, const char** why);
 wbx_status saturate_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const SatCall& k, ClipSlot& slot, wbx_saturate_stats* out,
                         wbx_clip_stats* stats, std::string* why);
+// reducing a clip's noise (wbx_denoise.hip), cut the same way: the checks make no device call (wbx_denoise.h's argument
+// checks first, then the clip: NULL for an unknown one, `replaces` where dst_clip is the source); the runs work under fx_mu
+// on the edit stream behind clipfx_prepare / clipfx_order
+wbx_status denoise_check(const ClipSrc* src, bool replaces, const DenCall& k, const char** why);
+wbx_status denoise_profile_check(const ClipSrc* src, uint64_t first_frame, uint64_t n_frames, uint32_t window, bool has_sums, bool has_hops,
+                                 const char** why);
+wbx_status denoise_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const DenCall& k, ClipSlot& slot, wbx_denoise_stats* out,
+                       std::string* why);
+wbx_status denoise_profile_run(wbx_ctx* c, const ClipSrc& src, uint64_t first_frame, uint64_t n_frames, uint32_t window, double* sums_out,
+                               uint64_t* hops_out, std::string* why);
 // stretching a clip (wbx_stretch.hip), cut the same way: the check makes no device call (wbx_stretch.h's
 // stretch_check_args first, then the clip); the run works under fx_mu on the edit stream behind clipfx_prepare / clipfx_order
 wbx_status stretch_check(const ClipSrc& src, const StretchCall& k, const char** why);

@@ -809,6 +809,34 @@ extern "C" wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample,
   });
 }
 
+// registered at the source's rate, with the range's frames
+extern "C" wbx_status wbx_engine_denoise_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                uint32_t window_frames, uint32_t smooth_hops, uint32_t smooth_bins, const double* thr,
+                                                double floor, uint32_t* new_sample, wbx_denoise_stats* stats) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "denoise_sample: new_sample is NULL");
+  SamplePin p(e);
+  const DenCall k{first_frame, n_frames, window_frames, smooth_hops, smooth_bins, thr, floor};
+  const wbx_status st = p.begin(sample, "denoise_sample: unknown sample", "denoise_sample: the pool's sample ids (2^24) would run out",
+                                nullptr, [&](const char** msg) { return denoise_check(&p.src, false, k, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, n_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return denoise_run(e->ctx, p.src, p.rate, k, slot, stats, why);
+  });
+}
+
+// a measurement: the sample pinned, no sample made
+extern "C" wbx_status wbx_engine_denoise_profile_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                        uint32_t window_frames, double* sums_out, uint64_t* hops_out) {
+  if (!e) return WBX_ERR_INVALID;
+  SamplePin p(e);
+  const wbx_status st = p.begin(sample, "denoise_profile_sample: unknown sample", nullptr, nullptr, [&](const char** msg) {
+    return denoise_profile_check(&p.src, first_frame, n_frames, window_frames, sums_out != nullptr, hops_out != nullptr, msg);
+  });
+  if (st != WBX_OK) return st;
+  return p.read([&](std::string* why) { return denoise_profile_run(e->ctx, p.src, first_frame, n_frames, window_frames, sums_out, hops_out, why); });
+}
+
 // pins the source and the key (no key with WBX_DYN_NO_KEY: the source alone); registered at the source's rate, with the
 // range's frames
 extern "C" wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t key_sample, uint64_t first_frame,

@@ -313,6 +313,44 @@ def _saturate_stats(st) -> dict:
     return {"peak_drive": st.peak_drive, "peak_index": st.peak_index, "beyond": st.beyond}
 
 
+def denoise_tables(window_frames: int):
+    """wbx_denoise_tables (host-only): the analysis and the synthesis tables of a window of `window_frames` (a power of two
+    in 64 .. 2048) as float32 arrays [2][B][W] each — [0] the cosine table (AC / YC), [1] the sine table (AS / YS),
+    B = W / 2 + 1.  WbxError (-4) for a window the call refuses"""
+    W = int(window_frames)
+    ok = 64 <= W <= 2048 and W & (W - 1) == 0
+    B = W // 2 + 1 if ok else 1
+    a, y = np.zeros((2, B, W if ok else 1), dtype=np.float32), np.zeros((2, B, W if ok else 1), dtype=np.float32)
+    _check(_ffi.lib().wbx_denoise_tables(W, a.ctypes.data, y.ctypes.data), "wbx_denoise_tables")
+    return a, y
+
+
+def denoise_threshold(sums, hops: int, strength: float) -> np.ndarray:
+    """wbx_denoise_threshold (host-only): strength * (sums / hops) — the per-bin threshold of a profile's sums"""
+    s = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+    out = np.zeros_like(s)
+    _check(_ffi.lib().wbx_denoise_threshold(s.ctypes.data, hops, s.size, float(strength), out.ctypes.data), "wbx_denoise_threshold")
+    return out
+
+
+def denoise_hops(n_frames: int, window_frames: int) -> int:
+    """wbx_denoise_hops (host-only): T = ceil(n_frames / (window_frames / 4)) + 3; 0 where the call refuses either"""
+    return int(_ffi.lib().wbx_denoise_hops(n_frames, window_frames))
+
+
+def denoise_band_hops(window_frames: int, channels: int) -> int:
+    """wbx_denoise_band_hops (host-only): the blocks of window_frames / 4 output frames one band of a call covers"""
+    return int(_ffi.lib().wbx_denoise_band_hops(window_frames, channels))
+
+
+def _denoise_thr(thr) -> np.ndarray:
+    return np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+
+
+def _denoise_stats(st) -> dict:
+    return {"hops": st.hops, "cells": st.cells, "open_cells": st.open_cells, "bands": st.bands}
+
+
 def stretch_steps(out_frames: int, window_frames: int) -> int:
     """wbx_stretch_steps (host-only): K = ceil(out_frames / (window_frames / 2)); 0 for a window a stretch refuses"""
     return int(_ffi.lib().wbx_stretch_steps(out_frames, window_frames))
@@ -772,6 +810,32 @@ class MixContext:
         """wbx_saturate_ms: device milliseconds of the last saturate call's launches"""
         out = C.c_double()
         _check(self.L.wbx_saturate_ms(self.h, C.byref(out)), "wbx_saturate_ms", self.h)
+        return out.value
+
+    def clip_denoise(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, window_frames: int, thr,
+                     floor: float = 0.1, smooth_hops: int = 2, smooth_bins: int = 1) -> dict:
+        """wbx_clip_denoise: `dst_clip` becomes a new F32 clip of n_frames frames = the range of `src_clip` through the
+        spectral gate: window_frames a power of two in 64 .. 2048, `thr` the per-channel, per-bin power thresholds
+        [channels][window_frames / 2 + 1] (denoise_threshold of clip_denoise_profile's sums), `floor` the linear gain of a
+        closed cell, the box of 2 smooth_hops + 1 hops x 2 smooth_bins + 1 bins.  No delay.  Returns {"hops", "cells",
+        "open_cells", "bands"}"""
+        t, st = _denoise_thr(thr), _ffi.DenoiseStats()
+        _check(self.L.wbx_clip_denoise(self.h, src_clip, first_frame, n_frames, window_frames, smooth_hops, smooth_bins,
+                                       t.ctypes.data, float(floor), dst_clip, C.byref(st)), "wbx_clip_denoise", self.h)
+        return _denoise_stats(st)
+
+    def clip_denoise_profile(self, clip: int, channels: int, first_frame: int, n_frames: int, window_frames: int):
+        """wbx_clip_denoise_profile: (sums float64[channels * B], hops) — per channel and bin the sum of the cells' power
+        over the complete windows of the range; a measurement, nothing allocated in the pool"""
+        sums, hops = np.zeros(channels * (window_frames // 2 + 1), dtype=np.float64), C.c_uint64()
+        _check(self.L.wbx_clip_denoise_profile(self.h, clip, first_frame, n_frames, window_frames, sums.ctypes.data, C.byref(hops)),
+               "wbx_clip_denoise_profile", self.h)
+        return sums, hops.value
+
+    def denoise_ms(self) -> float:
+        """wbx_denoise_ms: device milliseconds of the last denoise or profile call's launches"""
+        out = C.c_double()
+        _check(self.L.wbx_denoise_ms(self.h, C.byref(out)), "wbx_denoise_ms", self.h)
         return out.value
 
     def clip_stretch(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int,
@@ -1988,6 +2052,53 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _saturate_stats(ss), _clip_stats(st, channels)) if stats else (new.value, _saturate_stats(ss))
+
+    def denoise_sample(self, sample: int, window_frames: int, thr, floor: float = 0.1, smooth_hops: int = 2, smooth_bins: int = 1,
+                       first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
+                       frames: Optional[int] = None):
+        """wbx_engine_denoise_sample: a new sample = the range of `sample` through the spectral gate — see
+        MixContext.clip_denoise.  `frames` / `channels` as in export_sample.  The source is pinned against delete_sample for
+        the call's length; may be called while another thread runs process().  Returns (new id, the statistics)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "denoise_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        t, new, st = _denoise_thr(thr), C.c_uint32(), _ffi.DenoiseStats()
+        _check(self.L.wbx_engine_denoise_sample(self.h, sample, first_frame, n_frames, window_frames, smooth_hops, smooth_bins,
+                                                t.ctypes.data, float(floor), C.byref(new), C.byref(st)),
+               "wbx_engine_denoise_sample", self.h, True)
+        self._sample_shape[new.value] = (n_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return new.value, _denoise_stats(st)
+
+    def denoise_profile_sample(self, sample: int, window_frames: int, first_frame: int = 0, n_frames: Optional[int] = None,
+                               channels: Optional[int] = None, frames: Optional[int] = None):
+        """wbx_engine_denoise_profile_sample — see MixContext.clip_denoise_profile; `frames` / `channels` as in
+        export_sample.  Returns (sums float64[channels * B], hops).  May be called while another thread runs process();
+        delete_sample of the sample is refused meanwhile."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "denoise_profile_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        sums, hops = np.zeros(channels * (window_frames // 2 + 1), dtype=np.float64), C.c_uint64()
+        _check(self.L.wbx_engine_denoise_profile_sample(self.h, sample, first_frame, n_frames, window_frames, sums.ctypes.data,
+                                                        C.byref(hops)), "wbx_engine_denoise_profile_sample", self.h, True)
+        return sums, hops.value
+
+    def reduce_noise_sample(self, sample: int, noise_first: int, noise_frames: int, reduction_db: float = 20.0,
+                            sensitivity: float = 3.0, window: int = 1024, smooth_hops: int = 2, smooth_bins: int = 1,
+                            noise_sample: Optional[int] = None, **call):
+        """Noise reduction in one step: the profile of frames [noise_first, noise_first + noise_frames) of `noise_sample`
+        (None: of `sample` itself) — a stretch that holds the noise alone —, the threshold denoise_threshold(sums, hops,
+        sensitivity), floor = 10 ** (-reduction_db / 20), then denoise_sample.  The dB are converted here: a convenience
+        outside the bit-exact contract.  `call`: denoise_sample's first_frame, n_frames, frames, channels.  Returns (new id,
+        the statistics)"""
+        src = sample if noise_sample is None else noise_sample
+        sums, hops = self.denoise_profile_sample(src, window, noise_first, noise_frames, channels=call.get("channels"))
+        thr = denoise_threshold(sums, hops, sensitivity)
+        return self.denoise_sample(sample, window, thr, floor=10.0 ** (-float(reduction_db) / 20.0), smooth_hops=smooth_hops,
+                                   smooth_bins=smooth_bins, **call)
 
     def soft_clip_sample(self, sample: int, ceiling_db: float = -1.0, drive_db: float = 0.0, kind="cubic", oversample: int = 4,
                          guarantee: bool = True, bias: float = 0.0, quality="good", **call):
