@@ -935,6 +935,99 @@ wbx_status wbx_clip_denoise(wbx_ctx* ctx, uint32_t clip, uint64_t first_frame, u
                             uint32_t smooth_hops, uint32_t smooth_bins, const double* thr /* [channels][B] */, double floor,
                             uint32_t dst_clip, wbx_denoise_stats* stats);
 
+/* Reading a clip along a position curve (varispeed): frames [first_frame, first_frame + n_frames) of a resident F32 clip of
+ * 1 or 2 channels read at an arbitrary, caller-given position per output frame through a band-limited interpolator into a
+ * NEW F32 clip of out_frames frames, the source's rate and channels, without the samples leaving HBM: tape stop and start,
+ * a pitch bend or glide, vibrato, wow and flutter, scratching and reverse sweeps, conforming a recording whose clock
+ * drifted; behind wbx_clip_warp, pitch that changes over time at unchanged timing.  wbx_clip_resample and wbx_clip_pitch
+ * have one ratio per call; this call has a curve.  The result plays at speed 1.0 through the mix's unity row mode.  No
+ * reference counterpart.  This text is the specification; tests/varispeed_model.py restates it in numpy and every table
+ * word, position, tile and output sample equals that BIT FOR BIT.
+ *   curve     integers only.  knot_shift = g in 4 .. 10, G = 2^g output frames per interval.  knots[i], i in [0, K),
+ *             K = ceil(out_frames / G) + 1, is a signed 64-bit position in units of 2^-32 source frames relative to
+ *             first_frame and belongs to output frame i*G.  Output frame j = i*G + r lies at
+ *               pos = knots[i] + (((knots[i+1] - knots[i]) * r) >> g)
+ *             the product in 64 bits, the shift arithmetic (it floors, also for a descending curve whose difference G does
+ *             not divide).  Knots need not be monotone: a negative slope plays backwards, a zero slope freezes.  Every
+ *             knot lies in [-2^16, n_frames + 2^16] frames; every interval satisfies
+ *             (|knots[i+1] - knots[i]| >> 32) + 2 + T <= 4096 (about speed 15 at G = 256, far more at G = 16); K <= 2^22
+ *   filter    "Converting a clip's sample rate"'s, with a phase grid instead of a ratio.  guard_num / guard_den >= 1 is
+ *             the fastest speed the caller wants protected from aliasing; after dividing by their gcd, M = guard_num,
+ *             L = guard_den, and H, T = 2H, cutoff and beta are exactly what that section's quality rule gives for M / L
+ *             (guard_num == guard_den: H = Z, cutoff = frac).  T > 512 is refused as there.  One guard serves the call
+ *   tables    P = 256 / 512 / 2048 phases for WBX_SRC_FAST / GOOD / BEST.  h has P + 1 rows of T floats: row p is that
+ *             section's row formula at the fraction (double)p / (double)P — row P sits at exactly 1.0 —, divided by its own
+ *             ascending sum and rounded once to fp32.  D[p][k] = (float)((double)h[p+1][k] - (double)h[p][k]) for p < P
+ *   output    f = pos >> 32 (arithmetic), fr = pos & 0xFFFFFFFF, s = 32 - log2 P, p = fr >> s,
+ *             t = (double)(fr & (2^s - 1)) * 2^-s (exact: at most 24 bits).  Per channel two fp64 chains from +0.0 in
+ *             ascending k:  A = A + (double)h[p][k] * (double)x[f - (H-1) + k],  B = B + (double)D[p][k] * (double)x[...]
+ *             (fp32 times fp32 is exact in fp64, so an fma is the same),  then  y = (float)(A + t * B): ONE fp64
+ *             multiplication, ONE fp64 addition, one rounding, never an fma (t * B is not exact).  A NaN is stored as
+ *             0x7FC00000.  x is ZERO outside [0, n_frames) of the range, whatever the clip holds there, and nothing
+ *             outside the range is ever read: a curve may start before the range (a tape start out of silence) or run
+ *             past it.  Interpolating the coefficients linearly lets one product serve both rows: the kernel has no
+ *             per-tap coefficient arithmetic
+ * The filter is NOT an identity: speed 1.0 at integer positions is phase 0's low-pass, as a conversion's is.  At a constant
+ * speed whose phases fall on table rows (t = 0) the result equals wbx_clip_resample's at that ratio bit for bit.
+ *   tiles     the call is launched over runs of whole consecutive intervals chosen greedily from the front: at most 1024
+ *             output frames, and max_f - min_f + T <= 4096, min_f / max_f the least and greatest knots[] >> 32 over the
+ *             run's count + 1 knots.  A tile stages source frames [min_f - (H-1), max_f + H]: lo_frame = min_f - (H-1),
+ *             span = max_f - min_f + T.  The interval bound lets every interval stand alone
+ * wbx_clip_varispeed: dst_clip becomes a new F32 pool clip of out_frames frames (plus the pool's 16 zero frames of padding),
+ * replaced or allocated as wbx_clip_derive does it, on the same stream and behind the same ordering; one edit runs at a
+ * time.  stats_of_result (may be NULL): wbx_clip_measure of the whole result, a second pass over the output only.  The
+ * tables are kept on the device per context and (quality, guard) after their first use; knots and tiles are uploaded per
+ * call.
+ * Refused before any device call, nothing allocated, dst_clip and the statistics untouched, in this order:
+ * WBX_ERR_INVALID for n_frames or out_frames of 0 or >= 2^31 - 16; a knot_shift outside 4 .. 10; NULL knots; n_knots != K; an
+ * unknown quality; guard_num or guard_den of 0, or guard_num < guard_den.  WBX_ERR_UNSUPPORTED for K > 2^22 or T > 512.
+ * WBX_ERR_INVALID for a knot outside its bounds.  WBX_ERR_UNSUPPORTED for an interval past the span bound (the message
+ * names the interval and says to use a smaller knot_shift).  Then the clip — WBX_ERR_INVALID: an unknown source clip, a
+ * range past the clip, dst_clip equal to the source; WBX_ERR_UNSUPPORTED: a source that is not F32 or has more than 2
+ * channels; last, wbx_clip_derive's rule: WBX_ERR_INVALID for a dst_clip of 2^24 or more.  WBX_ERR_OOM as for
+ * wbx_clip_derive.
+ * Host-only, no device (wbx_varispeed.h, which a C++ compiler takes alone):
+ * wbx_varispeed_plan the filter's numbers (WBX_ERR_INVALID: NULL out, unknown quality, a bad guard; UNSUPPORTED: T > 512)
+ * wbx_varispeed_table h as [P+1][T] and d as [P][T] (either may be NULL; WBX_ERR_INVALID when cap_floats is below
+ *             (P+1)*T; nothing written after a refusal)
+ * wbx_varispeed_position pos of output frame j (WBX_ERR_INVALID: NULL, a knot_shift outside 4 .. 10, j past the curve:
+ *             (j >> g) + 1 >= n_knots unless j is the last knot's own frame)
+ * wbx_varispeed_check the refusals above that need no clip, in that order
+ * wbx_varispeed_tiles the tiles of a call wbx_varispeed_check accepts (refused as there): *n_tiles the count, the first
+ *             min(count, cap) records written (tiles may be NULL with cap 0)
+ * wbx_varispeed_max_knots 2^22
+ * wbx_varispeed_ms: device milliseconds between two events on the edits' stream around the uploads and the launch of the
+ * context's last completed varispeed call (layer 1's or layer 2's).  WBX_ERR_INVALID for NULL arguments or when none has
+ * completed.  For tools/bench_varispeed.py; nothing else reads it.
+ * Not offered: a cutoff that follows the speed within one call, more than 2^22 knots, intervals faster than the span bound,
+ * varispeed at render time or on live input, more than 2 channels, in-place edits. */
+typedef struct wbx_varispeed_info { /* 32 bytes */
+  uint32_t half_width;       /* H */
+  uint32_t taps;             /* T = 2H */
+  uint32_t phases;           /* P */
+  uint32_t reserved;
+  double cutoff, beta;
+} wbx_varispeed_info;
+typedef struct wbx_varispeed_tile { /* 24 bytes */
+  uint32_t first_out, n_out; /* output frames [first_out, first_out + n_out) */
+  int64_t lo_frame;          /* the first staged frame of the range (may be negative) */
+  uint32_t span;             /* staged frames per channel */
+  uint32_t reserved;
+} wbx_varispeed_tile;
+wbx_status wbx_varispeed_plan(int quality, uint32_t guard_num, uint32_t guard_den, wbx_varispeed_info* out);
+wbx_status wbx_varispeed_table(int quality, uint32_t guard_num, uint32_t guard_den, float* h, float* d, size_t cap_floats);
+wbx_status wbx_varispeed_position(const int64_t* knots, uint64_t n_knots, uint32_t knot_shift, uint64_t j, int64_t* pos);
+wbx_status wbx_varispeed_check(const int64_t* knots, uint64_t n_knots, uint32_t knot_shift, uint64_t n_frames,
+                               uint64_t out_frames, int quality, uint32_t guard_num, uint32_t guard_den);
+wbx_status wbx_varispeed_tiles(const int64_t* knots, uint64_t n_knots, uint32_t knot_shift, uint64_t n_frames,
+                               uint64_t out_frames, int quality, uint32_t guard_num, uint32_t guard_den,
+                               wbx_varispeed_tile* tiles, uint64_t cap, uint64_t* n_tiles);
+uint64_t wbx_varispeed_max_knots(void);
+wbx_status wbx_varispeed_ms(wbx_ctx* ctx, double* out);
+wbx_status wbx_clip_varispeed(wbx_ctx* ctx, uint32_t src_clip, uint32_t dst_clip, uint64_t first_frame, uint64_t n_frames,
+                              uint64_t out_frames, const int64_t* knots, uint64_t n_knots, uint32_t knot_shift, int quality,
+                              uint32_t guard_num, uint32_t guard_den, wbx_clip_stats* stats_of_result);
+
 /* Stretching a clip: frames [first_frame, first_frame + n_frames) of a resident F32 clip of 1 or 2 channels time-stretched
  * into a NEW F32 clip of out_frames frames — another LENGTH at the same PITCH — without the samples leaving HBM, by WSOLA
  * (waveform-similarity overlap-add): fitting a loop or a take to the session's tempo.  The result plays at speed 1.0 through
@@ -1933,6 +2026,14 @@ wbx_status wbx_engine_dynamics_sample(wbx_engine* e, uint32_t sample, uint32_t k
 wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint32_t os,
                                       int quality, const double* table, double drive, double makeup, uint32_t* new_sample,
                                       wbx_saturate_stats* saturate_stats, wbx_clip_stats* stats_of_result);
+/* wbx_clip_varispeed of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
+ * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
+ * and unpin.  *new_sample is a fresh sample id registered at the source's rate with out_frames frames and the source's
+ * channels.  Arguments and refusals are wbx_clip_varispeed's (there is no dst_clip to collide with). */
+wbx_status wbx_engine_varispeed_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                       uint64_t out_frames, const int64_t* knots, uint64_t n_knots, uint32_t knot_shift,
+                                       int quality, uint32_t guard_num, uint32_t guard_den, uint32_t* new_sample,
+                                       wbx_clip_stats* stats_of_result);
 /* wbx_clip_denoise of an engine sample, under wbx_engine_limit_sample's rules: the source is pinned for the call, so
  * wbx_engine_delete_sample refuses it meanwhile; the editor lock is held only to validate, pin, order the stream, publish
  * and unpin.  *new_sample is a fresh sample id registered at the source's rate with n_frames frames and the source's

@@ -395,6 +395,18 @@ struct Engine {
                                      stats_of_result), "saturate_sample");
     return id;
   }
+  // A NEW sample of out_frames frames holding the range read along a position curve (wbx.h "Reading a clip along a
+  // position curve"): knots[i] = the position of output frame i << knot_shift in 2^-32 source frames relative to
+  // first_frame, n_knots = ceil(out_frames / 2^knot_shift) + 1; guard_num / guard_den >= 1 = the fastest speed protected
+  // from aliasing.  The source's rate and channels.  The source is pinned for the call.  Editing thread, like derive_sample.
+  uint32_t varispeed_sample(uint32_t sample, uint64_t first_frame, uint64_t n_frames, uint64_t out_frames, const int64_t* knots,
+                            uint64_t n_knots, uint32_t knot_shift, int quality = WBX_SRC_GOOD, uint32_t guard_num = 1,
+                            uint32_t guard_den = 1, wbx_clip_stats* stats_of_result = nullptr) {
+    uint32_t id = 0;
+    check(wbx_engine_varispeed_sample(h, sample, first_frame, n_frames, out_frames, knots, n_knots, knot_shift, quality, guard_num,
+                                      guard_den, &id, stats_of_result), "varispeed_sample");
+    return id;
+  }
   // A NEW sample holding the range through the spectral gate (wbx.h "Reducing a clip's noise"): thr = channels x
   // (window_frames / 2 + 1) power thresholds (wbx_denoise_threshold of denoise_profile_sample's sums), floor the linear
   // gain of a closed cell; no delay, the source's length.  The source is pinned for the call.  Editing thread, like

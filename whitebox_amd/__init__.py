@@ -15,6 +15,7 @@ from .engine import convolve_frames, fir_design  # noqa: F401
 from .engine import limit_frames, limit_ramp  # noqa: F401
 from .engine import dynamics_check, dynamics_lookup, dynamics_table  # noqa: F401
 from .engine import saturate_check, saturate_launch_shape, saturate_lookup, saturate_table  # noqa: F401
+from .engine import varispeed_check, varispeed_knots, varispeed_plan, varispeed_position, varispeed_table, varispeed_tiles  # noqa: F401
 from .engine import denoise_band_hops, denoise_hops, denoise_tables, denoise_threshold  # noqa: F401
 from .engine import stretch_anchor, stretch_steps, stretch_window  # noqa: F401
 from .engine import warp_check, warp_launches, warp_segments, warp_steps  # noqa: F401

@@ -90,6 +90,16 @@ class SaturateStats(C.Structure):      # wbx_saturate_stats, 24 bytes
     _fields_ = [("peak_drive", C.c_double), ("peak_index", C.c_uint64), ("beyond", C.c_uint64)]
 
 
+class VarispeedInfo(C.Structure):      # wbx_varispeed_info, 32 bytes
+    _fields_ = [("half_width", C.c_uint32), ("taps", C.c_uint32), ("phases", C.c_uint32), ("reserved", C.c_uint32),
+                ("cutoff", C.c_double), ("beta", C.c_double)]
+
+
+class VarispeedTile(C.Structure):      # wbx_varispeed_tile, 24 bytes
+    _fields_ = [("first_out", C.c_uint32), ("n_out", C.c_uint32), ("lo_frame", C.c_int64), ("span", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class DenoiseStats(C.Structure):       # wbx_denoise_stats, 32 bytes
     _fields_ = [("hops", C.c_uint64), ("cells", C.c_uint64), ("open_cells", C.c_uint64), ("bands", C.c_uint32),
                 ("reserved", C.c_uint32)]
@@ -302,6 +312,16 @@ SYMBOLS = {
     "wbx_saturate_ms": (C.c_int, [_vp, _vp]),
     "wbx_clip_saturate": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(SaturateStats),
                                     C.POINTER(ClipStats)]),
+    "wbx_varispeed_plan": (C.c_int, [C.c_int, _u32, _u32, C.POINTER(VarispeedInfo)]),
+    "wbx_varispeed_table": (C.c_int, [C.c_int, _u32, _u32, _vp, _vp, _sz]),
+    "wbx_varispeed_position": (C.c_int, [_vp, C.c_uint64, _u32, C.c_uint64, C.POINTER(C.c_int64)]),
+    "wbx_varispeed_check": (C.c_int, [_vp, C.c_uint64, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _u32]),
+    "wbx_varispeed_tiles": (C.c_int, [_vp, C.c_uint64, _u32, C.c_uint64, C.c_uint64, C.c_int, _u32, _u32, _vp, C.c_uint64,
+                                      C.POINTER(C.c_uint64)]),
+    "wbx_varispeed_max_knots": (C.c_uint64, []),
+    "wbx_varispeed_ms": (C.c_int, [_vp, _vp]),
+    "wbx_clip_varispeed": (C.c_int, [_vp, _u32, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u32, C.c_int, _u32,
+                                     _u32, C.POINTER(ClipStats)]),
     "wbx_denoise_tables": (C.c_int, [_u32, _vp, _vp]),
     "wbx_denoise_threshold": (C.c_int, [_vp, C.c_uint64, _sz, _d, _vp]),
     "wbx_denoise_hops": (C.c_uint64, [C.c_uint64, _u32]),
@@ -439,6 +459,8 @@ SYMBOLS = {
                                              _u32, _u32, C.POINTER(_u32), C.POINTER(DynamicsStats), C.POINTER(ClipStats)]),
     "wbx_engine_saturate_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, C.c_int, _vp, _d, _d, C.POINTER(_u32),
                                              C.POINTER(SaturateStats), C.POINTER(ClipStats)]),
+    "wbx_engine_varispeed_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, C.c_uint64, _vp, C.c_uint64, _u32, C.c_int, _u32,
+                                              _u32, C.POINTER(_u32), C.POINTER(ClipStats)]),
     "wbx_engine_denoise_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _u32, _u32, _vp, _d, C.POINTER(_u32),
                                             C.POINTER(DenoiseStats)]),
     "wbx_engine_denoise_profile_sample": (C.c_int, [_vp, _u32, C.c_uint64, C.c_uint64, _u32, _vp, C.POINTER(C.c_uint64)]),

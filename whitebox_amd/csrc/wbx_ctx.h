@@ -25,6 +25,7 @@
 #include "wbx_loudness.h"
 #include "wbx_resample.h"
 #include "wbx_saturate.h"
+#include "wbx_varispeed.h"
 #include "wbx_splice.h"
 #include "wbx_stretch.h"
 #include "wbx_warp.h"
@@ -137,6 +138,20 @@ struct ResampleArgs {
   uint32_t tile, span, n_tiles;   // filled by launch_resample: outputs per tile, floats staged per channel and tile, tiles
 };
 void launch_resample(ResampleArgs a, hipStream_t s);
+// reading a clip along a position curve (wbx_varispeed.hip): a frame range of a planar F32 clip -> a new planar F32 clip
+struct VsArgs {
+  const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
+  float* dst[2];               // the new clip's rows (256-B aligned)
+  const float* table;          // device: [P][row] — row p holds h[p][k], D[p][k] pairs, k ascending (16-B aligned rows)
+  const long long* knots;      // device: [K]
+  const wbx_varispeed_tile* tiles;   // device: [n_tiles]
+  uint32_t n_in, n_out;        // frames of the range / of the result, both < 2^31 - 16
+  uint32_t n_tiles;
+  uint32_t H, T, row;          // the plan (wbx_varispeed.h); row: floats of one table row
+  uint32_t g, s;               // knot_shift; 32 - log2 P
+  uint32_t channels;           // 1 or 2
+};
+void launch_varispeed(const VsArgs& a, uint32_t lds_bytes, hipStream_t s);
 // measuring a clip's loudness (wbx_loudness.hip): hop energies behind the K filter, and the oversampled peak
 struct LoudnessArgs {
   const float* src[2];         // the source's channel rows at the RANGE's first frame (mono: src[1] unused)
@@ -538,6 +553,24 @@ struct ResampleTable {
   std::vector<float> host;     // the upload's source, until the stream has been waited for
 };
 
+// wbx_clip_varispeed's interleaved tables on the device, one per (quality, reduced guard) a context has read with — made at
+// first use, freed with the context (48 KB .. 8 MB each) —, the call's knots and tiles, and the timing events
+struct VsTable {
+  int quality = 0;
+  uint32_t gn = 0, gd = 0;
+  DevBuf<float> d;
+  std::vector<float> host;     // the upload's source, until the stream has been waited for
+};
+struct VsStage {
+  std::vector<VsTable> tables;
+  PinnedBuf<long long> h_knots;
+  DevBuf<long long> d_knots;
+  PinnedBuf<wbx_varispeed_tile> h_tiles;
+  DevBuf<wbx_varispeed_tile> d_tiles;
+  Event mark[2];               // (timing events) around the uploads and the launch of the last run: wbx_varispeed_ms
+  bool timed = false;          // the last run completed
+};
+
 // wbx_clip_loudness's results on the device and in pinned memory — grown on demand, freed with the context
 struct LoudnessStage {
   DevBuf<double> d_energy;
@@ -864,6 +897,7 @@ struct wbx_ctx {
   SpecStage spec;                         // wbx_clip_spectrum (under fx_mu, on fx.side.stream)
   AlignStage aln;                         // wbx_clip_align (under fx_mu, on fx.side.stream)
   SatStage sat;                           // wbx_clip_saturate (under fx_mu, on fx.side.stream)
+  VsStage vs;                             // wbx_clip_varispeed (under fx_mu, on fx.side.stream)
   DenStage den;                           // wbx_clip_denoise, wbx_clip_denoise_profile (under fx_mu, on fx.side.stream)
   PitchStage pit;                         // wbx_clip_pitch (under fx_mu, on fx.side.stream; shares str's window table and carry)
 
@@ -1105,6 +1139,13 @@ wbx_status dynamics_run(wbx_ctx* c, const ClipSrc& src, const ClipSrc* key, uint
 wbx_status saturate_check(const ClipSrc* src, bool replaces, const SatCall& k, const char** why);
 wbx_status saturate_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const SatCall& k, ClipSlot& slot, wbx_saturate_stats* out,
                         wbx_clip_stats* stats, std::string* why);
+// reading a clip along a position curve (wbx_varispeed.hip), cut the same way: the check makes no device call
+// (wbx_varispeed.h's varispeed_check_args first — sizes and curve are judged before the clip —, then the clip: NULL for an
+// unknown one, `replaces` where dst_clip is the source); the run works under fx_mu on the edit stream behind clipfx_prepare /
+// clipfx_order
+wbx_status varispeed_check(const ClipSrc* src, bool replaces, const VsCall& k, VsPlan* plan, const char** why);
+wbx_status varispeed_run(wbx_ctx* c, const ClipSrc& src, uint32_t rate, const VsCall& k, const VsPlan& plan, ClipSlot& slot,
+                         wbx_clip_stats* stats, std::string* why);
 // reducing a clip's noise (wbx_denoise.hip), cut the same way: the checks make no device call (wbx_denoise.h's argument
 // checks first, then the clip: NULL for an unknown one, `replaces` where dst_clip is the source); the runs work under fx_mu
 // on the edit stream behind clipfx_prepare / clipfx_order

@@ -809,6 +809,24 @@ extern "C" wbx_status wbx_engine_saturate_sample(wbx_engine* e, uint32_t sample,
   });
 }
 
+// registered at the source's rate, with out_frames frames
+extern "C" wbx_status wbx_engine_varispeed_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
+                                                  uint64_t out_frames, const int64_t* knots, uint64_t n_knots, uint32_t knot_shift,
+                                                  int quality, uint32_t guard_num, uint32_t guard_den, uint32_t* new_sample,
+                                                  wbx_clip_stats* stats_of_result) {
+  if (!e) return WBX_ERR_INVALID;
+  if (!new_sample) return efail(e, WBX_ERR_INVALID, "varispeed_sample: new_sample is NULL");
+  SamplePin p(e);
+  const VsCall k{first_frame, n_frames, out_frames, knots, n_knots, knot_shift, quality, guard_num, guard_den};
+  VsPlan plan;
+  const wbx_status st = p.begin(sample, "varispeed_sample: unknown sample", "varispeed_sample: the pool's sample ids (2^24) would run out",
+                                nullptr, [&](const char** msg) { return varispeed_check(&p.src, false, k, &plan, msg); });
+  if (st != WBX_OK) return st;
+  return p.make(p.src.channels, p.rate, out_frames, new_sample, [&](ClipSlot& slot, std::string* why) {
+    return varispeed_run(e->ctx, p.src, p.rate, k, plan, slot, stats_of_result, why);
+  });
+}
+
 // registered at the source's rate, with the range's frames
 extern "C" wbx_status wbx_engine_denoise_sample(wbx_engine* e, uint32_t sample, uint64_t first_frame, uint64_t n_frames,
                                                 uint32_t window_frames, uint32_t smooth_hops, uint32_t smooth_bins, const double* thr,

@@ -59,22 +59,30 @@ inline wbx_status resample_ratio(uint32_t src_rate, uint32_t dst_rate, uint32_t*
   return WBX_OK;
 }
 
-inline wbx_status resample_plan(uint32_t src_rate, uint32_t dst_rate, int quality, ResamplePlan* p, const char** why) {
-  ResampleQuality q;
-  if (!resample_quality(quality, &q)) return *why = "resample: unknown quality", WBX_ERR_INVALID;
-  uint32_t L = 0, M = 0;
-  const wbx_status st = resample_ratio(src_rate, dst_rate, &L, &M, why);
-  if (st != WBX_OK) return st;
+// the filter of a reduced ratio M / L at a known quality (wbx_varispeed.h plans its guard ratio through it too): H, T, cutoff
+// and beta; WBX_ERR_UNSUPPORTED for more than 512 taps, with the caller's reason
+inline wbx_status resample_filter(uint64_t L, uint64_t M, const ResampleQuality& q, ResamplePlan* p, const char** why, const char* too_long) {
   // H = ceil(Z / rho) with rho = min(1, L / M), in integers: ceil(Z * M / L) when converting downwards
   const uint64_t H = L < M ? ((uint64_t)q.zero_crossings * M + L - 1) / L : q.zero_crossings;
-  if (2 * H > kResampleMaxTaps) return *why = "resample: the ratio needs more than 512 taps at this quality", WBX_ERR_UNSUPPORTED;
+  if (2 * H > kResampleMaxTaps) return *why = too_long, WBX_ERR_UNSUPPORTED;
   const double rho = L < M ? (double)L / (double)M : 1.0;
-  p->L = L;
-  p->M = M;
   p->H = (uint32_t)H;
   p->T = (uint32_t)(2 * H);
   p->cutoff = q.frac * rho;
   p->beta = q.beta;
+  return WBX_OK;
+}
+
+inline wbx_status resample_plan(uint32_t src_rate, uint32_t dst_rate, int quality, ResamplePlan* p, const char** why) {
+  ResampleQuality q;
+  if (!resample_quality(quality, &q)) return *why = "resample: unknown quality", WBX_ERR_INVALID;
+  uint32_t L = 0, M = 0;
+  wbx_status st = resample_ratio(src_rate, dst_rate, &L, &M, why);
+  if (st != WBX_OK) return st;
+  st = resample_filter(L, M, q, p, why, "resample: the ratio needs more than 512 taps at this quality");
+  if (st != WBX_OK) return st;
+  p->L = L;
+  p->M = M;
   return WBX_OK;
 }
 
@@ -132,25 +140,28 @@ inline double resample_i0(double x) {
   return s;
 }
 
+// one row of a table: the T coefficients at the fractional position `frac` (0 <= frac <= 1) of a filter (H, T, cutoff,
+// beta; i0b = resample_i0(beta)), divided by their own ascending sum, rounded once to fp32
+inline void resample_row(const ResamplePlan& p, double i0b, double frac, float* out) {
+  const double Hd = (double)p.H;
+  double row[kResampleMaxTaps];
+  double sum = 0.0;
+  for (uint32_t k = 0; k < p.T; k++) {
+    const double d = (double)((int64_t)k - ((int64_t)p.H - 1)) - frac;
+    const double u = d / Hd;
+    double w = 1.0 - u * u;
+    if (w < 0.0) w = 0.0;
+    const double v = ((p.cutoff * resample_sinc(p.cutoff * d)) * resample_i0(p.beta * std::sqrt(w))) / i0b;
+    row[k] = v;
+    sum = sum + v;
+  }
+  for (uint32_t k = 0; k < p.T; k++) out[k] = (float)(row[k] / sum);
+}
+
 // out[p * T + k], p in [0, L), k in [0, T): phase p's coefficients, each phase divided by its own sum, rounded once to fp32
 inline void resample_table(const ResamplePlan& p, float* out) {
   const double i0b = resample_i0(p.beta);
-  const double Hd = (double)p.H;
-  double row[kResampleMaxTaps];
-  for (uint32_t ph = 0; ph < p.L; ph++) {
-    const double frac = (double)ph / (double)p.L;
-    double sum = 0.0;
-    for (uint32_t k = 0; k < p.T; k++) {
-      const double d = (double)((int64_t)k - ((int64_t)p.H - 1)) - frac;
-      const double u = d / Hd;
-      double w = 1.0 - u * u;
-      if (w < 0.0) w = 0.0;
-      const double v = ((p.cutoff * resample_sinc(p.cutoff * d)) * resample_i0(p.beta * std::sqrt(w))) / i0b;
-      row[k] = v;
-      sum = sum + v;
-    }
-    for (uint32_t k = 0; k < p.T; k++) out[(size_t)ph * p.T + k] = (float)(row[k] / sum);
-  }
+  for (uint32_t ph = 0; ph < p.L; ph++) resample_row(p, i0b, (double)ph / (double)p.L, out + (size_t)ph * p.T);
 }
 
 }  // namespace wbx

@@ -325,6 +325,85 @@ def denoise_tables(window_frames: int):
     return a, y
 
 
+def _vs_q(quality) -> int:
+    return _ffi.SRC_QUALITY.get(quality, quality)
+
+
+def _vs_knots(knots) -> np.ndarray:
+    return np.ascontiguousarray(knots, dtype=np.int64)
+
+
+def varispeed_plan(quality="good", guard_num: int = 1, guard_den: int = 1) -> dict:
+    """wbx_varispeed_plan (host-only): {"H", "T", "P", "cutoff", "beta"} of the interpolator that protects speeds up to
+    guard_num / guard_den (>= 1) from aliasing.  WbxError where the library refuses it"""
+    v = _ffi.VarispeedInfo()
+    _check(_ffi.lib().wbx_varispeed_plan(_vs_q(quality), guard_num, guard_den, C.byref(v)), "wbx_varispeed_plan")
+    return {"H": v.half_width, "T": v.taps, "P": v.phases, "cutoff": v.cutoff, "beta": v.beta}
+
+
+def varispeed_table(quality="good", guard_num: int = 1, guard_den: int = 1):
+    """wbx_varispeed_table (host-only): (h float32[P + 1][T], d float32[P][T]) — the phase rows and their differences"""
+    p = varispeed_plan(quality, guard_num, guard_den)
+    h = np.zeros((p["P"] + 1, p["T"]), dtype=np.float32)
+    d = np.zeros((p["P"], p["T"]), dtype=np.float32)
+    _check(_ffi.lib().wbx_varispeed_table(_vs_q(quality), guard_num, guard_den, h.ctypes.data, d.ctypes.data, h.size), "wbx_varispeed_table")
+    return h, d
+
+
+def varispeed_position(knots, knot_shift: int, j: int) -> int:
+    """wbx_varispeed_position (host-only): the position of output frame j on the curve, in 2^-32 source frames"""
+    k, out = _vs_knots(knots), C.c_int64()
+    _check(_ffi.lib().wbx_varispeed_position(k.ctypes.data, k.size, knot_shift, j, C.byref(out)), "wbx_varispeed_position")
+    return out.value
+
+
+def varispeed_check(knots, knot_shift: int, n_frames: int, out_frames: int, quality="good", guard_num: int = 1, guard_den: int = 1) -> int:
+    """wbx_varispeed_check (host-only): the status a call with these sizes and this curve is refused with before its clip
+    is looked at (0: accepted).  `knots` may be None (a NULL pointer)"""
+    k = None if knots is None else _vs_knots(knots)
+    return int(_ffi.lib().wbx_varispeed_check(None if k is None else k.ctypes.data, 0 if k is None else k.size, knot_shift, n_frames,
+                                              out_frames, _vs_q(quality), guard_num, guard_den))
+
+
+def varispeed_tiles(knots, knot_shift: int, n_frames: int, out_frames: int, quality="good", guard_num: int = 1, guard_den: int = 1) -> list:
+    """wbx_varispeed_tiles (host-only): the tiles a call is launched over, [(first_out, n_out, lo_frame, span)].  WbxError
+    where wbx_varispeed_check refuses the call"""
+    k, n = _vs_knots(knots), C.c_uint64()
+    L, args = _ffi.lib(), (knot_shift, n_frames, out_frames, _vs_q(quality), guard_num, guard_den)
+    _check(L.wbx_varispeed_tiles(k.ctypes.data, k.size, *args, None, 0, C.byref(n)), "wbx_varispeed_tiles")
+    rec = (_ffi.VarispeedTile * max(1, n.value))()
+    _check(L.wbx_varispeed_tiles(k.ctypes.data, k.size, *args, C.addressof(rec), n.value, C.byref(n)), "wbx_varispeed_tiles")
+    return [(t.first_out, t.n_out, t.lo_frame, t.span) for t in rec[:n.value]]
+
+
+def _vs_guard(speed: float):
+    """a guard >= max(1, speed) in sixteenths"""
+    return (max(16, int(np.ceil(float(speed) * 16.0 - 1e-9))), 16)
+
+
+def varispeed_knots(points, out_frames: int, knot_shift: int = 6, start: float = 0.0):
+    """The knots of a speed curve given as breakpoints (out_frame, speed), ascending in out_frame, with LINEAR speed ramps
+    between them (constant before the first and behind the last): the position is the integral of the speed from `start`
+    (source frames) at output frame 0.  Float arithmetic on the host, outside the bit-exact contract; the call is exact for
+    the knots returned.  Returns (knots int64[K], (guard_num, guard_den)) — the guard covers the fastest breakpoint"""
+    pts = [(float(j), float(s)) for j, s in points]
+    assert pts and all(a[0] < b[0] for a, b in zip(pts, pts[1:])), "varispeed_knots: breakpoints ascend in out_frame"
+    G = 1 << knot_shift
+    K = (out_frames + G - 1) // G + 1
+    j = np.arange(K, dtype=np.float64) * G
+    jp = np.array([p[0] for p in pts])
+    sp = np.array([p[1] for p in pts])
+    # position at the breakpoints (trapezoids), from output frame 0 where the speed is the first breakpoint's
+    at = np.concatenate(([0.0], np.cumsum(0.5 * (sp[1:] + sp[:-1]) * np.diff(jp)))) + sp[0] * jp[0]
+    seg = np.clip(np.searchsorted(jp, j, side="right") - 1, 0, len(pts) - 1)
+    dj = j - jp[seg]
+    slope = np.zeros(len(pts))
+    slope[:-1] = np.diff(sp) / np.diff(jp)
+    pos = np.where(j < jp[0], sp[0] * j, at[seg] + sp[seg] * dj + 0.5 * slope[seg] * dj * dj)
+    knots = np.array([int(round((float(start) + float(v)) * 4294967296.0)) for v in pos], dtype=np.int64)
+    return knots, _vs_guard(np.max(np.abs(sp)))
+
+
 def denoise_threshold(sums, hops: int, strength: float) -> np.ndarray:
     """wbx_denoise_threshold (host-only): strength * (sums / hops) — the per-bin threshold of a profile's sums"""
     s = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
@@ -810,6 +889,26 @@ class MixContext:
         """wbx_saturate_ms: device milliseconds of the last saturate call's launches"""
         out = C.c_double()
         _check(self.L.wbx_saturate_ms(self.h, C.byref(out)), "wbx_saturate_ms", self.h)
+        return out.value
+
+    def clip_varispeed(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, out_frames: int, knots,
+                       knot_shift: int, quality="good", guard_num: int = 1, guard_den: int = 1, stats_channels: int = 0):
+        """wbx_clip_varispeed: `dst_clip` becomes a new F32 clip of out_frames frames = the range of `src_clip` read along
+        the position curve `knots` (int64, 2^-32 source frames relative to first_frame, one per 2^knot_shift output frames
+        and one more) through the band-limited interpolator of `quality`, protected from aliasing up to the speed
+        guard_num / guard_den.  `knots` may be None (refused).  With `stats_channels` (the clip's channel count) returns
+        the result's wbx_clip_measure statistics"""
+        k, st = (None if knots is None else _vs_knots(knots)), _ffi.ClipStats()
+        _check(self.L.wbx_clip_varispeed(self.h, src_clip, dst_clip, first_frame, n_frames, out_frames,
+                                         None if k is None else k.ctypes.data, 0 if k is None else k.size, knot_shift,
+                                         _vs_q(quality), guard_num, guard_den, C.byref(st) if stats_channels else None),
+               "wbx_clip_varispeed", self.h)
+        return _clip_stats(st, stats_channels) if stats_channels else None
+
+    def varispeed_ms(self) -> float:
+        """wbx_varispeed_ms: device milliseconds of the last varispeed call's uploads and launch"""
+        out = C.c_double()
+        _check(self.L.wbx_varispeed_ms(self.h, C.byref(out)), "wbx_varispeed_ms", self.h)
         return out.value
 
     def clip_denoise(self, src_clip: int, dst_clip: int, first_frame: int, n_frames: int, window_frames: int, thr,
@@ -2052,6 +2151,117 @@ class Engine:
         if sample in self._sample_rate:
             self._sample_rate[new.value] = self._sample_rate[sample]
         return (new.value, _saturate_stats(ss), _clip_stats(st, channels)) if stats else (new.value, _saturate_stats(ss))
+
+    def varispeed_sample(self, sample: int, out_frames: int, knots, knot_shift: int, quality="good", guard_num: int = 1,
+                         guard_den: int = 1, first_frame: int = 0, n_frames: Optional[int] = None,
+                         channels: Optional[int] = None, frames: Optional[int] = None, stats: bool = False):
+        """wbx_engine_varispeed_sample: a new sample of out_frames frames = the range of `sample` read along the position
+        curve `knots` — see MixContext.clip_varispeed.  `frames` / `channels` as in export_sample.  The source is pinned
+        against delete_sample for the call's length; may be called while another thread runs process().  Returns the new
+        id, with `stats` (id, the result's statistics)."""
+        frames, channels = self._shape_of(sample, frames, channels)
+        if n_frames is None:
+            assert frames is not None, "varispeed_sample: give n_frames, or frames (the sample's length)"
+            n_frames = frames - first_frame
+        k, new, st = (None if knots is None else _vs_knots(knots)), C.c_uint32(), _ffi.ClipStats()
+        _check(self.L.wbx_engine_varispeed_sample(self.h, sample, first_frame, n_frames, out_frames,
+                                                  None if k is None else k.ctypes.data, 0 if k is None else k.size, knot_shift,
+                                                  _vs_q(quality), guard_num, guard_den, C.byref(new), C.byref(st) if stats else None),
+               "wbx_engine_varispeed_sample", self.h, True)
+        self._sample_shape[new.value] = (out_frames, channels)
+        if sample in self._sample_rate:
+            self._sample_rate[new.value] = self._sample_rate[sample]
+        return (new.value, _clip_stats(st, channels)) if stats else new.value
+
+    def _vs_range(self, what, sample, call):
+        frames, _ = self._shape_of(sample, call.get("frames"), call.get("channels"))
+        n = call.get("n_frames")
+        if n is None:
+            assert frames is not None, what + ": give n_frames, or frames (the sample's length)"
+            n = frames - call.get("first_frame", 0)
+        return n
+
+    def tape_stop_sample(self, sample: int, at_frame: int, ramp_frames: int, quality="good", knot_shift: int = 6, **call):
+        """A tape stop: the range plays at speed 1 up to output frame `at_frame`, then the speed falls linearly to 0 over
+        `ramp_frames`; the result has at_frame + ramp_frames frames.  The knots come from varispeed_knots: a convenience
+        outside the bit-exact contract, the samples are the model's for the knots reported back.  `call`:
+        varispeed_sample's first_frame, n_frames, frames, channels.  Returns (new id, {"knots", "knot_shift", "out_frames",
+        "guard"})"""
+        self._vs_range("tape_stop_sample", sample, call)
+        out_frames = int(at_frame) + int(ramp_frames)
+        pts = [(0, 1.0), (int(at_frame), 1.0), (out_frames, 0.0)] if at_frame > 0 else [(0, 1.0), (out_frames, 0.0)]
+        knots, guard = varispeed_knots(pts, out_frames, knot_shift)
+        new = self.varispeed_sample(sample, out_frames, knots, knot_shift, quality, guard[0], guard[1], **call)
+        return new, {"knots": knots, "knot_shift": knot_shift, "out_frames": out_frames, "guard": guard}
+
+    def vibrato_sample(self, sample: int, rate_hz: float, depth_cents: float, quality="good", knot_shift: int = 4,
+                       rate: Optional[int] = None, **call):
+        """Vibrato (wow, flutter): the range at its own length, read at j + a sin(2 pi rate_hz j / rate), a chosen so that
+        the speed swings between 2^(-depth_cents / 1200) and 2^(depth_cents / 1200) about 1.  Outside the bit-exact
+        contract, like tape_stop_sample.  Returns (new id, {"knots", "knot_shift", "out_frames", "guard"})"""
+        n = self._vs_range("vibrato_sample", sample, call)
+        rate = self._sample_rate.get(sample, self.audio_sample_rate) if rate is None else rate
+        dev = 2.0 ** (float(depth_cents) / 1200.0) - 1.0
+        w = 2.0 * np.pi * float(rate_hz) / float(rate)
+        G = 1 << knot_shift
+        j = np.arange((n + G - 1) // G + 1, dtype=np.float64) * G
+        pos = j + (dev / w) * np.sin(w * j)
+        knots = np.array([int(round(float(v) * 4294967296.0)) for v in pos], dtype=np.int64)
+        guard = _vs_guard(1.0 + dev)
+        new = self.varispeed_sample(sample, n, knots, knot_shift, quality, guard[0], guard[1], **call)
+        return new, {"knots": knots, "knot_shift": knot_shift, "out_frames": n, "guard": guard}
+
+    def drift_sample(self, sample: int, ppm: float, quality="good", knot_shift: int = 10, **call):
+        """A recording whose clock ran `ppm` parts per million fast conformed: the range read at the constant speed
+        1 + ppm / 10^6 into round(n / speed) frames (guard 1: the interpolator's own margin covers a drift).  The knots are
+        exact integers of that speed as a fraction.  Returns (new id, {"knots", "knot_shift", "out_frames", "guard"})"""
+        n = self._vs_range("drift_sample", sample, call)
+        speed = 1 + Fraction(float(ppm)).limit_denominator(10 ** 9) / 10 ** 6
+        out_frames = max(1, int(round(n / speed)))
+        G = 1 << knot_shift
+        K = (out_frames + G - 1) // G + 1
+        knots = np.array([int((i * G * speed * (1 << 32)).__floor__()) for i in range(K)], dtype=np.int64)
+        new = self.varispeed_sample(sample, out_frames, knots, knot_shift, quality, 1, 1, **call)
+        return new, {"knots": knots, "knot_shift": knot_shift, "out_frames": out_frames, "guard": (1, 1)}
+
+    def pitch_curve_sample(self, sample: int, segments, quality="good", window_frames: int = 2048, tolerance_frames: int = 512,
+                           **call):
+        """Pitch that changes over time at unchanged timing: `segments` = [(first_frame, ratio)] relative to the range, the
+        first at 0, each ratio (within 1/8 .. 8) holding up to the next segment.  warp_sample stretches each segment by its
+        ratio into an intermediate sample; this call then plays the intermediate back at that ratio (knot_shift 4), so every
+        boundary keeps its frame and the result has the range's length.  Boundaries are moved to multiples of 16 frames (a
+        knot stands there); the intermediate is deleted.  Outside the bit-exact contract, like tape_stop_sample: the result
+        is warp's model followed by this call's model for the markers and knots reported back.  Returns (new id, {"markers",
+        "mid_frames", "knots", "knot_shift", "out_frames", "guard"})"""
+        n = self._vs_range("pitch_curve_sample", sample, call)
+        seg = sorted((min(n, (int(f) + 8) // 16 * 16), Fraction(float(r)).limit_denominator(1 << 12)) for f, r in segments)
+        assert seg and seg[0][0] == 0, "pitch_curve_sample: the first segment starts at frame 0"
+        bounds, ratios = [], []
+        for f, r in seg:
+            if bounds and f == bounds[-1]:
+                ratios[-1] = r
+            elif f < n:
+                bounds.append(f)
+                ratios.append(r)
+        bounds.append(n)
+        mid = [0]
+        for a, b, r in zip(bounds, bounds[1:], ratios):
+            mid.append(mid[-1] + max(1, int(round((b - a) * r))))
+        markers = list(zip(bounds[1:-1], mid[1:-1]))
+        tmp, _ = self.warp_sample(sample, mid[-1], markers, window_frames, tolerance_frames, **call)
+        K = (n + 15) // 16 + 1
+        knots, s = np.zeros(K, dtype=np.int64), 0
+        for i in range(K):
+            j = i * 16
+            while s + 2 < len(bounds) and j >= bounds[s + 1]:
+                s += 1
+            knots[i] = (mid[s] << 32) + ((j - bounds[s]) * ((mid[s + 1] - mid[s]) << 32)) // (bounds[s + 1] - bounds[s])
+        guard = _vs_guard(max(float(r) for r in ratios))
+        try:
+            new = self.varispeed_sample(tmp, n, knots, 4, quality, guard[0], guard[1], frames=mid[-1], channels=call.get("channels"))
+        finally:
+            self.delete_sample(tmp)
+        return new, {"markers": markers, "mid_frames": mid[-1], "knots": knots, "knot_shift": 4, "out_frames": n, "guard": guard}
 
     def denoise_sample(self, sample: int, window_frames: int, thr, floor: float = 0.1, smooth_hops: int = 2, smooth_bins: int = 1,
                        first_frame: int = 0, n_frames: Optional[int] = None, channels: Optional[int] = None,
